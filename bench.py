@@ -11,6 +11,11 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W      (N > 1: l
   * after the first region rank 0 also writes that region's line to STDERR (``[bench] early line ...``), for a log reader;
     stdout carries exactly one line.
 
+A plain run sets up, warms up, times the K steps of the headline partition and prints the line.  ``--full`` adds what the headline
+does not need: the CPU baseline and the strict-arithmetic region (N = 1, fp32), and at N > 1 the other partitions, the chunked and
+bf16-wire regions and the link preflight.  ``--dump-outputs DIR`` writes what the last timed step computed (``step_outputs``) as
+``DIR/<name>.npy`` in float32, so that two builds can be compared output for output: the inputs depend on the arguments alone.
+
 Workload (BASELINE.json configs[2], the configuration the metric is quoted on):
 synthetic random hypergraph, |V| = |E| = 1M per GPU, every hyperedge has 16 distinct uniformly drawn members
 (nnz = 16M per GPU), d = 128, fp32, AllDeepSets (HalfNLHconv x2 with 2-layer LayerNorm MLPs, aggr = add,
@@ -27,8 +32,8 @@ N > 1 -- two partitions of the same job (allset_amd/dist.py, DESIGN.md section 7
            one reduce-scatter of the [n_V, d] vertex table per direction;
   columns  column-sharded aggregation: every rank holds the whole incidence and d/N feature columns of every row;
            four all-to-alls per direction-pair, 1/N of the row scheme's bytes at N = 8, overlapped with the dense work.
-Both are timed in every N > 1 run, each in its own region of the same K steps (plus the column partition with the chunked
-overlapped exchange), and appear under ``partitions``, so a scaling record always carries the north-star partition.
+Under ``--full`` both are timed in an N > 1 run, each in its own region of the same K steps (plus the column partition with the
+chunked overlapped exchange), and appear under ``partitions``; a plain run times ``--shard``'s partition alone.
 ``value`` / ``ms_per_step`` are those of ``--shard`` -- ``rows`` by default since round 5 (the north star's partition); ``columns`` /
 ``hybrid`` pin another one, ``auto`` reports the FASTEST of the exact (fp32-wire) executions this run timed;
 ``partitions.fastest_exact`` always names that one.  N = 2 x C >= 4 adds the hybrid partition (2 target groups x C column groups,
@@ -47,9 +52,9 @@ Extra objects in the JSON line:
                 ``per_kernel`` = the same arithmetic for every timed kernel that states its algorithmic bytes.
   aggregation   the aggregation-only figure (all gather-kernel time per step): the north star's
                 "% of HBM roofline on the V->E->V aggregation".
-  cpu_baseline  the oracle (a restatement of the reference's CPU torch_scatter path) timed on this box's host cores
-                on the SAME hypergraph and features the GPU ran (copied back), median of ``--cpu-iters`` (3) iterations at
-                full size after a warm-up on a 1/10 sample (rank 0, N = 1 only).
+  cpu_baseline  ``--full`` only (null otherwise): the oracle (a restatement of the reference's CPU torch_scatter path) timed on
+                this box's host cores on the SAME hypergraph and features the GPU ran (copied back), median of ``--cpu-iters`` (3)
+                iterations at full size after a warm-up on a 1/10 sample (rank 0, N = 1 only).
 """
 from __future__ import annotations
 
@@ -97,7 +102,7 @@ def parse_args(argv=None):
     ap.add_argument("--shard", default="rows", choices=["auto", "rows", "columns", "hybrid"],
                     help="N > 1: which partition is timed as `value` ('auto' = allset_amd.dist.choose_sharding)")
     ap.add_argument("--partitions", default="both", choices=["both", "primary"],
-                    help="N > 1: 'both' also times the other partition in a second region and reports it under `partitions`")
+                    help="N > 1 with --full: 'both' also times the other partition in a second region and reports it under `partitions`")
     ap.add_argument("--pipeline-chunks", type=int, default=1,
                     help="--shard columns: chunks of owned rows whose all-to-alls overlap the other chunks' dense work "
                          "(1 = off, the default: blocking all-to-alls; 0 = allset_amd.dist.auto_chunks: 4 at 1M rows per GPU, "
@@ -109,10 +114,10 @@ def parse_args(argv=None):
                          "as one hipGraph and time K replays -- the same kernels on the same data, without the ~100 host launches "
                          "per step that are ~10 %% of a step in the bf16 regime (configs[4] per-GPU shape)")
     ap.add_argument("--chunk-entry", type=int, default=-1,
-                    help="N > 1: chunk count of the extra timed region of the column partition with the chunked, overlapped exchange "
+                    help="N > 1 with --full: chunk count of the extra timed region of the column partition with the chunked, overlapped exchange "
                          "(-1 = allset_amd.dist.auto_chunks: 4 at 1M rows per GPU, none below 500k; 0 = skip)")
     ap.add_argument("--no-wire-entry", dest="wire_entry", action="store_false",
-                    help="N > 1: skip the extra timed region of the primary partition with the opt-in bf16 wire format")
+                    help="N > 1 with --full: skip the extra timed region of the primary partition with the opt-in bf16 wire format")
     ap.add_argument("--self-loops", action="store_true",
                     help="variant (SURVEY 8(d1)): add one singleton hyperedge per vertex as Add_Self_Loops does (single GPU only)")
     ap.add_argument("--model", default="deepsets", choices=["deepsets", "pma"],
@@ -129,7 +134,7 @@ def parse_args(argv=None):
                     help="arithmetic of the fused fp32 Linear kernels (allset_amd.dense.set_arithmetic; include/allset_hip_ext.h "
                          "ALLSET_ARITH_*): auto = fp16x3 where built, strict = the exact three-bf16-plane split everywhere")
     ap.add_argument("--no-strict-entry", dest="strict_entry", action="store_false",
-                    help="N = 1, fp32: skip the second timed region that repeats the K steps in the strict arithmetic "
+                    help="N = 1, fp32, --full: skip the second timed region that repeats the K steps in the strict arithmetic "
                          "(reported as `strict` / dense_tail.strict_ms_per_step, never `value`)")
     ap.add_argument("--cpu-sample-n", type=int, default=0,
                     help="|V| = |E| of the CPU-baseline sample (0 = the GPU workload itself, copied back to the host)")
@@ -139,10 +144,18 @@ def parse_args(argv=None):
                          "the regions that finished and ends the process (the first region gets 3x)")
     ap.add_argument("--preflight", default="auto", choices=["auto", "on", "off"],
                     help="time the layer's four collectives at this job's message sizes after the first region and report GB/s per "
-                         "link under `preflight` (auto = when N > 1)")
+                         "link under `preflight` (auto = when N > 1 under --full)")
     ap.add_argument("--cpu-threads", type=int, default=32,
                     help="host threads for the CPU baseline (32 is the fastest setting for torch's scatter_add_/"
                          "index_select on the 2x128-thread GPU box: profiles/r01_cpu_threads_probe.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the strict-arithmetic region "
+                         "(N = 1, fp32) and, at N > 1, the other partitions, the chunked / bf16-wire regions and the link preflight. "
+                         "Off by default: a plain run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32): the layer "
+                         "output and the input gradient (a fixed seeded sample of rows), every parameter gradient and every "
+                         "parameter after the Adam update; rank 0's arrays at N > 1.  At most 64 MB in all")
     return ap.parse_args(argv)
 
 
@@ -395,6 +408,9 @@ def run_partition(args, mode, world, rank, dev, hooks=None):
         import contextlib
         deferred = contextlib.nullcontext
 
+    keep_out = bool(getattr(args, "dump_outputs", None)) and rank == 0
+    last = {}
+
     def step():
         opt.zero_grad(set_to_none=True)
         x.grad = None
@@ -412,6 +428,8 @@ def run_partition(args, mode, world, rank, dev, hooks=None):
             out.backward(G)
         adist.allreduce_grads(params)
         opt.step()
+        if keep_out:
+            last["out"] = out.detach()         # (under capture: the graph's own output tensor, refreshed by every replay)
 
     if graph_mode:            # one hipGraph per step (allset_amd/graphs.py explains what makes the path capturable)
         from allset_amd import dense as _dense
@@ -466,10 +484,54 @@ def run_partition(args, mode, world, rank, dev, hooks=None):
     res = {"mode": mode, "elapsed": elapsed, "nnz_total": nnz_total, "rows": rows, "n_v": hg.n_v, "n_e": n_e_global,
            "kernels": timer.summary() if timer is not None else {}, "ms_per_step": elapsed / args.steps * 1e3,
            "value": job_value(nnz_total, d, elapsed, args.steps)}
-    if hooks.get("keep_inputs") or (world == 1 and rank == 0 and not attn and not args.no_cpu_baseline and on_gpu):
+    if hooks.get("keep_inputs") or (world == 1 and rank == 0 and not attn and args.full and not args.no_cpu_baseline and on_gpu):
         ei = hg.local_edge_index if hasattr(hg, "local_edge_index") else hg.edge_index
         res["edge_index_cpu"], res["x_cpu"] = ei.detach().cpu(), x.detach().float().cpu()
+    if keep_out:
+        res["outputs"] = step_outputs(args, last["out"], x.grad, {"v2e": v2e, "e2v": e2v})
     return res
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: all arrays together
+DUMP_ROW_BYTES = 8 << 20       # per row-wise array (layer output, input gradient): a fixed seeded sample of rows above this
+
+
+def step_outputs(args, out, x_grad, modules):
+    """What the last timed step handed its caller, as float32 host arrays: the layer output and d(loss)/dx (the same fixed sample
+    of rows, drawn from --seed, when the tensor is larger than DUMP_ROW_BYTES), every parameter gradient and every parameter after
+    the Adam update.  Parameters too are reduced to a fixed seeded sample of their entries if the whole set would exceed DUMP_BYTES."""
+    import numpy as np
+    rows = out.shape[0]
+    k = max(1, min(rows, DUMP_ROW_BYTES // (4 * max(out.shape[1], x_grad.shape[1]))))
+    pick = torch.from_numpy(np.sort(np.random.default_rng(args.seed).choice(rows, size=k, replace=False))).to(out.device)
+    arrays = {"out": out.index_select(0, pick), "x_grad": x_grad.index_select(0, pick)}
+    for mname, mod in modules.items():
+        for pname, p in mod.named_parameters():
+            arrays[f"param.{mname}.{pname}"] = p.detach()
+            arrays[f"grad.{mname}.{pname}"] = p.grad.detach() if p.grad is not None else torch.zeros_like(p)
+    arrays = {n: t.float().cpu().numpy() for n, t in arrays.items()}
+    rowwise = ("out", "x_grad")
+    left = DUMP_BYTES - sum(arrays[n].nbytes for n in rowwise)
+    sizes = sorted(a.size for n, a in arrays.items() if n not in rowwise)
+    if sum(sizes) * 4 > left:                       # the largest per-array entry count that fits, applied as a cap
+        budget, cap = left // 4, 0
+        for i, s in enumerate(sizes):
+            if sum(sizes[:i]) + s * (len(sizes) - i) > budget:
+                cap = (budget - sum(sizes[:i])) // (len(sizes) - i)
+                break
+        for i, n in enumerate(sorted(n for n in arrays if n not in rowwise)):
+            a = arrays[n].reshape(-1)
+            if a.size > cap:
+                sel = np.sort(np.random.default_rng([args.seed, i]).choice(a.size, size=cap, replace=False))
+                arrays[n] = a[sel]
+    return arrays
+
+
+def dump_outputs(path, arrays) -> None:
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cfg_index(args) -> int:
@@ -775,7 +837,8 @@ def assemble_line(args, world, primary, state, cpu_mode=False, final=True):
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["ms_per_step"],
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
         "arithmetic": (f"{args.arith}: `value` is measured with fp32 products formed from two scaled fp16 planes (fp16x3) wherever that kernel is "
-                       "built; the same K steps on the exact three-plane bf16 split (bf16x6) are timed in the same run: `strict`"
+                       "built" + ("; the same K steps on the exact three-plane bf16 split (bf16x6) are timed in the same run: `strict`"
+                                  if (state.get("strict") is not None or "strict" in errors) else "")
                        if args.dtype == "f32" and args.arith in ("auto", "fp16x3") else args.arith),
         "dtype_note": ("fp32 tensors end to end; aggregation kernels: plain fp32 adds; dense tail: fp32 products formed on the 16-bit "
                        "matrix pipes and accumulated in fp32 -- at 128 x 128 (the forward and the one-pass backward) and in the tiled "
@@ -908,6 +971,8 @@ def main(argv=None, hooks=None):
     if args.pipeline_chunks <= 0:
         args.pipeline_chunks = adist.auto_chunks(args.n_per_gpu)
     primary, other = resolve_modes(args, world)
+    if not args.full:
+        other = None                                                  # a plain run times the headline partition only
 
     # Region order.  N > 1 with both partitions: `rows` first whatever the primary is -- the north-star partition, on the
     # plainest collectives (one all-gather, one reduce-scatter) -- so that a scaling record exists before any all-to-all runs.
@@ -916,7 +981,7 @@ def main(argv=None, hooks=None):
         order = ["rows"] + [m for m in order if m != "rows"]
     # N = 2 x C >= 4: the hybrid partition (2 target groups x C column groups, 128-byte gather rows at d = 128, C = 4) right after
     # `rows` -- its own `partitions` entry; `value` only under --shard auto (the fastest exact execution) or --shard hybrid
-    hyb = hybrid_mode(args, world) if (args.partitions == "both" or args.shard == "hybrid") else None
+    hyb = hybrid_mode(args, world) if ((args.partitions == "both" and args.full) or args.shard == "hybrid") else None
     if args.shard == "hybrid":
         if hyb is None:
             raise SystemExit(f"--shard hybrid: no hybrid partition for {world} ranks at d = {args.d}")
@@ -927,13 +992,13 @@ def main(argv=None, hooks=None):
     elif hyb is not None:
         order = (order[:1] + [hyb] + order[1:]) if order[0] == "rows" else (order + [hyb])
     wire_key = primary + "+bf16wire"
-    want_wire = world > 1 and args.dtype == "f32" and args.wire_entry and args.pipeline_chunks <= 1
+    want_wire = args.full and world > 1 and args.dtype == "f32" and args.wire_entry and args.pipeline_chunks <= 1
     # N > 1: the column partition once more with the chunked, overlapped exchange (off by default: it has never run over xGMI;
     # its own `partitions` entry so that the first multi-GPU lease measures what the overlap is worth -- never `value`)
     kc = adist.auto_chunks(args.n_per_gpu) if args.chunk_entry < 0 else args.chunk_entry
     chunk_key = f"columns+chunks{kc}"
-    want_chunks = world > 1 and "columns" in order and args.pipeline_chunks <= 1 and kc > 1
-    want_preflight = dist.is_initialized() and (args.preflight == "on" or (args.preflight == "auto" and world > 1))
+    want_chunks = args.full and world > 1 and "columns" in order and args.pipeline_chunks <= 1 and kc > 1
+    want_preflight = dist.is_initialized() and (args.preflight == "on" or (args.preflight == "auto" and world > 1 and args.full))
     state = {"results": {}, "errors": {}, "order": order + ([chunk_key] if want_chunks else []) + ([wire_key] if want_wire else []),
              "preflight": None, "cpu_baseline": None}
     exit_fn = hooks.get("exit", os._exit)
@@ -1006,14 +1071,15 @@ def main(argv=None, hooks=None):
 
     # N = 1, fp32: the same K steps once more in the STRICT arithmetic (the exact-split bf16x6 kernels everywhere) -- both numbers in
     # one run, the default's as `value`
-    if (world == 1 and not cpu_mode and args.dtype == "f32" and args.strict_entry and args.arith == "auto" and not args.hip_graph):
+    if (args.full and world == 1 and not cpu_mode and args.dtype == "f32" and args.strict_entry and args.arith == "auto"
+            and not args.hip_graph):
         from allset_amd import dense as _dense
         prev_arith = _dense.set_arithmetic("strict")
         try:
             torch.cuda.empty_cache()
             sres = region("strict", lambda: run_partition(args, primary, world, rank, dev, hooks))
             if sres is not None:
-                sres.pop("edge_index_cpu", None); sres.pop("x_cpu", None)
+                sres.pop("edge_index_cpu", None); sres.pop("x_cpu", None); sres.pop("outputs", None)
                 state["strict"] = sres
         finally:
             _dense.set_arithmetic(prev_arith)
@@ -1021,7 +1087,9 @@ def main(argv=None, hooks=None):
     line = None
     if rank == 0:
         res = state["results"].get(primary) or next(iter(state["results"].values()))
-        if world == 1 and not args.no_cpu_baseline and args.model != "pma" and not cpu_mode:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res["outputs"])
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model != "pma" and not cpu_mode:
             state["cpu_baseline"] = cpu_baseline(args, args.d, args.degree, res.get("edge_index_cpu"), res.get("x_cpu"))
         line = assemble_line(args, world, primary, state, cpu_mode)
         print(json.dumps(line), flush=True)

@@ -6,6 +6,7 @@ import os
 import socket
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.multiprocessing as mp
@@ -90,7 +91,7 @@ def _tuple_incidences(hg, mode):
         hg.halo_e2v = (torch.stack([hloc[1], hloc[0]]), hg.halo.n_needed)
 
 
-def _bench_worker(rank, world, port, model, q, extra=()):
+def _bench_worker(rank, world, port, model, q, extra=("--full",)):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import bench
@@ -145,6 +146,68 @@ def test_bench_two_ranks_runs_both_partitions_and_reports_one_line(model):
     assert all(v["ms"] > 0 and v["gbps_per_link"] > 0 for v in pf.values())
 
 
+def _two_rank_run(extra):
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_bench_worker, args=(r, world, port, "deepsets", q, extra)) for r in range(world)]
+    for p in procs:
+        p.start()
+    results = sorted([q.get(timeout=300) for _ in range(world)], key=lambda t: t[0])
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    return results[0][1]
+
+
+def test_bench_plain_run_times_the_headline_partition_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the run times the `rows` partition alone (no other partition, chunked or bf16-wire region, no preflight, no
+    CPU baseline); --dump-outputs writes the last timed step's output, input gradient, parameter gradients and updated parameters
+    as float32 .npy files, and the same arguments give the same arrays in a second run."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        line = _two_rank_run(("--dump-outputs", str(d)))
+        parts = line["partitions"]
+        assert [k for k in parts if k not in ("note", "value_note", "fastest_exact")] == ["rows"] and parts["rows"]["is_value"]
+        assert "preflight" not in line and "strict" not in line and line["cpu_baseline"] is None
+        assert line["steps"] == 2 and line["ms_per_step"] == parts["rows"]["ms_per_step"] > 0
+        files = sorted(os.listdir(d))
+        assert "out.npy" in files and "x_grad.npy" in files
+        assert any(f.startswith("grad.v2e.") for f in files) and any(f.startswith("param.e2v.") for f in files)
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert arrays["out.npy"].shape == (120, 32) and arrays["x_grad.npy"].shape == (120, 32)   # rank 0's owned rows, all of them
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][f], dumps[1][f], err_msg=f)
+
+
+def test_bench_dump_samples_rows_and_parameters_within_the_budget(monkeypatch):
+    """step_outputs: row-wise arrays larger than DUMP_ROW_BYTES are a fixed seeded row sample (same rows in both), and parameters are
+    capped to a seeded sample of their entries when the whole set would exceed DUMP_BYTES."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_ROW_BYTES", 100 * 8 * 4)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 100 * 8 * 4 + 4 * 600)
+    args = bench.parse_args(["--seed", "3"])
+    out, gx = torch.arange(1000 * 8.0).view(1000, 8), -torch.arange(1000 * 8.0).view(1000, 8)
+    lin = torch.nn.Linear(8, 40)
+    lin(torch.ones(2, 8)).sum().backward()
+    a = bench.step_outputs(args, out, gx, {"m": lin})
+    assert a["out"].shape == (100, 8) and np.array_equal(a["out"], -a["x_grad"])
+    assert sorted(a) == ["grad.m.bias", "grad.m.weight", "out", "param.m.bias", "param.m.weight", "x_grad"]
+    assert a["param.m.bias"].size == 40 and a["grad.m.bias"].size == 40                   # under the cap: whole
+    assert a["param.m.weight"].size == a["grad.m.weight"].size == (600 - 80) // 2             # over it: a sample
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BYTES
+    b = bench.step_outputs(args, out, gx, {"m": lin})
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def _hang_worker(rank, world, port, label, q):
     """bench.main with rank 1 parked at the start of region ``label``: rank 0 blocks in that region's first collective; the watchdog
     must print the line assembled from the regions that DID finish and end the process (here: hand it to the test, then exit)."""
@@ -164,7 +227,7 @@ def _hang_worker(rank, world, port, label, q):
         os._exit(0)
     hooks = {"device": "cpu", "aggregate": _oracle_aggregate, "kernels": TorchPmaKernels, "incidences": _tuple_incidences, "exit": exit_fn}
     argv = ["--gpus", str(world), "--n-per-gpu", "120", "--degree", "4", "--feature-dim", "32", "--steps", "2", "--warmup", "1",
-            "--dropout", "0.0", "--region-timeout", "8", "--shard", "auto"]      # (auto: `value` would have been the fastest partition)
+            "--dropout", "0.0", "--region-timeout", "8", "--shard", "auto", "--full"]      # (auto: `value` would have been the fastest partition)
     real_stdout = sys.stdout
     sys.stdout = buf                                   # (the watchdog thread prints through sys.stdout too)
     try:
@@ -208,7 +271,7 @@ def test_bench_two_ranks_locality_variant_uses_the_boundary_vertex_exchange():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_bench_worker, args=(r, world, port, "deepsets", q, ("--locality", "0.9"))) for r in range(world)]
+    procs = [ctx.Process(target=_bench_worker, args=(r, world, port, "deepsets", q, ("--locality", "0.9", "--full"))) for r in range(world)]
     for p in procs:
         p.start()
     results = sorted([q.get(timeout=300) for _ in range(world)], key=lambda t: t[0])

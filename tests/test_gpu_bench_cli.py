@@ -33,7 +33,7 @@ def test_bench_under_torchrun_one_rank_rccl_group(shard, model):
     env = dict(os.environ, ALLSET_FORCE_COLLECTIVES="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--n-per-gpu", "20000", "--shard", shard, "--model", model, "--pipeline-chunks", "2"]
+           "--n-per-gpu", "20000", "--shard", shard, "--model", model, "--pipeline-chunks", "2", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     line = _json_line(res.stdout)
@@ -52,7 +52,7 @@ def test_bench_under_torchrun_one_rank_rccl_group(shard, model):
 
 def test_bench_default_line_small(tmp_path):
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--n-per-gpu", "30000",
-                          "--cpu-threads", "8"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--cpu-threads", "8", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     line = _json_line(res.stdout)
     assert line["config"]["parallelism"] == "single GPU" and "partitions" not in line
@@ -70,3 +70,29 @@ def test_bench_default_line_small(tmp_path):
     assert dt["strict_ms_per_step"] == strict["dense_tail_ms_per_step"] > 0 and strict["ms_per_step"] > 0
     assert any(k.startswith("fused_linear") for k in strict["kernels"])
     assert line["config"]["workload"].startswith("variant of BASELINE configs[2] (30000 rows per GPU)")
+
+
+@pytest.mark.parametrize("launch", ["eager", "graph"])
+def test_bench_plain_line_and_dumped_outputs(launch, tmp_path):
+    """A plain run (no --full): the headline line only -- no strict region, no CPU baseline -- with exactly --steps timed steps, and
+    --dump-outputs writes the last timed step's arrays as float32 (the layer output and input gradient as the same seeded row
+    sample, parameter gradients and updated parameters), also when the step is one hipGraph replay."""
+    import numpy as np
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--n-per-gpu", "30000",
+           "--dump-outputs", str(out)] + (["--hip-graph"] if launch == "graph" else [])
+    res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+    line = _json_line(res.stdout)
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+    assert line["unit"] == "edges*d/s" and line["higher_is_better"] is True and line["metric"].startswith("edges*d aggregated")
+    assert abs(line["value"] - line["config"]["nnz"] * 128 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert "strict" not in line and line["cpu_baseline"] is None and "partitions" not in line
+    arrays = {f: np.load(out / f) for f in os.listdir(out)}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["out.npy"].shape == arrays["x_grad.npy"].shape == (16384, 128)
+    assert float(np.abs(arrays["x_grad.npy"]).max()) > 0 and float(np.abs(arrays["out.npy"]).max()) > 0
+    grads = [f for f in arrays if f.startswith("grad.")]
+    assert len(grads) == len([f for f in arrays if f.startswith("param.")]) > 0
+    assert all(float(np.abs(arrays[f]).max()) > 0 for f in grads if f.endswith(".weight"))
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20

@@ -379,7 +379,7 @@ def test_bench_two_ranks_one_gpu_gloo():
         env = dict(os.environ, ALLSET_DIST_BACKEND="gloo")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-               "--n-per-gpu", "20000", "--model", model, "--pipeline-chunks", str(chunks)]
+               "--n-per-gpu", "20000", "--model", model, "--pipeline-chunks", str(chunks), "--full"]
         res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
         assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
         lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -402,7 +402,7 @@ def test_bench_bare_command_spawns_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["ALLSET_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n-per-gpu", "20000", "--d", "128",
-           "--chunk-entry", "2"]
+           "--chunk-entry", "2", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -432,7 +432,7 @@ def test_bench_hung_second_region_keeps_the_first_regions_line():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ALLSET_DIST_BACKEND="gloo", ALLSET_BENCH_TEST_HANG="columns:1")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n-per-gpu", "20000",
-           "--region-timeout", "8", "--preflight", "off"]       # (first region: 3 x 8 s)
+           "--region-timeout", "8", "--preflight", "off", "--full"]       # (first region: 3 x 8 s)
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -455,7 +455,7 @@ def test_bench_eight_ranks_one_gpu_gloo(model):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["ALLSET_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--n-per-gpu", "8000",
-           "--model", model, "--chunk-entry", "2", "--region-timeout", "300"]
+           "--model", model, "--chunk-entry", "2", "--region-timeout", "300", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -484,7 +484,7 @@ def test_bench_two_ranks_locality_variant_with_halo_exchange():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["ALLSET_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n-per-gpu", "20000",
-           "--locality", "0.9", "--chunk-entry", "0", "--no-wire-entry"]
+           "--locality", "0.9", "--chunk-entry", "0", "--no-wire-entry", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])

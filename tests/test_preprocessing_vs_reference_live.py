@@ -1,68 +1,51 @@
-"""CPU, build container only (skipped where /root/reference is absent): allset_amd.preprocessing against the LIVE
-reference functions (reference preprocessing.py:394-469, 22-144, imported through oracle/ref_shim.py) on randomised
-block edge lists -- sizes, duplicate-free incidences, size-1 hyperedges, vertices without hyperedges.  Index work:
-bit-exact, compared as lexicographically sorted edge lists (the reference's own sorts are unstable)."""
+"""CPU: allset_amd.preprocessing against the reference functions (reference preprocessing.py:394-469, 22-144) on randomised
+block edge lists -- sizes, duplicate-free incidences, size-1 hyperedges, vertices without hyperedges.  Index work: bit-exact,
+compared as lexicographically sorted edge lists (the reference's own sorts are unstable).  The reference's results are the ones
+oracle/gen_live_fixtures.py recorded in tests/golden/live_preprocessing.npz (the edge lists are rebuilt from their seeds); where the
+reference itself is importable (oracle/ref_shim.py) every configuration is run through it LIVE as well."""
 import os
 from types import SimpleNamespace
 
 import numpy as np
-import pytest
 import torch
-from hypothesis import given, settings, strategies as st
 
+import util
+from oracle import gen_live_fixtures as live
 from oracle import ref_shim
 
-pytestmark = pytest.mark.skipif(not ref_shim.available(), reason="/root/reference not present (GPU box)")
+canon = live.canon
 
 
-def canon(ei) -> np.ndarray:
-    a = ei.cpu().numpy() if torch.is_tensor(ei) else np.asarray(ei)
-    return a[:, np.lexsort((a[1], a[0]))]
-
-
-@settings(deadline=None, max_examples=int(os.environ.get("ALLSET_HYPOTHESIS_EXAMPLES", "40")),
-          derandomize=os.environ.get("ALLSET_HYPOTHESIS_RANDOM", "0") != "1")
-@given(n_v=st.integers(3, 60), n_e=st.integers(1, 30), extra=st.integers(0, 150), singles=st.integers(0, 8), sd=st.integers(0, 10 ** 6))
-def test_preprocessing_equals_live_reference(n_v, n_e, extra, singles, sd):
+def test_preprocessing_equals_live_reference():
     from allset_amd import preprocessing as P
-    ref_pre = ref_shim.import_reference_preprocessing()
-    rng = np.random.default_rng(sd)
-    # every hyperedge gets a member; `singles` of them stay size-1, each owned by a distinct vertex (the reference's
-    # Add_Self_Loops indexes out of bounds otherwise, preprocessing.py:428-440); the last vertex id is present
-    singles = min(singles, n_e, n_v - 1)
-    owners = rng.permutation(n_v - 1)[:singles]
-    pairs = {(int(owners[e]), e) for e in range(singles)}
-    for e in range(singles, n_e):                      # every other hyperedge has at least two distinct members
-        a = int(rng.integers(n_v))
-        pairs.add((a, e))
-        pairs.add(((a + 1 + int(rng.integers(n_v - 1))) % n_v, e))
-    if singles < n_e:
-        pairs.add((n_v - 1, n_e - 1))
-    for _ in range(extra):
-        if singles < n_e:
-            pairs.add((int(rng.integers(n_v)), int(rng.integers(singles, n_e))))
-    pairs = sorted(pairs)
-    v = np.array([p[0] for p in pairs], dtype=np.int64)
-    e = np.array([p[1] for p in pairs], dtype=np.int64) + n_v
-    block = np.concatenate([np.stack([v, e]), np.stack([e, v])], axis=1)
-    block = block[:, rng.permutation(block.shape[1])]
+    configs = live.preproc_configs()
+    with np.load(os.path.join(util.GOLDEN, "live_preprocessing.npz"), allow_pickle=False) as z:
+        rec = {k: z[k] for k in z.files}
+    assert len(configs) == live.N_PREPROC and f"c{len(configs) - 1}/sl" in rec
+    for i, c in enumerate(configs):
+        refs = [("recorded", {k.split("/", 1)[1]: v for k, v in rec.items() if k.startswith(f"c{i}/")})]
+        if ref_shim.available():
+            refs.append(("live", live.reference_preprocessing(c)))
+        block, n_v, n_e = live.preproc_block(c), c["n_v"], c["n_e"]
 
-    def fresh():
-        return SimpleNamespace(edge_index=torch.from_numpy(block).clone(), n_x=[n_v], num_hyperedges=[n_e])
-    r, p = ref_pre.ExtractV2E(fresh()), P.ExtractV2E(fresh())
-    np.testing.assert_array_equal(canon(p.edge_index), canon(r.edge_index))
-    r, p = ref_pre.Add_Self_Loops(r), P.Add_Self_Loops(p)
-    np.testing.assert_array_equal(canon(p.edge_index), canon(r.edge_index))
-    assert int(p.totedges) == int(r.totedges)
-    sl = canon(r.edge_index)
-    for opt in ("all_one", "deg_half_sym"):
-        rn = ref_pre.norm_contruction(SimpleNamespace(edge_index=torch.from_numpy(sl).clone()), option=opt)
-        pn = P.norm_contruction(SimpleNamespace(edge_index=torch.from_numpy(sl).clone()), option=opt)
-        assert pn.norm.dtype == rn.norm.dtype
-        np.testing.assert_allclose(pn.norm.numpy(), rn.norm.numpy(), rtol=1e-6, atol=1e-7)
-    for th in (0, 3):
-        def de():
-            return SimpleNamespace(edge_index=torch.from_numpy(sl).clone(), n_x=torch.tensor([n_v]), num_hyperedges=[n_e],
-                                   totedges=int(r.totedges))
-        re_, pe = ref_pre.expand_edge_index(de(), edge_th=th), P.expand_edge_index(de(), edge_th=th)
-        np.testing.assert_array_equal(canon(pe.edge_index), canon(re_.edge_index))
+        def fresh():
+            return SimpleNamespace(edge_index=torch.from_numpy(block).clone(), n_x=[n_v], num_hyperedges=[n_e])
+        p = P.ExtractV2E(fresh())
+        got = {"v2e": canon(p.edge_index)}
+        p = P.Add_Self_Loops(p)
+        got.update(sl=canon(p.edge_index), totedges=int(p.totedges))
+        for label, r in refs:
+            what = f"{label} c{i} {c}"
+            np.testing.assert_array_equal(got["v2e"], r["v2e"], err_msg=what)
+            np.testing.assert_array_equal(got["sl"], r["sl"], err_msg=what)
+            assert got["totedges"] == int(r["totedges"]), what
+            sl = r["sl"]
+            for opt in ("all_one", "deg_half_sym"):
+                pn = P.norm_contruction(SimpleNamespace(edge_index=torch.from_numpy(sl).clone()), option=opt)
+                rn = r["norm_" + opt]
+                assert pn.norm.numpy().dtype == rn.dtype, (what, opt)
+                np.testing.assert_allclose(pn.norm.numpy(), rn, rtol=1e-6, atol=1e-7, err_msg=what)
+            for th in (0, 3):
+                de = SimpleNamespace(edge_index=torch.from_numpy(sl).clone(), n_x=torch.tensor([n_v]), num_hyperedges=[n_e],
+                                     totedges=int(r["totedges"]))
+                np.testing.assert_array_equal(canon(P.expand_edge_index(de, edge_th=th).edge_index), r[f"expand_{th}"], err_msg=what)

@@ -204,3 +204,21 @@ def assert_matches_golden(res: dict, g: Dict[str, np.ndarray], big: bool, rtol: 
                 tol = (rtol * 10) * float(g["gabs_" + name]) + 1e-6
                 assert abs(float(got.double().sum()) - float(g["gsum_" + name])) <= tol, name
                 assert abs(float(got.double().abs().sum()) - float(g["gabs_" + name])) <= tol, name
+
+
+def assert_matches_entry(got: torch.Tensor, e: dict, what: str, rtol: float, atol: float) -> None:
+    """``got`` against a reference result recorded by oracle/gen_live_fixtures.py (``load_table`` / ``entry`` form): a whole tensor
+    elementwise; a sampled one elementwise at its sampled entries, and over the whole tensor through its sum and absolute sum
+    within the bound the elementwise tolerance implies (rtol * abs-sum + atol * size)."""
+    assert e["kind"] in ("full", "sample"), (what, e["kind"])
+    assert tuple(got.shape) == tuple(e["shape"]), (what, tuple(got.shape), e["shape"])
+    exp = torch.from_numpy(np.asarray(e["value"]))
+    if e["kind"] == "full":
+        torch.testing.assert_close(got, exp.to(got.dtype).reshape(got.shape), rtol=rtol, atol=atol, msg=lambda m: f"{what}: {m}")
+        return
+    flat = got.detach().reshape(-1)
+    torch.testing.assert_close(flat[torch.from_numpy(e["idx"])], exp.to(got.dtype), rtol=rtol, atol=atol,
+                               msg=lambda m: f"{what} (sampled entries): {m}")
+    bound = rtol * e["abs"] + atol * e["size"]
+    assert abs(float(flat.double().sum()) - e["sum"]) <= bound, (what, "sum", float(flat.double().sum()), e["sum"], bound)
+    assert abs(float(flat.double().abs().sum()) - e["abs"]) <= bound, (what, "abs-sum", float(flat.double().abs().sum()), e["abs"], bound)

@@ -9,11 +9,11 @@ ALLSET_ABI_TRACE=$OUT/abi_trace.json timeout 1500 rocprofv3 --kernel-trace --sta
 find $OUT/audit -name '*kernel_trace.csv' -delete; find $OUT/audit -name '*agent_info.csv' -delete; find $OUT/audit -name '*domain_stats.csv' -delete
 python tools/kernel_audit.py report $OUT/abi_trace.json $OUT/audit > $OUT/${TAG}_kernel_audit.md 2>&1; grep -n "never launched\.$" $OUT/${TAG}_kernel_audit.md
 rm -rf $OUT/audit $OUT/abi_trace.json
-timeout 900 python bench.py > $OUT/${TAG}_bench_line.json 2>$OUT/${TAG}_bench.err; tail -2 $OUT/${TAG}_bench.err
+timeout 900 python bench.py --full > $OUT/${TAG}_bench_line.json 2>$OUT/${TAG}_bench.err; tail -2 $OUT/${TAG}_bench.err
 python tools/bench_summary.py $OUT/${TAG}_bench_line.json
 rm -rf $OUT/prof
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_traced_bench_line.json 2>/dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_traced_bench_line.json 2>/dev/null
 S=$(find $OUT/prof -name '*kernel_stats.csv' | head -1); cp "$S" $OUT/${TAG}_bench_kernel_stats.csv; head -4 $OUT/${TAG}_bench_kernel_stats.csv | cut -c1-150
 rm -rf $OUT/prof
 timeout 300 python tools/tuned_config_step.py > $OUT/${TAG}_tuned_config_step.txt 2>&1; grep "non-zeros" $OUT/${TAG}_tuned_config_step.txt
-timeout 600 python bench.py --model pma --no-cpu-baseline --partitions primary > $OUT/${TAG}_pma_bench_line.json 2>/dev/null; python tools/bench_summary.py $OUT/${TAG}_pma_bench_line.json | head -3
+timeout 600 python bench.py --full --model pma --no-cpu-baseline --partitions primary > $OUT/${TAG}_pma_bench_line.json 2>/dev/null; python tools/bench_summary.py $OUT/${TAG}_pma_bench_line.json | head -3

@@ -19,10 +19,10 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python tools/traffic_json.py c3 $OUT/pmc_${TAG}_FETCH_SIZE $OUT/pmc_${TAG}_WRITE_SIZE
 mkdir -p $OUT/profiles_new && cp profiles/hbm_traffic.json profiles/hbm_traffic_pma.json $OUT/profiles_new/
-timeout 900 python bench.py > $OUT/${TAG}_bench_line.json 2>$OUT/${TAG}_bench.err; tail -2 $OUT/${TAG}_bench.err
+timeout 900 python bench.py --full > $OUT/${TAG}_bench_line.json 2>$OUT/${TAG}_bench.err; tail -2 $OUT/${TAG}_bench.err
 python tools/bench_summary.py $OUT/${TAG}_bench_line.json
 rm -rf $OUT/prof_${TAG}
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG} -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_traced_bench_line.json 2>/dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG} -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_traced_bench_line.json 2>/dev/null
 S=$(find $OUT/prof_${TAG} -name '*kernel_stats.csv' | head -1); cp "$S" $OUT/${TAG}_bench_kernel_stats.csv; head -7 $OUT/${TAG}_bench_kernel_stats.csv | cut -c1-150
 find $OUT/prof_${TAG} -name '*kernel_trace.csv' -delete
 for c in FETCH_SIZE WRITE_SIZE "SQ_INSTS_VALU SQ_INSTS_MFMA" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
@@ -34,16 +34,16 @@ python tools/pmc_sum.py fused_linear_bwd_f16x3 $OUT/pmc_${TAG}f_* > $OUT/${TAG}_
 python tools/pmc_sum.py fused_linear_fwd_roles $OUT/pmc_${TAG}f_* >> $OUT/${TAG}_pmc_dense.txt
 cat $OUT/${TAG}_pmc_dense.txt | head -30
 find $OUT/pmc_${TAG}* -name '*kernel_trace.csv' -delete
-timeout 600 python bench.py --model pma --no-cpu-baseline --partitions primary > $OUT/${TAG}_pma_bench_line.json 2>/dev/null
-timeout 600 python bench.py --norm bn --no-cpu-baseline > $OUT/${TAG}_bn_bench_line.json 2>/dev/null
-timeout 600 python bench.py --degree-dist poisson --no-cpu-baseline > $OUT/${TAG}_poisson_bench_line.json 2>/dev/null
-timeout 600 python bench.py --dropout 0 --no-cpu-baseline > $OUT/${TAG}_bench_line_dropout0.json 2>/dev/null
+timeout 600 python bench.py --full --model pma --no-cpu-baseline --partitions primary > $OUT/${TAG}_pma_bench_line.json 2>/dev/null
+timeout 600 python bench.py --full --norm bn --no-cpu-baseline > $OUT/${TAG}_bn_bench_line.json 2>/dev/null
+timeout 600 python bench.py --full --degree-dist poisson --no-cpu-baseline > $OUT/${TAG}_poisson_bench_line.json 2>/dev/null
+timeout 600 python bench.py --full --dropout 0 --no-cpu-baseline > $OUT/${TAG}_bench_line_dropout0.json 2>/dev/null
 python tools/bench_summary.py $OUT/${TAG}_pma_bench_line.json $OUT/${TAG}_poisson_bench_line.json $OUT/${TAG}_bench_line_dropout0.json | grep json
-timeout 600 python bench.py --d 256 --no-cpu-baseline > $OUT/${TAG}_d256_bench_line.json 2>/dev/null
+timeout 600 python bench.py --full --d 256 --no-cpu-baseline > $OUT/${TAG}_d256_bench_line.json 2>/dev/null
 timeout 600 python bench.py --dtype bf16 --d 256 --model pma --degree-dist zipf --n-per-gpu 250000 --no-cpu-baseline --partitions primary > $OUT/${TAG}_c5_shape_bench_line.json 2>/dev/null
 timeout 600 python bench.py --dtype bf16 --d 256 --model pma --degree-dist zipf --n-per-gpu 250000 --no-cpu-baseline --partitions primary --hip-graph > $OUT/${TAG}_c5_shape_graph_bench_line.json 2>/dev/null
 python tools/bench_summary.py $OUT/${TAG}_d256_bench_line.json $OUT/${TAG}_c5_shape_bench_line.json $OUT/${TAG}_c5_shape_graph_bench_line.json | grep -v "^    "
-timeout 600 python bench.py --d 512 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_d512_bench_line.json 2>/dev/null
+timeout 600 python bench.py --full --d 512 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_d512_bench_line.json 2>/dev/null
 # configs[4] per-GPU shape: the rocprofv3 summary of the same command, the gather kernels' HBM-traffic passes (stamped), the bf16 Linear's ablation arms
 rm -rf $OUT/prof_${TAG}_c5
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_c5 -- python bench.py --dtype bf16 --d 256 --model pma --degree-dist zipf --n-per-gpu 250000 --steps 20 --warmup 5 --no-cpu-baseline --partitions primary > $OUT/${TAG}_c5_traced_bench_line.json 2>/dev/null
