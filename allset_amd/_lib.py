@@ -22,6 +22,7 @@ SUM, MEAN, MAX, MIN = 0, 1, 2, 3
 F32, BF16 = 0, 1
 REDUCE_AS_TREE = 0x100
 ARITH_AUTO, ARITH_BF16X6, ARITH_FP16X3 = 0, 1, 2          # include/allset_hip_ext.h ALLSET_ARITH_*
+ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2                       # include/allset_hip_ext.h ALLSET_HCONV_ACT_*
 REDUCE_CODES = {"add": SUM, "sum": SUM, "mean": MEAN, "max": MAX, "min": MIN}
 
 # name -> argtypes, in the order of include/allset_hip.h.  Every function returns int except
@@ -212,6 +213,13 @@ SIGNATURES = {
                               c_int64, _P],
     "allset_ln_res_bwd": [_P, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, _P, c_int, c_float, c_uint64, _P, c_int64, _P,
                           c_int64, c_int64, c_int64, _P, _P],
+    # hypergraph-convolution baselines (under ABI 15, additions only; detect with allset_hconv_supported)
+    "allset_hconv_supported": [],
+    "allset_hconv_fwd": [c_int, c_int64, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_float, c_uint64, _P, _P, c_int64, c_int64, c_int64,
+                         c_int64, _P],
+    "allset_hconv_bwd_epi_slices": [c_int64, POINTER(c_int64)],
+    "allset_hconv_bwd_epi": [_P, c_int64, _P, c_int64, c_int, c_float, c_uint64, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64,
+                             _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

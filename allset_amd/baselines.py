@@ -1,0 +1,188 @@
+"""The hypergraph-convolution baselines of the reference behind its own module surface: ``HypergraphConv`` / ``HCHA`` (HGNN is
+HCHA with ``symdegnorm``) and ``HNHNConv`` / ``HNHN`` (reference layers.py:233-494, models.py:207-292).
+
+Each conv is a Linear and two degree-scaled segment sums over the V-E incidence, V->E then E->V.  Both hops are one HIP kernel
+each (``functional.scaled_propagate``, csrc/hconv.hip) with the per-row scales, the bias, the activation and the dropout that
+follow them in the reference fused into the E->V launch (HNHN's ``relu`` in between into the V->E launch).  The scales are
+computed once from the edge list (``preprocessing.generate_norm_HCHA`` / ``generate_norm_HNHN``) and live on the ``data`` object,
+as the reference keeps HNHN's.  Device fp32 only: like the AllSet layers there is no CPU path for the propagate.
+"""
+from __future__ import annotations
+
+from types import SimpleNamespace
+from typing import Optional
+
+import torch
+import torch.nn as nn
+from torch.nn import Parameter
+
+from . import dense
+from ._lib import AllSetHipError
+from .functional import scaled_propagate
+from .incidence import Incidence, cached_incidence
+from .layers import _linear, glorot, zeros
+from .preprocessing import generate_norm_HCHA
+
+Tensor = torch.Tensor
+
+
+def _incidence(x: Tensor, edge_index) -> Incidence:
+    if isinstance(edge_index, Incidence):
+        return edge_index
+    if not (x.is_cuda and x.dtype == torch.float32):
+        raise AllSetHipError("the hypergraph-convolution baselines run on ROCm device fp32 tensors (no CPU path)")
+    return cached_incidence(edge_index, n_src=x.shape[0])     # hyperedges: max(id) + 1 rows (reference layers.py:422-423)
+
+
+def _hcha_scales(data, x: Tensor, symdegnorm: bool):
+    """``(D, B)`` of ``data`` for this normalisation; computed once and attached to ``data`` when it has none (or the other kind)."""
+    if getattr(data, 'HCHA_D', None) is None or getattr(data, 'HCHA_symdegnorm', None) != bool(symdegnorm) \
+            or data.HCHA_D.shape[0] != x.shape[0] or data.HCHA_D.device != x.device:
+        generate_norm_HCHA(data, symdegnorm)
+    return data.HCHA_D, data.HCHA_B
+
+
+class HypergraphConv(nn.Module):
+    """``X' = D^-1 H B^-1 H^T X Theta + bias`` (``symdegnorm``: ``D^-1/2 H B^-1 H^T D^-1/2 X Theta + bias``), reference
+    layers.py:318-494 without attention.  ``weight`` is [in, out] (not nn.Linear's layout) and glorot-initialised, ``bias`` zeros."""
+
+    def __init__(self, in_channels, out_channels, symdegnorm=False, use_attention=False, heads=1,
+                 concat=True, negative_slope=0.2, dropout=0, bias=True, **kwargs):
+        super().__init__()
+        if use_attention:
+            raise NotImplementedError("HypergraphConv(use_attention=True) is not built (the reference's models never construct it)")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.use_attention = False
+        self.symdegnorm = symdegnorm
+        self.heads = 1
+        self.concat = True
+        self.weight = Parameter(torch.empty(in_channels, out_channels))
+        if bias and concat:
+            self.bias = Parameter(torch.empty(heads * out_channels))
+        elif bias and not concat:
+            self.bias = Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter('bias', None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot(self.weight)
+        zeros(self.bias)
+
+    def forward(self, x: Tensor, hyperedge_index, hyperedge_weight: Optional[Tensor] = None, *, scales=None,
+                act: Optional[str] = None, p: float = 0.0) -> Tensor:
+        """``scales`` = ``(D, B)`` from ``preprocessing.generate_norm_HCHA`` (derived from ``hyperedge_index`` when None);
+        ``act`` / ``p``: the activation and dropout the model applies next, fused into the E->V launch."""
+        if hyperedge_weight is not None:
+            raise NotImplementedError("HypergraphConv: hyperedge weights other than ones are not built (the reference never passes any)")
+        inc = _incidence(x, hyperedge_index)
+        if scales is None:
+            if isinstance(hyperedge_index, Incidence):
+                raise ValueError("HypergraphConv: pass scales=(D, B) together with a prebuilt Incidence")
+            scales = _hcha_scales(SimpleNamespace(x=x, edge_index=hyperedge_index), x, self.symdegnorm)
+        D, B = scales
+        xw = dense.linear(x, self.weight.t(), None)          # x Theta: the [in, out] weight read transposed by the GEMM, no copy
+        if self.symdegnorm:
+            h = scaled_propagate(xw, inc, 'v2e', r=D, s=B)
+        else:
+            h = scaled_propagate(xw, inc, 'v2e', s=B)
+        return scaled_propagate(h, inc, 'e2v', s=D, bias=self.bias, act=act, p=p)
+
+    def __repr__(self):
+        return "{}({}, {})".format(self.__class__.__name__, self.in_channels, self.out_channels)
+
+
+class HCHA(nn.Module):
+    """Reference models.py:252-292: ``[in -> hidden] + [hidden -> hidden] x (L - 2) + [hidden -> classes]`` (two convs at L = 1),
+    ``elu`` and dropout between convs (fused into each conv's E->V launch), nothing after the last."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.num_layers = args.All_num_layers
+        self.dropout = args.dropout
+        self.symdegnorm = args.HCHA_symdegnorm
+        self.convs = nn.ModuleList()
+        self.convs.append(HypergraphConv(args.num_features, args.MLP_hidden, self.symdegnorm))
+        for _ in range(self.num_layers - 2):
+            self.convs.append(HypergraphConv(args.MLP_hidden, args.MLP_hidden, self.symdegnorm))
+        self.convs.append(HypergraphConv(args.MLP_hidden, args.num_classes, self.symdegnorm))
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+
+    def forward(self, data):
+        x = data.x
+        inc = _incidence(x, data.edge_index)
+        scales = _hcha_scales(data, x, self.symdegnorm)
+        p = float(self.dropout) if self.training else 0.0
+        for conv in self.convs[:-1]:
+            x = conv(x, inc, scales=scales, act='elu', p=p)
+        return self.convs[-1](x, inc, scales=scales)
+
+
+class HNHNConv(nn.Module):
+    """Reference layers.py:233-316: ``x = D_v_beta * weight_v2e(x)``, ``h = D_e_beta_inv * sum_{v in e} x_v`` (``relu`` if
+    ``nonlinear_inbetween``), ``h = D_e_alpha * weight_e2v(h)``, ``out = D_v_alpha_inv * sum_{e ni v} h_e``.  The norms come from
+    ``data`` (``preprocessing.generate_norm_HNHN``)."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, heads=1, nonlinear_inbetween=True,
+                 concat=True, bias=True, **kwargs):
+        super().__init__()
+        self.in_channels = in_channels
+        self.hidden_channels = hidden_channels
+        self.out_channels = out_channels
+        self.nonlinear_inbetween = nonlinear_inbetween
+        self.heads = heads
+        self.concat = True
+        self.weight_v2e = nn.Linear(in_channels, hidden_channels)
+        self.weight_e2v = nn.Linear(hidden_channels, out_channels)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.weight_v2e.reset_parameters()
+        self.weight_e2v.reset_parameters()
+
+    def forward(self, x: Tensor, data, *, inc: Optional[Incidence] = None, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+        for name in ('D_v_beta', 'D_e_beta_inv', 'D_e_alpha', 'D_v_alpha_inv'):
+            if getattr(data, name, None) is None:
+                raise ValueError(f"HNHNConv: data.{name} is missing (preprocessing.generate_norm_HNHN computes the norms)")
+        inc = inc if inc is not None else _incidence(x, data.edge_index)
+        h = scaled_propagate(_linear(self.weight_v2e, x), inc, 'v2e', r=data.D_v_beta, s=data.D_e_beta_inv,
+                             act='relu' if self.nonlinear_inbetween else None)
+        return scaled_propagate(_linear(self.weight_e2v, h), inc, 'e2v', r=data.D_e_alpha, s=data.D_v_alpha_inv, act=act, p=p)
+
+    def __repr__(self):
+        return "{}({}, {}, {})".format(self.__class__.__name__, self.in_channels, self.hidden_channels, self.out_channels)
+
+
+class HNHN(nn.Module):
+    """Reference models.py:207-249: one conv at L = 1 (nothing after it); otherwise ``relu`` and dropout between convs (fused
+    into each conv's E->V launch)."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.num_layers = args.All_num_layers
+        self.dropout = args.dropout
+        nl = args.HNHN_nonlinear_inbetween
+        self.convs = nn.ModuleList()
+        if self.num_layers == 1:
+            self.convs.append(HNHNConv(args.num_features, args.MLP_hidden, args.num_classes, nonlinear_inbetween=nl))
+        else:
+            self.convs.append(HNHNConv(args.num_features, args.MLP_hidden, args.MLP_hidden, nonlinear_inbetween=nl))
+            for _ in range(self.num_layers - 2):
+                self.convs.append(HNHNConv(args.MLP_hidden, args.MLP_hidden, args.MLP_hidden, nonlinear_inbetween=nl))
+            self.convs.append(HNHNConv(args.MLP_hidden, args.MLP_hidden, args.num_classes, nonlinear_inbetween=nl))
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+
+    def forward(self, data):
+        x = data.x
+        inc = _incidence(x, data.edge_index)
+        p = float(self.dropout) if self.training else 0.0
+        for conv in self.convs[:-1]:
+            x = conv(x, data, inc=inc, act='relu', p=p)
+        return self.convs[-1](x, data, inc=inc)

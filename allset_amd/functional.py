@@ -359,3 +359,57 @@ def pma_attention_weights(alpha: Tensor, m: Tensor, l: Tensor, inc: Incidence, n
     p = torch.empty_like(p_csr)
     p[csr.perm.long()] = p_csr
     return p
+
+
+# ---- degree-scaled propagate of the hypergraph-convolution baselines (HCHA / HGNN / HNHN; csrc/hconv.hip) ----------------------
+class _ScaledPropagate(torch.autograd.Function):
+    """``y = drop_p(act(s * (H^T or H)(r * x) + bias))`` -- one kernel forward; backward: the epilogue's kernel (only when there is
+    an epilogue) and the same propagate kernel over the opposite CSR with ``r`` and ``s`` swapped.  ``r`` / ``s`` are constants."""
+
+    @staticmethod
+    def forward(ctx, x, bias, inc, to_dst, r, s, act, p):
+        from . import dense
+        fwd, bwd = (inc.by_dst, inc.by_src) if to_dst else (inc.by_src, inc.by_dst)
+        n_t, n_s = (inc.n_dst, inc.n_src) if to_dst else (inc.n_src, inc.n_dst)
+        if x.shape[0] != n_s:
+            raise _lib.AllSetHipError(f"scaled_propagate: x has {x.shape[0]} rows, the incidence gathers from {n_s}")
+        seed = dense._draw_seed() if p > 0.0 else 0
+        base = dense._seed_base() if p > 0.0 else None
+        y = ops.hconv_propagate(fwd, x, n_t, r, s, bias, act, p, seed, base)
+        epi = act is not None or p > 0.0 or bias is not None
+        ctx.save_for_backward(y if epi else None)
+        ctx.cfg = (bwd, n_s, r, s, act, p, seed, base, epi)
+        ctx.bias_param = bias
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        from . import dense
+        (y,) = ctx.saved_tensors
+        bwd, n_s, r, s, act, p, seed, base, epi = ctx.cfg
+        need_b = ctx.bias_param is not None and ctx.needs_input_grad[1]
+        gb = None
+        if epi:
+            g, part = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=need_b)
+            if need_b:
+                # (inside dense.deferred_param_grads(): queued for the step's one batched reduction, and None here)
+                (gb,) = dense._defer_or_reduce(part, [(ctx.bias_param, 0, (y.shape[1],))], defer=True)
+        else:
+            g = gy
+        gx = ops.hconv_propagate(bwd, g, n_s, r=s, s=r) if ctx.needs_input_grad[0] else None
+        return gx, gb, None, None, None, None, None, None
+
+
+def scaled_propagate(x: Tensor, inc: Incidence, direction: str, r: Optional[Tensor] = None, s: Optional[Tensor] = None,
+                     bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+    """One hop of a hypergraph convolution over ``inc`` (sources = vertices, targets = hyperedges):
+    ``direction`` 'v2e': ``y[e] = drop_p(act(s[e] * sum_{v in e} r[v] * x[v] + bias))``;
+    'e2v': ``y[v] = drop_p(act(s[v] * sum_{e ni v} r[e] * x[e] + bias))``.
+    ``r`` (per gathered row), ``s`` (per output row) and ``bias`` may be None; ``act`` None / 'relu' / 'elu'; ``p`` the dropout
+    probability (0 outside training).  Differentiable in ``x`` and ``bias``."""
+    if direction not in ("v2e", "e2v"):
+        raise ValueError(f"scaled_propagate: direction must be 'v2e' or 'e2v', got {direction!r}")
+    if act not in ops.HCONV_ACTS:
+        raise ValueError(f"scaled_propagate: act must be None, 'relu' or 'elu', got {act!r}")
+    return _ScaledPropagate.apply(x, bias, inc, direction == "v2e", r, s, act, float(p))

@@ -5,7 +5,7 @@ tensors; outputs are allocated with torch (plumbing) and filled by the HIP kerne
 from __future__ import annotations
 
 from collections import defaultdict
-from ctypes import byref, c_size_t
+from ctypes import byref, c_int64 as c_int64_t, c_size_t
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
@@ -494,3 +494,65 @@ def pma_merge_pack(out_loc: Tensor, m_loc: Tensor, l_loc: Tensor, m_glob: Tensor
                                                 ptr(m_glob.contiguous()), ptr(buf), ldp, n, heads, d // heads, stream_of(dev)),
               "allset_pma_merge_pack")
     return buf if ldp == width else buf[:, :width]
+
+
+# ---- degree-scaled propagate of the hypergraph-convolution baselines (csrc/hconv.hip) -----------------------------------------
+HCONV_ACTS = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "relu": _lib.ACT_RELU, "elu": _lib.ACT_ELU}
+
+
+def hconv_propagate(csr: CSR, x: Tensor, n_t: int, r: Optional[Tensor] = None, s: Optional[Tensor] = None,
+                    bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0, seed: int = 0,
+                    seed_base: Optional[Tensor] = None) -> Tensor:
+    """``y[t] = drop_p(act(s[t] * sum_{j in row t} r[col_j] * x[col_j] + bias))`` over ``csr`` (rows = outputs, the first ``n_t``
+    rows of it).  ``r`` f32[n_s], ``s`` f32[n_t], ``bias`` f32[d]: each optional.  fp32 only."""
+    dev = require_device(csr.rowptr, x, r, s, bias)
+    _f32(x, "hconv_propagate")
+    for t, what in ((r, "r"), (s, "s"), (bias, "bias")):
+        if t is not None:
+            _f32(t, f"hconv_propagate {what}")
+    r = r.contiguous() if r is not None else None
+    s = s.contiguous() if s is not None else None
+    bias = bias.contiguous() if bias is not None else None
+    x = _rowmajor(x)
+    n_s, d = x.shape
+    if r is not None and r.numel() < n_s:
+        raise _lib.AllSetHipError(f"hconv_propagate: r has {r.numel()} entries for {n_s} gathered rows")
+    if s is not None and s.numel() < n_t:
+        raise _lib.AllSetHipError(f"hconv_propagate: s has {s.numel()} entries for {n_t} output rows")
+    if bias is not None and bias.numel() != d:
+        raise _lib.AllSetHipError(f"hconv_propagate: bias has {bias.numel()} entries for width {d}")
+    if n_t > csr.n_rows or csr.n_cols > n_s:
+        raise _lib.AllSetHipError(f"hconv_propagate: CSR of {csr.n_rows} x {csr.n_cols} against {n_t} outputs / {n_s} gathered rows")
+    y = torch.empty((n_t, d), dtype=torch.float32, device=dev)
+    nnz = csr.col.numel()
+    flat_ok = d % 4 == 0 and d <= 256 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+    variant = csr.variant("segreduce", n_t) if flat_ok else 1
+    order = csr.row_order if (variant == 1 and csr.row_order is not None and csr.row_order.numel() == n_t) else None
+    algo = nnz * (4 * d + 4 + (4 if r is not None else 0)) + (n_t + 1) * 4 + n_t * 4 * d
+    with on_device(dev), _timed("hconv_fwd", dev, algo):
+        check(_lib.load().allset_hconv_fwd(variant, nnz, ptr(order), ptr(csr.rowptr), ptr(csr.col), ptr(r), ptr(s), ptr(x), _ld(x),
+                                           ptr(bias), HCONV_ACTS[act], float(p), int(seed), ptr(seed_base), ptr(y), max(d, 1),
+                                           n_t, n_s, d, stream_of(dev)), "allset_hconv_fwd")
+    return y
+
+
+def hconv_bwd_epi(gy: Tensor, y: Tensor, act: Optional[str], p: float, seed: int, seed_base: Optional[Tensor],
+                  want_bias: bool) -> Tuple[Tensor, Optional[Tensor]]:
+    """Backward of :func:`hconv_propagate`'s epilogue: ``(g, part)`` with ``g = gy * keep / (1 - p) * act'(y)`` and, when
+    ``want_bias``, the bias gradient's column partials [P, M] (M = d rounded up to 4) for ``dense.reduce_partials*``."""
+    dev = require_device(gy, y)
+    _f32(gy, "hconv_bwd_epi")
+    gy, y = _rowmajor(gy), _rowmajor(y)
+    n, d = y.shape
+    g = torch.empty((n, d), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    part, P, M = None, 0, (d + 3) // 4 * 4
+    if want_bias:
+        ns = c_int64_t(0)
+        check(lib.allset_hconv_bwd_epi_slices(n, byref(ns)), "allset_hconv_bwd_epi_slices")
+        P = ns.value
+        part = torch.empty((P, M), dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("hconv_bwd_epi", dev, 3 * n * d * 4):
+        check(lib.allset_hconv_bwd_epi(ptr(gy), _ld(gy), ptr(y), _ld(y), HCONV_ACTS[act], float(p), int(seed), ptr(seed_base),
+                                       ptr(g), max(d, 1), ptr(part), P, M, n, d, stream_of(dev)), "allset_hconv_bwd_epi")
+    return g, part

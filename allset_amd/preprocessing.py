@@ -130,3 +130,64 @@ def expand_edge_index(data, edge_th=0):
     new_e = base[rep_e[keep]] + i[keep]
     data.edge_index = _sort_by_vertex(torch.stack([new_v, new_e])).contiguous()
     return data
+
+
+# ---- degree scales of the hypergraph-convolution baselines (HCHA / HGNN / HNHN) ---------------------------------------------------
+# Computed once, on the device the ids live on, from the [V; E] edge list (no dense incidence matrix); stored as attributes of
+# ``data``.  A reciprocal of zero is 0 (the reference's ``D[D == inf] = 0``); a power of zero with a negative exponent is inf, as in
+# the reference's numpy ``DV ** beta``.
+
+def _vertex_edge_ids(edge_index: Tensor, num_nodes: int):
+    v, e = edge_index[0], edge_index[1]
+    e = e - e.min() if e.numel() else e
+    num_edges = int(e.max()) + 1 if e.numel() else 0          # the reference's max(id) + 1 (layers.py:422-423)
+    return v, e, num_nodes, num_edges
+
+
+def _inv0(t: Tensor) -> Tensor:
+    out = 1.0 / t
+    out[torch.isinf(out)] = 0
+    return out
+
+
+def generate_norm_HCHA(data, symdegnorm: bool = False):
+    """The scales ``HypergraphConv.forward`` derives from ``hyperedge_index`` on every call (reference layers.py:438-470), once:
+    ``data.HCHA_D`` [N] = 1 / deg(v) (``symdegnorm``: deg(v)^-1/2), ``data.HCHA_B`` [M] = 1 / |e|, inf -> 0, float32 as in the
+    reference; N = ``data.x`` rows (``data.n_x[0]`` without features), M = max hyperedge id + 1 after re-basing to 0."""
+    num_nodes = data.x.shape[0] if getattr(data, 'x', None) is not None else _first(data.n_x)
+    v, e, N, M = _vertex_edge_ids(data.edge_index, num_nodes)
+    deg = torch.bincount(v, minlength=N).to(torch.float32)
+    size = torch.bincount(e, minlength=M).to(torch.float32)
+    data.HCHA_D = _inv0(deg.pow(0.5) if symdegnorm else deg)
+    data.HCHA_B = _inv0(size)
+    data.HCHA_symdegnorm = bool(symdegnorm)
+    return data
+
+
+def generate_norm_HNHN(H, data, args):
+    """HNHN's normalisations (reference preprocessing.py:295-340) from the edge list; ``H`` (the reference's dense incidence matrix)
+    is not used and may be None.  With beta = ``args.HNHN_beta``, alpha = ``args.HNHN_alpha``:
+    ``D_v_beta = deg^beta``, ``D_e_beta_inv = 1 / sum_{v in e} deg(v)^beta``, ``D_e_alpha = |e|^alpha``,
+    ``D_v_alpha_inv = 1 / sum_{e ni v} |e|^alpha`` (1/0 -> 0), computed in float64 and stored as float32.  Hyperedges are indexed by
+    id - min id (what the model's propagate indexes them by) over max id + 1 entries."""
+    alpha, beta = float(args.HNHN_alpha), float(args.HNHN_beta)
+    v, e, N, M = _vertex_edge_ids(data.edge_index, _first(data.n_x))
+    DV = torch.bincount(v, minlength=N).to(torch.float64)
+    DE = torch.bincount(e, minlength=M).to(torch.float64)
+    D_v_beta = DV.pow(beta)
+    D_e_alpha = DE.pow(alpha)
+    D_e_beta = torch.zeros(M, dtype=torch.float64, device=v.device).index_add_(0, e, D_v_beta[v])
+    D_v_alpha = torch.zeros(N, dtype=torch.float64, device=v.device).index_add_(0, v, D_e_alpha[e])
+    data.D_e_alpha = D_e_alpha.float()
+    data.D_v_alpha_inv = _inv0(D_v_alpha).float()
+    data.D_v_beta = D_v_beta.float()
+    data.D_e_beta_inv = _inv0(D_e_beta).float()
+    return data
+
+
+def rebase_hyperedge_ids(data):
+    """``data.edge_index[1] -= data.edge_index[1].min()`` (reference train.py:381,388), without modifying the tensor in place."""
+    ei = data.edge_index
+    if ei.numel():
+        data.edge_index = torch.stack([ei[0], ei[1] - ei[1].min()]).contiguous()
+    return data

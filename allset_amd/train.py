@@ -11,11 +11,13 @@ Datasets: the reference's raw-data archive is not part of its repository (SURVEY
 HyperGCN on-disk format the reference's ``load_citation_dataset`` consumes (``features.pickle`` scipy-sparse,
 ``labels.pickle`` list, ``hypergraph.pickle`` dict{hyperedge: [nodes]}; load_other_datasets.py:130-163) when
 ``--raw_data_dir`` points at it, and otherwise generates ``--dname synthetic`` (a planted-partition hypergraph with
-noisy class-indicator features).  The baseline methods of the reference (HGNN, HCHA, HyperGCN, ...) are out of
-scope and rejected.
+noisy class-indicator features).  Of the reference's baselines, the hypergraph convolutions HGNN, HCHA and HNHN are
+built (``allset_amd/baselines.py``; same preprocessing branches, train.py:375-388, and the same ``--HCHA_symdegnorm`` /
+``--HNHN_*`` flags); HyperGCN, CEGCN, CEGAT, UniGCNII and MLP are out of scope and rejected.
 
     python -m allset_amd.train --method AllSetTransformer --dname synthetic --epochs 50 --runs 2 --heads 4 \\
         --MLP_hidden 128 --All_num_layers 1
+    python -m allset_amd.train --method HCHA --dname synthetic --epochs 50 --runs 2      # HGNN: --method HGNN --HCHA_symdegnorm
 """
 from __future__ import annotations
 
@@ -35,9 +37,11 @@ import torch.nn.functional as F
 from . import dense
 from ._lib import AllSetHipError
 from .models import SetGNN
-from .preprocessing import Add_Self_Loops, ExtractV2E, expand_edge_index, norm_contruction
+from .preprocessing import (Add_Self_Loops, ExtractV2E, expand_edge_index, generate_norm_HCHA, generate_norm_HNHN, norm_contruction,
+                            rebase_hyperedge_ids)
 
 ALLSET_METHODS = ('AllSetTransformer', 'AllDeepSets')
+BASELINE_METHODS = ('HGNN', 'HCHA', 'HNHN')
 
 
 # --------------------------------------------------------------------------------------------------
@@ -355,8 +359,24 @@ def count_parameters(model):
 
 
 # --------------------------------------------------------------------------------------------------
-# command line (reference train.py:221-289, flags of the AllSet methods; baseline-only flags are accepted and ignored)
+# model / command line (reference train.py:221-289: the flags of the AllSet methods and of HGNN / HCHA / HNHN -- --HCHA_symdegnorm,
+# --HNHN_alpha / _beta / _nonlinear_inbetween; the flags of the other baselines are accepted and ignored)
 # --------------------------------------------------------------------------------------------------
+
+def build_model(args, data):
+    """The model of ``args.method``: the AllSet methods through ``parse_method``, the hypergraph-convolution baselines of reference
+    train.py:77-88 (HGNN is the reference's ``HCHA(args)`` too: ``--HCHA_symdegnorm`` selects the symmetric normalisation)."""
+    if args.method in ('HGNN', 'HCHA'):
+        from .baselines import HCHA
+        return HCHA(args)
+    if args.method == 'HNHN':
+        from .baselines import HNHN
+        return HNHN(args)
+    if args.method in ALLSET_METHODS:
+        return parse_method(args, data)
+    raise ValueError(f"method {args.method!r}: only {ALLSET_METHODS + BASELINE_METHODS} are built "
+                     "(HyperGCN, CEGCN, CEGAT, UniGCNII and MLP are out of scope)")
+
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
@@ -447,7 +467,18 @@ def load_data(args) -> HypergraphData:
 
 
 def preprocess(args, data: HypergraphData) -> HypergraphData:
-    """The AllSet branch of reference train.py:344-353."""
+    """The AllSet branch of reference train.py:344-353, and the HNHN / HCHA / HGNN branches (:375-388): hyperedge ids re-based to 0,
+    HNHN's norms computed before the re-base; HCHA's scales are computed here too (the reference derives them per forward)."""
+    if args.method in BASELINE_METHODS:
+        data = ExtractV2E(data)
+        if args.add_self_loop:
+            data = Add_Self_Loops(data)
+        if args.method == 'HNHN':
+            data = generate_norm_HNHN(None, data, args)
+        data = rebase_hyperedge_ids(data)
+        if args.method in ('HCHA', 'HGNN'):
+            data = generate_norm_HCHA(data, args.HCHA_symdegnorm)
+        return data
     data = ExtractV2E(data)
     if args.add_self_loop:
         data = Add_Self_Loops(data)
@@ -457,14 +488,14 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
 
 
 def run(args) -> dict:
-    if args.method not in ALLSET_METHODS:
-        raise ValueError(f"method {args.method!r}: only {ALLSET_METHODS} are built")
+    if args.method not in ALLSET_METHODS + BASELINE_METHODS:
+        raise ValueError(f"method {args.method!r}: only {ALLSET_METHODS + BASELINE_METHODS} are built")
     if args.seed is not None:
         np.random.seed(args.seed)
         torch.manual_seed(args.seed)
     data = preprocess(args, load_data(args))
     splits = [rand_train_test_idx(data.y, args.train_prop, args.valid_prop) for _ in range(args.runs)]
-    model = parse_method(args, data)
+    model = build_model(args, data)
     if args.cuda not in (0, 1) or not torch.cuda.is_available():
         raise RuntimeError("allset_amd has no CPU path for the aggregation kernels: run with --cuda 0 on an MI355X")
     device = torch.device(f'cuda:{args.cuda}')
