@@ -5,6 +5,6 @@ from .incidence import Incidence, cached_incidence          # noqa: F401
 from .functional import deepsets_aggregate, pma_aggregate, pma_attention_weights, scaled_propagate   # noqa: F401
 from .layers import MLP, PMA, HalfNLHconv, glorot, zeros    # noqa: F401
 from .models import SetGNN                                  # noqa: F401
-from .baselines import HCHA, HNHN, HNHNConv, HypergraphConv  # noqa: F401
+from .baselines import CEGCN, GCNConv, HCHA, HNHN, HNHNConv, HypergraphConv  # noqa: F401
 
 __version__ = "0.1.0"

@@ -220,6 +220,12 @@ SIGNATURES = {
     "allset_hconv_bwd_epi_slices": [c_int64, POINTER(c_int64)],
     "allset_hconv_bwd_epi": [_P, c_int64, _P, c_int64, c_int, c_float, c_uint64, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64,
                              _P],
+    # clique-expansion baseline CEGCN (under ABI 15, additions only)
+    "allset_hconv_fwd_w": [c_int, c_int64, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_float, c_uint64, _P, _P, c_int64, c_int64, c_int64,
+                           c_int64, _P],
+    "allset_clique_count": [_P, c_int64, _P, _P],
+    "allset_clique_emit": [_P, _P, _P, _P, c_int64, _P, _P],
+    "allset_gcn_norm": [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

@@ -6,6 +6,10 @@ each (``functional.scaled_propagate``, csrc/hconv.hip) with the per-row scales, 
 follow them in the reference fused into the E->V launch (HNHN's ``relu`` in between into the V->E launch).  The scales are
 computed once from the edge list (``preprocessing.generate_norm_HCHA`` / ``generate_norm_HNHN``) and live on the ``data`` object,
 as the reference keeps HNHN's.  Device fp32 only: like the AllSet layers there is no CPU path for the propagate.
+
+The clique-expansion baseline ``GCNConv`` / ``CEGCN`` (reference models.py:80-128) propagates over the weighted V2V graph of
+``preprocessing.ConstructV2V`` + ``norm_contruction(TYPE='V2V')`` with the per-edge-weight form of the same kernel
+(``functional.weighted_propagate``).
 """
 from __future__ import annotations
 
@@ -18,7 +22,7 @@ from torch.nn import Parameter
 
 from . import dense
 from ._lib import AllSetHipError
-from .functional import scaled_propagate
+from .functional import scaled_propagate, weighted_propagate
 from .incidence import Incidence, cached_incidence
 from .layers import _linear, glorot, zeros
 from .preprocessing import generate_norm_HCHA
@@ -120,6 +124,115 @@ class HCHA(nn.Module):
         for conv in self.convs[:-1]:
             x = conv(x, inc, scales=scales, act='elu', p=p)
         return self.convs[-1](x, inc, scales=scales)
+
+
+class CEGraph:
+    """The clique expansion a CEGCN forward propagates over: the edge list's two CSR orientations (``Incidence`` with ``n`` rows
+    on both sides) and the edge weights routed into each CSR's order once.  Holds strong references to every tensor a captured
+    graph reads."""
+
+    def __init__(self, edge_index: Tensor, norm: Optional[Tensor], n: int):
+        if not (edge_index.is_cuda and (norm is None or norm.is_cuda)):
+            raise AllSetHipError("the clique-expansion baselines run on ROCm device tensors (no CPU path)")
+        self.edge_index, self.norm, self.n = edge_index, norm, int(n)
+        self.inc = Incidence.from_edge_index(edge_index, n_src=self.n, n_dst=self.n)
+        if norm is None:
+            self.w_dst = self.w_src = None
+        else:
+            if norm.numel() != edge_index.shape[1]:
+                raise ValueError(f"CEGraph: {norm.numel()} edge weights for {edge_index.shape[1]} edges")
+            w = norm.reshape(-1).to(torch.float32)
+            self.w_dst = w.index_select(0, self.inc.perm_dst_long()).contiguous()
+            self.w_src = w.index_select(0, self.inc.perm_src_long()).contiguous()
+
+    def matches(self, edge_index: Tensor, norm: Optional[Tensor], n: int) -> bool:
+        return self.edge_index is edge_index and self.norm is norm and self.n == n
+
+
+class GCNConv(nn.Module):
+    """torch_geometric 1.6.3 ``GCNConv(in, out, normalize=False)`` as the reference's CEGCN builds it (models.py:94-108):
+    ``out = propagate(x @ weight) + bias`` with messages from ``edge_index[0]`` into ``edge_index[1]`` scaled by the edge weight,
+    over ``x.shape[0]`` output rows.  ``weight`` is [in, out], glorot-initialised; ``bias`` zeros.  The propagate, the bias and
+    the activation / dropout the model applies next are one launch (``functional.weighted_propagate``, csrc/hconv.hip)."""
+
+    def __init__(self, in_channels, out_channels, improved=False, cached=False, add_self_loops=True, normalize=True, bias=True,
+                 **kwargs):
+        super().__init__()
+        if normalize:
+            raise NotImplementedError("GCNConv(normalize=True) is not built: normalise once with "
+                                      "preprocessing.norm_contruction(data, TYPE='V2V') and pass normalize=False, as CEGCN does")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.weight = Parameter(torch.empty(in_channels, out_channels))
+        if bias:
+            self.bias = Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter('bias', None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot(self.weight)
+        zeros(self.bias)
+
+    def forward(self, x: Tensor, edge_index, edge_weight: Optional[Tensor] = None, *, act: Optional[str] = None,
+                p: float = 0.0) -> Tensor:
+        """``edge_index``: the [2, E] int64 edge list (with ``edge_weight``) or a prebuilt :class:`CEGraph`; ``act`` / ``p``: the
+        activation and dropout the model applies next, fused into the launch."""
+        graph = edge_index if isinstance(edge_index, CEGraph) else CEGraph(edge_index, edge_weight, x.shape[0])
+        xw = dense.linear(x, self.weight.t(), None)          # x @ weight: the [in, out] weight read transposed by the GEMM, no copy
+        return weighted_propagate(xw, graph.inc, graph.w_dst, graph.w_src, bias=self.bias, act=act, p=p)
+
+    def __repr__(self):
+        return "{}({}, {})".format(self.__class__.__name__, self.in_channels, self.out_channels)
+
+
+class CEGCN(nn.Module):
+    """Reference models.py:80-128: ``[in -> hid] + [hid -> hid] x (L - 2) + [hid -> out]`` GCN convs (two at L = 1) over the clique
+    expansion (``data.edge_index`` / ``data.norm`` from ``ConstructV2V`` + ``norm_contruction(TYPE='V2V')``).  Between convs:
+    ``relu``, the normalisation, dropout.  ``Normalization='bn'`` is ``BatchNorm1d(hid)``; every other value, the driver's default
+    ``'ln'`` included, is ``Identity`` -- then ``relu`` and dropout ride in each non-final conv's launch.  With ``'bn'`` the ``relu``
+    does, then the BatchNorm and the hash dropout (``dense.hash_dropout``) follow as their own steps."""
+
+    def __init__(self, in_dim, hid_dim, out_dim, num_layers, dropout, Normalization='bn'):
+        super().__init__()
+        self.convs = nn.ModuleList()
+        self.normalizations = nn.ModuleList()
+        bn = Normalization == 'bn'
+        self.convs.append(GCNConv(in_dim, hid_dim, normalize=False))
+        self.normalizations.append(nn.BatchNorm1d(hid_dim) if bn else nn.Identity())
+        for _ in range(num_layers - 2):
+            self.convs.append(GCNConv(hid_dim, hid_dim, normalize=False))
+            self.normalizations.append(nn.BatchNorm1d(hid_dim) if bn else nn.Identity())
+        self.convs.append(GCNConv(hid_dim, out_dim, normalize=False))
+        self.dropout = dropout
+        self._graph: Optional[CEGraph] = None
+
+    def reset_parameters(self):
+        for layer in self.convs:
+            layer.reset_parameters()
+        for normalization in self.normalizations:
+            if not isinstance(normalization, nn.Identity):
+                normalization.reset_parameters()
+
+    def graph(self, data, x: Tensor) -> CEGraph:
+        """The V2V graph of ``data``, built on first sight and kept (with the tensors it came from) for later forwards."""
+        norm = getattr(data, 'norm', None)
+        if self._graph is None or not self._graph.matches(data.edge_index, norm, x.shape[0]):
+            self._graph = CEGraph(data.edge_index, norm, x.shape[0])
+        return self._graph
+
+    def forward(self, data):
+        x = data.x
+        graph = self.graph(data, x)
+        p = float(self.dropout) if self.training else 0.0
+        for i, conv in enumerate(self.convs[:-1]):
+            nm = self.normalizations[i]
+            if isinstance(nm, nn.Identity):
+                x = conv(x, graph, act='relu', p=p)
+            else:
+                x = dense.batch_norm(nm, conv(x, graph, act='relu'))
+                x = dense.hash_dropout(x, p, self.training)        # the library's hash mask: reproducible, capturable
+        return self.convs[-1](x, graph)
 
 
 class HNHNConv(nn.Module):

@@ -14,12 +14,17 @@
 //   * XCD-contiguous workgroup order, and the CSR's long-rows-first order (row_order) when the caller has one;
 //   * a short-row variant (several consecutive rows per lane group, one stream of incidences) below a mean degree of 6.
 // Algorithmic bytes per launch: nnz * (4d + 4) + (n_t + 1) * 4 + n_t * 4d, plus 4 * nnz for the r gathers.
+//
+// allset_hconv_fwd_w (CEGCN's GCNConv hop over the clique expansion) is the same launch with a per-INCIDENCE weight w[j] in place
+// of the per-source r[col_j]: w is read in CSR order next to the column ids (one coalesced load per 64 incidences), so the
+// backward over the transposed CSR takes w permuted into that CSR's order, once per graph.
 #include "common.h"
 
 namespace allset {
 namespace hconv {
 
 enum { kActNone = 0, kActRelu = 1, kActElu = 2 };
+enum { kScNone = 0, kScR = 1, kScW = 2 };   // per-incidence scale: none, r[col_j] (per gathered row), w[j] (per CSR position)
 constexpr int kUnroll = 8;
 constexpr int kFlatRows = 7;          // rows per lane group in the short-row kernel (kFlatRows + 1 rowptr entries fit in 8 lanes)
 
@@ -66,7 +71,8 @@ __device__ __forceinline__ Epi resolve(Epi e, const uint64_t* seed_base) {
   return e;
 }
 
-template <int VEC, int LPR, bool HAS_R>
+// SC: kScNone, kScR (r indexed by the gathered row id) or kScW (r is the weight stream, indexed by CSR position)
+template <int VEC, int LPR, int SC>
 __global__ __launch_bounds__(kBlock) void hconv_fwd_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ r,
     const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy, int n_t, int d,
@@ -94,7 +100,8 @@ __global__ __launch_bounds__(kBlock) void hconv_fwd_kernel(
       float my_r = 0.f;
       if (lane < n) {
         my_col = col[base + lane];
-        if constexpr (HAS_R) my_r = r[my_col];
+        if constexpr (SC == kScR) my_r = r[my_col];
+        if constexpr (SC == kScW) my_r = r[base + lane];
       }
       for (int j = 0; j < n; j += NS * kUnroll) {
         Raw<float, VEC> raw[kUnroll];
@@ -103,7 +110,7 @@ __global__ __launch_bounds__(kBlock) void hconv_fwd_kernel(
         for (int u = 0; u < kUnroll; ++u) {
           const int jj = j + u * NS + slot;
           const int src = __shfl(my_col, jj & (kWave - 1));
-          if constexpr (HAS_R) rr[u] = __shfl(my_r, jj & (kWave - 1)); else rr[u] = 1.f;
+          if constexpr (SC != kScNone) rr[u] = __shfl(my_r, jj & (kWave - 1)); else rr[u] = 1.f;
           if (jj < n && active) raw[u] = load_raw<float, VEC>(x + static_cast<int64_t>(src) * ldx + c0);
           else raw[u] = zero_raw<float, VEC>();
         }
@@ -112,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void hconv_fwd_kernel(
           const FVec<VEC> v = unpack<float, VEC>(raw[u]);
           // (a skipped slot holds v == 0, but its rr is the broadcast of another incidence's scale, which may be inf (HNHN's
           //  deg^beta of an isolated vertex): skip it explicitly so that 0 * inf never reaches the sum)
-          if constexpr (HAS_R) {
+          if constexpr (SC != kScNone) {
             if (j + u * NS + slot < n) {
 #pragma unroll
               for (int k = 0; k < VEC; ++k) acc[k] = fmaf(rr[u], v.v[k], acc[k]);
@@ -138,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void hconv_fwd_kernel(
 
 // short-row variant: each LPR-lane group owns kFlatRows consecutive rows and walks their incidences as one stream
 // (segreduce_flat_kernel's scheme); single column chunk (d <= LPR * 4), 16-byte rows
-template <int LPR, bool HAS_R>
+template <int LPR, int SC>
 __global__ __launch_bounds__(kBlock) void hconv_flat_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ r,
     const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy, int n_t, int d, Epi epi,
@@ -184,7 +191,8 @@ __global__ __launch_bounds__(kBlock) void hconv_flat_kernel(
     float my_r = 0.f;
     if (li < n) {
       my_col = col[base + li];
-      if constexpr (HAS_R) my_r = r[my_col];
+      if constexpr (SC == kScR) my_r = r[my_col];
+      if constexpr (SC == kScW) my_r = r[base + li];
     }
     for (int j = 0; j < n; j += kUnroll) {
       Raw<float, VEC> raw[kUnroll];
@@ -193,7 +201,7 @@ __global__ __launch_bounds__(kBlock) void hconv_flat_kernel(
       for (int u = 0; u < kUnroll; ++u) {
         const int jj = j + u;
         const int src = __shfl(my_col, lane0 + (jj & (LPR - 1)));
-        if constexpr (HAS_R) rr[u] = __shfl(my_r, lane0 + (jj & (LPR - 1))); else rr[u] = 1.f;
+        if constexpr (SC != kScNone) rr[u] = __shfl(my_r, lane0 + (jj & (LPR - 1))); else rr[u] = 1.f;
         if (jj < n && active) raw[u] = load_raw<float, VEC>(x + static_cast<int64_t>(src) * ldx + c0);
         else raw[u] = zero_raw<float, VEC>();
       }
@@ -274,22 +282,24 @@ static inline int pick_lpr(int64_t d) {           // smallest power of two >= d 
 }
 
 template <int VEC, int LPR>
-static void launch_fwd(bool has_r, unsigned grid, hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* r,
+static void launch_fwd(int sc, unsigned grid, hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* r,
                        const float* x, int64_t ldx, float* y, int64_t ldy, int n_t, int d, const int32_t* row_order, const Epi& e,
                        const uint64_t* seed_base) {
-  if (has_r) hconv_fwd_kernel<VEC, LPR, true><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, row_order, e, seed_base);
-  else       hconv_fwd_kernel<VEC, LPR, false><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, row_order, e, seed_base);
+  if (sc == kScR)      hconv_fwd_kernel<VEC, LPR, kScR><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, row_order, e, seed_base);
+  else if (sc == kScW) hconv_fwd_kernel<VEC, LPR, kScW><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, row_order, e, seed_base);
+  else                 hconv_fwd_kernel<VEC, LPR, kScNone><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, row_order, e, seed_base);
 }
 
 template <int LPR>
-static void launch_flat(bool has_r, hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* r, const float* x,
+static void launch_flat(int sc, hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* r, const float* x,
                         int64_t ldx, float* y, int64_t ldy, int n_t, int d, const Epi& e, const uint64_t* seed_base) {
   constexpr int NS = kWave / LPR;
   const int64_t groups = (static_cast<int64_t>(n_t) + kFlatRows - 1) / kFlatRows;
   const int64_t waves = (groups + NS - 1) / NS;
   const unsigned grid = static_cast<unsigned>((waves + kWavesPerBlock - 1) / kWavesPerBlock);
-  if (has_r) hconv_flat_kernel<LPR, true><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, e, seed_base);
-  else       hconv_flat_kernel<LPR, false><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, e, seed_base);
+  if (sc == kScR)      hconv_flat_kernel<LPR, kScR><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, e, seed_base);
+  else if (sc == kScW) hconv_flat_kernel<LPR, kScW><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, e, seed_base);
+  else                 hconv_flat_kernel<LPR, kScNone><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, e, seed_base);
 }
 
 }  // namespace hconv
@@ -300,11 +310,11 @@ using namespace allset::hconv;
 
 extern "C" int allset_hconv_supported(void) { return 1; }
 
-extern "C" int allset_hconv_fwd(int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
-                                const float* r, const float* s, const float* x, int64_t ldx, const float* bias, int act, float p,
-                                uint64_t seed, const uint64_t* seed_base, float* y, int64_t ldy, int64_t n_t, int64_t n_s,
-                                int64_t d, void* stream) {
-  clear_error();
+// r: per gathered row (sc = kScR) or per CSR position (sc = kScW); NULL = ones
+static int hconv_fwd_impl(int sc, int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                          const float* r, const float* s, const float* x, int64_t ldx, const float* bias, int act, float p,
+                          uint64_t seed, const uint64_t* seed_base, float* y, int64_t ldy, int64_t n_t, int64_t n_s,
+                          int64_t d, void* stream) {
   ALLSET_REQUIRE(variant >= 0 && variant <= 2, "hconv_fwd: bad variant %d", variant);
   ALLSET_REQUIRE(act >= kActNone && act <= kActElu, "hconv_fwd: bad act %d", act);
   ALLSET_REQUIRE(p >= 0.f && p < 1.f, "hconv_fwd: dropout p must be in [0,1)");
@@ -331,7 +341,7 @@ extern "C" int allset_hconv_fwd(int variant, int64_t nnz, const int32_t* row_ord
     set_error("hconv_fwd: the short-row variant needs 16-byte aligned rows and d <= 256");
     return ALLSET_ERR_UNSUPPORTED;
   }
-  const bool has_r = r != nullptr;
+  const int has_r = r != nullptr ? sc : kScNone;
   if (use_flat) {
     switch (pick_lpr(d)) {
       case 8:  launch_flat<8>(has_r, st, rowptr, col, r, x, ldx, y, ldy, nt, di, ep, seed_base); break;
@@ -354,6 +364,24 @@ extern "C" int allset_hconv_fwd(int variant, int64_t nnz, const int32_t* row_ord
   }
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
+}
+
+extern "C" int allset_hconv_fwd(int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                                const float* r, const float* s, const float* x, int64_t ldx, const float* bias, int act, float p,
+                                uint64_t seed, const uint64_t* seed_base, float* y, int64_t ldy, int64_t n_t, int64_t n_s,
+                                int64_t d, void* stream) {
+  clear_error();
+  return hconv_fwd_impl(kScR, variant, nnz, row_order, rowptr, col, r, s, x, ldx, bias, act, p, seed, seed_base, y, ldy, n_t, n_s, d,
+                        stream);
+}
+
+extern "C" int allset_hconv_fwd_w(int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                                  const float* w, const float* s, const float* x, int64_t ldx, const float* bias, int act, float p,
+                                  uint64_t seed, const uint64_t* seed_base, float* y, int64_t ldy, int64_t n_t, int64_t n_s,
+                                  int64_t d, void* stream) {
+  clear_error();
+  return hconv_fwd_impl(kScW, variant, nnz, row_order, rowptr, col, w, s, x, ldx, bias, act, p, seed, seed_base, y, ldy, n_t, n_s, d,
+                        stream);
 }
 
 extern "C" int allset_hconv_bwd_epi_slices(int64_t n, int64_t* n_slices) {

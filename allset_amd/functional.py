@@ -401,6 +401,56 @@ class _ScaledPropagate(torch.autograd.Function):
         return gx, gb, None, None, None, None, None, None
 
 
+class _WeightedPropagate(torch.autograd.Function):
+    """``y = drop_p(act(A_w x + bias))`` over the target-major CSR with the per-incidence weights ``w_dst`` -- one kernel forward;
+    backward: the epilogue's kernel (only when there is an epilogue) and the same kernel over the source-major CSR with the weights
+    in that CSR's order, ``w_src``.  The weights are constants."""
+
+    @staticmethod
+    def forward(ctx, x, bias, inc, w_dst, w_src, act, p):
+        from . import dense
+        if x.shape[0] != inc.n_src:
+            raise _lib.AllSetHipError(f"weighted_propagate: x has {x.shape[0]} rows, the graph gathers from {inc.n_src}")
+        seed = dense._draw_seed() if p > 0.0 else 0
+        base = dense._seed_base() if p > 0.0 else None
+        y = ops.hconv_propagate_w(inc.by_dst, x, inc.n_dst, w_dst, bias, act, p, seed, base)
+        epi = act is not None or p > 0.0 or bias is not None
+        ctx.save_for_backward(y if epi else None)
+        ctx.cfg = (inc, w_src, act, p, seed, base, epi)
+        ctx.bias_param = bias
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        from . import dense
+        (y,) = ctx.saved_tensors
+        inc, w_src, act, p, seed, base, epi = ctx.cfg
+        need_b = ctx.bias_param is not None and ctx.needs_input_grad[1]
+        gb = None
+        if epi:
+            g, part = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=need_b)
+            if need_b:
+                (gb,) = dense._defer_or_reduce(part, [(ctx.bias_param, 0, (y.shape[1],))], defer=True)
+        else:
+            g = gy
+        gx = ops.hconv_propagate_w(inc.by_src, g, inc.n_src, w_src) if ctx.needs_input_grad[0] else None
+        return gx, gb, None, None, None, None, None
+
+
+def weighted_propagate(x: Tensor, inc: Incidence, w_dst: Optional[Tensor], w_src: Optional[Tensor], bias: Optional[Tensor] = None,
+                       act: Optional[str] = None, p: float = 0.0) -> Tensor:
+    """One GCN hop (PyG ``GCNConv.propagate`` with ``edge_weight``): ``y[t] = drop_p(act(sum_{edges s -> t} w_e * x[s] + bias))``
+    over ``inc`` (sources -> targets; ``inc.n_dst`` output rows).  ``w_dst`` / ``w_src``: the edge weights routed into
+    ``inc.by_dst`` / ``inc.by_src`` order (both None = ones).  ``act`` None / 'relu' / 'elu'; ``p`` the dropout probability.
+    Differentiable in ``x`` and ``bias``."""
+    if act not in ops.HCONV_ACTS:
+        raise ValueError(f"weighted_propagate: act must be None, 'relu' or 'elu', got {act!r}")
+    if (w_dst is None) != (w_src is None):
+        raise ValueError("weighted_propagate: give the weights in both CSR orders, or neither")
+    return _WeightedPropagate.apply(x, bias, inc, w_dst, w_src, act, float(p))
+
+
 def scaled_propagate(x: Tensor, inc: Incidence, direction: str, r: Optional[Tensor] = None, s: Optional[Tensor] = None,
                      bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0) -> Tensor:
     """One hop of a hypergraph convolution over ``inc`` (sources = vertices, targets = hyperedges):

@@ -536,6 +536,78 @@ def hconv_propagate(csr: CSR, x: Tensor, n_t: int, r: Optional[Tensor] = None, s
     return y
 
 
+def hconv_propagate_w(csr: CSR, x: Tensor, n_t: int, w: Optional[Tensor] = None, bias: Optional[Tensor] = None,
+                      act: Optional[str] = None, p: float = 0.0, seed: int = 0, seed_base: Optional[Tensor] = None) -> Tensor:
+    """``y[t] = drop_p(act(sum_{j in row t} w[j] * x[col_j] + bias))`` over ``csr`` with ``w`` f32[nnz] per incidence in ``csr``'s
+    own order (None = ones).  fp32 only."""
+    dev = require_device(csr.rowptr, x, w, bias)
+    _f32(x, "hconv_propagate_w")
+    for t, what in ((w, "w"), (bias, "bias")):
+        if t is not None:
+            _f32(t, f"hconv_propagate_w {what}")
+    w = w.contiguous() if w is not None else None
+    bias = bias.contiguous() if bias is not None else None
+    x = _rowmajor(x)
+    n_s, d = x.shape
+    nnz = csr.col.numel()
+    if w is not None and w.numel() != nnz:
+        raise _lib.AllSetHipError(f"hconv_propagate_w: w has {w.numel()} entries for {nnz} incidences")
+    if bias is not None and bias.numel() != d:
+        raise _lib.AllSetHipError(f"hconv_propagate_w: bias has {bias.numel()} entries for width {d}")
+    if n_t > csr.n_rows or csr.n_cols > n_s:
+        raise _lib.AllSetHipError(f"hconv_propagate_w: CSR of {csr.n_rows} x {csr.n_cols} against {n_t} outputs / {n_s} gathered rows")
+    y = torch.empty((n_t, d), dtype=torch.float32, device=dev)
+    flat_ok = d % 4 == 0 and d <= 256 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+    variant = csr.variant("segreduce", n_t) if flat_ok else 1
+    order = csr.row_order if (variant == 1 and csr.row_order is not None and csr.row_order.numel() == n_t) else None
+    algo = nnz * (4 * d + 4 + (4 if w is not None else 0)) + (n_t + 1) * 4 + n_t * 4 * d
+    with on_device(dev), _timed("hconv_fwd_w", dev, algo):
+        check(_lib.load().allset_hconv_fwd_w(variant, nnz, ptr(order), ptr(csr.rowptr), ptr(csr.col), ptr(w), None, ptr(x), _ld(x),
+                                             ptr(bias), HCONV_ACTS[act], float(p), int(seed), ptr(seed_base), ptr(y), max(d, 1),
+                                             n_t, n_s, d, stream_of(dev)), "allset_hconv_fwd_w")
+    return y
+
+
+# ---- clique expansion and its GCN normalisation (csrc/clique.hip) -----------------------------------------------------------------
+def clique_pairs(rowptr: Tensor, member: Tensor, edge_of: Tensor) -> Tensor:
+    """Every pair (member[a], member[b]), a < b, of every row of the hyperedge -> member CSR (``rowptr`` int32[n_e + 1], ``member``
+    int32 ascending within rows, ``edge_of`` int32 the row of each position) as int64 keys ``member[a] << 32 | member[b]``, rows in
+    order.  Raises ``ValueError`` before emitting when the pair count would not fit an int32-indexed CSR."""
+    dev = require_device(rowptr, member, edge_of)
+    n_e, nnz = rowptr.numel() - 1, member.numel()
+    lib = _lib.load()
+    cnt = torch.empty(n_e, dtype=torch.int64, device=dev)
+    with on_device(dev), _timed("clique_count", dev, (n_e + 1) * 4 + n_e * 8):
+        check(lib.allset_clique_count(ptr(rowptr), n_e, ptr(cnt), stream_of(dev)), "allset_clique_count")
+    off = torch.cumsum(cnt, 0) - cnt
+    total = int(cnt.sum()) if n_e > 0 else 0                                   # one host sync: the output size
+    if total + nnz >= 2 ** 31 - 1:
+        raise ValueError(f"clique expansion: {total} vertex pairs do not fit an int32-indexed CSR (at most {2 ** 31 - 2 - nnz} here)")
+    keys = torch.empty(total, dtype=torch.int64, device=dev)
+    with on_device(dev), _timed("clique_emit", dev, nnz * 16 + n_e * 8 + total * 12):
+        check(lib.allset_clique_emit(ptr(rowptr), ptr(member), ptr(edge_of), ptr(off), nnz, ptr(keys), stream_of(dev)),
+              "allset_clique_emit")
+    return keys
+
+
+def gcn_norm(src: Tensor, dst: Tensor, m: Optional[Tensor], n: int) -> Tuple[Tensor, Tensor]:
+    """torch_geometric 1.6.3 ``gcn_norm(edge_index, m, add_self_loops=True)`` for edges without self-loops, ids in [0, n):
+    ``(edge_index int64[2, E + n] = [pairs | loops 0..n-1], w f32[E + n])``, ``w = deg^-1/2[src] * m * deg^-1/2[dst]``."""
+    dev = require_device(src, dst, m)
+    src, dst = src.contiguous(), dst.contiguous()
+    if m is not None:
+        _f32(m, "gcn_norm m")
+        m = m.contiguous()
+    E = src.numel()
+    ei = torch.empty((2, E + n), dtype=torch.int64, device=dev)
+    w = torch.empty(E + n, dtype=torch.float32, device=dev)
+    deg = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("gcn_norm", dev, E * (16 + 4 + 4) + (E + n) * (16 + 4) + n * 4):
+        check(_lib.load().allset_gcn_norm(ptr(src), ptr(dst), ptr(m), E, n, ptr(deg), ptr(ei[0]), ptr(ei[1]), ptr(w), stream_of(dev)),
+              "allset_gcn_norm")
+    return ei, w
+
+
 def hconv_bwd_epi(gy: Tensor, y: Tensor, act: Optional[str], p: float, seed: int, seed_base: Optional[Tensor],
                   want_bias: bool) -> Tuple[Tensor, Optional[Tensor]]:
     """Backward of :func:`hconv_propagate`'s epilogue: ``(g, part)`` with ``g = gy * keep / (1 - p) * act'(y)`` and, when

@@ -88,8 +88,77 @@ def norm_contruction(data, option='all_one', TYPE='V2E'):
             HEdeg = torch.bincount(e - cidx).to(torch.float32)
             data.norm = Vdeg.pow(-0.5)[v] * HEdeg.pow(-0.5)[e - cidx]
     elif TYPE == 'V2V':
-        raise NotImplementedError("TYPE='V2V' (gcn_norm for the clique-expansion baselines) is outside the AllSet path")
+        data.edge_index, data.norm = gcn_norm(data.edge_index, data.norm, add_self_loops=True)
     return data
+
+
+# ---- clique expansion of the CEGCN baseline (reference preprocessing.py:343-391, 466-468; csrc/clique.hip) ------------------------
+# Device programs: ids on the host go through the current ROCm device and come back to the host, so train.py's order
+# (preprocess, then move ``data`` to the device) is kept.
+
+def _on_device(t: Tensor) -> Tensor:
+    if t.is_cuda:
+        return t
+    if not torch.cuda.is_available():
+        from ._lib import AllSetHipError
+        raise AllSetHipError("the clique expansion runs on a ROCm device (csrc/clique.hip); no device is available")
+    return t.to(torch.device('cuda', torch.cuda.current_device()))
+
+
+def ConstructV2V(data):
+    """Clique expansion of a V->E edge list (reference preprocessing.py:343-391): every pair ``(i, j)``, ``i < j``, of members of a
+    hyperedge with at least two members, in ONE direction (``edge_index[0] = i``), once; ``data.norm`` = the number of hyperedges
+    sharing the pair (float32).  Size-1 hyperedges contribute nothing.  The reference emits pairs in dict insertion order; here
+    they come sorted by ``(i, j)``.  Duplicate incidences (which the loaders never produce) count once."""
+    ei = data.edge_index
+    home = ei.device
+    ei = _on_device(ei)
+    dev = ei.device
+    v, e = ei[0], ei[1]
+    if v.numel() == 0:
+        data.edge_index = torch.zeros((2, 0), dtype=torch.int64, device=home)
+        data.norm = torch.zeros(0, dtype=torch.float32, device=home)
+        return data
+    e = e - e.min()
+    n_v = int(v.max()) + 1
+    key = torch.unique(e * n_v + v)                              # sorted by (hyperedge, vertex): members ascending
+    e, v = key // n_v, key % n_v
+    n_e = int(e[-1]) + 1
+    rowptr = torch.zeros(n_e + 1, dtype=torch.int32, device=dev)
+    rowptr[1:] = torch.cumsum(torch.bincount(e, minlength=n_e), 0).to(torch.int32)
+    from . import ops
+    pairs = ops.clique_pairs(rowptr, v.to(torch.int32), e.to(torch.int32))
+    pairs, mult = torch.unique_consecutive(torch.sort(pairs).values, return_counts=True)
+    data.edge_index = torch.stack([pairs >> 32, pairs & 0xFFFFFFFF]).to(home)
+    data.norm = mult.to(torch.float32).to(home)
+    return data
+
+
+def gcn_norm(edge_index, edge_weight=None, add_self_loops=True):
+    """torch_geometric 1.6.3 ``gcn_norm(edge_index, edge_weight, add_self_loops=True)`` as ``norm_contruction(TYPE='V2V')`` calls it:
+    ``N = edge_index.max() + 1`` (not the vertex count: ids >= N get no loop), one self-loop of weight 1 per id < N,
+    ``deg[j]`` = the weights into ``j``, ``w = deg^-1/2[src] * m * deg^-1/2[dst]``.  Returns ``(edge_index [pairs | loops], w)``
+    on the device ``edge_index`` came from.  The graph must have no self-loops (``ConstructV2V`` emits none).  The degree is a
+    float atomic sum: exact and run-to-run identical for integer weights below 2^24 (``ConstructV2V``'s multiplicities); other
+    weights may differ from run to run in their last bits."""
+    if not add_self_loops:
+        raise NotImplementedError("gcn_norm(add_self_loops=False) is not built (the reference's V2V branch adds them)")
+    home = edge_index.device
+    ei = _on_device(edge_index)
+    if ei.dim() != 2 or ei.shape[0] != 2 or ei.shape[1] == 0:
+        raise ValueError(f"gcn_norm: expected a non-empty [2, E] edge list, got {tuple(ei.shape)}")
+    src, dst = ei[0].to(torch.int64), ei[1].to(torch.int64)
+    if bool((src == dst).any()):
+        raise ValueError("gcn_norm: the edge list has self-loops; the clique expansion (ConstructV2V) never emits any")
+    if int(ei.min()) < 0:
+        raise ValueError("gcn_norm: negative vertex id")
+    n = int(ei.max()) + 1
+    m = edge_weight.to(device=ei.device, dtype=torch.float32) if edge_weight is not None else None
+    if m is not None and m.numel() != src.numel():
+        raise ValueError(f"gcn_norm: {m.numel()} weights for {src.numel()} edges")
+    from . import ops
+    out, w = ops.gcn_norm(src, dst, m, n)
+    return out.to(home), w.to(home)
 
 
 def expand_edge_index(data, edge_th=0):

@@ -13,7 +13,8 @@ HyperGCN on-disk format the reference's ``load_citation_dataset`` consumes (``fe
 ``--raw_data_dir`` points at it, and otherwise generates ``--dname synthetic`` (a planted-partition hypergraph with
 noisy class-indicator features).  Of the reference's baselines, the hypergraph convolutions HGNN, HCHA and HNHN are
 built (``allset_amd/baselines.py``; same preprocessing branches, train.py:375-388, and the same ``--HCHA_symdegnorm`` /
-``--HNHN_*`` flags); HyperGCN, CEGCN, CEGAT, UniGCNII and MLP are out of scope and rejected.
+``--HNHN_*`` flags), and so is the clique-expansion CEGCN (branch :354-357, ``--normalization``); CEGAT is not built yet, and
+HyperGCN, UniGCNII and MLP are out of scope; all four are rejected.
 
     python -m allset_amd.train --method AllSetTransformer --dname synthetic --epochs 50 --runs 2 --heads 4 \\
         --MLP_hidden 128 --All_num_layers 1
@@ -37,11 +38,12 @@ import torch.nn.functional as F
 from . import dense
 from ._lib import AllSetHipError
 from .models import SetGNN
-from .preprocessing import (Add_Self_Loops, ExtractV2E, expand_edge_index, generate_norm_HCHA, generate_norm_HNHN, norm_contruction,
-                            rebase_hyperedge_ids)
+from .preprocessing import (Add_Self_Loops, ConstructV2V, ExtractV2E, expand_edge_index, generate_norm_HCHA, generate_norm_HNHN,
+                            norm_contruction, rebase_hyperedge_ids)
 
 ALLSET_METHODS = ('AllSetTransformer', 'AllDeepSets')
 BASELINE_METHODS = ('HGNN', 'HCHA', 'HNHN')
+CE_METHODS = ('CEGCN',)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -372,10 +374,21 @@ def build_model(args, data):
     if args.method == 'HNHN':
         from .baselines import HNHN
         return HNHN(args)
+    if args.method == 'CEGCN':
+        # a CE model on a V-E incidence computes nonsense without an error (in the reference too): insist on the V2V branch
+        if data is None or not getattr(data, 'clique_expansion', False):
+            raise ValueError("method 'CEGCN' runs on the clique expansion: pass data through train.preprocess (ExtractV2E -> "
+                             "ConstructV2V -> norm_contruction(TYPE='V2V')) before build_model")
+        from .baselines import CEGCN
+        return CEGCN(in_dim=args.num_features, hid_dim=args.MLP_hidden, out_dim=args.num_classes, num_layers=args.All_num_layers,
+                     dropout=args.dropout, Normalization=args.normalization)
     if args.method in ALLSET_METHODS:
         return parse_method(args, data)
-    raise ValueError(f"method {args.method!r}: only {ALLSET_METHODS + BASELINE_METHODS} are built "
-                     "(HyperGCN, CEGCN, CEGAT, UniGCNII and MLP are out of scope)")
+    if args.method == 'CEGAT':
+        raise ValueError("method 'CEGAT' is not built yet (its GAT attention kernel is open work; CEGCN runs on the same "
+                         "clique-expansion branch)")
+    raise ValueError(f"method {args.method!r}: only {ALLSET_METHODS + BASELINE_METHODS + CE_METHODS} are built "
+                     "(HyperGCN, UniGCNII and MLP are out of scope)")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -468,7 +481,14 @@ def load_data(args) -> HypergraphData:
 
 def preprocess(args, data: HypergraphData) -> HypergraphData:
     """The AllSet branch of reference train.py:344-353, and the HNHN / HCHA / HGNN branches (:375-388): hyperedge ids re-based to 0,
-    HNHN's norms computed before the re-base; HCHA's scales are computed here too (the reference derives them per forward)."""
+    HNHN's norms computed before the re-base; HCHA's scales are computed here too (the reference derives them per forward); and the
+    clique-expansion branch of CEGCN (:354-357: no self-loop hyperedges there, whatever ``--add_self_loop`` says)."""
+    if args.method in CE_METHODS:
+        data = ExtractV2E(data)
+        data = ConstructV2V(data)
+        data = norm_contruction(data, TYPE='V2V')
+        data.clique_expansion = True                        # what build_model checks for CEGCN
+        return data
     if args.method in BASELINE_METHODS:
         data = ExtractV2E(data)
         if args.add_self_loop:
@@ -488,8 +508,8 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
 
 
 def run(args) -> dict:
-    if args.method not in ALLSET_METHODS + BASELINE_METHODS:
-        raise ValueError(f"method {args.method!r}: only {ALLSET_METHODS + BASELINE_METHODS} are built")
+    if args.method not in ALLSET_METHODS + BASELINE_METHODS + CE_METHODS:
+        raise ValueError(f"method {args.method!r}: only {ALLSET_METHODS + BASELINE_METHODS + CE_METHODS} are built")
     if args.seed is not None:
         np.random.seed(args.seed)
         torch.manual_seed(args.seed)

@@ -746,6 +746,32 @@ int allset_hconv_bwd_epi(const float* gy, int64_t ldg, const float* y, int64_t l
                          const uint64_t* seed_base, float* g, int64_t ldo, float* part, int64_t n_slices, int64_t M, int64_t n,
                          int64_t d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Clique-expansion baseline CEGCN (reference models.py:80-128; preprocessing.py:343-391 ConstructV2V and norm_contruction
+ * TYPE='V2V', i.e. torch_geometric 1.6.3 gcn_norm with self-loops).  Added under ABI 15, additions only.
+ *
+ * allset_hconv_fwd_w: allset_hconv_fwd with a per-INCIDENCE weight w (f32[nnz] in this CSR's order, NULL = ones) in place of r:
+ *   y[t,:] = drop_p( act( s[t] * sum_{j in [rowptr[t], rowptr[t+1])} w[j] * x[col[j],:] + bias ) )
+ * Its backward is this same call over the transposed CSR with w permuted into that CSR's order and no epilogue.
+ *
+ * allset_clique_count: cnt[e] = k_e (k_e - 1) / 2 (int64) for the rows of a hyperedge -> member CSR (rowptr int32[n_e + 1]).
+ * allset_clique_emit: for that CSR with members ascending within each row (member int32[nnz]), edge_of int32[nnz] the row of each
+ *   position and off int64[n_e] the exclusive scan of cnt: every pair (member[a], member[b]), a < b within a row, as the key
+ *   member[a] << 32 | member[b] at keys[off[e] + ...] (keys int64[sum cnt]).
+ * allset_gcn_norm: n_pairs edges src -> dst (int64, ids in [0, n), no self-loops) with weights m (f32, NULL = ones): writes
+ *   src_out / dst_out (int64[n_pairs + n]: the pairs, then one loop per id 0..n-1) and w f32[n_pairs + n] =
+ *   deg^-1/2[src] * m * deg^-1/2[dst] with deg[j] = 1 + sum of m over the pairs into j.  deg: f32[n] workspace.  The degree is a
+ *   float atomic sum: run-to-run identical for integer m below 2^24 only.
+ * ------------------------------------------------------------------------------------------- */
+int allset_hconv_fwd_w(int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col, const float* w,
+                       const float* s, const float* x, int64_t ldx, const float* bias, int act, float p, uint64_t seed,
+                       const uint64_t* seed_base, float* y, int64_t ldy, int64_t n_t, int64_t n_s, int64_t d, void* stream);
+int allset_clique_count(const int32_t* rowptr, int64_t n_e, int64_t* cnt, void* stream);
+int allset_clique_emit(const int32_t* rowptr, const int32_t* member, const int32_t* edge_of, const int64_t* off, int64_t nnz,
+                       int64_t* keys, void* stream);
+int allset_gcn_norm(const int64_t* src, const int64_t* dst, const float* m, int64_t n_pairs, int64_t n, float* deg,
+                    int64_t* src_out, int64_t* dst_out, float* w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
