@@ -226,6 +226,14 @@ SIGNATURES = {
     "allset_clique_count": [_P, c_int64, _P, _P],
     "allset_clique_emit": [_P, _P, _P, _P, c_int64, _P, _P],
     "allset_gcn_norm": [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P],
+    # clique-expansion baseline CEGAT: the GAT attention hop (under ABI 15, additions only; detect with allset_gat_supported)
+    "allset_gat_supported": [],
+    "allset_gat_fwd": [c_int, c_int64, _P, _P, _P, _P, _P, _P, c_int64, c_float, _P, c_int, c_float, c_uint64, _P, c_int, _P, c_int64, _P,
+                       c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P],
+    "allset_gat_bwd_stats": [_P, c_int64, _P, c_float, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_float, _P, _P, c_int64,
+                             c_int64, c_int64, _P],
+    "allset_gat_bwd_src": [c_int, c_int64, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_float, _P, c_int64, _P, c_int64, c_int64,
+                           c_int64, c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

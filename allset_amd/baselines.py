@@ -9,7 +9,9 @@ as the reference keeps HNHN's.  Device fp32 only: like the AllSet layers there i
 
 The clique-expansion baseline ``GCNConv`` / ``CEGCN`` (reference models.py:80-128) propagates over the weighted V2V graph of
 ``preprocessing.ConstructV2V`` + ``norm_contruction(TYPE='V2V')`` with the per-edge-weight form of the same kernel
-(``functional.weighted_propagate``).
+(``functional.weighted_propagate``).  Its attention sibling ``GATConv`` / ``CEGAT`` (reference models.py:131-183) runs over the same
+pairs, without weights and with one loop on every vertex, through the softmax-attention hop ``functional.gat_propagate``
+(csrc/gat.hip).
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ from torch.nn import Parameter
 
 from . import dense
 from ._lib import AllSetHipError
-from .functional import scaled_propagate, weighted_propagate
+from .functional import gat_propagate, scaled_propagate, weighted_propagate
 from .incidence import Incidence, cached_incidence
 from .layers import _linear, glorot, zeros
 from .preprocessing import generate_norm_HCHA
@@ -219,6 +221,145 @@ class CEGCN(nn.Module):
         norm = getattr(data, 'norm', None)
         if self._graph is None or not self._graph.matches(data.edge_index, norm, x.shape[0]):
             self._graph = CEGraph(data.edge_index, norm, x.shape[0])
+        return self._graph
+
+    def forward(self, data):
+        x = data.x
+        graph = self.graph(data, x)
+        p = float(self.dropout) if self.training else 0.0
+        for i, conv in enumerate(self.convs[:-1]):
+            nm = self.normalizations[i]
+            if isinstance(nm, nn.Identity):
+                x = conv(x, graph, act='relu', p=p)
+            else:
+                x = dense.batch_norm(nm, conv(x, graph, act='relu'))
+                x = dense.hash_dropout(x, p, self.training)        # the library's hash mask: reproducible, capturable
+        return self.convs[-1](x, graph)
+
+
+class CEGATGraph:
+    """The graph a CEGAT forward attends over, as torch_geometric 1.6.3's ``GATConv`` derives it from ``edge_index`` on every call:
+    existing self-loops dropped, one loop added for every one of the ``n`` vertices (isolated ones included), edge weights ignored.
+    Both CSR orientations, built once; holds strong references to every tensor a captured graph reads."""
+
+    def __init__(self, edge_index: Tensor, n: int):
+        if not edge_index.is_cuda:
+            raise AllSetHipError("the clique-expansion baselines run on ROCm device tensors (no CPU path)")
+        self.edge_index, self.n = edge_index, int(n)
+        keep = edge_index[0] != edge_index[1]
+        loops = torch.arange(self.n, dtype=edge_index.dtype, device=edge_index.device)
+        self.attention_index = torch.cat([edge_index[:, keep], loops.unsqueeze(0).repeat(2, 1)], dim=1).contiguous()
+        self.inc = Incidence.from_edge_index(self.attention_index, n_src=self.n, n_dst=self.n)
+
+    def matches(self, edge_index: Tensor, n: int) -> bool:
+        return self.edge_index is edge_index and self.n == n
+
+
+class GATConv(nn.Module):
+    """torch_geometric 1.6.3 ``GATConv`` as the reference's CEGAT builds it (models.py:147-163): ``xw = lin_l(x)`` viewed as
+    ``[n, heads, C]``, ``al = (xw * att_l).sum(-1)``, ``ar = (xw * att_r).sum(-1)``, self-loops removed and one added per vertex,
+    ``e = leaky_relu(al[source] + ar[target])`` softmax-normalised over each target's incoming edges, ``out[target] = sum e * xw[source]``,
+    heads concatenated (``concat``) or averaged, then ``+ bias``.  ``lin_r`` is the same module object as ``lin_l`` (one weight, two
+    names in the ``state_dict``).  The hop, the bias and the activation / dropout the model applies next are one launch
+    (``functional.gat_propagate``, csrc/gat.hip).  Dropout on the attention coefficients and bipartite inputs are not built."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
+                 bias=True, **kwargs):
+        super().__init__()
+        if not isinstance(in_channels, int):
+            raise NotImplementedError("GATConv: bipartite (in_l, in_r) inputs are not built (the reference never uses them)")
+        if dropout > 0.0:
+            raise NotImplementedError("GATConv: dropout on the attention coefficients is not built (the reference never sets it)")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.heads = heads
+        self.concat = concat
+        self.negative_slope = negative_slope
+        self.dropout = dropout
+        self.add_self_loops = add_self_loops
+        self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=False)
+        self.lin_r = self.lin_l
+        self.att_l = Parameter(torch.empty(1, heads, out_channels))
+        self.att_r = Parameter(torch.empty(1, heads, out_channels))
+        if bias and concat:
+            self.bias = Parameter(torch.empty(heads * out_channels))
+        elif bias and not concat:
+            self.bias = Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter('bias', None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot(self.lin_l.weight)
+        glorot(self.lin_r.weight)            # the same tensor drawn a second time, as 1.6.3 does: it consumes RNG state
+        glorot(self.att_l)
+        glorot(self.att_r)
+        zeros(self.bias)
+
+    def forward(self, x: Tensor, edge_index, *, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+        """``edge_index``: the [2, E] int64 edge list or a prebuilt :class:`CEGATGraph`; ``act`` / ``p``: the activation and dropout
+        the model applies next, fused into the launch."""
+        if isinstance(x, (tuple, list)):
+            raise NotImplementedError("GATConv: bipartite (x_l, x_r) inputs are not built (the reference never uses them)")
+        if isinstance(edge_index, CEGATGraph):
+            graph = edge_index
+        elif self.add_self_loops:
+            graph = CEGATGraph(edge_index, x.shape[0])
+        else:
+            graph = SimpleNamespace(inc=Incidence.from_edge_index(edge_index, n_src=x.shape[0], n_dst=x.shape[0]))
+        H, C = self.heads, self.out_channels
+        xw = dense.linear(x, self.lin_l.weight, None)
+        xh = xw.view(-1, H, C)
+        al = (xh * self.att_l).sum(dim=-1)
+        ar = (xh * self.att_r).sum(dim=-1)
+        return gat_propagate(xw, al, ar, graph.inc, H, self.negative_slope, self.concat, bias=self.bias, act=act, p=p)
+
+    def __repr__(self):
+        return "{}({}, {}, heads={})".format(self.__class__.__name__, self.in_channels, self.out_channels, self.heads)
+
+
+class CEGAT(nn.Module):
+    """Reference models.py:131-183: ``GATConv(in, hid, heads)``, ``GATConv(heads * hid, hid)`` x (L - 2),
+    ``GATConv(heads * hid, out, heads=output_heads, concat=False)`` (two convs at L = 1) over the clique expansion's pairs
+    (``data.edge_index`` from ``ConstructV2V`` + ``norm_contruction(TYPE='V2V')``; ``data.norm`` is ignored, as in the reference).
+    Between convs: ``relu``, the normalisation, dropout -- fused into the hop with ``Identity``; with ``'bn'`` the ``relu`` is, then
+    ``dense.batch_norm`` and ``dense.hash_dropout`` follow, as in :class:`CEGCN`.
+
+    The reference's module fails at its first forward for two families of arguments, refused here at construction:
+    ``num_layers > 2`` with ``heads > 1`` (a middle conv emits ``hid`` columns, the next expects ``heads * hid``) and
+    ``Normalization='bn'`` with ``heads > 1`` (``BatchNorm1d(hid)`` applied to ``heads * hid`` columns)."""
+
+    def __init__(self, in_dim, hid_dim, out_dim, num_layers, heads, output_heads, dropout, Normalization='bn'):
+        super().__init__()
+        bn = Normalization == 'bn'
+        if num_layers > 2 and heads > 1:
+            raise ValueError(f"CEGAT: num_layers={num_layers} with heads={heads} cannot run (in the reference either): the middle "
+                             f"convs emit hid_dim={hid_dim} columns but the conv behind them expects heads * hid_dim={heads * hid_dim}")
+        if bn and heads > 1:
+            raise ValueError(f"CEGAT: Normalization='bn' with heads={heads} cannot run (in the reference either): BatchNorm1d({hid_dim}) "
+                             f"meets the first conv's heads * hid_dim={heads * hid_dim} columns")
+        self.convs = nn.ModuleList()
+        self.normalizations = nn.ModuleList()
+        self.convs.append(GATConv(in_dim, hid_dim, heads))
+        self.normalizations.append(nn.BatchNorm1d(hid_dim) if bn else nn.Identity())
+        for _ in range(num_layers - 2):
+            self.convs.append(GATConv(heads * hid_dim, hid_dim))
+            self.normalizations.append(nn.BatchNorm1d(hid_dim) if bn else nn.Identity())
+        self.convs.append(GATConv(heads * hid_dim, out_dim, heads=output_heads, concat=False))
+        self.dropout = dropout
+        self._graph: Optional[CEGATGraph] = None
+
+    def reset_parameters(self):
+        for layer in self.convs:
+            layer.reset_parameters()
+        for normalization in self.normalizations:
+            if not isinstance(normalization, nn.Identity):
+                normalization.reset_parameters()
+
+    def graph(self, data, x: Tensor) -> CEGATGraph:
+        """The attention graph of ``data``, built on first sight and kept (with the tensors it came from) for later forwards."""
+        if self._graph is None or not self._graph.matches(data.edge_index, x.shape[0]):
+            self._graph = CEGATGraph(data.edge_index, x.shape[0])
         return self._graph
 
     def forward(self, data):

@@ -463,3 +463,66 @@ def scaled_propagate(x: Tensor, inc: Incidence, direction: str, r: Optional[Tens
     if act not in ops.HCONV_ACTS:
         raise ValueError(f"scaled_propagate: act must be None, 'relu' or 'elu', got {act!r}")
     return _ScaledPropagate.apply(x, bias, inc, direction == "v2e", r, s, act, float(p))
+
+
+# ---- GAT attention hop of the clique-expansion baseline CEGAT (csrc/gat.hip) ----------------------------------------------------
+class _GatPropagate(torch.autograd.Function):
+    """``y = drop_p(act(concat_h or mean_h softmax_j(lrelu(al[s_j] + ar[t])) x[s_j] + bias))`` -- one kernel forward.  Backward:
+    the epilogue's kernel (only when there is an epilogue), one pass over the target rows for the softmax statistics and the whole
+    of ``gar``, one gather pass over the source-major CSR for ``gx`` and ``gal``.  Saved: ``x``, ``al``, ``ar``, ``y``, the
+    positive-logit part of the aggregate (``aggpos`` [n, H*C], ``ppos`` [n, H]), ``m``, ``l``, and -- head-mean form only -- the
+    aggregate itself (the concat form rebuilds it from ``y``, ``bias`` and the mask)."""
+
+    @staticmethod
+    def forward(ctx, x, al, ar, bias, inc, heads, slope, concat, act, p):
+        from . import dense
+        if x.shape[0] != inc.n_src:
+            raise _lib.AllSetHipError(f"gat_propagate: x has {x.shape[0]} rows, the graph gathers from {inc.n_src}")
+        seed = dense._draw_seed() if p > 0.0 else 0
+        base = dense._seed_base() if p > 0.0 else None
+        want = any(ctx.needs_input_grad[:4])
+        y, agg, aggpos, ppos, m, l = ops.gat_fwd(inc.by_dst, x, al, ar, heads, slope, inc.n_dst, concat, bias, act, p, seed, base,
+                                                 want_grad=want)
+        epi = act is not None or p > 0.0 or bias is not None
+        ctx.save_for_backward(x, al, ar, y if (epi or concat) else None, agg, aggpos, ppos, m, l)
+        ctx.cfg = (inc, heads, slope, concat, act, p, seed, base, epi)
+        ctx.bias_param = bias
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        from . import dense
+        x, al, ar, y, agg, aggpos, ppos, m, l = ctx.saved_tensors
+        inc, heads, slope, concat, act, p, seed, base, epi = ctx.cfg
+        need_b = ctx.bias_param is not None and ctx.needs_input_grad[3]
+        gb = None
+        if epi:
+            g, part = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=need_b)
+            if need_b:
+                # (inside dense.deferred_param_grads(): queued for the step's one batched reduction, and None here)
+                (gb,) = dense._defer_or_reduce(part, [(ctx.bias_param, 0, (y.shape[1],))], defer=True)
+        else:
+            g = gy
+        if concat:
+            stats, gar = ops.gat_bwd_stats(g, aggpos, ppos, m, l, slope, y=y, bias=ctx.bias_param, p=p)
+        else:
+            g = (g * (1.0 / heads)).repeat(1, heads)                   # the head mean's backward: g / H to every head
+            stats, gar = ops.gat_bwd_stats(g, aggpos, ppos, m, l, slope, agg=agg)
+        gx, gal = ops.gat_bwd_src(inc.by_src, x, al, ar, g, stats, slope)
+        return gx, gal, gar, gb, None, None, None, None, None, None
+
+
+def gat_propagate(x: Tensor, al: Tensor, ar: Tensor, inc: Incidence, heads: int, negative_slope: float = 0.2, concat: bool = True,
+                  bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+    """One GAT hop (torch_geometric 1.6.3 ``GATConv.propagate`` + bias, without attention dropout) over ``inc`` (sources -> targets;
+    ``inc.n_dst`` output rows): with ``e_j = leaky_relu(al[s_j, h] + ar[t, h])`` and ``p_j`` its softmax over the edges into ``t``,
+    ``agg[t, h] = sum_j p_j x[s_j, h]``; ``y = drop_p(act(agg + bias))`` with the heads side by side (``concat``) or averaged.
+    ``x`` [n_src, heads * C], ``al`` [n_src, heads], ``ar`` [n_dst, heads]; ``act`` None / 'relu'; ``p`` the dropout probability on
+    the OUTPUT (the library's hash mask).  Differentiable in ``x``, ``al``, ``ar`` and ``bias``."""
+    if act not in ops.GAT_ACTS:
+        raise ValueError(f"gat_propagate: act must be None or 'relu', got {act!r}")
+    _lib.require_device(x, al, ar)
+    if al.dtype != torch.float32 or ar.dtype != torch.float32:
+        al, ar = al.float(), ar.float()
+    return _GatPropagate.apply(x, al, ar, bias, inc, int(heads), float(negative_slope), bool(concat), act, float(p))

@@ -628,3 +628,94 @@ def hconv_bwd_epi(gy: Tensor, y: Tensor, act: Optional[str], p: float, seed: int
         check(lib.allset_hconv_bwd_epi(ptr(gy), _ld(gy), ptr(y), _ld(y), HCONV_ACTS[act], float(p), int(seed), ptr(seed_base),
                                        ptr(g), max(d, 1), ptr(part), P, M, n, d, stream_of(dev)), "allset_hconv_bwd_epi")
     return g, part
+
+
+# ---- GAT attention hop of the clique-expansion baseline CEGAT (csrc/gat.hip) ----------------------------------------------------
+GAT_ACTS = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "relu": _lib.ACT_RELU}
+GAT_MAX_HEADS, GAT_MAX_WIDTH = 64, 512
+
+
+def _gat_order(csr: CSR, n_rows: int) -> Optional[Tensor]:
+    return csr.row_order if (csr.row_order is not None and csr.row_order.numel() == n_rows) else None
+
+
+def gat_fwd(csr: CSR, x: Tensor, al: Tensor, ar: Tensor, heads: int, slope: float, n_t: int, concat: bool = True,
+            bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0, seed: int = 0,
+            seed_base: Optional[Tensor] = None, want_grad: bool = False):
+    """One GAT hop over ``csr`` (rows = targets, the first ``n_t`` of them): ``(y, agg, aggpos, ppos, m, l)``.  ``x`` f32[n_s, H*C],
+    ``al`` f32[n_s, H], ``ar`` f32[n_t, H].  ``agg`` (the pre-epilogue rows) only in the head-mean form with ``want_grad``;
+    ``aggpos`` / ``ppos`` (the positive-logit part of ``agg`` and of the softmax mass) only with ``want_grad``.  fp32 only."""
+    dev = require_device(csr.rowptr, x, al, ar, bias)
+    for t, what in ((x, "x"), (al, "al"), (ar, "ar"), (bias, "bias")):
+        if t is not None:
+            _f32(t, f"gat_fwd {what}")
+    x, al, ar = _rowmajor(x), al.contiguous(), ar.contiguous()
+    bias = bias.contiguous() if bias is not None else None
+    n_s, d = x.shape
+    H = int(heads)
+    if H < 1 or d % H != 0 or d == 0:
+        raise _lib.AllSetHipError(f"gat_fwd: width {d} does not split into {H} heads")
+    C = d // H
+    if tuple(al.shape) != (n_s, H) or tuple(ar.shape) != (n_t, H):
+        raise _lib.AllSetHipError(f"gat_fwd: al {tuple(al.shape)} / ar {tuple(ar.shape)} against ({n_s}, {H}) / ({n_t}, {H})")
+    width = d if concat else C
+    if bias is not None and bias.numel() != width:
+        raise _lib.AllSetHipError(f"gat_fwd: bias has {bias.numel()} entries for width {width}")
+    if n_t > csr.n_rows or csr.n_cols > n_s:
+        raise _lib.AllSetHipError(f"gat_fwd: CSR of {csr.n_rows} x {csr.n_cols} against {n_t} outputs / {n_s} gathered rows")
+    y = torch.empty((n_t, width), dtype=torch.float32, device=dev)
+    m = torch.empty((n_t, H), dtype=torch.float32, device=dev)
+    l = torch.empty((n_t, H), dtype=torch.float32, device=dev)
+    agg = torch.empty((n_t, d), dtype=torch.float32, device=dev) if (want_grad and not concat) else None
+    aggpos = torch.empty((n_t, d), dtype=torch.float32, device=dev) if want_grad else None
+    ppos = torch.empty((n_t, H), dtype=torch.float32, device=dev) if want_grad else None
+    nnz = csr.col.numel()
+    algo = nnz * (4 * d + 4 * H + 4) + (n_t + 1) * 4 + n_t * (4 * width + 12 * H) + (n_t * (4 * d + 4 * H) if want_grad else 0) \
+        + (n_t * 4 * d if agg is not None else 0)
+    with on_device(dev), _timed("gat_fwd", dev, algo):
+        check(_lib.load().allset_gat_fwd(1, nnz, ptr(_gat_order(csr, n_t)), ptr(csr.rowptr), ptr(csr.col), ptr(al), ptr(ar), ptr(x),
+                                         _ld(x), float(slope), ptr(bias), GAT_ACTS[act], float(p), int(seed), ptr(seed_base),
+                                         1 if concat else 0, ptr(y), max(width, 1), ptr(agg), d, ptr(aggpos), d, ptr(ppos), ptr(m),
+                                         ptr(l), n_t, n_s, H, C, stream_of(dev)), "allset_gat_fwd")
+    return y, agg, aggpos, ppos, m, l
+
+
+def gat_bwd_stats(g: Tensor, aggpos: Tensor, ppos: Tensor, m: Tensor, l: Tensor, slope: float, agg: Optional[Tensor] = None,
+                  y: Optional[Tensor] = None, bias: Optional[Tensor] = None, p: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """``(stats [n_t, H, 2] = {m + log(l + 1e-16), <agg, g>}, gar [n_t, H])`` from the gradient ``g`` at ``agg``.  ``agg`` as saved by
+    the head-mean forward, or None: rebuilt from the concat form's ``y``, ``bias`` and ``p`` wherever ``g != 0``."""
+    dev = require_device(g, aggpos, ppos, m, l, agg, y, bias)
+    _f32(g, "gat_bwd_stats")
+    g = _rowmajor(g)
+    n_t, d = g.shape
+    H = m.shape[1]
+    if agg is None and y is None:
+        raise _lib.AllSetHipError("gat_bwd_stats: give agg, or the forward's y to rebuild it from")
+    src = agg if agg is not None else y
+    if tuple(src.shape) != (n_t, d) or tuple(aggpos.shape) != (n_t, d):
+        raise _lib.AllSetHipError(f"gat_bwd_stats: g {tuple(g.shape)} against rows of shape {tuple(src.shape)} / {tuple(aggpos.shape)}")
+    stats = torch.empty((n_t, H, 2), dtype=torch.float32, device=dev)
+    gar = torch.empty((n_t, H), dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("gat_bwd_stats", dev, 3 * n_t * d * 4 + n_t * H * 24):
+        check(_lib.load().allset_gat_bwd_stats(ptr(y), _ld(y) if y is not None else d, ptr(bias), float(p), ptr(agg), d, ptr(aggpos), d,
+                                               ptr(ppos), ptr(g), _ld(g), ptr(m), ptr(l), float(slope), ptr(stats), ptr(gar), n_t, H,
+                                               d // H, stream_of(dev)), "allset_gat_bwd_stats")
+    return stats, gar
+
+
+def gat_bwd_src(csrT: CSR, x: Tensor, al: Tensor, ar: Tensor, g: Tensor, stats: Tensor, slope: float) -> Tuple[Tensor, Tensor]:
+    """``(gx [n_s, H*C], gal [n_s, H])`` in one gather pass over ``csrT`` (rows = sources, cols = targets)."""
+    dev = require_device(csrT.rowptr, x, al, ar, g, stats)
+    x, g, al, ar = _rowmajor(x), _rowmajor(g), al.contiguous(), ar.contiguous()
+    n_s, d = x.shape
+    n_t, H = ar.shape
+    if n_s > csrT.n_rows or csrT.n_cols > n_t or g.shape[0] != n_t or g.shape[1] != d:
+        raise _lib.AllSetHipError(f"gat_bwd_src: CSR of {csrT.n_rows} x {csrT.n_cols} against {n_s} sources / g {tuple(g.shape)}")
+    gx = torch.empty((n_s, d), dtype=torch.float32, device=dev)
+    gal = torch.empty((n_s, H), dtype=torch.float32, device=dev)
+    nnz = csrT.col.numel()
+    with on_device(dev), _timed("gat_bwd_src", dev, nnz * (4 * d + 12 * H + 4) + (n_s + 1) * 4 + n_s * (8 * d + 8 * H)):
+        check(_lib.load().allset_gat_bwd_src(1, nnz, ptr(_gat_order(csrT, n_s)), ptr(csrT.rowptr), ptr(csrT.col), ptr(al), ptr(ar),
+                                             ptr(x), _ld(x), ptr(g), _ld(g), ptr(stats), float(slope), ptr(gx), d, ptr(gal), n_s, n_t,
+                                             H, d // H, stream_of(dev)), "allset_gat_bwd_src")
+    return gx, gal

@@ -13,8 +13,8 @@ HyperGCN on-disk format the reference's ``load_citation_dataset`` consumes (``fe
 ``--raw_data_dir`` points at it, and otherwise generates ``--dname synthetic`` (a planted-partition hypergraph with
 noisy class-indicator features).  Of the reference's baselines, the hypergraph convolutions HGNN, HCHA and HNHN are
 built (``allset_amd/baselines.py``; same preprocessing branches, train.py:375-388, and the same ``--HCHA_symdegnorm`` /
-``--HNHN_*`` flags), and so is the clique-expansion CEGCN (branch :354-357, ``--normalization``); CEGAT is not built yet, and
-HyperGCN, UniGCNII and MLP are out of scope; all four are rejected.
+``--HNHN_*`` flags), and so are the clique-expansion CEGCN and CEGAT (branch :354-357, ``--normalization``; CEGAT also ``--heads`` /
+``--output_heads``); HyperGCN, UniGCNII and MLP are out of scope and rejected.
 
     python -m allset_amd.train --method AllSetTransformer --dname synthetic --epochs 50 --runs 2 --heads 4 \\
         --MLP_hidden 128 --All_num_layers 1
@@ -43,7 +43,7 @@ from .preprocessing import (Add_Self_Loops, ConstructV2V, ExtractV2E, expand_edg
 
 ALLSET_METHODS = ('AllSetTransformer', 'AllDeepSets')
 BASELINE_METHODS = ('HGNN', 'HCHA', 'HNHN')
-CE_METHODS = ('CEGCN',)
+CE_METHODS = ('CEGCN', 'CEGAT')
 
 
 # --------------------------------------------------------------------------------------------------
@@ -382,11 +382,17 @@ def build_model(args, data):
         from .baselines import CEGCN
         return CEGCN(in_dim=args.num_features, hid_dim=args.MLP_hidden, out_dim=args.num_classes, num_layers=args.All_num_layers,
                      dropout=args.dropout, Normalization=args.normalization)
+    if args.method == 'CEGAT':
+        ei = getattr(data, 'edge_index', None) if data is not None else None
+        if not getattr(data, 'clique_expansion', False) or not torch.is_tensor(ei) or ei.dim() != 2 or ei.shape[0] != 2 \
+                or ei.dtype.is_floating_point:
+            raise ValueError("method 'CEGAT' attends over the clique expansion's [2, E] integer edge_index: pass data through "
+                             "train.preprocess (ExtractV2E -> ConstructV2V -> norm_contruction(TYPE='V2V')) before build_model")
+        from .baselines import CEGAT
+        return CEGAT(in_dim=args.num_features, hid_dim=args.MLP_hidden, out_dim=args.num_classes, num_layers=args.All_num_layers,
+                     heads=args.heads, output_heads=args.output_heads, dropout=args.dropout, Normalization=args.normalization)
     if args.method in ALLSET_METHODS:
         return parse_method(args, data)
-    if args.method == 'CEGAT':
-        raise ValueError("method 'CEGAT' is not built yet (its GAT attention kernel is open work; CEGCN runs on the same "
-                         "clique-expansion branch)")
     raise ValueError(f"method {args.method!r}: only {ALLSET_METHODS + BASELINE_METHODS + CE_METHODS} are built "
                      "(HyperGCN, UniGCNII and MLP are out of scope)")
 
@@ -482,12 +488,12 @@ def load_data(args) -> HypergraphData:
 def preprocess(args, data: HypergraphData) -> HypergraphData:
     """The AllSet branch of reference train.py:344-353, and the HNHN / HCHA / HGNN branches (:375-388): hyperedge ids re-based to 0,
     HNHN's norms computed before the re-base; HCHA's scales are computed here too (the reference derives them per forward); and the
-    clique-expansion branch of CEGCN (:354-357: no self-loop hyperedges there, whatever ``--add_self_loop`` says)."""
+    clique-expansion branch of CEGCN / CEGAT (:354-357: no self-loop hyperedges there, whatever ``--add_self_loop`` says)."""
     if args.method in CE_METHODS:
         data = ExtractV2E(data)
         data = ConstructV2V(data)
         data = norm_contruction(data, TYPE='V2V')
-        data.clique_expansion = True                        # what build_model checks for CEGCN
+        data.clique_expansion = True                        # what build_model checks for CEGCN / CEGAT
         return data
     if args.method in BASELINE_METHODS:
         data = ExtractV2E(data)

@@ -772,6 +772,48 @@ int allset_clique_emit(const int32_t* rowptr, const int32_t* member, const int32
 int allset_gcn_norm(const int64_t* src, const int64_t* dst, const float* m, int64_t n_pairs, int64_t n, float* deg,
                     int64_t* src_out, int64_t* dst_out, float* w, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Clique-expansion baseline CEGAT (reference models.py:131-183): the attention hop of torch_geometric 1.6.3's GATConv.
+ * Added under ABI 15, additions only; detect with allset_gat_supported() (returns 1).  fp32, row-major.  H heads of C channels,
+ * H <= 64, H * C <= 512 (ALLSET_ERR_UNSUPPORTED beyond).  x f32[n_s, H*C], al f32[n_s, H], ar f32[n_t, H] (both dense, pitch H).
+ *
+ * allset_gat_fwd over a CSR whose rows are targets:
+ *   e_j = leaky_relu(al[col[j], h] + ar[t, h], slope);  m[t,h] = max_j e_j;  l[t,h] = sum_j exp(e_j - m[t,h])
+ *   agg[t,h,:] = sum_j exp(e_j - m[t,h]) / (l[t,h] + 1e-16) * x[col[j],h,:]            (empty row: agg = 0, m = l = 0)
+ *   concat != 0:  y[t, 0..H*C) = drop_p(act(agg[t,:] + bias[H*C]))
+ *   concat == 0:  y[t, 0..C)   = drop_p(act(mean_h agg[t,h,:] + bias[C]))
+ * act: ALLSET_HCONV_ACT_NONE / _RELU.  bias may be NULL.  Dropout as in allset_hconv_fwd: hash of (seed, t * width + c) with width
+ * the row width of y; seed_base may be NULL.  m, l: f32[n_t, H], always written.  agg (f32[n_t, ldagg], may be NULL): the
+ * pre-epilogue rows, written in the head-mean form only (in the concat form the backward rebuilds them from y).  aggpos
+ * (f32[n_t, ldpos]) and ppos (f32[n_t, H]), both or neither: the part of agg, and of sum_j p_j, that comes from incidences with
+ * e_j > 0 -- what allset_gat_bwd_stats needs; NULL when no gradient will be asked for.  variant: 0 / 1 one wavefront per row
+ * (row_order int32[n_t] or NULL is its processing order); 2, a short-row kernel, is not built (ALLSET_ERR_UNSUPPORTED).
+ *
+ * allset_gat_bwd_stats: from g = the gradient at agg (f32[n_t, H*C]; after allset_hconv_bwd_epi, and for the head-mean form
+ * broadcast over the heads and divided by H), stats[t,h] = {m + log(l + 1e-16), delta = <agg[t,h,:], g[t,h,:]>} (f32[n_t, H, 2],
+ * 8-byte aligned) and the target-term gradient
+ *   gar[t,h] = sum_j p_j lrelu'(al[col[j],h] + ar[t,h]) (<x[col[j],h,:], g[t,h,:]> - delta)
+ *            = (1 - slope) * (<aggpos[t,h,:], g[t,h,:]> - delta * ppos[t,h])                      (lrelu'(0) = slope)
+ * in one pass over the rows: no per-incidence gradient, no atomics.  agg != NULL: read from there; agg == NULL: rebuilt as
+ * y * (1 - p) - bias wherever g != 0 (y, bias, p of the concat-form forward call).
+ *
+ * allset_gat_bwd_src over the transposed CSR (rows = sources, colT = targets), one gather pass:
+ *   gx[s,h,:] = sum_j p_j g[t_j,h,:]      gal[s,h] = sum_j p_j lrelu'(al[s,h] + ar[t_j,h]) (<x[s,h,:], g[t_j,h,:]> - delta[t_j,h])
+ * with p_j = exp(e_j - stats[t_j,h,0]).  Every sum has a fixed order: results are bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------- */
+int allset_gat_supported(void);
+int allset_gat_fwd(int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col, const float* al,
+                   const float* ar, const float* x, int64_t ldx, float slope, const float* bias, int act, float p, uint64_t seed,
+                   const uint64_t* seed_base, int concat, float* y, int64_t ldy, float* agg, int64_t ldagg, float* aggpos,
+                   int64_t ldpos, float* ppos, float* m, float* l, int64_t n_t, int64_t n_s, int64_t H, int64_t C, void* stream);
+int allset_gat_bwd_stats(const float* y, int64_t ldy, const float* bias, float p, const float* agg, int64_t ldagg,
+                         const float* aggpos, int64_t ldpos, const float* ppos, const float* g, int64_t ldg, const float* m,
+                         const float* l, float slope, float* stats, float* gar, int64_t n_t, int64_t H, int64_t C, void* stream);
+int allset_gat_bwd_src(int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptrT, const int32_t* colT,
+                       const float* al, const float* ar, const float* x, int64_t ldx, const float* g, int64_t ldg,
+                       const float* stats, float slope, float* gx, int64_t ldgx, float* gal, int64_t n_s, int64_t n_t, int64_t H,
+                       int64_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
