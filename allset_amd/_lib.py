@@ -234,6 +234,10 @@ SIGNATURES = {
                              c_int64, c_int64, _P],
     "allset_gat_bwd_src": [c_int, c_int64, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_float, _P, c_int64, _P, c_int64, c_int64,
                            c_int64, c_int64, _P],
+    # UniGCNII baseline: the E->V hop with the initial-residual step (under ABI 15, additions only; detect with allset_unigcn_supported)
+    "allset_unigcn_supported": [],
+    "allset_unigcn_hop_fwd": [c_int, c_int64, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_float, c_int, _P, c_int64, _P, c_int64, c_int64,
+                              c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

@@ -12,11 +12,18 @@ The clique-expansion baseline ``GCNConv`` / ``CEGCN`` (reference models.py:80-12
 (``functional.weighted_propagate``).  Its attention sibling ``GATConv`` / ``CEGAT`` (reference models.py:131-183) runs over the same
 pairs, without weights and with one loop on every vertex, through the softmax-attention hop ``functional.gat_propagate``
 (csrc/gat.hip).
+
+``UniGCNIIConv`` / ``UniGCNII`` (reference models.py:911-996) run over the same V-E incidence as the AllSet layers: per layer a V->E
+mean (``scaled_propagate`` with ``degE / |e|``), then the E->V sum with ``degV``, the optional row normalisation and GCNII's initial
+residual in one launch (``functional.unigcn_hop``, csrc/unigcn.hip), then the identity-mapping step as one GEMM with the folded
+weight ``(1 - beta) I + beta W`` and the one-pass ``relu`` + dropout.
 """
 from __future__ import annotations
 
 from types import SimpleNamespace
 from typing import Optional
+
+import math
 
 import torch
 import torch.nn as nn
@@ -24,7 +31,7 @@ from torch.nn import Parameter
 
 from . import dense
 from ._lib import AllSetHipError
-from .functional import gat_propagate, scaled_propagate, weighted_propagate
+from .functional import gat_propagate, initial_residual, scaled_propagate, unigcn_hop, weighted_propagate
 from .incidence import Incidence, cached_incidence
 from .layers import _linear, glorot, zeros
 from .preprocessing import generate_norm_HCHA
@@ -440,3 +447,121 @@ class HNHN(nn.Module):
         for conv in self.convs[:-1]:
             x = conv(x, data, inc=inc, act='relu', p=p)
         return self.convs[-1](x, data, inc=inc)
+
+
+class UniGraph:
+    """What a UniGCNII forward propagates over: the vertex-hyperedge ``Incidence`` of the (sorted, de-duplicated) pairs ``V``, ``E``
+    and the degree scales as flat device vectors -- ``degV`` [N], and ``scaleE`` [M] = ``degE / |e|`` (the V->E mean and the ``degE``
+    factor as one per-row scale).  Built once; holds strong references to every tensor a captured graph reads."""
+
+    def __init__(self, V: Tensor, E: Tensor, degV: Tensor, degE: Tensor, device):
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise AllSetHipError("the UniGCNII baseline runs on ROCm device fp32 tensors (no CPU path)")
+        self.V, self.E, self.degV_arg, self.degE_arg = V, E, degV, degE
+        n, m = degV.shape[0], degE.shape[0]
+        self.edge_index = torch.stack([V.reshape(-1), E.reshape(-1)]).to(device=device, dtype=torch.int64).contiguous()
+        self.inc = Incidence.from_edge_index(self.edge_index, n_src=n, n_dst=m)
+        self.degV = degV.to(device=device, dtype=torch.float32).reshape(-1).contiguous()
+        rp = self.inc.by_dst.rowptr
+        size = (rp[1:] - rp[:-1]).clamp(min=1).to(torch.float32)
+        self.scaleE = (degE.to(device=device, dtype=torch.float32).reshape(-1) / size).contiguous()
+        self.device = device
+
+    def matches(self, V, E, degV, degE, device) -> bool:
+        return self.V is V and self.E is E and self.degV_arg is degV and self.degE_arg is degE and self.device == torch.device(device)
+
+
+def _unignn_scales(args):
+    degV, degE = getattr(args, 'UniGNN_degV', None), getattr(args, 'UniGNN_degE', None)
+    if not (torch.is_tensor(degV) and torch.is_tensor(degE)):
+        raise ValueError("UniGCNII: args.UniGNN_degV / args.UniGNN_degE are missing (preprocessing.generate_norm_UniGNN computes them)")
+    return degV, degE
+
+
+class UniGCNIIConv(nn.Module):
+    """Reference models.py:911-944: ``Xe = degE * mean_{v in e} X[v]``, ``Xv = degV * sum_{e ni v} Xe[e]`` (row-normalised with a
+    detached norm under ``args.UniGNN_use_norm``), ``Xi = (1 - alpha) Xv + alpha X0``, ``out = (1 - beta) Xi + beta W(Xi)``.  The last
+    step is ONE GEMM with the folded weight ``(1 - beta) I + beta W``, built by small torch ops that stay in autograd (``W.grad`` is
+    ``beta`` times the folded weight's gradient)."""
+
+    def __init__(self, args, in_features, out_features):
+        super().__init__()
+        self.W = nn.Linear(in_features, out_features, bias=False)
+        self.args = args
+
+    def reset_parameters(self):
+        self.W.reset_parameters()
+
+    def folded_weight(self, beta: float) -> Tensor:
+        w = self.W.weight
+        if w.shape[0] != w.shape[1]:
+            raise ValueError(f"UniGCNIIConv: the identity mapping needs a square W, got {tuple(w.shape)}")
+        return torch.eye(w.shape[0], dtype=w.dtype, device=w.device).mul_(1.0 - beta).add(w, alpha=beta)
+
+    def forward(self, X: Tensor, vertex, edges, alpha, beta, X0: Tensor) -> Tensor:
+        """``vertex`` / ``edges``: the pair lists, or a prebuilt :class:`UniGraph` as ``vertex`` (``edges`` is then ignored)."""
+        if isinstance(vertex, UniGraph):
+            graph = vertex
+        else:
+            degV, degE = _unignn_scales(self.args)
+            graph = UniGraph(vertex, edges, degV, degE, X.device)
+        Xe = scaled_propagate(X, graph.inc, 'v2e', s=graph.scaleE)
+        Xi = unigcn_hop(Xe, X0, graph.inc, graph.degV, alpha, bool(getattr(self.args, 'UniGNN_use_norm', False)))
+        return dense.linear(Xi, self.folded_weight(beta), None)
+
+
+class UniGCNII(nn.Module):
+    """Reference models.py:948-996: ``Linear(nfeat, d)`` with ``d = nhid * nhead``, ``nlayer`` :class:`UniGCNIIConv` of width ``d``,
+    ``Linear(d, nclass)``; dropout 0.2 on the input, before every conv and before the last Linear, ``alpha`` = 0.1, ``lamda`` = 0.5
+    (``beta_i = log(lamda / (i + 1) + 1)``), whatever ``--dropout`` says.  ``V`` / ``E``: the sorted, de-duplicated pairs of
+    ``preprocessing.ConstructH_pairs``; the degree scales are read from ``args.UniGNN_degV`` / ``UniGNN_degE``.  The ``relu`` behind a
+    conv and the dropout in front of the next layer are one pass (``dense.relu_dropout``); training-mode masks are the library's hash
+    dropout.  ``reg_params`` (the conv weights) and ``non_reg_params`` (first and last Linear) are the reference's two optimizer groups."""
+
+    def __init__(self, args, nfeat, nhid, nclass, nlayer, nhead, V, E):
+        super().__init__()
+        self.args = args
+        self.V = V
+        self.E = E
+        nhid = nhid * nhead
+        self.act = nn.ReLU()
+        self.input_drop = nn.Dropout(0.6)
+        self.dropout = nn.Dropout(0.2)
+        self.convs = nn.ModuleList()
+        self.convs.append(nn.Linear(nfeat, nhid))
+        for _ in range(nlayer):
+            self.convs.append(UniGCNIIConv(args, nhid, nhid))
+        self.convs.append(nn.Linear(nhid, nclass))
+        self.reg_params = list(self.convs[1:-1].parameters())
+        self.non_reg_params = list(self.convs[0:1].parameters()) + list(self.convs[-1:].parameters())
+        self._graph: Optional[UniGraph] = None
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+
+    def graph(self, x: Tensor) -> UniGraph:
+        """The incidence and scales on ``x``'s device, built on first sight and kept for later forwards."""
+        degV, degE = _unignn_scales(self.args)
+        if self._graph is None or not self._graph.matches(self.V, self.E, degV, degE, x.device):
+            if degV.shape[0] != x.shape[0]:
+                raise ValueError(f"UniGCNII: args.UniGNN_degV has {degV.shape[0]} rows, data.x has {x.shape[0]}")
+            self._graph = UniGraph(self.V, self.E, degV, degE, x.device)
+        return self._graph
+
+    def forward(self, data):
+        x = data.x
+        if not (x.is_cuda and x.dtype == torch.float32):
+            raise AllSetHipError("the UniGCNII baseline runs on ROCm device fp32 tensors (no CPU path)")
+        graph = self.graph(x)
+        lamda, alpha = 0.5, 0.1
+        p = float(self.dropout.p) if self.training else 0.0
+        x = dense.hash_dropout(x, p, self.training)
+        x0 = initial_residual(dense.relu_dropout(_linear(self.convs[0], x), 0.0))
+        x = dense.hash_dropout(x0, p, self.training)
+        for i, conv in enumerate(self.convs[1:-1]):
+            beta = math.log(lamda / (i + 1) + 1)
+            # relu, and the dropout in front of the next layer (the next conv, or the last Linear), in one pass
+            x = dense.relu_dropout(conv(x, graph, None, alpha, beta, x0), p)
+        return _linear(self.convs[-1], x)

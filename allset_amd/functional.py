@@ -526,3 +526,109 @@ def gat_propagate(x: Tensor, al: Tensor, ar: Tensor, inc: Incidence, heads: int,
     if al.dtype != torch.float32 or ar.dtype != torch.float32:
         al, ar = al.float(), ar.float()
     return _GatPropagate.apply(x, al, ar, bias, inc, int(heads), float(negative_slope), bool(concat), act, float(p))
+
+
+# ---- UniGCNII: the E->V hop with GCNII's initial-residual step (csrc/unigcn.hip) ---------------------------------------------------
+class _GradSink:
+    """Where the hops of one forward add their ``alpha * gXi`` in place: ``x0`` feeds every layer, its gradient is one buffer."""
+
+    def __init__(self):
+        self.acc: Optional[Tensor] = None
+
+    def add(self, g: Tensor, alpha: float) -> None:
+        if self.acc is None:
+            self.acc = g * alpha
+        else:
+            self.acc.add_(g, alpha=alpha)
+
+
+class _InitialResidual(torch.autograd.Function):
+    """Identity on ``x0`` whose output carries a :class:`_GradSink`.  Every ``unigcn_hop`` that reads the output is a dependency of
+    this node, so its backward runs after theirs and hands the accumulated buffer (plus whatever autograd itself summed from other
+    uses of the output) to ``x0``."""
+
+    @staticmethod
+    def forward(ctx, x0, sink):
+        ctx.sink = sink
+        ctx.set_materialize_grads(False)
+        return x0.view_as(x0)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        acc, ctx.sink.acc = ctx.sink.acc, None
+        if acc is None:
+            return g, None
+        if g is not None:
+            acc.add_(g)
+        return acc, None
+
+
+def initial_residual(x0: Tensor) -> Tensor:
+    """``x0`` for the hops of one UniGCNII forward: they accumulate its gradient in place instead of returning one tensor each."""
+    if not (torch.is_grad_enabled() and x0.requires_grad):
+        return x0
+    sink = _GradSink()
+    out = _InitialResidual.apply(x0, sink)
+    out._allset_grad_sink = sink
+    return out
+
+
+class _UniGCNHop(torch.autograd.Function):
+    """``Xi = (1 - alpha) * t * degV * (H Xe) + alpha * x0`` with ``t`` the detached row-norm scale -- one kernel forward where the
+    width is built (``ops.unigcn_hop_supported``), else the ``hconv`` launch plus torch ops.  Backward: ``gXe`` is the ``hconv``
+    launch over the hyperedge-major CSR with ``r = (1 - alpha) * degV * t`` (``t`` saved, a constant); ``gx0 = alpha * gXi``,
+    added in place to the sink of :func:`initial_residual` when ``x0`` came from there."""
+
+    @staticmethod
+    def forward(ctx, xe, x0, inc, degV, alpha, use_norm, sink, variant):
+        n_v = inc.n_src
+        if xe.shape[0] != inc.n_dst:
+            raise _lib.AllSetHipError(f"unigcn_hop: xe has {xe.shape[0]} rows, the incidence has {inc.n_dst} hyperedges")
+        if ops.unigcn_hop_supported(xe, x0):
+            xi, t = ops.unigcn_hop_fwd(inc.by_src, xe, x0, n_v, degV, alpha, use_norm, variant)
+        else:                                                    # width not built: correct, unfused
+            a = ops.hconv_propagate(inc.by_src, xe, n_v, s=degV)
+            t = None
+            if use_norm:
+                nrm = a.norm(dim=1)
+                t = torch.where(nrm > 0, 1.0 / nrm, torch.zeros_like(nrm))
+                a = a * t.unsqueeze(1)
+            xi = torch.add(x0 * alpha, a, alpha=1.0 - alpha)
+        ctx.save_for_backward(t)
+        ctx.cfg = (inc, degV, alpha, sink)
+        return xi
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (t,) = ctx.saved_tensors
+        inc, degV, alpha, sink = ctx.cfg
+        g = g.contiguous()
+        gxe = gx0 = None
+        if ctx.needs_input_grad[0]:
+            r = degV * (1.0 - alpha) if t is None else degV * t * (1.0 - alpha)
+            gxe = ops.hconv_propagate(inc.by_dst, g, inc.n_dst, r=r)
+        if ctx.needs_input_grad[1]:
+            if sink is not None:
+                sink.add(g, alpha)
+            else:
+                gx0 = g * alpha
+        return gxe, gx0, None, None, None, None, None, None
+
+
+def unigcn_hop(xe: Tensor, x0: Tensor, inc: Incidence, degV: Tensor, alpha: float, use_norm: bool, variant: Optional[int] = None) -> Tensor:
+    """The E->V hop of a UniGCNII layer over ``inc`` (sources = vertices, targets = hyperedges) with GCNII's initial residual:
+    ``a[v] = degV[v] * sum_{e ni v} xe[e]``, ``t[v] = 1 / ||a[v]||`` (0 for a zero row; a constant of the backward, as the reference's
+    ``normalize_l2``) when ``use_norm`` else 1, ``Xi[v] = (1 - alpha) * t[v] * a[v] + alpha * x0[v]``.  ``xe`` [n_dst, d], ``x0``
+    [n_src, d], ``degV`` [n_src] (or [n_src, 1]).  Device fp32 only.  Differentiable in ``xe`` and ``x0``.  ``variant``: kernel
+    variant override (tests)."""
+    _lib.require_device(xe, x0, degV)
+    if xe.dtype != torch.float32 or x0.dtype != torch.float32:
+        raise _lib.AllSetHipError("unigcn_hop: fp32 tensors only")
+    degV = degV.reshape(-1)
+    if degV.dtype != torch.float32 or degV.numel() != inc.n_src or x0.shape[0] != inc.n_src or x0.shape[1] != xe.shape[1]:
+        raise _lib.AllSetHipError(f"unigcn_hop: degV {tuple(degV.shape)} {degV.dtype} / x0 {tuple(x0.shape)} do not fit {inc.n_src} "
+                                  f"vertices of width {xe.shape[1]}")
+    sink = getattr(x0, "_allset_grad_sink", None)
+    return _UniGCNHop.apply(xe, x0, inc, degV.contiguous(), float(alpha), bool(use_norm), sink, variant)

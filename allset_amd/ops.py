@@ -719,3 +719,47 @@ def gat_bwd_src(csrT: CSR, x: Tensor, al: Tensor, ar: Tensor, g: Tensor, stats: 
                                              ptr(x), _ld(x), ptr(g), _ld(g), ptr(stats), float(slope), ptr(gx), d, ptr(gal), n_s, n_t,
                                              H, d // H, stream_of(dev)), "allset_gat_bwd_src")
     return gx, gal
+
+
+# ---- UniGCNII: the E->V hop with GCNII's initial-residual step (csrc/unigcn.hip) ---------------------------------------------------
+UNIGCN_MAX_WIDTH = 512
+
+
+def unigcn_hop_supported(xe: Tensor, x0: Tensor) -> bool:
+    """Is the fused launch built for these operands?  fp32, width a multiple of 4 up to 512, 16-byte aligned rows."""
+    d = xe.shape[1]
+    return (xe.dtype == x0.dtype == torch.float32 and 0 < d <= UNIGCN_MAX_WIDTH and d % 4 == 0
+            and all(t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= d and t.data_ptr() % 16 == 0 for t in (xe, x0)))
+
+
+def unigcn_hop_fwd(csr: CSR, xe: Tensor, x0: Tensor, n_t: int, degV: Optional[Tensor], alpha: float, use_norm: bool,
+                   variant: Optional[int] = None) -> Tuple[Tensor, Optional[Tensor]]:
+    """``(xi, t)``: ``xi[v] = (1 - alpha) * t[v] * a[v] + alpha * x0[v]`` with ``a[v] = degV[v] * sum_{j in row v} xe[col_j]`` over
+    ``csr`` (rows = vertices) and ``t[v] = 1 / ||a[v]||`` (0 for a zero row) when ``use_norm``, else ``t`` is None (= ones).  One launch;
+    raises where the width is not built (see :func:`unigcn_hop_supported`)."""
+    dev = require_device(csr.rowptr, xe, x0, degV)
+    _f32(xe, "unigcn_hop_fwd")
+    _f32(x0, "unigcn_hop_fwd x0")
+    xe, x0 = _rowmajor(xe), _rowmajor(x0)
+    n_s, d = xe.shape
+    if x0.shape != (n_t, d):
+        raise _lib.AllSetHipError(f"unigcn_hop_fwd: x0 is {tuple(x0.shape)}, expected {(n_t, d)}")
+    if degV is not None:
+        _f32(degV, "unigcn_hop_fwd degV")
+        degV = degV.contiguous()
+        if degV.numel() < n_t:
+            raise _lib.AllSetHipError(f"unigcn_hop_fwd: degV has {degV.numel()} entries for {n_t} output rows")
+    if n_t > csr.n_rows or csr.n_cols > n_s:
+        raise _lib.AllSetHipError(f"unigcn_hop_fwd: CSR of {csr.n_rows} x {csr.n_cols} against {n_t} outputs / {n_s} gathered rows")
+    xi = torch.empty((n_t, d), dtype=torch.float32, device=dev)
+    t = torch.empty(n_t, dtype=torch.float32, device=dev) if use_norm else None
+    nnz = csr.col.numel()
+    if variant is None:
+        variant = csr.variant("segreduce", n_t) if d <= 256 else 1
+    order = csr.row_order if (variant == 1 and csr.row_order is not None and csr.row_order.numel() == n_t) else None
+    algo = nnz * (4 * d + 4) + (n_t + 1) * 4 + 2 * n_t * 4 * d + n_t * 4 * (1 + int(use_norm))
+    with on_device(dev), _timed("unigcn_hop_fwd", dev, algo):
+        check(_lib.load().allset_unigcn_hop_fwd(variant, nnz, ptr(order), ptr(csr.rowptr), ptr(csr.col), ptr(degV), ptr(xe), _ld(xe),
+                                                ptr(x0), _ld(x0), float(alpha), int(bool(use_norm)), ptr(xi), max(d, 1), ptr(t), n_t,
+                                                n_s, d, stream_of(dev)), "allset_unigcn_hop_fwd")
+    return xi, t

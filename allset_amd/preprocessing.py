@@ -8,6 +8,8 @@ Same function names, ``data`` attributes and results as reference ``src/preproce
 * ``norm_contruction``  (:451-469)  per-incidence ``norm``: 'all_one' (int64 ones) or 'deg_half_sym'
 * ``expand_edge_index`` (:22-144)   "exclude-self" expansion: hyperedge e of size k becomes k hyperedges e_i,
                                      e_i containing every member except the i-th
+* ``ConstructH_pairs``  (:186-203)  ``ConstructH`` as sorted, de-duplicated (vertex, hyperedge) pairs instead of a dense matrix,
+                                     and ``generate_norm_UniGNN`` (train.py:405-412): UniGCNII's degree scales
 
 The reference implements these with Python loops over vertices / hyperedges and ``i not in list`` scans --
 O(n_V * k), minutes at 1M vertices.  Here each is a handful of sorts / bincounts / prefix sums.  Where the
@@ -252,6 +254,49 @@ def generate_norm_HNHN(H, data, args):
     data.D_v_beta = D_v_beta.float()
     data.D_e_beta_inv = _inv0(D_e_beta).float()
     return data
+
+
+# ---- UniGCNII (reference train.py:390-412, preprocessing.py:186-203) ----------------------------------------------------------------
+def ConstructH_pairs(data):
+    """The reference's ``ConstructH`` + ``torch_sparse.from_scipy(csr_matrix(H))`` without the dense 0/1 matrix: the (vertex, hyperedge)
+    pairs of ``data.edge_index`` ([V; E], hyperedge ids anywhere) de-duplicated (a 0/1 matrix holds a repeated pair once), hyperedges
+    renumbered 0..M-1 in the sorted order of the ids that occur, sorted by vertex then hyperedge.  Sets ``data.edge_index`` = the int64
+    ``[V; E]`` pairs and ``data.UniGNN_sizes`` = ``(N, M)`` with N = ``data.x`` rows (vertices in no hyperedge keep their row, as
+    H's zero rows do); returns ``data``."""
+    ei = data.edge_index
+    n = int(data.x.shape[0])
+    if ei.numel() == 0:
+        raise ValueError("ConstructH_pairs: the edge list is empty")
+    if int(ei[0].min()) < 0 or int(ei[0].max()) >= n:
+        raise ValueError(f"ConstructH_pairs: vertex ids span [{int(ei[0].min())}, {int(ei[0].max())}] but data.x has {n} rows")
+    ids, e = torch.unique(ei[1], return_inverse=True)                 # sorted ids -> 0..M-1
+    m = int(ids.numel())
+    key = torch.unique(ei[0].to(torch.int64) * m + e)                 # sorted by (vertex, hyperedge), duplicates once
+    data.edge_index = torch.stack([key // m, key % m]).contiguous()
+    data.UniGNN_sizes = (n, m)
+    return data
+
+
+def generate_norm_UniGNN(data, args):
+    """UniGCNII's degree scales (reference train.py:405-412) from the pairs of :func:`ConstructH_pairs`, in float32 as there:
+    ``degV`` [N, 1] = (number of hyperedges of v)^-1/2 with inf -> 1 (a vertex in no hyperedge), ``degE`` [M, 1] = (mean over the
+    members of e of their hyperedge counts)^-1/2; stored as ``args.UniGNN_degV`` / ``args.UniGNN_degE``.  Also
+    ``data.UniGNN_scaleE`` [M] = ``degE / |e|``: the per-hyperedge scale that makes the V->E mean and the ``degE`` factor one
+    ``scaled_propagate``.  Returns ``(degV, degE, scaleE)``."""
+    if getattr(data, 'UniGNN_sizes', None) is None:
+        raise ValueError("generate_norm_UniGNN: pass data through ConstructH_pairs first")
+    n, m = data.UniGNN_sizes
+    v, e = data.edge_index[0], data.edge_index[1]
+    degV = torch.bincount(v, minlength=n).to(torch.float32)
+    size = torch.bincount(e, minlength=m).to(torch.float32)
+    degE = torch.zeros(m, dtype=torch.float32, device=v.device).index_add_(0, e, degV[v]) / size.clamp(min=1)
+    degE = degE.pow(-0.5)
+    degV = degV.pow(-0.5)
+    degV[torch.isinf(degV)] = 1
+    args.UniGNN_degV = degV.view(-1, 1)
+    args.UniGNN_degE = degE.view(-1, 1)
+    data.UniGNN_scaleE = degE / size
+    return args.UniGNN_degV, args.UniGNN_degE, data.UniGNN_scaleE
 
 
 def rebase_hyperedge_ids(data):

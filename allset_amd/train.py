@@ -14,11 +14,13 @@ HyperGCN on-disk format the reference's ``load_citation_dataset`` consumes (``fe
 noisy class-indicator features).  Of the reference's baselines, the hypergraph convolutions HGNN, HCHA and HNHN are
 built (``allset_amd/baselines.py``; same preprocessing branches, train.py:375-388, and the same ``--HCHA_symdegnorm`` /
 ``--HNHN_*`` flags), and so are the clique-expansion CEGCN and CEGAT (branch :354-357, ``--normalization``; CEGAT also ``--heads`` /
-``--output_heads``); HyperGCN, UniGCNII and MLP are out of scope and rejected.
+``--output_heads``), and UniGCNII (branch :390-412, ``--UniGNN_use-norm``; its two-group Adam of :463-467 ignores ``--lr`` / ``--wd``
+as there); HyperGCN and MLP are out of scope and rejected.
 
     python -m allset_amd.train --method AllSetTransformer --dname synthetic --epochs 50 --runs 2 --heads 4 \\
         --MLP_hidden 128 --All_num_layers 1
     python -m allset_amd.train --method HCHA --dname synthetic --epochs 50 --runs 2      # HGNN: --method HGNN --HCHA_symdegnorm
+    python -m allset_amd.train --method UniGCNII --dname synthetic --epochs 50 --runs 2 --All_num_layers 4
 """
 from __future__ import annotations
 
@@ -38,12 +40,14 @@ import torch.nn.functional as F
 from . import dense
 from ._lib import AllSetHipError
 from .models import SetGNN
-from .preprocessing import (Add_Self_Loops, ConstructV2V, ExtractV2E, expand_edge_index, generate_norm_HCHA, generate_norm_HNHN,
-                            norm_contruction, rebase_hyperedge_ids)
+from .preprocessing import (Add_Self_Loops, ConstructH_pairs, ConstructV2V, ExtractV2E, expand_edge_index, generate_norm_HCHA,
+                            generate_norm_HNHN, generate_norm_UniGNN, norm_contruction, rebase_hyperedge_ids)
 
 ALLSET_METHODS = ('AllSetTransformer', 'AllDeepSets')
 BASELINE_METHODS = ('HGNN', 'HCHA', 'HNHN')
 CE_METHODS = ('CEGCN', 'CEGAT')
+UNIGNN_METHODS = ('UniGCNII',)
+BUILT_METHODS = ALLSET_METHODS + BASELINE_METHODS + CE_METHODS + UNIGNN_METHODS
 
 
 # --------------------------------------------------------------------------------------------------
@@ -391,10 +395,31 @@ def build_model(args, data):
         from .baselines import CEGAT
         return CEGAT(in_dim=args.num_features, hid_dim=args.MLP_hidden, out_dim=args.num_classes, num_layers=args.All_num_layers,
                      heads=args.heads, output_heads=args.output_heads, dropout=args.dropout, Normalization=args.normalization)
+    if args.method == 'UniGCNII':
+        ei = getattr(data, 'edge_index', None) if data is not None else None
+        if getattr(data, 'UniGNN_sizes', None) is None or not torch.is_tensor(ei) or ei.dim() != 2 or ei.shape[0] != 2 \
+                or ei.dtype.is_floating_point or not torch.is_tensor(getattr(args, 'UniGNN_degV', None)) \
+                or not torch.is_tensor(getattr(args, 'UniGNN_degE', None)):
+            raise ValueError("method 'UniGCNII' runs on the de-duplicated (vertex, hyperedge) pairs and their degree scales: pass data "
+                             "through train.preprocess (ExtractV2E -> [Add_Self_Loops] -> ConstructH_pairs -> generate_norm_UniGNN) "
+                             "before build_model")
+        from .baselines import UniGCNII
+        return UniGCNII(args, nfeat=args.num_features, nhid=args.MLP_hidden, nclass=args.num_classes, nlayer=args.All_num_layers,
+                        nhead=args.heads, V=ei[0], E=ei[1])
     if args.method in ALLSET_METHODS:
         return parse_method(args, data)
-    raise ValueError(f"method {args.method!r}: only {ALLSET_METHODS + BASELINE_METHODS + CE_METHODS} are built "
-                     "(HyperGCN, UniGCNII and MLP are out of scope)")
+    raise ValueError(f"method {args.method!r}: only {BUILT_METHODS} are built (HyperGCN and MLP are out of scope)")
+
+
+def make_optimizer(args, model):
+    """The run's Adam (``allset_amd.optim.FusedAdam``: one launch per parameter group).  UniGCNII trains as in reference
+    train.py:463-467: weight decay 0.01 on the conv weights, 5e-4 on the first and last Linear, lr 0.01 -- ``--lr`` / ``--wd`` are
+    ignored for it, as there."""
+    from .optim import FusedAdam
+    if args.method in UNIGNN_METHODS:
+        return FusedAdam([dict(params=model.reg_params, weight_decay=0.01), dict(params=model.non_reg_params, weight_decay=5e-4)],
+                         lr=0.01)
+    return FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -488,12 +513,20 @@ def load_data(args) -> HypergraphData:
 def preprocess(args, data: HypergraphData) -> HypergraphData:
     """The AllSet branch of reference train.py:344-353, and the HNHN / HCHA / HGNN branches (:375-388): hyperedge ids re-based to 0,
     HNHN's norms computed before the re-base; HCHA's scales are computed here too (the reference derives them per forward); and the
-    clique-expansion branch of CEGCN / CEGAT (:354-357: no self-loop hyperedges there, whatever ``--add_self_loop`` says)."""
+    clique-expansion branch of CEGCN / CEGAT (:354-357: no self-loop hyperedges there, whatever ``--add_self_loop`` says); and the
+    UniGCNII branch (:390-412) with the dense incidence matrix replaced by its sorted, de-duplicated pairs."""
     if args.method in CE_METHODS:
         data = ExtractV2E(data)
         data = ConstructV2V(data)
         data = norm_contruction(data, TYPE='V2V')
         data.clique_expansion = True                        # what build_model checks for CEGCN / CEGAT
+        return data
+    if args.method in UNIGNN_METHODS:
+        data = ExtractV2E(data)
+        if args.add_self_loop:
+            data = Add_Self_Loops(data)
+        data = ConstructH_pairs(data)                       # what build_model checks for UniGCNII (data.UniGNN_sizes)
+        generate_norm_UniGNN(data, args)                    # args.UniGNN_degV / args.UniGNN_degE, as the reference keeps them
         return data
     if args.method in BASELINE_METHODS:
         data = ExtractV2E(data)
@@ -514,8 +547,8 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
 
 
 def run(args) -> dict:
-    if args.method not in ALLSET_METHODS + BASELINE_METHODS + CE_METHODS:
-        raise ValueError(f"method {args.method!r}: only {ALLSET_METHODS + BASELINE_METHODS + CE_METHODS} are built")
+    if args.method not in BUILT_METHODS:
+        raise ValueError(f"method {args.method!r}: only {BUILT_METHODS} are built (HyperGCN and MLP are out of scope)")
     if args.seed is not None:
         np.random.seed(args.seed)
         torch.manual_seed(args.seed)
@@ -526,6 +559,9 @@ def run(args) -> dict:
         raise RuntimeError("allset_amd has no CPU path for the aggregation kernels: run with --cuda 0 on an MI355X")
     device = torch.device(f'cuda:{args.cuda}')
     model, data = model.to(device), data.to(device)
+    if args.method in UNIGNN_METHODS:                      # (reference train.py:438-440)
+        args.UniGNN_degV = args.UniGNN_degV.to(device)
+        args.UniGNN_degE = args.UniGNN_degE.to(device)
     num_params = count_parameters(model)
     logger = Logger(args.runs, args)
     runtimes = []
@@ -548,8 +584,7 @@ def _run_loop(args, model, data, splits, device, logger, runtimes, num_params):
         model.reset_parameters()
         # same Adam as the reference (train.py:469) as one kernel launch over all parameters (allset_amd/optim.py: torch's fused
         # capturable Adam takes ~40 us for the ~20 small tensors of a Cora-sized model, a tenth of a replayed step)
-        from .optim import FusedAdam
-        optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd)
+        optimizer = make_optimizer(args, model)
         # the train-split loss as one forward and one backward kernel (allset_amd/losses.py): same value as
         # criterion(F.log_softmax(out, dim=1)[train_idx], y[train_idx]), the split as a 0/1 row mask made once per run
         from .losses import nll_log_softmax, split_mask
@@ -575,7 +610,7 @@ def _run_loop(args, model, data, splits, device, logger, runtimes, num_params):
                 del graphed_step, graphed_eval                # a captured step keeps its memory pool alive
                 graphed_step = graphed_eval = None
                 model.reset_parameters()
-                optimizer = FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd)
+                optimizer = make_optimizer(args, model)
         # evaluate() of the reference (train.py:483: three accuracies + three losses per epoch, each through .cpu()) as one kernel
         # whose six numbers stay on the device: they are read back once per run (and every display_step epochs for the progress
         # line) -- at dataset scale the per-epoch host round trips cost several times the 0.4 ms training step

@@ -814,6 +814,26 @@ int allset_gat_bwd_src(int variant, int64_t nnz, const int32_t* row_order, const
                        const float* stats, float slope, float* gx, int64_t ldgx, float* gal, int64_t n_s, int64_t n_t, int64_t H,
                        int64_t C, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * UniGCNII baseline (reference models.py:911-996): the E->V hop with GCNII's initial-residual step in one launch.
+ * Added under ABI 15, additions only; detect with allset_unigcn_supported() (returns 1).  fp32, row-major.
+ *
+ * allset_unigcn_hop_fwd over a CSR whose rows are vertices and whose columns are hyperedges (xe f32[n_s, d]):
+ *   a = degV[v] * sum_{j in [rowptr[v], rowptr[v+1])} xe[col[j],:]
+ *   t = use_norm ? (||a||_2 > 0 ? 1 / ||a||_2 : 0) : 1                 (t_out[v] = t when use_norm; t_out may be NULL otherwise)
+ *   xi[v,:] = (1 - alpha) * t * a + alpha * x0[v,:]
+ * degV (f32[n_t]) may be NULL (= ones).  Built for d a multiple of 4 up to 512 with 16-byte aligned rows (pointers and leading
+ * dimensions): ALLSET_ERR_UNSUPPORTED otherwise, and the caller composes the hop from allset_hconv_fwd.  variant: 0 auto
+ * (short-row kernel when nnz / n_t < 6 and n_t > 16384), 1 one wavefront per row (row_order int32[n_t] or NULL is its processing
+ * order), 2 short-row kernel (d <= 256).  One wavefront (or lane group) owns a whole row: every sum has a fixed order, results
+ * are bit-identical from run to run.  The backward is allset_hconv_fwd over the transposed CSR with
+ * r[v] = (1 - alpha) * degV[v] * t[v] (t is a constant of the backward, as in the reference), and gx0 = alpha * gxi.
+ * ------------------------------------------------------------------------------------------- */
+int allset_unigcn_supported(void);
+int allset_unigcn_hop_fwd(int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                          const float* degV, const float* xe, int64_t ldxe, const float* x0, int64_t ldx0, float alpha, int use_norm,
+                          float* xi, int64_t ldxi, float* t_out, int64_t n_t, int64_t n_s, int64_t d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
