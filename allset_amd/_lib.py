@@ -238,6 +238,15 @@ SIGNATURES = {
     "allset_unigcn_supported": [],
     "allset_unigcn_hop_fwd": [c_int, c_int64, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_float, c_int, _P, c_int64, _P, c_int64, c_int64,
                               c_int64, _P],
+    # HyperGCN baseline: the on-device Laplacian approximation and its two-pass hop (under ABI 15, additions only; detect with
+    # allset_hypergcn_supported)
+    "allset_hypergcn_supported": [],
+    "allset_hypergcn_project": [_P, c_int64, _P, _P, c_int64, c_int64, _P],
+    "allset_hypergcn_select": [_P, _P, _P, _P, c_int, _P, _P, _P, _P, c_int64, c_int64, c_int64, _P],
+    "allset_hypergcn_degree": [_P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int64, c_int64, c_int64, _P],
+    "allset_hypergcn_v2e": [c_int, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P],
+    "allset_hypergcn_e2v": [c_int, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_int64, _P, c_int, c_float, c_uint64, _P, _P,
+                            c_int64, c_int64, c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

@@ -17,6 +17,11 @@ pairs, without weights and with one loop on every vertex, through the softmax-at
 mean (``scaled_propagate`` with ``degE / |e|``), then the E->V sum with ``degV``, the optional row normalisation and GCNII's initial
 residual in one launch (``functional.unigcn_hop``, csrc/unigcn.hip), then the identity-mapping step as one GEMM with the folded
 weight ``(1 - beta) I + beta W`` and the one-pass ``relu`` + dropout.
+
+``HyperGraphConvolution`` / ``HyperGCN`` (reference utils.py:11-199, models.py:29-77): the per-hyperedge Laplacian approximation is
+built on the device as a structure of roles (``functional.hypergcn_structure``) and each layer is one GEMM and one two-pass hop with
+the bias, ``relu`` and dropout in its second launch (``functional.hypergcn_propagate``, csrc/hypergcn.hip); the N x N adjacency is
+never formed, and the re-approximating mode rebuilds the structure per layer and forward without leaving the device.
 """
 from __future__ import annotations
 
@@ -31,7 +36,8 @@ from torch.nn import Parameter
 
 from . import dense
 from ._lib import AllSetHipError
-from .functional import gat_propagate, initial_residual, scaled_propagate, unigcn_hop, weighted_propagate
+from .functional import (HyperGCNStructure, gat_propagate, hypergcn_propagate, hypergcn_structure, initial_residual, scaled_propagate,
+                         unigcn_hop, weighted_propagate)
 from .incidence import Incidence, cached_incidence
 from .layers import _linear, glorot, zeros
 from .preprocessing import generate_norm_HCHA
@@ -565,3 +571,199 @@ class UniGCNII(nn.Module):
             # relu, and the dropout in front of the next layer (the next conv, or the last Linear), in one pass
             x = dense.relu_dropout(conv(x, graph, None, alpha, beta, x0), p)
         return _linear(self.convs[-1], x)
+
+
+# ---- HyperGCN ---------------------------------------------------------------------------------------------------------------------
+def hypergcn_check_pairs(v_ids: Tensor, e_ids: Tensor, mediators: bool) -> None:
+    """The two input families HyperGCN refuses, from the (vertex, hyperedge) pairs alone (any device, one pass at construction):
+    a pair that occurs twice (the reference tells mediators from extremes by value, which makes a repeated member a third semantics
+    none of its loaders produces), and -- under ``mediators`` -- a hyperedge of one member (the reference's weight 1 / (2k - 3) is -1
+    there, the degree negative and the logits NaN)."""
+    v, e = v_ids.reshape(-1).long(), e_ids.reshape(-1).long()
+    if v.numel() == 0:
+        return
+    span = int(v.max()) + 1
+    key = e * span + v
+    uniq, counts = torch.unique(key, return_counts=True)
+    if uniq.numel() != key.numel():
+        first = int(uniq[counts > 1][0])
+        raise ValueError(f"HyperGCN: vertex {first % span} occurs {int(counts[counts > 1][0])} times in hyperedge {first // span}; "
+                         "every (vertex, hyperedge) pair must occur once")
+    if mediators:
+        sizes = torch.bincount(e)
+        single = (sizes == 1).nonzero().reshape(-1)
+        if single.numel():
+            raise ValueError(f"HyperGCN with mediators: hyperedge {int(single[0])} has a single member (the reference's weight "
+                             "1 / (2k - 3) is negative there and its logits are NaN); drop singleton hyperedges or run without mediators")
+
+
+class HyperGraphConvolution(nn.Module):
+    """Reference utils.py:11-55: ``A (H W) + bias`` with ``W`` [a, b] and ``bias`` [b] both drawn ``uniform(-1/sqrt(b), 1/sqrt(b))``,
+    ``W`` first.  ``structure``: a :class:`functional.HyperGCNStructure` (``reapproximate`` False), or the vertex -> hyperedge
+    ``Incidence`` when ``reapproximate``: the structure is then rebuilt from the detached ``H W`` and the projection vector ``rv`` on
+    the device, with no host synchronisation.  ``rv`` defaults to the layer's own buffer ``self.rv`` [b], which
+    :meth:`refresh_rv` redraws in place from a ``torch.Generator`` (the model's); the stream is torch's, not numpy's
+    ``np.random.rand``, so projections differ from the reference's draw for draw while following the same distribution."""
+
+    def __init__(self, a, b, reapproximate=True, cuda=None):
+        super().__init__()
+        self.a, self.b = a, b
+        self.reapproximate = reapproximate
+        self.W = Parameter(torch.empty(a, b))
+        self.bias = Parameter(torch.empty(b))
+        self.rv: Optional[Tensor] = None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        std = 1. / math.sqrt(self.W.size(1))
+        self.W.data.uniform_(-std, std)
+        self.bias.data.uniform_(-std, std)
+
+    def refresh_rv(self, generator: Optional[torch.Generator] = None) -> Tensor:
+        """Draw ``self.rv ~ U[0, 1)^b`` in place (allocated on the parameters' device at first use): a captured graph that reads
+        the buffer sees the new values at its next replay."""
+        dev = self.W.device
+        if self.rv is None or self.rv.device != dev:
+            self.rv = torch.empty(self.b, dtype=torch.float32, device=dev)
+        self.rv.uniform_(0.0, 1.0, generator=generator)
+        return self.rv
+
+    def forward(self, structure, H: Tensor, m=True, *, rv: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0,
+                fused: Optional[bool] = None) -> Tensor:
+        """``act`` / ``p``: the ``relu`` and dropout the model applies next, fused into the hop's second launch."""
+        if not (H.is_cuda and H.dtype == torch.float32):
+            raise AllSetHipError("the HyperGCN baseline runs on ROCm device fp32 tensors (no CPU path)")
+        HW = dense.linear(H, self.W.t(), None)               # H W: the [a, b] weight read transposed by the GEMM, no copy
+        if self.reapproximate:
+            if not isinstance(structure, Incidence):
+                raise ValueError("HyperGraphConvolution(reapproximate=True) takes the vertex -> hyperedge Incidence as its structure")
+            if rv is None:
+                if self.rv is None or self.rv.device != HW.device:
+                    if torch.cuda.is_current_stream_capturing():
+                        raise RuntimeError("HyperGraphConvolution: draw the projection vector (refresh_rv) before capturing a graph")
+                    self.refresh_rv()
+                rv = self.rv
+            structure = hypergcn_structure(HW, rv, structure, bool(m))
+        elif not isinstance(structure, HyperGCNStructure):
+            raise ValueError("HyperGraphConvolution(reapproximate=False) takes a functional.HyperGCNStructure")
+        return hypergcn_propagate(HW, structure, self.bias, act=act, p=p, fused=fused)
+
+    def __repr__(self):
+        return self.__class__.__name__ + ' (' + str(self.a) + ' -> ' + str(self.b) + ')'
+
+
+def hypergcn_widths(num_features: int, num_layers: int, num_classes: int, dname: Optional[str]) -> list:
+    """Reference models.py:40-46: ``[F, 2^(L+2), 2^(L+1), ..., 2^4, C]``, the exponents two higher for ``dname == 'citeseer'``."""
+    h = [num_features]
+    for i in range(num_layers - 1):
+        h.append(2 ** (num_layers - i + (4 if dname == 'citeseer' else 2)))
+    h.append(num_classes)
+    return h
+
+
+class HyperGCN(nn.Module):
+    """Reference models.py:29-77.  ``V``: the number of vertices; ``E``: the hypergraph as a vertex -> hyperedge ``Incidence`` or an
+    int64 ``[2, nnz]`` edge list (row 0 vertex ids, row 1 hyperedge ids from 0; any device) -- not the reference's Python dict; ``X``:
+    the features (kept for the signature: the fast structure is built from the ``data.x`` of the first forward, which is the same
+    tensor in the driver).  ``relu`` follows every layer, the last included; dropout ``args.dropout`` every layer but the last.
+
+    ``args.HyperGCN_fast``: ONE structure from ``data.x`` shared by all layers, built lazily on the first forward (the model is
+    constructed on the host and moved to the device afterwards) or by :meth:`build_structure`.  Otherwise every layer rebuilds its
+    structure from its own ``H W`` in every forward, on the device, without a host synchronisation: the forward can be captured by
+    ``torch.cuda.graph``; inside a capture the projection vectors are read as they are, so call :meth:`refresh_projections`
+    between replays (an eager forward does it itself).
+
+    Projection vectors come from ``self.generator``, a ``torch.Generator`` on the model's device seeded with ``self.rv_seed`` (drawn
+    from torch's global generator after the parameters, so ``torch.manual_seed`` fixes it; :meth:`seed_projections` re-seeds).  The
+    stream cannot equal numpy's ``np.random.rand`` of the reference.  ``forward(data, rv=[...])`` takes explicit vectors instead.
+
+    Refused at construction (``ValueError``): a repeated (vertex, hyperedge) pair, and a singleton hyperedge under mediators."""
+
+    def __init__(self, V, E, X, num_features, num_layers, num_classes, args):
+        super().__init__()
+        self.n_vertices = int(V)
+        self.m = bool(args.HyperGCN_mediators)
+        self.fast = bool(args.HyperGCN_fast)
+        if isinstance(E, Incidence):
+            rp = E.by_dst.rowptr
+            e_ids = torch.repeat_interleave(torch.arange(E.n_dst, device=rp.device), (rp[1:] - rp[:-1]).long())
+            hypergcn_check_pairs(E.by_dst.col, e_ids, self.m)
+            if E.n_src != self.n_vertices:
+                raise ValueError(f"HyperGCN: the incidence has {E.n_src} vertices, V = {self.n_vertices}")
+            self._inc, self._pairs = E, None
+        else:
+            if not torch.is_tensor(E) or E.dim() != 2 or E.shape[0] != 2 or E.dtype.is_floating_point:
+                raise ValueError("HyperGCN: E is the vertex -> hyperedge Incidence or an integer [2, nnz] edge list")
+            if E.numel() and (int(E[0].min()) < 0 or int(E[0].max()) >= self.n_vertices or int(E[1].min()) < 0):
+                raise ValueError(f"HyperGCN: vertex ids must lie in [0, {self.n_vertices}) and hyperedge ids start at 0")
+            hypergcn_check_pairs(E[0], E[1], self.m)
+            self._inc, self._pairs = None, E.to(torch.int64)
+        h = hypergcn_widths(num_features, num_layers, num_classes, getattr(args, 'dname', None))
+        self.layers = nn.ModuleList([HyperGraphConvolution(h[i], h[i + 1], not self.fast) for i in range(num_layers)])
+        self.do, self.l = args.dropout, num_layers
+        self.structure: Optional[HyperGCNStructure] = None       # fast mode: built on the first forward
+        self.rv_seed = int(torch.randint(0, 2 ** 62, (1,)))
+        self.generator: Optional[torch.Generator] = None
+
+    def reset_parameters(self):
+        for layer in self.layers:
+            layer.reset_parameters()
+
+    # ---- projections --------------------------------------------------------------------------------------------------------------
+    def seed_projections(self, seed: int) -> None:
+        self.rv_seed = int(seed)
+        self.generator = None
+
+    def _generator(self, device) -> torch.Generator:
+        if self.generator is None or self.generator.device != device:
+            self.generator = torch.Generator(device=device)
+            self.generator.manual_seed(self.rv_seed)
+        return self.generator
+
+    def refresh_projections(self) -> None:
+        """Redraw every layer's projection vector in place (re-approximating mode; nothing to do in fast mode)."""
+        if self.fast:
+            return
+        gen = self._generator(self.layers[0].W.device)
+        for layer in self.layers:
+            layer.refresh_rv(gen)
+
+    # ---- structure ----------------------------------------------------------------------------------------------------------------
+    def incidence(self, device) -> Incidence:
+        if self._inc is None or self._inc.device != device:
+            if self._pairs is None:
+                raise AllSetHipError(f"HyperGCN: the incidence lives on {self._inc.device}, the features on {device}")
+            n_e = int(self._pairs[1].max()) + 1 if self._pairs.numel() else 0
+            self._inc = Incidence.from_edge_index(self._pairs.to(device).contiguous(), n_src=self.n_vertices, n_dst=n_e)
+        return self._inc
+
+    def build_structure(self, x: Tensor, rv: Optional[Tensor] = None) -> HyperGCNStructure:
+        """Fast mode's one structure, from ``x`` and ``rv`` [x.shape[1]] (drawn from the model's generator when None)."""
+        if rv is None:
+            rv = torch.empty(x.shape[1], dtype=torch.float32, device=x.device).uniform_(0.0, 1.0, generator=self._generator(x.device))
+        self.structure = hypergcn_structure(x, rv, self.incidence(x.device), self.m)
+        return self.structure
+
+    def forward(self, data, rv=None):
+        """``rv``: explicit projection vectors, one [width of layer i's output] per layer (re-approximating mode only)."""
+        H = data.x
+        if not (H.is_cuda and H.dtype == torch.float32):
+            raise AllSetHipError("the HyperGCN baseline runs on ROCm device fp32 tensors (no CPU path)")
+        if H.shape[0] != self.n_vertices:
+            raise ValueError(f"HyperGCN: data.x has {H.shape[0]} rows, V = {self.n_vertices}")
+        if self.fast:
+            if rv is not None:
+                raise ValueError("HyperGCN(fast): the one projection vector goes to build_structure(x, rv)")
+            if self.structure is None or self.structure.inc.device != H.device:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("HyperGCN(fast): run one forward (or build_structure) before capturing a graph")
+                self.build_structure(H)
+            structure = self.structure
+        else:
+            structure = self.incidence(H.device)
+            if rv is None and not torch.cuda.is_current_stream_capturing():
+                self.refresh_projections()
+        p = float(self.do) if self.training else 0.0
+        for i, hidden in enumerate(self.layers):
+            H = hidden(structure, H, self.m, rv=None if rv is None else rv[i], act='relu', p=p if i < self.l - 1 else 0.0)
+        return H

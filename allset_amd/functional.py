@@ -632,3 +632,126 @@ def unigcn_hop(xe: Tensor, x0: Tensor, inc: Incidence, degV: Tensor, alpha: floa
                                   f"vertices of width {xe.shape[1]}")
     sink = getattr(x0, "_allset_grad_sink", None)
     return _UniGCNHop.apply(xe, x0, inc, degV.contiguous(), float(alpha), bool(use_norm), sink, variant)
+
+
+# ---- HyperGCN: the Laplacian approximation as a structure of roles, and its hop (csrc/hypergcn.hip) ---------------------------------
+class HyperGCNStructure:
+    """What one HyperGCN hop needs in place of the reference's sparse ``A = D^-1/2 (W + I) D^-1/2``: per hyperedge the extremes
+    ``S`` / ``I`` of the projection (int32, -1 for an empty hyperedge), the weight ``w`` and the size; per vertex ``dinv = D^-1/2`` and
+    the self coefficient ``selfc``; per incidence of ``inc.by_src`` the row ``colx`` of the per-hyperedge buffer that the E->V pass
+    gathers.  ``inc``: sources = vertices, targets = hyperedges.  Every tensor is a constant of autograd."""
+
+    def __init__(self, inc: Incidence, mediators: bool, S: Tensor, I: Tensor, w: Tensor, size: Tensor, dinv: Tensor, selfc: Tensor,
+                 colx: Tensor):
+        self.inc, self.mediators = inc, bool(mediators)
+        self.S, self.I, self.w, self.size, self.dinv, self.selfc, self.colx = S, I, w, size, dinv, selfc, colx
+
+    @property
+    def n_pq(self) -> int:
+        return (2 if self.mediators else 1) * self.inc.n_dst
+
+
+def hypergcn_structure(z: Tensor, rv: Tensor, inc: Incidence, mediators: bool) -> HyperGCNStructure:
+    """The structure of reference ``utils.Laplacian(V, E, z, mediators)`` for the projection vector ``rv`` [z.shape[1]]: three launches
+    (projection, per-hyperedge first arg-max / arg-min in the caller's edge-list order, degrees), no host synchronisation.  ``inc``:
+    the vertex -> hyperedge incidence (every (vertex, hyperedge) pair once; no singleton hyperedge under ``mediators`` --
+    ``baselines.HyperGCN`` checks both at construction)."""
+    _lib.require_device(z, rv)
+    if z.shape[0] != inc.n_src:
+        raise _lib.AllSetHipError(f"hypergcn_structure: z has {z.shape[0]} rows, the incidence has {inc.n_src} vertices")
+    with torch.no_grad():
+        p = ops.hypergcn_project(z.detach(), rv.detach())
+        S, I, w, size = ops.hypergcn_select(inc.by_dst, p, mediators)
+        dinv, selfc, colx = ops.hypergcn_degree(inc.by_src, S, I, w, size, mediators)
+    return HyperGCNStructure(inc, mediators, S, I, w, size, dinv, selfc, colx)
+
+
+def _identity_csr(inc: Incidence, n: int) -> ops.CSR:
+    """rows = columns = 0..n-1: ``hconv_propagate`` over it is the bare epilogue (bias, activation, hash dropout)."""
+    hit = getattr(inc, "_identity_csr", None)
+    if hit is None or hit.n_rows != n:
+        ar = torch.arange(n + 1, dtype=torch.int32, device=inc.device)
+        hit = ops.CSR(ar, ar[:n].contiguous(), ar[:n].contiguous(), n, n, 1)
+        inc._identity_csr = hit
+    return hit
+
+
+def _hypergcn_apply(x: Tensor, st: HyperGCNStructure, fused: bool, bias=None, act=None, p=0.0, seed=0, base=None, variant=None) -> Tensor:
+    """``drop_p(act(A x + bias))``: the two launches of csrc/hypergcn.hip, or (``fused`` False: a width that is not built) the same
+    sums composed from the ``hconv`` launches and torch ops."""
+    inc = st.inc
+    if fused:
+        pq = ops.hypergcn_v2e(inc.by_dst, st.S, st.I, st.w, st.dinv, x, st.mediators)
+        return ops.hypergcn_e2v(inc.by_src, st.colx, pq, st.dinv, st.selfc, x, bias, act, p, seed, base, variant)
+    y = x * st.dinv.unsqueeze(1)
+    Sl, Il = st.S.long().clamp(min=0), st.I.long().clamp(min=0)
+    w = torch.where(st.S >= 0, st.w, torch.zeros_like(st.w))
+    if st.mediators:
+        same = (st.S == st.I)
+        f = (w * torch.where(same, 2.0, 1.0)).unsqueeze(1)
+        T = ops.hconv_propagate(inc.by_dst, x, inc.n_dst, r=st.dinv)
+        ext = y[Sl] + torch.where(same.unsqueeze(1), torch.zeros_like(y[Il]), y[Il])
+        pq = torch.stack([f * ext, f * T], dim=1).reshape(2 * inc.n_dst, x.shape[1])
+    else:
+        pq = w.unsqueeze(1) * (y[Sl] + y[Il])
+    csr = inc.by_src._replace(col=st.colx.clamp(min=0), n_cols=pq.shape[0])
+    agg = ops.hconv_propagate_w(csr, pq, inc.n_src, w=(st.colx >= 0).to(torch.float32))
+    out = st.dinv.unsqueeze(1) * (agg + st.selfc.unsqueeze(1) * y)
+    if bias is None and act is None and p == 0.0:
+        return out
+    return ops.hconv_propagate(_identity_csr(inc, inc.n_src), out, inc.n_src, bias=bias, act=act, p=p, seed=seed, seed_base=base)
+
+
+class _HyperGCNPropagate(torch.autograd.Function):
+    """``y = drop_p(act(A x + bias))`` with ``A`` given by a :class:`HyperGCNStructure`.  Backward: the epilogue's kernel
+    (``hconv_bwd_epi``: the mask and ``act'`` from the saved output) and, ``A`` being symmetric, the same hop on the masked gradient."""
+
+    @staticmethod
+    def forward(ctx, x, bias, st, act, p, variant, fused):
+        from . import dense
+        seed = dense._draw_seed() if p > 0.0 else 0
+        base = dense._seed_base() if p > 0.0 else None
+        y = _hypergcn_apply(x, st, fused, bias, act, p, seed, base, variant)
+        epi = act is not None or p > 0.0 or bias is not None
+        ctx.save_for_backward(y if epi else None)
+        ctx.cfg = (st, act, p, seed, base, epi, variant, fused)
+        ctx.bias_param = bias
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        from . import dense
+        (y,) = ctx.saved_tensors
+        st, act, p, seed, base, epi, variant, fused = ctx.cfg
+        need_b = ctx.bias_param is not None and ctx.needs_input_grad[1]
+        gb = None
+        if epi:
+            g, part = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=need_b)
+            if need_b:
+                # (inside dense.deferred_param_grads(): queued for the step's one batched reduction, and None here)
+                (gb,) = dense._defer_or_reduce(part, [(ctx.bias_param, 0, (y.shape[1],))], defer=True)
+        else:
+            g = gy.contiguous()
+        gx = _hypergcn_apply(g, st, fused, variant=variant) if ctx.needs_input_grad[0] else None
+        return gx, gb, None, None, None, None, None
+
+
+def hypergcn_propagate(x: Tensor, structure: HyperGCNStructure, bias: Optional[Tensor] = None, act: Optional[str] = None,
+                       p: float = 0.0, variant: Optional[int] = None, fused: Optional[bool] = None) -> Tensor:
+    """One HyperGCN hop ``drop_p(act(A x + bias))`` with ``A = D^-1/2 (W + I) D^-1/2`` of ``structure`` (never materialised): a V->E
+    pass writing two rows per hyperedge and the fused E->V pass.  ``x`` [n_vertices, d] device fp32; ``act`` None / 'relu'; ``p`` the
+    dropout probability (the library's hash mask).  Differentiable in ``x`` and ``bias``.  ``variant``: kernel variant of the E->V
+    pass (tests); ``fused``: None = the HIP hop where the width is built (``ops.hypergcn_hop_supported``) and the composition from
+    ``hconv`` launches and torch ops otherwise; True insists on the HIP hop (an unbuilt width raises); False forces the composition."""
+    if act not in ops.HYPERGCN_ACTS:
+        raise ValueError(f"hypergcn_propagate: act must be None or 'relu', got {act!r}")
+    _lib.require_device(x)
+    if x.dtype != torch.float32:
+        raise _lib.AllSetHipError("hypergcn_propagate: fp32 tensors only")
+    if x.shape[0] != structure.inc.n_src:
+        raise _lib.AllSetHipError(f"hypergcn_propagate: x has {x.shape[0]} rows, the structure has {structure.inc.n_src} vertices")
+    x = ops._rowmajor(x)
+    if fused is None:
+        fused = ops.hypergcn_hop_supported(x)
+    return _HyperGCNPropagate.apply(x, bias, structure, act, float(p), variant, bool(fused))

@@ -763,3 +763,128 @@ def unigcn_hop_fwd(csr: CSR, xe: Tensor, x0: Tensor, n_t: int, degV: Optional[Te
                                                 ptr(x0), _ld(x0), float(alpha), int(bool(use_norm)), ptr(xi), max(d, 1), ptr(t), n_t,
                                                 n_s, d, stream_of(dev)), "allset_unigcn_hop_fwd")
     return xi, t
+
+
+# ---- HyperGCN: the on-device Laplacian approximation and its two-pass hop (csrc/hypergcn.hip) -----------------------------------------
+HYPERGCN_MAX_WIDTH = 256             # 16-byte lanes: multiples of 4 up to here
+HYPERGCN_MAX_SCALAR_WIDTH = 64       # one column per lane: any width up to here (the class counts of the last layer)
+HYPERGCN_ACTS = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "relu": _lib.ACT_RELU}
+
+
+def _rows16(*ts: Tensor) -> bool:
+    return all(t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 for t in ts)
+
+
+def hypergcn_hop_supported(x: Tensor) -> bool:
+    """Are the two hop launches built for this operand?  fp32; width a multiple of 4 up to 256 with 16-byte aligned rows, or any
+    width up to 64."""
+    d = x.shape[1]
+    if x.dtype != torch.float32 or d <= 0 or x.stride(1) != 1 or x.stride(0) < d:
+        return False
+    return (d % 4 == 0 and d <= HYPERGCN_MAX_WIDTH and _rows16(x)) or d <= HYPERGCN_MAX_SCALAR_WIDTH
+
+
+def hypergcn_project(z: Tensor, rv: Tensor) -> Tensor:
+    """``p[v] = z[v] . rv`` (f32[n]); rows with equal values give equal bits."""
+    dev = require_device(z, rv)
+    _f32(z, "hypergcn_project")
+    _f32(rv, "hypergcn_project rv")
+    z = _rowmajor(z)
+    rv = rv.reshape(-1).contiguous()
+    n, d = z.shape
+    if rv.numel() != d:
+        raise _lib.AllSetHipError(f"hypergcn_project: rv has {rv.numel()} entries for width {d}")
+    p = torch.empty(n, dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("hypergcn_project", dev, n * d * 4 + d * 4 + n * 4):
+        check(_lib.load().allset_hypergcn_project(ptr(z), _ld(z), ptr(rv), ptr(p), n, d, stream_of(dev)), "allset_hypergcn_project")
+    return p
+
+
+def hypergcn_select(csr_e: CSR, p: Tensor, mediators: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``(S, I, w, size)`` per row of the hyperedge-major ``csr_e``: the members at the first arg-max / arg-min of ``p`` in edge-list
+    order (ties by ``csr_e.perm``), the weight 1 / (2k - 3) (mediators) or 1 / k, and the size k."""
+    dev = require_device(csr_e.rowptr, p)
+    _f32(p, "hypergcn_select")
+    p = p.contiguous()
+    n_e, n_v, nnz = csr_e.n_rows, csr_e.n_cols, csr_e.col.numel()
+    if p.numel() < n_v:
+        raise _lib.AllSetHipError(f"hypergcn_select: p has {p.numel()} entries for {n_v} vertices")
+    S = torch.empty(n_e, dtype=torch.int32, device=dev)
+    I = torch.empty(n_e, dtype=torch.int32, device=dev)
+    size = torch.empty(n_e, dtype=torch.int32, device=dev)
+    w = torch.empty(n_e, dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("hypergcn_select", dev, nnz * 12 + n_e * 20):
+        check(_lib.load().allset_hypergcn_select(ptr(csr_e.rowptr), ptr(csr_e.col), ptr(csr_e.perm), ptr(p), int(bool(mediators)),
+                                                 ptr(S), ptr(I), ptr(w), ptr(size), n_e, n_v, nnz, stream_of(dev)),
+              "allset_hypergcn_select")
+    return S, I, w, size
+
+
+def hypergcn_degree(csr_v: CSR, S: Tensor, I: Tensor, w: Tensor, size: Tensor, mediators: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(dinv, selfc, colx)`` over the vertex-major ``csr_v``: ``D^-1/2``, the self coefficient of the E->V pass and, per incidence
+    of ``csr_v``, the row of the per-hyperedge buffer that pass gathers (-1: none)."""
+    dev = require_device(csr_v.rowptr, S, I, w, size)
+    n_v, n_e, nnz = csr_v.n_rows, csr_v.n_cols, csr_v.col.numel()
+    for t, dt, what in ((S, torch.int32, "S"), (I, torch.int32, "I"), (size, torch.int32, "size"), (w, torch.float32, "w")):
+        if t.dtype != dt or t.numel() < n_e or not t.is_contiguous():
+            raise _lib.AllSetHipError(f"hypergcn_degree: {what} must be contiguous {dt} with at least {n_e} entries")
+    dinv = torch.empty(n_v, dtype=torch.float32, device=dev)
+    selfc = torch.empty(n_v, dtype=torch.float32, device=dev)
+    colx = torch.empty(nnz, dtype=torch.int32, device=dev)
+    with on_device(dev), _timed("hypergcn_degree", dev, nnz * 24 + n_v * 12):
+        check(_lib.load().allset_hypergcn_degree(ptr(csr_v.rowptr), ptr(csr_v.col), ptr(S), ptr(I), ptr(w), ptr(size),
+                                                 int(bool(mediators)), ptr(dinv), ptr(selfc), ptr(colx), n_v, n_e, nnz, stream_of(dev)),
+              "allset_hypergcn_degree")
+    return dinv, selfc, colx
+
+
+def hypergcn_v2e(csr_e: CSR, S: Tensor, I: Tensor, w: Tensor, dinv: Tensor, x: Tensor, mediators: bool) -> Tensor:
+    """The per-hyperedge rows of one hop: f32[2 n_e, d] (``P_e``, ``Q_e`` interleaved) with mediators, f32[n_e, d] without."""
+    dev = require_device(csr_e.rowptr, S, I, w, dinv, x)
+    _f32(x, "hypergcn_v2e")
+    x = _rowmajor(x)
+    n_v, d = x.shape
+    n_e, nnz = csr_e.n_rows, csr_e.col.numel()
+    if csr_e.n_cols > n_v or dinv.numel() < n_v or min(S.numel(), I.numel(), w.numel()) < n_e:
+        raise _lib.AllSetHipError(f"hypergcn_v2e: {n_v} feature rows / {dinv.numel()} dinv entries against a CSR of {n_e} x {csr_e.n_cols}")
+    pq = torch.empty(((2 if mediators else 1) * n_e, d), dtype=torch.float32, device=dev)
+    order = csr_e.row_order if (csr_e.row_order is not None and csr_e.row_order.numel() == n_e) else None
+    algo = (nnz * (4 * d + 8) + (n_e + 1) * 4 if mediators else 2 * n_e * (4 * d + 4)) + 12 * n_e + pq.numel() * 4
+    with on_device(dev), _timed("hypergcn_v2e", dev, algo):
+        check(_lib.load().allset_hypergcn_v2e(int(bool(mediators)), nnz, ptr(order), ptr(csr_e.rowptr), ptr(csr_e.col), ptr(S), ptr(I),
+                                              ptr(w), ptr(dinv), ptr(x), _ld(x), ptr(pq), max(d, 1), n_e, n_v, d, stream_of(dev)),
+              "allset_hypergcn_v2e")
+    return pq
+
+
+def hypergcn_e2v(csr_v: CSR, colx: Tensor, pq: Tensor, dinv: Tensor, selfc: Tensor, x: Tensor, bias: Optional[Tensor] = None,
+                 act: Optional[str] = None, p: float = 0.0, seed: int = 0, seed_base: Optional[Tensor] = None,
+                 variant: Optional[int] = None) -> Tensor:
+    """``y[v] = drop_p(act(dinv[v] * (selfc[v] * dinv[v] * x[v] + sum_{j in row v, colx_j >= 0} pq[colx_j]) + bias))`` over the
+    vertex-major ``csr_v`` with ``colx`` in place of its columns."""
+    dev = require_device(csr_v.rowptr, colx, pq, dinv, selfc, x, bias)
+    _f32(x, "hypergcn_e2v")
+    _f32(pq, "hypergcn_e2v pq")
+    x, pq = _rowmajor(x), _rowmajor(pq)
+    n_v, d = x.shape
+    nnz = csr_v.col.numel()
+    if n_v != csr_v.n_rows or pq.shape[1] != d or colx.numel() != nnz or colx.dtype != torch.int32 or dinv.numel() < n_v \
+            or selfc.numel() < n_v:
+        raise _lib.AllSetHipError(f"hypergcn_e2v: x {tuple(x.shape)} / pq {tuple(pq.shape)} / colx {colx.numel()} do not fit a CSR of "
+                                  f"{csr_v.n_rows} rows and {nnz} incidences")
+    if bias is not None:
+        _f32(bias, "hypergcn_e2v bias")
+        bias = bias.contiguous()
+        if bias.numel() != d:
+            raise _lib.AllSetHipError(f"hypergcn_e2v: bias has {bias.numel()} entries for width {d}")
+    y = torch.empty((n_v, d), dtype=torch.float32, device=dev)
+    flat_ok = d % 4 == 0 and d <= HYPERGCN_MAX_WIDTH and _rows16(x, pq)
+    if variant is None:
+        variant = csr_v.variant("segreduce", n_v) if flat_ok else 1
+    order = csr_v.row_order if (variant == 1 and csr_v.row_order is not None and csr_v.row_order.numel() == n_v) else None
+    algo = nnz * (4 * d + 4) + (n_v + 1) * 4 + 8 * n_v + 2 * n_v * 4 * d
+    with on_device(dev), _timed("hypergcn_e2v", dev, algo):
+        check(_lib.load().allset_hypergcn_e2v(variant, nnz, ptr(order), ptr(csr_v.rowptr), ptr(colx), ptr(pq), _ld(pq), pq.shape[0],
+                                              ptr(dinv), ptr(selfc), ptr(x), _ld(x), ptr(bias), HYPERGCN_ACTS[act], float(p), int(seed),
+                                              ptr(seed_base), ptr(y), max(d, 1), n_v, d, stream_of(dev)), "allset_hypergcn_e2v")
+    return y

@@ -15,12 +15,14 @@ noisy class-indicator features).  Of the reference's baselines, the hypergraph c
 built (``allset_amd/baselines.py``; same preprocessing branches, train.py:375-388, and the same ``--HCHA_symdegnorm`` /
 ``--HNHN_*`` flags), and so are the clique-expansion CEGCN and CEGAT (branch :354-357, ``--normalization``; CEGAT also ``--heads`` /
 ``--output_heads``), and UniGCNII (branch :390-412, ``--UniGNN_use-norm``; its two-group Adam of :463-467 ignores ``--lr`` / ``--wd``
-as there); HyperGCN and MLP are out of scope and rejected.
+as there), and HyperGCN (branch :359-360, ``--HyperGCN_mediators`` / ``--HyperGCN_fast``, both on by default as there, with
+``--no-HyperGCN_mediators`` / ``--no-HyperGCN_fast`` to switch them off); MLP is out of scope and rejected.
 
     python -m allset_amd.train --method AllSetTransformer --dname synthetic --epochs 50 --runs 2 --heads 4 \\
         --MLP_hidden 128 --All_num_layers 1
     python -m allset_amd.train --method HCHA --dname synthetic --epochs 50 --runs 2      # HGNN: --method HGNN --HCHA_symdegnorm
     python -m allset_amd.train --method UniGCNII --dname synthetic --epochs 50 --runs 2 --All_num_layers 4
+    python -m allset_amd.train --method HyperGCN --dname synthetic --epochs 50 --runs 2 --no-HyperGCN_fast
 """
 from __future__ import annotations
 
@@ -47,7 +49,8 @@ ALLSET_METHODS = ('AllSetTransformer', 'AllDeepSets')
 BASELINE_METHODS = ('HGNN', 'HCHA', 'HNHN')
 CE_METHODS = ('CEGCN', 'CEGAT')
 UNIGNN_METHODS = ('UniGCNII',)
-BUILT_METHODS = ALLSET_METHODS + BASELINE_METHODS + CE_METHODS + UNIGNN_METHODS
+HYPERGCN_METHODS = ('HyperGCN',)
+BUILT_METHODS = ALLSET_METHODS + BASELINE_METHODS + CE_METHODS + UNIGNN_METHODS + HYPERGCN_METHODS
 
 
 # --------------------------------------------------------------------------------------------------
@@ -406,9 +409,18 @@ def build_model(args, data):
         from .baselines import UniGCNII
         return UniGCNII(args, nfeat=args.num_features, nhid=args.MLP_hidden, nclass=args.num_classes, nlayer=args.All_num_layers,
                         nhead=args.heads, V=ei[0], E=ei[1])
+    if args.method == 'HyperGCN' and data is not None and getattr(data, 'HyperGCN_pairs', None) is not None:
+        # (data that never saw the HyperGCN branch of preprocess falls through to the error below: on another branch's edge list
+        #  -- self-loop hyperedges, hyperedge ids behind the vertex ids -- the model would compute something else without an error)
+        from .baselines import HyperGCN
+        return HyperGCN(V=data.x.shape[0], E=data.HyperGCN_pairs, X=data.x, num_features=args.num_features,
+                        num_layers=args.All_num_layers, num_classes=args.num_classes, args=args)
     if args.method in ALLSET_METHODS:
         return parse_method(args, data)
-    raise ValueError(f"method {args.method!r}: only {BUILT_METHODS} are built (HyperGCN and MLP are out of scope)")
+    if args.method == 'HyperGCN':
+        raise ValueError("method 'HyperGCN' runs on the zero-based (vertex, hyperedge) pairs of train.preprocess (ExtractV2E only, no "
+                         "self-loop hyperedges): pass data through it before build_model; on other data the method is out of scope")
+    raise ValueError(f"method {args.method!r}: only {BUILT_METHODS} are built (MLP is out of scope)")
 
 
 def make_optimizer(args, model):
@@ -462,6 +474,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--UniGNN_degV', default=0)
     p.add_argument('--UniGNN_degE', default=0)
     # additions of this driver (absent from the reference)
+    # (the reference declares --HyperGCN_mediators / --HyperGCN_fast store_true and defaults both to True, train.py:263-285: they
+    #  cannot be switched off there, and the re-approximating path would be unreachable from the command line)
+    p.add_argument('--no-HyperGCN_mediators', dest='HyperGCN_mediators', action='store_false')
+    p.add_argument('--no-HyperGCN_fast', dest='HyperGCN_fast', action='store_false')
     p.add_argument('--raw_data_dir', default=None, help='directory holding <dname>/{features,labels,hypergraph}.pickle')
     p.add_argument('--processed_data', default=None,
                    help="the reference's processed file <root>/<dname>/processed/data.pt (or its directory)")
@@ -471,7 +487,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help='1: capture the training step, the eval forward and the metrics as hipGraphs (allset_amd/graphs.py); '
                         '0: eager launches; -1 (default): graphs where the loop is launch-bound (at most 200k vertices), eager '
                         'above; a failed capture falls back to eager launches with a warning')
-    p.set_defaults(PMA=True, add_self_loop=True, exclude_self=False, GPR=False, LearnMask=False)
+    p.set_defaults(PMA=True, add_self_loop=True, exclude_self=False, GPR=False, LearnMask=False, HyperGCN_mediators=True,
+                   HyperGCN_fast=True)
     return p
 
 
@@ -514,7 +531,8 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
     """The AllSet branch of reference train.py:344-353, and the HNHN / HCHA / HGNN branches (:375-388): hyperedge ids re-based to 0,
     HNHN's norms computed before the re-base; HCHA's scales are computed here too (the reference derives them per forward); and the
     clique-expansion branch of CEGCN / CEGAT (:354-357: no self-loop hyperedges there, whatever ``--add_self_loop`` says); and the
-    UniGCNII branch (:390-412) with the dense incidence matrix replaced by its sorted, de-duplicated pairs."""
+    UniGCNII branch (:390-412) with the dense incidence matrix replaced by its sorted, de-duplicated pairs; and the HyperGCN branch
+    (:359-360): the V->E half alone, kept as zero-based (vertex, hyperedge) pairs in ``data.HyperGCN_pairs``."""
     if args.method in CE_METHODS:
         data = ExtractV2E(data)
         data = ConstructV2V(data)
@@ -527,6 +545,12 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
             data = Add_Self_Loops(data)
         data = ConstructH_pairs(data)                       # what build_model checks for UniGCNII (data.UniGNN_sizes)
         generate_norm_UniGNN(data, args)                    # args.UniGNN_degV / args.UniGNN_degE, as the reference keeps them
+        return data
+    if args.method in HYPERGCN_METHODS:                     # (reference train.py:359-360: ExtractV2E only, no self-loop hyperedges)
+        data = ExtractV2E(data)
+        pairs = data.edge_index.clone()
+        pairs[1] -= pairs[1].min()                          # hyperedge ids from 0, as the reference's get_HyperGCN_He_dict keys them
+        data.HyperGCN_pairs = pairs                         # what build_model checks for HyperGCN
         return data
     if args.method in BASELINE_METHODS:
         data = ExtractV2E(data)
@@ -548,7 +572,7 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
 
 def run(args) -> dict:
     if args.method not in BUILT_METHODS:
-        raise ValueError(f"method {args.method!r}: only {BUILT_METHODS} are built (HyperGCN and MLP are out of scope)")
+        raise ValueError(f"method {args.method!r}: only {BUILT_METHODS} are built (MLP is out of scope)")
     if args.seed is not None:
         np.random.seed(args.seed)
         torch.manual_seed(args.seed)
@@ -622,9 +646,14 @@ def _run_loop(args, model, data, splits, device, logger, runtimes, num_params):
             from .graphs import GraphedCallable
             graphed_metrics = GraphedCallable(
                 lambda: torch.cat([split_metrics(graphed_eval.out, y_all, sp, counts), graphed_step.loss.detach().reshape(1)]), device)
+        refresh_rv = getattr(model, 'refresh_projections', None) if not getattr(model, 'fast', True) else None
         for epoch in range(args.epochs):
             if use_graph:
+                if refresh_rv is not None:                 # (HyperGCN without --HyperGCN_fast: a replay reads the vectors as they are)
+                    refresh_rv()
                 graphed_step()
+                if refresh_rv is not None:
+                    refresh_rv()
                 graphed_eval()
                 hist[epoch] = graphed_metrics()
                 if args.display_step > 0 and epoch % args.display_step == 0:

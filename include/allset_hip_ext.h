@@ -834,6 +834,47 @@ int allset_unigcn_hop_fwd(int variant, int64_t nnz, const int32_t* row_order, co
                           const float* degV, const float* xe, int64_t ldxe, const float* x0, int64_t ldx0, float alpha, int use_norm,
                           float* xi, int64_t ldxi, float* t_out, int64_t n_t, int64_t n_s, int64_t d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * HyperGCN baseline (reference utils.py:11-199, models.py:29-77): the Laplacian approximation built on the device and the hop
+ * y = drop_p(act(A x + bias)), A = D^-1/2 (W + I) D^-1/2, without the N x N matrix.
+ * Added under ABI 15, additions only; detect with allset_hypergcn_supported() (returns 1).  fp32, row-major, int32 ids.
+ *
+ * Structure, from a feature matrix z f32[n_v, d] and a projection vector rv f32[d]:
+ *   allset_hypergcn_project : p[v] = z[v,:] . rv  (rows with equal values give equal bits)
+ *   allset_hypergcn_select  : over the hyperedge-major CSR (rowptr, col, perm = CSR position -> edge-list position), per
+ *       hyperedge e: S[e] / I[e] = the member at the first arg-max / arg-min of p in edge-list order (-1 for an empty hyperedge),
+ *       size[e] = k, w[e] = 1 / (2k - 3) with mediators, 1 / k without (0 for k = 0)
+ *   allset_hypergcn_degree  : over the vertex-major CSR (rows = vertices, col = hyperedges): dinv[v] = D[v]^-1/2 with
+ *       D = rowsum(W + I), selfc[v] = 1 - sum of w[e] over the hyperedges with S != I of which v is an extreme, and per
+ *       incidence j of that CSR colx[j] = the row of pq that the E->V pass gathers: with mediators 2e + 1 for an extreme of e and
+ *       2e for a mediator; without, e for an extreme and -1 (nothing) otherwise.  A (vertex, hyperedge) pair must occur once.
+ * Hop, with y = dinv * x:
+ *   allset_hypergcn_v2e : mediators: pq f32[2 n_e, d], pq[2e] = f w (sum of y over the members that are S or I),
+ *       pq[2e + 1] = f w sum_{u in e} y[u], f = 2 if S == I else 1; no mediators: pq f32[n_e, d], pq[e] = w (y[S] + y[I]) (the CSR
+ *       arguments are ignored and may be NULL)
+ *   allset_hypergcn_e2v : y[v] = drop_p(act(dinv[v] * (selfc[v] * dinv[v] * x[v] + sum_{j in row v, colx[j] >= 0} pq[colx[j]]) + bias))
+ *       over the vertex-major rowptr; act 0 none / 1 relu; dropout mask and seed convention of allset_hconv_fwd (element index
+ *       v * d + column), so allset_hconv_bwd_epi is the epilogue's backward.  A is symmetric: the backward in x is the same two
+ *       calls on the masked gradient without an epilogue.  variant: 0 auto / 1 one wavefront per row / 2 short rows.
+ * Widths built: d % 4 == 0 up to 256 with 16-byte aligned rows (pointers and leading dimensions), and any d <= 64; anything else
+ * returns ALLSET_ERR_UNSUPPORTED (v2e / e2v) and the caller composes the hop from allset_hconv_fwd.  No atomics: results are
+ * bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------- */
+int allset_hypergcn_supported(void);
+int allset_hypergcn_project(const float* z, int64_t ldz, const float* rv, float* p, int64_t n, int64_t d, void* stream);
+int allset_hypergcn_select(const int32_t* rowptr, const int32_t* col, const int32_t* perm, const float* p, int mediators, int32_t* S,
+                           int32_t* I, float* w, int32_t* size, int64_t n_e, int64_t n_v, int64_t nnz, void* stream);
+int allset_hypergcn_degree(const int32_t* rowptr, const int32_t* col, const int32_t* S, const int32_t* I, const float* w,
+                           const int32_t* size, int mediators, float* dinv, float* selfc, int32_t* colx, int64_t n_v, int64_t n_e,
+                           int64_t nnz, void* stream);
+int allset_hypergcn_v2e(int mediators, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                        const int32_t* S, const int32_t* I, const float* w, const float* dinv, const float* x, int64_t ldx, float* pq,
+                        int64_t ldpq, int64_t n_e, int64_t n_v, int64_t d, void* stream);
+int allset_hypergcn_e2v(int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* colx,
+                        const float* pq, int64_t ldpq, int64_t n_pq, const float* dinv, const float* selfc, const float* x, int64_t ldx,
+                        const float* bias, int act, float p, uint64_t seed, const uint64_t* seed_base, float* y, int64_t ldy,
+                        int64_t n_v, int64_t d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
