@@ -247,6 +247,12 @@ SIGNATURES = {
     "allset_hypergcn_v2e": [c_int, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P],
     "allset_hypergcn_e2v": [c_int, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_int64, _P, c_int, c_float, c_uint64, _P, _P,
                             c_int64, c_int64, c_int64, _P],
+    # UniGNN baselines: the E->V hop with the row tail, UniGAT's V->E hop with the attention logit (under ABI 15, additions only;
+    # detect with allset_unignn_supported)
+    "allset_unignn_supported": [],
+    "allset_unignn_hop_fwd": [c_int, c_int64, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_float, _P, c_int, c_int, c_float, c_uint64, _P,
+                              _P, c_int64, _P, c_int64, c_int64, c_int64, _P],
+    "allset_unignn_v2e_att_fwd": [c_int, c_int64, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

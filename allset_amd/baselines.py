@@ -22,6 +22,11 @@ weight ``(1 - beta) I + beta W`` and the one-pass ``relu`` + dropout.
 built on the device as a structure of roles (``functional.hypergcn_structure``) and each layer is one GEMM and one two-pass hop with
 the bias, ``relu`` and dropout in its second launch (``functional.hypergcn_propagate``, csrc/hypergcn.hip); the N x N adjacency is
 never formed, and the re-approximating mode rebuilds the structure per layer and forward without leaving the device.
+
+``UniGCNConv`` / ``UniGCNConv2`` / ``UniGINConv`` / ``UniSAGEConv`` / ``UniGATConv`` / ``UniGNN`` (reference models.py:601-907): the V->E
+hop is ``scaled_propagate`` (UniGAT: ``functional.unigat_edge``, with the attention logit in the launch), the E->V hop
+``functional.unignn_hop`` with the self term, the degree scale, the detached row normalisation, ``relu`` and dropout in its launch
+(csrc/unignn.hip); UniGAT's E->V hop is the AllSet softmax pooling ``functional.pma_aggregate``.
 """
 from __future__ import annotations
 
@@ -36,8 +41,8 @@ from torch.nn import Parameter
 
 from . import dense
 from ._lib import AllSetHipError
-from .functional import (HyperGCNStructure, gat_propagate, hypergcn_propagate, hypergcn_structure, initial_residual, scaled_propagate,
-                         unigcn_hop, weighted_propagate)
+from .functional import (HyperGCNStructure, gat_propagate, hypergcn_propagate, hypergcn_structure, initial_residual, pma_aggregate,
+                         scaled_propagate, unigat_edge, unigcn_hop, unignn_hop, unignn_row_tail, weighted_propagate)
 from .incidence import Incidence, cached_incidence
 from .layers import _linear, glorot, zeros
 from .preprocessing import generate_norm_HCHA
@@ -571,6 +576,254 @@ class UniGCNII(nn.Module):
             # relu, and the dropout in front of the next layer (the next conv, or the last Linear), in one pass
             x = dense.relu_dropout(conv(x, graph, None, alpha, beta, x0), p)
         return _linear(self.convs[-1], x)
+
+
+# ---- UniGNN: UniGCN, UniGCN2, UniGIN, UniSAGE, UniGAT ------------------------------------------------------------------------------
+_UNIGNN_AGGREGATES = ('mean', 'sum')
+
+
+class UniGNNGraph(UniGraph):
+    """:class:`UniGraph` with what the five plain UniGNN convs need beside it, each as a flat device vector built once: ``degE`` alone
+    (``first_aggregate='sum'``), ``inv_size`` = ``1 / |e|`` (the V->E mean of the convs without degree scales), ``inv_deg`` =
+    ``1 / max(deg(v), 1)`` (UniSAGE's ``second_aggregate='mean'``), and ``inc_ev``, the hyperedge -> vertex direction of the same two
+    CSRs with one output row per vertex (UniGAT's softmax pooling).  Holds strong references to every tensor a captured graph reads."""
+
+    def __init__(self, V: Tensor, E: Tensor, degV: Tensor, degE: Tensor, device):
+        super().__init__(V, E, degV, degE, device)
+        self.degE = degE.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        re_, rv = self.inc.by_dst.rowptr, self.inc.by_src.rowptr
+        self.inv_size = (1.0 / (re_[1:] - re_[:-1]).clamp(min=1).to(torch.float32)).contiguous()
+        self.inv_deg = (1.0 / (rv[1:] - rv[:-1]).clamp(min=1).to(torch.float32)).contiguous()
+        self.inc_ev = self.inc.reversed(n_dst=self.inc.n_src)
+
+    def edge_scale(self, first_aggregate: str, with_degE: bool) -> Optional[Tensor]:
+        """The per-hyperedge scale of the V->E hop: the mean's ``1 / |e|`` and / or ``degE``, as one vector (None = ones)."""
+        if first_aggregate == 'mean':
+            return self.scaleE if with_degE else self.inv_size
+        return self.degE if with_degE else None
+
+
+def _unignn_first_aggregate(args) -> str:
+    agg = getattr(args, 'first_aggregate', 'mean')
+    if agg not in _UNIGNN_AGGREGATES:
+        raise NotImplementedError(f"UniGNN: first_aggregate={agg!r} is not built: the V->E hop is a sum or a mean over the members of "
+                                  f"a hyperedge ({_UNIGNN_AGGREGATES})")
+    return agg
+
+
+def _unignn_second_aggregate(args) -> str:
+    agg = getattr(args, 'second_aggregate', 'sum')
+    if agg not in _UNIGNN_AGGREGATES:
+        raise NotImplementedError(f"UniGNN: second_aggregate={agg!r} is not built: the E->V hop is a sum or a mean over the hyperedges "
+                                  f"of a vertex ({_UNIGNN_AGGREGATES})")
+    return agg
+
+
+def _unignn_degrees(args):
+    degV, degE = getattr(args, 'degV', None), getattr(args, 'degE', None)
+    if not (torch.is_tensor(degV) and torch.is_tensor(degE)):
+        raise ValueError("UniGNN: args.degV / args.degE are missing (preprocessing.generate_norm_UniGNN computes them; train.preprocess "
+                         "sets both)")
+    return degV, degE
+
+
+def _unignn_post(x: Tensor, act: Optional[str], p: float) -> Tensor:
+    """The activation and dropout behind a conv whose last step is not a hop: one pass."""
+    if act == 'relu':
+        return dense.relu_dropout(x, p)
+    return dense.hash_dropout(x, p, p > 0.0)
+
+
+class _UniConv(nn.Module):
+    """What the five convs share (reference models.py:601-790): the constructor's signature and attributes, ``__repr__``, the graph
+    argument.  ``forward(X, vertex, edges, *, act=None, p=0.0)``: ``vertex`` / ``edges`` are the pair lists, or ``vertex`` is a prebuilt
+    :class:`UniGNNGraph` (``edges`` is then ignored); ``act`` / ``p``: the activation and dropout the model applies next, fused into the
+    conv's last launch."""
+    _bias = False
+
+    def __init__(self, args, in_channels, out_channels, heads=8, dropout=0., negative_slope=0.2):
+        super().__init__()
+        self.W = nn.Linear(in_channels, heads * out_channels, bias=self._bias)
+        self.heads = heads
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.negative_slope = negative_slope
+        self.dropout = dropout
+        self.args = args
+        _unignn_first_aggregate(args)
+
+    def reset_parameters(self):
+        self.W.reset_parameters()
+
+    def _graph(self, X: Tensor, vertex, edges) -> UniGNNGraph:
+        if isinstance(vertex, UniGNNGraph):
+            return vertex
+        if not (X.is_cuda and X.dtype == torch.float32):
+            raise AllSetHipError("the UniGNN baselines run on ROCm device fp32 tensors (no CPU path)")
+        degV, degE = _unignn_degrees(self.args)
+        return UniGNNGraph(vertex, edges, degV, degE, X.device)
+
+    def _use_norm(self) -> bool:
+        return bool(getattr(self.args, 'use_norm', False))
+
+    def __repr__(self):
+        return '{}({}, {}, heads={})'.format(self.__class__.__name__, self.in_channels, self.out_channels, self.heads)
+
+
+class UniGCNConv(_UniConv):
+    """Reference models.py:694-737: ``X = W(X)``, ``Xe = degE * agg_{v in e} X[v]``, ``Xv = degV * sum_{e ni v} Xe[e]``, row-normalised
+    (detached norm) under ``args.use_norm``.  The E->V sum, ``degV``, the norm and the model's ``relu`` + dropout are one launch."""
+
+    def forward(self, X: Tensor, vertex, edges=None, *, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+        g = self._graph(X, vertex, edges)
+        Xe = scaled_propagate(_linear(self.W, X), g.inc, 'v2e', s=g.edge_scale(_unignn_first_aggregate(self.args), True))
+        return unignn_hop(Xe, g.inc, s=g.degV, use_norm=self._use_norm(), act=act, p=p)
+
+
+class UniGCNConv2(_UniConv):
+    """Reference models.py:742-788: the two hops and the norm of :class:`UniGCNConv` first, the Linear (with bias) last.  The hop
+    carries the norm only; ``relu`` + dropout follow the GEMM in one pass."""
+    _bias = True
+
+    def forward(self, X: Tensor, vertex, edges=None, *, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+        g = self._graph(X, vertex, edges)
+        Xe = scaled_propagate(X, g.inc, 'v2e', s=g.edge_scale(_unignn_first_aggregate(self.args), True))
+        Xv = unignn_hop(Xe, g.inc, s=g.degV, use_norm=self._use_norm())
+        return _unignn_post(_linear(self.W, Xv), act, p)
+
+
+class UniGINConv(_UniConv):
+    """Reference models.py:646-689: ``X = W(X)``, ``Xe = agg_{v in e} X[v]``, ``X = (1 + eps) X + sum_{e ni v} Xe[e]``, then the norm.
+    ``1 + eps`` reaches the hop as a device scalar, so a captured graph follows the parameter."""
+
+    def __init__(self, args, in_channels, out_channels, heads=8, dropout=0., negative_slope=0.2):
+        super().__init__(args, in_channels, out_channels, heads, dropout, negative_slope)
+        self.eps = nn.Parameter(torch.Tensor([0.]))
+
+    def reset_parameters(self):
+        self.W.reset_parameters()
+        zeros(self.eps)
+
+    def forward(self, X: Tensor, vertex, edges=None, *, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+        g = self._graph(X, vertex, edges)
+        X = _linear(self.W, X)
+        Xe = scaled_propagate(X, g.inc, 'v2e', s=g.edge_scale(_unignn_first_aggregate(self.args), False))
+        return unignn_hop(Xe, g.inc, xs=X, c=1 + self.eps, use_norm=self._use_norm(), act=act, p=p)
+
+
+class UniSAGEConv(_UniConv):
+    """Reference models.py:601-641: ``X = W(X)``, ``Xe = agg_{v in e} X[v]``, ``X = X + agg2_{e ni v} Xe[e]`` with ``agg2`` =
+    ``args.second_aggregate`` (sum / mean), then the norm."""
+
+    def __init__(self, args, in_channels, out_channels, heads=8, dropout=0., negative_slope=0.2):
+        super().__init__(args, in_channels, out_channels, heads, dropout, negative_slope)
+        _unignn_second_aggregate(args)
+
+    def forward(self, X: Tensor, vertex, edges=None, *, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+        g = self._graph(X, vertex, edges)
+        X = _linear(self.W, X)
+        Xe = scaled_propagate(X, g.inc, 'v2e', s=g.edge_scale(_unignn_first_aggregate(self.args), False))
+        s = g.inv_deg if _unignn_second_aggregate(self.args) == 'mean' else None
+        return unignn_hop(Xe, g.inc, s=s, xs=X, c=1.0, use_norm=self._use_norm(), act=act, p=p)
+
+
+class UniGATConv(_UniConv):
+    """Reference models.py:792-854: ``X0 = W(X)`` as ``[N, H, C]``, ``Xe = agg_{v in e} X0[v]``, ``alpha_e = <Xe, att_e>`` per head,
+    ``Xv[v] = sum_{e ni v} softmax_e(leaky_relu(alpha_e)) Xe[e]``, the norm, ``+ X0`` under ``skip_sum``.  The V->E hop writes the
+    logits in its own launch (``functional.unigat_edge``); the logit depends on the gathered hyperedge alone, so the E->V hop is the
+    AllSet softmax pooling (``functional.pma_aggregate``) over the hyperedge -> vertex direction.  ``att_v`` is an unused parameter, as
+    in the reference.  Dropout on the attention coefficients is not built."""
+
+    def __init__(self, args, in_channels, out_channels, heads=8, dropout=0., negative_slope=0.2, skip_sum=False):
+        if dropout > 0.0:
+            raise NotImplementedError("UniGATConv: dropout on the attention coefficients (attn_drop > 0) is not built")
+        super().__init__(args, in_channels, out_channels, heads, dropout, negative_slope)
+        self.att_v = nn.Parameter(torch.Tensor(1, heads, out_channels))
+        self.att_e = nn.Parameter(torch.Tensor(1, heads, out_channels))
+        self.attn_drop = nn.Dropout(dropout)
+        self.leaky_relu = nn.LeakyReLU(negative_slope)
+        self.skip_sum = skip_sum
+        self.reset_attention()
+
+    def reset_attention(self):
+        glorot(self.att_v)
+        glorot(self.att_e)
+
+    def reset_parameters(self):
+        self.W.reset_parameters()
+        self.reset_attention()
+
+    def forward(self, X: Tensor, vertex, edges=None, *, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+        g = self._graph(X, vertex, edges)
+        H = self.heads
+        X0 = _linear(self.W, X)
+        Xe, ae = unigat_edge(X0, g.inc, g.edge_scale(_unignn_first_aggregate(self.args), False), self.att_e, H)
+        Xv, _, _ = pma_aggregate(Xe, ae, g.inc_ev, H, self.negative_slope)
+        return unignn_row_tail(Xv, skip=X0 if self.skip_sum else None, use_norm=self._use_norm(), act=act, p=p)
+
+
+UNIGNN_CONVS = {'UniGAT': UniGATConv, 'UniGCN': UniGCNConv, 'UniGCN2': UniGCNConv2, 'UniGIN': UniGINConv, 'UniSAGE': UniSAGEConv}
+
+
+class UniGNN(nn.Module):
+    """Reference models.py:869-907: ``conv_out = Conv(nhid * nhead, nclass, heads=1)`` and ``convs = [Conv(nfeat, nhid, heads=nhead)] +
+    [Conv(nhid * nhead, nhid, heads=nhead)] * (nlayer - 2)`` with ``Conv`` chosen by ``args.model_name``; input dropout, then per conv the
+    activation and dropout, then ``conv_out`` and ``log_softmax``.  ``V`` / ``E``: the sorted, de-duplicated pairs of
+    ``preprocessing.ConstructH_pairs``; ``args.degV`` / ``args.degE`` the scales of ``generate_norm_UniGNN``.  ``relu`` and the dropout
+    ride in each conv's last launch; ``prelu`` runs unfused (conv, ``nn.PReLU``, hash dropout).  Training-mode masks are the library's
+    hash dropout."""
+
+    def __init__(self, args, nfeat, nhid, nclass, nlayer, nhead, V, E):
+        super().__init__()
+        if args.model_name not in UNIGNN_CONVS:
+            raise ValueError(f"UniGNN: args.model_name={args.model_name!r} is not one of {tuple(sorted(UNIGNN_CONVS))}")
+        Conv = UNIGNN_CONVS[args.model_name]
+        self.args = args
+        self.conv_out = Conv(args, nhid * nhead, nclass, heads=1, dropout=args.attn_drop)
+        self.convs = nn.ModuleList(
+            [Conv(args, nfeat, nhid, heads=nhead, dropout=args.attn_drop)] +
+            [Conv(args, nhid * nhead, nhid, heads=nhead, dropout=args.attn_drop) for _ in range(nlayer - 2)])
+        self.V = V
+        self.E = E
+        act = {'relu': nn.ReLU(), 'prelu': nn.PReLU()}
+        self.act = act[args.activation]
+        self.input_drop = nn.Dropout(args.input_drop)
+        self.dropout = nn.Dropout(args.dropout)
+        self._graph: Optional[UniGNNGraph] = None
+
+    def reset_parameters(self):
+        """(The reference's module has none and its driver's call fails; this one redraws every conv as its constructor does.)"""
+        self.conv_out.reset_parameters()
+        for conv in self.convs:
+            conv.reset_parameters()
+        if isinstance(self.act, nn.PReLU):
+            with torch.no_grad():
+                self.act.weight.fill_(0.25)
+
+    def graph(self, x: Tensor) -> UniGNNGraph:
+        """The incidence and scales on ``x``'s device, built on first sight and kept for later forwards."""
+        degV, degE = _unignn_degrees(self.args)
+        if self._graph is None or not self._graph.matches(self.V, self.E, degV, degE, x.device):
+            if degV.shape[0] != x.shape[0]:
+                raise ValueError(f"UniGNN: args.degV has {degV.shape[0]} rows, the features have {x.shape[0]}")
+            self._graph = UniGNNGraph(self.V, self.E, degV, degE, x.device)
+        return self._graph
+
+    def forward(self, X):
+        """``X``: the feature tensor, as the reference takes it, or a ``data`` object with ``.x``.  Returns log-probabilities."""
+        X = X if torch.is_tensor(X) else X.x
+        if not (X.is_cuda and X.dtype == torch.float32):
+            raise AllSetHipError("the UniGNN baselines run on ROCm device fp32 tensors (no CPU path)")
+        graph = self.graph(X)
+        p = float(self.dropout.p) if self.training else 0.0
+        X = dense.hash_dropout(X, float(self.input_drop.p), self.training)
+        for conv in self.convs:
+            if isinstance(self.act, nn.ReLU):
+                X = conv(X, graph, act='relu', p=p)
+            else:
+                X = dense.hash_dropout(self.act(conv(X, graph)), p, self.training)
+        X = self.conv_out(X, graph)
+        return torch.log_softmax(X, dim=1)
 
 
 # ---- HyperGCN ---------------------------------------------------------------------------------------------------------------------

@@ -755,3 +755,164 @@ def hypergcn_propagate(x: Tensor, structure: HyperGCNStructure, bias: Optional[T
     if fused is None:
         fused = ops.hypergcn_hop_supported(x)
     return _HyperGCNPropagate.apply(x, bias, structure, act, float(p), variant, bool(fused))
+
+
+# ---- UniGNN: the E->V hop with the row tail, UniGAT's V->E hop with the attention logit (csrc/unignn.hip) ------------------------------
+class _UniGNNHop(torch.autograd.Function):
+    """``y = drop_p(act(t * (s * (H xe) + c * xs)))`` with ``t`` the detached row-norm scale -- one kernel forward where the width is
+    built (``ops.unignn_hop_supported``), else the ``hconv`` launches plus torch ops (same hash mask).  Backward: the epilogue's kernel
+    (only when there is an activation or dropout), ``gxe`` the ``hconv`` launch over the hyperedge-major CSR with ``r = s * t`` (``t``
+    saved, a constant), ``gxs = c * t * g`` and, for a tensor ``c``, ``gc = sum_v t[v] <g[v], xs[v]>`` (torch ops)."""
+
+    @staticmethod
+    def forward(ctx, xe, xs, c_t, inc, s, c_f, use_norm, act, p, variant):
+        from . import dense
+        n_v = inc.n_src
+        if xe.shape[0] != inc.n_dst:
+            raise _lib.AllSetHipError(f"unignn_hop: xe has {xe.shape[0]} rows, the incidence has {inc.n_dst} hyperedges")
+        seed = dense._draw_seed() if p > 0.0 else 0
+        base = dense._seed_base() if p > 0.0 else None
+        c = c_t.detach() if c_t is not None else c_f
+        if ops.unignn_hop_supported(xe, xs):
+            y, t = ops.unignn_hop_fwd(inc.by_src, xe, n_v, s, xs, c, use_norm, act, p, seed, base, variant)
+        else:                                                    # width not built: correct, unfused
+            a = ops.hconv_propagate(inc.by_src, xe, n_v, s=s)
+            if xs is not None:
+                a = a + xs * c
+            t = None
+            if use_norm:
+                nrm = a.norm(dim=1)
+                t = torch.where(nrm > 0, 1.0 / nrm, torch.zeros_like(nrm))
+                a = a * t.unsqueeze(1)
+            y = a if (act is None and p == 0.0) else \
+                ops.hconv_propagate(_identity_csr(inc, n_v), a, n_v, act=act, p=p, seed=seed, seed_base=base)
+        epi = act is not None or p > 0.0
+        need_c = c_t is not None and ctx.needs_input_grad[2]
+        ctx.save_for_backward(t, y if epi else None, xs if need_c else None, c_t)
+        ctx.cfg = (inc, s, c_f, act, p, seed, base, epi)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        t, y, xs, c_t = ctx.saved_tensors
+        inc, s, c_f, act, p, seed, base, epi = ctx.cfg
+        if epi:
+            g, _ = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=False)
+        else:
+            g = gy.contiguous()
+        gxe = gxs = gc = None
+        if ctx.needs_input_grad[0]:
+            r = s if t is None else (t if s is None else s * t)
+            gxe = ops.hconv_propagate(inc.by_dst, g, inc.n_dst, r=r)
+        c = c_t if c_t is not None else c_f
+        if ctx.needs_input_grad[1]:
+            gxs = g * c if t is None else g * (t * c).unsqueeze(1)
+        if c_t is not None and ctx.needs_input_grad[2]:
+            dots = (g * xs).sum(dim=1)
+            gc = (dots if t is None else dots * t).sum().reshape(c_t.shape)
+        return gxe, gxs, gc, None, None, None, None, None, None, None
+
+
+def unignn_hop(xe: Tensor, inc: Incidence, *, s: Optional[Tensor] = None, xs: Optional[Tensor] = None, c=1.0, use_norm: bool = False,
+               act: Optional[str] = None, p: float = 0.0, variant: Optional[int] = None) -> Tensor:
+    """The E->V hop of a UniGNN conv over ``inc`` (sources = vertices, targets = hyperedges) with the row tail in the same launch:
+    ``a[v] = s[v] * sum_{e ni v} xe[e] + c * xs[v]``, ``t[v] = 1 / ||a[v]||`` (0 for a zero row; a constant of the backward, as the
+    reference's ``normalize_l2``) when ``use_norm`` else 1, ``y[v] = drop_p(act(t[v] * a[v]))``.  ``xe`` [n_dst, d]; ``s`` [n_src] (or
+    [n_src, 1]) and ``xs`` [n_src, d] optional; ``c`` a float or a one-element device tensor (read on the device: a captured graph sees
+    its current value); ``act`` None / 'relu'; ``p`` the dropout probability (the library's hash mask).  Device fp32 only.
+    Differentiable in ``xe``, ``xs`` and a tensor ``c``.  ``variant``: kernel variant override (tests)."""
+    if act not in ops.UNIGNN_ACTS:
+        raise ValueError(f"unignn_hop: act must be None or 'relu', got {act!r}")
+    c_t = c if torch.is_tensor(c) else None
+    _lib.require_device(xe, xs, s, c_t)
+    if xe.dtype != torch.float32 or (xs is not None and xs.dtype != torch.float32) or (c_t is not None and c_t.dtype != torch.float32):
+        raise _lib.AllSetHipError("unignn_hop: fp32 tensors only")
+    if s is not None:
+        s = s.reshape(-1)
+        if s.dtype != torch.float32 or s.numel() != inc.n_src:
+            raise _lib.AllSetHipError(f"unignn_hop: s {tuple(s.shape)} {s.dtype} does not fit {inc.n_src} vertices")
+        s = s.contiguous()
+    if xs is not None and (xs.shape[0] != inc.n_src or xs.shape[1] != xe.shape[1]):
+        raise _lib.AllSetHipError(f"unignn_hop: xs {tuple(xs.shape)} does not fit {inc.n_src} vertices of width {xe.shape[1]}")
+    if c_t is not None and c_t.numel() != 1:
+        raise _lib.AllSetHipError(f"unignn_hop: c has {c_t.numel()} elements, expected one")
+    return _UniGNNHop.apply(xe, xs, c_t, inc, s, 1.0 if c_t is not None else float(c), bool(use_norm), act, float(p), variant)
+
+
+class _UniGATEdge(torch.autograd.Function):
+    """``xe = s * (H^T x)``, ``ae[e, h] = <xe[e, h, :], att_e[h, :]>`` -- one kernel forward where the shape is built
+    (``ops.unignn_v2e_att_supported``), else the ``hconv`` launch plus a torch reduction.  Backward (torch ops around one ``hconv``
+    launch): ``gxe_total = gxe + gae (x) att_e``, ``gx`` its propagate over the vertex-major CSR with ``r = s``,
+    ``gatt_e = sum_e gae[e, h] * xe[e, h, :]``."""
+
+    @staticmethod
+    def forward(ctx, x, att_e, inc, s, heads, variant):
+        if x.shape[0] != inc.n_src:
+            raise _lib.AllSetHipError(f"unigat_edge: x has {x.shape[0]} rows, the incidence has {inc.n_src} vertices")
+        if ops.unignn_v2e_att_supported(x, heads):
+            xe, ae = ops.unignn_v2e_att_fwd(inc.by_dst, x, inc.n_dst, s, att_e, heads, variant)
+        else:                                                    # channels not a multiple of 4 (the class count): unfused
+            xe = ops.hconv_propagate(inc.by_dst, x, inc.n_dst, s=s)
+            ae = (xe.view(xe.shape[0], heads, -1) * att_e.reshape(1, heads, -1)).sum(dim=-1)
+        ctx.save_for_backward(xe, att_e)
+        ctx.cfg = (inc, s, heads)
+        ctx.set_materialize_grads(False)
+        return xe, ae
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gxe, gae):
+        xe, att_e = ctx.saved_tensors
+        inc, s, heads = ctx.cfg
+        gx = gatt = None
+        M, d = xe.shape
+        if gae is not None:
+            extra = (gae.unsqueeze(-1) * att_e.reshape(1, heads, -1)).reshape(M, d)
+            gxe = extra if gxe is None else gxe + extra
+            if ctx.needs_input_grad[1]:
+                gatt = (gae.unsqueeze(-1) * xe.view(M, heads, -1)).sum(dim=0).reshape(att_e.shape)
+        if ctx.needs_input_grad[0] and gxe is not None:
+            gx = ops.hconv_propagate(inc.by_src, gxe.contiguous(), inc.n_src, r=s)
+        return gx, gatt, None, None, None, None
+
+
+def unigat_edge(x: Tensor, inc: Incidence, s: Optional[Tensor], att_e: Tensor, heads: int, variant: Optional[int] = None
+                ) -> Tuple[Tensor, Tensor]:
+    """UniGAT's V->E hop over ``inc`` (sources = vertices, targets = hyperedges) with the attention logit in the same launch:
+    ``xe[e] = s[e] * sum_{v in e} x[v]`` and ``ae[e, h] = <xe[e, h, :], att_e[h, :]>``.  ``x`` [n_src, heads * C]; ``s`` [n_dst] or None
+    (``1 / |e|`` for the mean); ``att_e`` of ``heads * C`` elements (any shape).  Returns ``(xe [n_dst, heads * C], ae [n_dst, heads])``.
+    Device fp32 only.  Differentiable in ``x`` and ``att_e``."""
+    _lib.require_device(x, s, att_e)
+    if x.dtype != torch.float32 or att_e.dtype != torch.float32:
+        raise _lib.AllSetHipError("unigat_edge: fp32 tensors only")
+    heads = int(heads)
+    if heads <= 0 or x.shape[1] % heads != 0 or att_e.numel() != x.shape[1]:
+        raise _lib.AllSetHipError(f"unigat_edge: x of width {x.shape[1]} / att_e of {att_e.numel()} elements do not fit {heads} heads")
+    if s is not None:
+        s = s.reshape(-1)
+        if s.dtype != torch.float32 or s.numel() != inc.n_dst:
+            raise _lib.AllSetHipError(f"unigat_edge: s {tuple(s.shape)} {s.dtype} does not fit {inc.n_dst} hyperedges")
+        s = s.contiguous()
+    return _UniGATEdge.apply(ops._rowmajor(x), att_e, inc, s, heads, variant)
+
+
+def unignn_row_tail(a: Tensor, skip: Optional[Tensor] = None, use_norm: bool = False, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+    """UniGAT's row tail behind the attention pooling: ``t = 1 / ||a||`` (detached, 0 for a zero row) under ``use_norm``,
+    ``y = drop_p(act(t * a + skip))`` -- the reference normalises first and adds the skip term afterwards.  Without norm and skip this
+    is the one-pass ``dense.relu_dropout``; otherwise the norm and the sum are torch ops over [N, d] and only the ``relu`` + dropout
+    pass is the library's (no fused kernel for this tail yet: DESIGN.md section 14 lists the passes it leaves)."""
+    from . import dense
+    if act not in ops.UNIGNN_ACTS:
+        raise ValueError(f"unignn_row_tail: act must be None or 'relu', got {act!r}")
+    _lib.require_device(a, skip)
+    if a.dtype != torch.float32 or (skip is not None and skip.dtype != torch.float32):
+        raise _lib.AllSetHipError("unignn_row_tail: fp32 tensors only")
+    if use_norm:
+        nrm = a.detach().norm(dim=1, keepdim=True)
+        a = a * torch.where(nrm > 0, 1.0 / nrm, torch.zeros_like(nrm))
+    if skip is not None:
+        a = a + skip
+    if act == 'relu':
+        return dense.relu_dropout(a, p)
+    return dense.hash_dropout(a, p, p > 0.0)

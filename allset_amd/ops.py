@@ -765,6 +765,106 @@ def unigcn_hop_fwd(csr: CSR, xe: Tensor, x0: Tensor, n_t: int, degV: Optional[Te
     return xi, t
 
 
+# ---- UniGNN: the E->V hop with the row tail, UniGAT's V->E hop with the attention logit (csrc/unignn.hip) ------------------------------
+UNIGNN_MAX_WIDTH = 512
+UNIGNN_ACTS = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "relu": _lib.ACT_RELU}
+
+
+def unignn_hop_supported(xe: Tensor, xs: Optional[Tensor] = None) -> bool:
+    """Is the fused E->V launch built for these operands?  fp32, width a multiple of 4 up to 512, 16-byte aligned rows."""
+    d = xe.shape[1]
+    ts = (xe,) if xs is None else (xe, xs)
+    return (all(t.dtype == torch.float32 for t in ts) and 0 < d <= UNIGNN_MAX_WIDTH and d % 4 == 0
+            and all(t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= d and t.data_ptr() % 16 == 0 for t in ts))
+
+
+def unignn_hop_fwd(csr: CSR, xe: Tensor, n_t: int, s: Optional[Tensor] = None, xs: Optional[Tensor] = None, c=1.0,
+                   use_norm: bool = False, act: Optional[str] = None, p: float = 0.0, seed: int = 0,
+                   seed_base: Optional[Tensor] = None, variant: Optional[int] = None) -> Tuple[Tensor, Optional[Tensor]]:
+    """``(y, t)``: ``y[v] = drop_p(act(t[v] * a[v]))`` with ``a[v] = s[v] * sum_{j in row v} xe[col_j] + c * xs[v]`` over ``csr`` (rows =
+    vertices) and ``t[v] = 1 / ||a[v]||`` (0 for a zero row) when ``use_norm``, else ``t`` is None (= ones).  ``c``: a float, or a device
+    fp32 tensor of one element (read by the kernel).  One launch; raises where the width is not built (:func:`unignn_hop_supported`)."""
+    c_dev = c if torch.is_tensor(c) else None
+    dev = require_device(csr.rowptr, xe, xs, s, c_dev)
+    _f32(xe, "unignn_hop_fwd")
+    xe = _rowmajor(xe)
+    n_s, d = xe.shape
+    if xs is not None:
+        _f32(xs, "unignn_hop_fwd xs")
+        xs = _rowmajor(xs)
+        if xs.shape != (n_t, d):
+            raise _lib.AllSetHipError(f"unignn_hop_fwd: xs is {tuple(xs.shape)}, expected {(n_t, d)}")
+    if s is not None:
+        _f32(s, "unignn_hop_fwd s")
+        s = s.contiguous()
+        if s.numel() < n_t:
+            raise _lib.AllSetHipError(f"unignn_hop_fwd: s has {s.numel()} entries for {n_t} output rows")
+    if c_dev is not None:
+        _f32(c_dev, "unignn_hop_fwd c")
+        if c_dev.numel() != 1:
+            raise _lib.AllSetHipError(f"unignn_hop_fwd: c has {c_dev.numel()} elements, expected one")
+    if n_t > csr.n_rows or csr.n_cols > n_s:
+        raise _lib.AllSetHipError(f"unignn_hop_fwd: CSR of {csr.n_rows} x {csr.n_cols} against {n_t} outputs / {n_s} gathered rows")
+    y = torch.empty((n_t, d), dtype=torch.float32, device=dev)
+    t = torch.empty(n_t, dtype=torch.float32, device=dev) if use_norm else None
+    nnz = csr.col.numel()
+    if variant is None:
+        variant = csr.variant("segreduce", n_t) if d <= 256 else 1
+    order = csr.row_order if (variant == 1 and csr.row_order is not None and csr.row_order.numel() == n_t) else None
+    algo = (nnz * (4 * d + 4) + (n_t + 1) * 4 + n_t * 4 * d * (1 + int(xs is not None))
+            + n_t * 4 * (int(s is not None) + int(bool(use_norm))))
+    with on_device(dev), _timed("unignn_hop_fwd", dev, algo):
+        check(_lib.load().allset_unignn_hop_fwd(variant, nnz, ptr(order), ptr(csr.rowptr), ptr(csr.col), ptr(s), ptr(xe), _ld(xe),
+                                                ptr(xs), _ld(xs) if xs is not None else 0, 0.0 if c_dev is not None else float(c),
+                                                ptr(c_dev), int(bool(use_norm)), UNIGNN_ACTS[act], float(p), int(seed),
+                                                ptr(seed_base), ptr(y), max(d, 1), ptr(t), n_t, n_s, d, stream_of(dev)),
+              "allset_unignn_hop_fwd")
+    return y, t
+
+
+def unignn_v2e_att_supported(x: Tensor, heads: int) -> bool:
+    """Is the fused V->E launch built?  fp32, ``heads`` heads of C channels with C a multiple of 4, heads * C up to 512, 16-byte rows."""
+    d = x.shape[1]
+    return (x.dtype == torch.float32 and heads > 0 and 0 < d <= UNIGNN_MAX_WIDTH and d % heads == 0 and (d // heads) % 4 == 0
+            and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= d and x.data_ptr() % 16 == 0)
+
+
+def unignn_v2e_att_fwd(csr: CSR, x: Tensor, n_t: int, s: Optional[Tensor], att: Tensor, heads: int,
+                       variant: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """``(xe, ae)``: ``xe[e] = s[e] * sum_{j in row e} x[col_j]`` over ``csr`` (rows = hyperedges) and ``ae[e, h] = <xe[e, h, :], att[h, :]>``
+    (``att`` f32 of ``heads * C`` elements).  One launch; raises where the shape is not built (:func:`unignn_v2e_att_supported`)."""
+    dev = require_device(csr.rowptr, x, s, att)
+    _f32(x, "unignn_v2e_att_fwd")
+    _f32(att, "unignn_v2e_att_fwd att")
+    x = _rowmajor(x)
+    att = att.reshape(-1).contiguous()
+    if att.data_ptr() % 16 != 0:                 # (a view at an odd offset: the kernel reads att 16 bytes per lane; d floats, copied)
+        att = att.clone()
+    n_s, d = x.shape
+    H = int(heads)
+    if H <= 0 or d % H != 0 or att.numel() != d:
+        raise _lib.AllSetHipError(f"unignn_v2e_att_fwd: width {d} / att of {att.numel()} elements do not fit {H} heads")
+    if s is not None:
+        _f32(s, "unignn_v2e_att_fwd s")
+        s = s.contiguous()
+        if s.numel() < n_t:
+            raise _lib.AllSetHipError(f"unignn_v2e_att_fwd: s has {s.numel()} entries for {n_t} output rows")
+    if n_t > csr.n_rows or csr.n_cols > n_s:
+        raise _lib.AllSetHipError(f"unignn_v2e_att_fwd: CSR of {csr.n_rows} x {csr.n_cols} against {n_t} outputs / {n_s} gathered rows")
+    xe = torch.empty((n_t, d), dtype=torch.float32, device=dev)
+    ae = torch.empty((n_t, H), dtype=torch.float32, device=dev)
+    nnz = csr.col.numel()
+    if variant is None:
+        variant = csr.variant("segreduce", n_t) if d <= 256 else 1
+    order = csr.row_order if (variant == 1 and csr.row_order is not None and csr.row_order.numel() == n_t) else None
+    algo = nnz * (4 * d + 4) + (n_t + 1) * 4 + n_t * (4 * d + 4 * H + 4 * int(s is not None)) + 4 * d
+    with on_device(dev), _timed("unignn_v2e_att_fwd", dev, algo):
+        check(_lib.load().allset_unignn_v2e_att_fwd(variant, nnz, ptr(order), ptr(csr.rowptr), ptr(csr.col), ptr(s), ptr(x), _ld(x),
+                                                    ptr(att), ptr(xe), max(d, 1), ptr(ae), n_t, n_s, H, d // H, stream_of(dev)),
+              "allset_unignn_v2e_att_fwd")
+    return xe, ae
+
+
 # ---- HyperGCN: the on-device Laplacian approximation and its two-pass hop (csrc/hypergcn.hip) -----------------------------------------
 HYPERGCN_MAX_WIDTH = 256             # 16-byte lanes: multiples of 4 up to here
 HYPERGCN_MAX_SCALAR_WIDTH = 64       # one column per lane: any width up to here (the class counts of the last layer)

@@ -15,7 +15,8 @@ noisy class-indicator features).  Of the reference's baselines, the hypergraph c
 built (``allset_amd/baselines.py``; same preprocessing branches, train.py:375-388, and the same ``--HCHA_symdegnorm`` /
 ``--HNHN_*`` flags), and so are the clique-expansion CEGCN and CEGAT (branch :354-357, ``--normalization``; CEGAT also ``--heads`` /
 ``--output_heads``), and UniGCNII (branch :390-412, ``--UniGNN_use-norm``; its two-group Adam of :463-467 ignores ``--lr`` / ``--wd``
-as there), and HyperGCN (branch :359-360, ``--HyperGCN_mediators`` / ``--HyperGCN_fast``, both on by default as there, with
+as there), the plain UniGNN model with one of its five convs (``--method UniGCN | UniGCN2 | UniGIN | UniSAGE | UniGAT``: UniGCNII's
+preprocessing branch, the ``--UniGNN_*`` flags below, the default one-group Adam), and HyperGCN (branch :359-360, ``--HyperGCN_mediators`` / ``--HyperGCN_fast``, both on by default as there, with
 ``--no-HyperGCN_mediators`` / ``--no-HyperGCN_fast`` to switch them off); MLP is out of scope and rejected.
 
     python -m allset_amd.train --method AllSetTransformer --dname synthetic --epochs 50 --runs 2 --heads 4 \\
@@ -23,6 +24,7 @@ as there), and HyperGCN (branch :359-360, ``--HyperGCN_mediators`` / ``--HyperGC
     python -m allset_amd.train --method HCHA --dname synthetic --epochs 50 --runs 2      # HGNN: --method HGNN --HCHA_symdegnorm
     python -m allset_amd.train --method UniGCNII --dname synthetic --epochs 50 --runs 2 --All_num_layers 4
     python -m allset_amd.train --method HyperGCN --dname synthetic --epochs 50 --runs 2 --no-HyperGCN_fast
+    python -m allset_amd.train --method UniGAT --dname synthetic --epochs 50 --runs 2 --heads 2
 """
 from __future__ import annotations
 
@@ -50,7 +52,8 @@ BASELINE_METHODS = ('HGNN', 'HCHA', 'HNHN')
 CE_METHODS = ('CEGCN', 'CEGAT')
 UNIGNN_METHODS = ('UniGCNII',)
 HYPERGCN_METHODS = ('HyperGCN',)
-BUILT_METHODS = ALLSET_METHODS + BASELINE_METHODS + CE_METHODS + UNIGNN_METHODS + HYPERGCN_METHODS
+UNIGNN_CONV_METHODS = ('UniGCN', 'UniGCN2', 'UniGIN', 'UniSAGE', 'UniGAT')       # the plain UniGNN model, one conv each
+BUILT_METHODS = ALLSET_METHODS + BASELINE_METHODS + CE_METHODS + UNIGNN_METHODS + HYPERGCN_METHODS + UNIGNN_CONV_METHODS
 
 
 # --------------------------------------------------------------------------------------------------
@@ -409,6 +412,18 @@ def build_model(args, data):
         from .baselines import UniGCNII
         return UniGCNII(args, nfeat=args.num_features, nhid=args.MLP_hidden, nclass=args.num_classes, nlayer=args.All_num_layers,
                         nhead=args.heads, V=ei[0], E=ei[1])
+    if args.method in UNIGNN_CONV_METHODS:
+        ei = getattr(data, 'edge_index', None) if data is not None else None
+        if getattr(data, 'UniGNN_sizes', None) is None or not torch.is_tensor(ei) or ei.dim() != 2 or ei.shape[0] != 2 \
+                or ei.dtype.is_floating_point or not torch.is_tensor(getattr(args, 'UniGNN_degV', None)) \
+                or not torch.is_tensor(getattr(args, 'UniGNN_degE', None)):
+            raise ValueError(f"method {args.method!r} runs on the de-duplicated (vertex, hyperedge) pairs and their degree scales: pass "
+                             "data through train.preprocess (ExtractV2E -> [Add_Self_Loops] -> ConstructH_pairs -> "
+                             "generate_norm_UniGNN) before build_model")
+        from .baselines import UniGNN
+        unignn_args(args)
+        return UniGNN(args, nfeat=args.num_features, nhid=args.MLP_hidden, nclass=args.num_classes, nlayer=args.All_num_layers,
+                      nhead=args.heads, V=ei[0], E=ei[1])
     if args.method == 'HyperGCN' and data is not None and getattr(data, 'HyperGCN_pairs', None) is not None:
         # (data that never saw the HyperGCN branch of preprocess falls through to the error below: on another branch's edge list
         #  -- self-loop hyperedges, hyperedge ids behind the vertex ids -- the model would compute something else without an error)
@@ -421,6 +436,20 @@ def build_model(args, data):
         raise ValueError("method 'HyperGCN' runs on the zero-based (vertex, hyperedge) pairs of train.preprocess (ExtractV2E only, no "
                          "self-loop hyperedges): pass data through it before build_model; on other data the method is out of scope")
     raise ValueError(f"method {args.method!r}: only {BUILT_METHODS} are built (MLP is out of scope)")
+
+
+def unignn_args(args):
+    """The names the reference's UniGNN convs read from ``args`` (models.py:601-907), set from this driver's flags: ``model_name`` from
+    ``--method``, the ``--UniGNN_*`` flags without their prefix, ``degV`` / ``degE`` from ``UniGNN_degV`` / ``UniGNN_degE``."""
+    args.model_name = args.method
+    args.first_aggregate = getattr(args, 'UniGNN_first_aggregate', 'mean')
+    args.second_aggregate = getattr(args, 'UniGNN_second_aggregate', 'sum')
+    args.activation = getattr(args, 'UniGNN_activation', 'relu')
+    args.input_drop = getattr(args, 'UniGNN_input_drop', 0.6)
+    args.attn_drop = getattr(args, 'UniGNN_attn_drop', 0.0)
+    args.use_norm = bool(getattr(args, 'UniGNN_use_norm', False))
+    args.degV, args.degE = args.UniGNN_degV, args.UniGNN_degE
+    return args
 
 
 def make_optimizer(args, model):
@@ -478,6 +507,13 @@ def build_parser() -> argparse.ArgumentParser:
     #  cannot be switched off there, and the re-approximating path would be unreachable from the command line)
     p.add_argument('--no-HyperGCN_mediators', dest='HyperGCN_mediators', action='store_false')
     p.add_argument('--no-HyperGCN_fast', dest='HyperGCN_fast', action='store_false')
+    # (the plain UniGNN model, --method UniGCN / UniGCN2 / UniGIN / UniSAGE / UniGAT: what its convs read from args, with the
+    #  defaults of the UniGNN paper's scripts; --UniGNN_use-norm, --heads, --MLP_hidden, --All_num_layers and --dropout as for UniGCNII)
+    p.add_argument('--UniGNN_first_aggregate', default='mean', help="V->E aggregation: 'mean' or 'sum'")
+    p.add_argument('--UniGNN_second_aggregate', default='sum', help="E->V aggregation of UniSAGE: 'sum' or 'mean'")
+    p.add_argument('--UniGNN_activation', default='relu', choices=['relu', 'prelu'])
+    p.add_argument('--UniGNN_input_drop', default=0.6, type=float)
+    p.add_argument('--UniGNN_attn_drop', default=0.0, type=float)
     p.add_argument('--raw_data_dir', default=None, help='directory holding <dname>/{features,labels,hypergraph}.pickle')
     p.add_argument('--processed_data', default=None,
                    help="the reference's processed file <root>/<dname>/processed/data.pt (or its directory)")
@@ -539,7 +575,7 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
         data = norm_contruction(data, TYPE='V2V')
         data.clique_expansion = True                        # what build_model checks for CEGCN / CEGAT
         return data
-    if args.method in UNIGNN_METHODS:
+    if args.method in UNIGNN_METHODS + UNIGNN_CONV_METHODS:
         data = ExtractV2E(data)
         if args.add_self_loop:
             data = Add_Self_Loops(data)
@@ -583,9 +619,11 @@ def run(args) -> dict:
         raise RuntimeError("allset_amd has no CPU path for the aggregation kernels: run with --cuda 0 on an MI355X")
     device = torch.device(f'cuda:{args.cuda}')
     model, data = model.to(device), data.to(device)
-    if args.method in UNIGNN_METHODS:                      # (reference train.py:438-440)
+    if args.method in UNIGNN_METHODS + UNIGNN_CONV_METHODS:       # (reference train.py:438-440)
         args.UniGNN_degV = args.UniGNN_degV.to(device)
         args.UniGNN_degE = args.UniGNN_degE.to(device)
+        if args.method in UNIGNN_CONV_METHODS:
+            args.degV, args.degE = args.UniGNN_degV, args.UniGNN_degE
     num_params = count_parameters(model)
     logger = Logger(args.runs, args)
     runtimes = []

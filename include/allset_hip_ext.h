@@ -875,6 +875,40 @@ int allset_hypergcn_e2v(int variant, int64_t nnz, const int32_t* row_order, cons
                         const float* bias, int act, float p, uint64_t seed, const uint64_t* seed_base, float* y, int64_t ldy,
                         int64_t n_v, int64_t d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * UniGNN baselines (reference models.py:601-907: UniGCNConv, UniGCNConv2, UniGINConv, UniSAGEConv, UniGATConv): the two hops with
+ * the row tail of the reference in the same launch.
+ * Added under ABI 15, additions only; detect with allset_unignn_supported() (returns 1).  fp32, row-major.
+ *
+ * allset_unignn_hop_fwd over a CSR whose rows are vertices and whose columns are hyperedges (xe f32[n_s, d]):
+ *   a = s[v] * sum_{j in [rowptr[v], rowptr[v+1])} xe[col[j],:] + c * xs[v,:]
+ *   t = use_norm ? (||a||_2 > 0 ? 1 / ||a||_2 : 0) : 1                 (t_out[v] = t when use_norm; t_out may be NULL otherwise)
+ *   y[v,:] = drop_p(act(t * a))
+ * s (f32[n_t]) and xs (f32[n_t, d], pitch ldxs) may each be NULL (= ones / no self term).  c: the host value, or -- c_dev not
+ * NULL -- the float c_dev points to on the device, read at kernel start (a captured graph sees a new value at its next replay).
+ * act: ALLSET_HCONV_ACT_NONE or ALLSET_HCONV_ACT_RELU.  Dropout as in allset_hconv_fwd (hash of (seed, v * d + column), seed_base
+ * may be NULL), so allset_hconv_bwd_epi is the backward of act and dropout.  The rest of the backward is allset_hconv_fwd over the
+ * transposed CSR with r[v] = s[v] * t[v] (t is a constant of the backward, as in the reference) and gxs = c * t * g.
+ *
+ * allset_unignn_v2e_att_fwd over a CSR whose rows are hyperedges and whose columns are vertices (x f32[n_s, H*C]):
+ *   xe[e,:] = s[e] * sum_{j in [rowptr[e], rowptr[e+1])} x[col[j],:]
+ *   ae[e,h] = <xe[e,h,:], att[h,:]>                                     (att f32[H*C], ae f32[n_t, H] dense)
+ *
+ * Both are built for d (= H * C) a multiple of 4 up to 512 -- allset_unignn_v2e_att_fwd for C a multiple of 4 -- with 16-byte
+ * aligned rows (pointers and leading dimensions): ALLSET_ERR_UNSUPPORTED otherwise, and the caller composes the hop from
+ * allset_hconv_fwd.  variant: 0 auto (short-row kernel when nnz / n_t < 6 and n_t > 16384), 1 one wavefront per row (row_order
+ * int32[n_t] or NULL is its processing order), 2 short-row kernel (d <= 256).  One wavefront (or lane group) owns a whole row:
+ * every sum has a fixed order, results are bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------- */
+int allset_unignn_supported(void);
+int allset_unignn_hop_fwd(int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                          const float* s, const float* xe, int64_t ldxe, const float* xs, int64_t ldxs, float c, const float* c_dev,
+                          int use_norm, int act, float p, uint64_t seed, const uint64_t* seed_base, float* y, int64_t ldy,
+                          float* t_out, int64_t n_t, int64_t n_s, int64_t d, void* stream);
+int allset_unignn_v2e_att_fwd(int variant, int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                              const float* s, const float* x, int64_t ldx, const float* att, float* xe, int64_t ldxe, float* ae,
+                              int64_t n_t, int64_t n_s, int64_t H, int64_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
