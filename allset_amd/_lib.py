@@ -253,6 +253,18 @@ SIGNATURES = {
     "allset_unignn_hop_fwd": [c_int, c_int64, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_float, _P, c_int, c_int, c_float, c_uint64, _P,
                               _P, c_int64, _P, c_int64, c_int64, c_int64, _P],
     "allset_unignn_v2e_att_fwd": [c_int, c_int64, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P],
+    # HAN baseline: the DGL-style attention hop and the semantic attention (under ABI 15, additions only; detect with
+    # allset_han_supported)
+    "allset_han_supported": [],
+    "allset_han_hop_fwd": [c_int64, _P, _P, _P, _P, _P, c_int64, c_float, _P, c_float, c_uint64, _P, _P, c_int64, _P, c_int64, _P, _P,
+                           c_int64, c_int64, c_int64, _P],
+    "allset_han_hop_bwd_stats": [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P, c_float, _P, c_int64, _P, _P, c_int64, c_int64,
+                                 c_int64, _P],
+    "allset_han_hop_bwd_src": [c_int64, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_float, c_float, c_uint64, _P, _P, c_int64,
+                               _P, c_int64, c_int64, c_int64, _P],
+    "allset_han_sem_blocks": [c_int64, c_int64, POINTER(c_int64)],
+    "allset_han_sem_fwd": [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P],
+    "allset_han_sem_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

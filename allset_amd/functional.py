@@ -916,3 +916,111 @@ def unignn_row_tail(a: Tensor, skip: Optional[Tensor] = None, use_norm: bool = F
     if act == 'relu':
         return dense.relu_dropout(a, p)
     return dense.hash_dropout(a, p, p > 0.0)
+
+
+# ---- HAN baseline: the DGL-style attention hop and the semantic attention (csrc/han.hip) ---------------------------------------------
+class _HanGatPropagate(torch.autograd.Function):
+    """``y = elu(sum_j softmax_j(lrelu(el[s_j] + er[t])) * keep_j / (1 - p) * x[s_j] + bias)`` -- one kernel forward, written into
+    column block ``block`` of ``out`` when one is given (``out`` is then returned, marked dirty).  Backward: one pass over the target
+    rows (elu', the softmax statistics, the whole of ``ger``), one gather pass over the source-major CSR (``gx``, ``gel``) that
+    regenerates the edge mask from the seed.  Saved: ``x``, ``el``, ``er``, the positive-logit part of the aggregate (``outpos``
+    [n, H*C], ``ppos`` [n, H]) and ``lse``; ``y`` is read back where it was written."""
+
+    @staticmethod
+    def forward(ctx, x, el, er, bias, graph, heads, slope, p, out, block):
+        from . import dense
+        n, d = x.shape
+        if n != graph.n:
+            raise _lib.AllSetHipError(f"han_gat_propagate: x has {n} rows, the graph has {graph.n} nodes")
+        seed = dense._draw_seed() if p > 0.0 else 0
+        base = dense._seed_base() if p > 0.0 else None
+        want = any(ctx.needs_input_grad[:4])
+        if out is None:
+            ret = torch.empty((n, d), dtype=torch.float32, device=x.device)
+            y = ret
+        else:
+            if out.dim() != 2 or out.shape[0] != n or out.shape[1] < (block + 1) * d or out.stride(1) != 1 or out.dtype != torch.float32:
+                raise _lib.AllSetHipError(f"han_gat_propagate: out {tuple(out.shape)} cannot hold block {block} of width {d} for {n} rows")
+            ctx.mark_dirty(out)
+            ret = out
+            y = out.detach()[:, block * d:(block + 1) * d]
+        outpos, ppos, lse = ops.han_hop_fwd(graph.rowptr, graph.col, x, el, er, heads, slope, bias, p, seed, base, y, want)
+        # the output itself when it is this call's own tensor (saved the regular way: version-checked, no reference cycle); of a
+        # stacked buffer only a detached alias of the block can be kept -- later hops write OTHER columns of the same storage, so
+        # its version counter moves legitimately and cannot be checked: the caller must leave a written block alone until backward
+        ctx.save_for_backward(x, el, er, bias, outpos, ppos, lse, ret if out is None else None)
+        ctx.y_block = y if out is not None else None
+        ctx.cfg = (graph, heads, slope, p, seed, base, block, d, out is not None)
+        return ret
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        x, el, er, bias, outpos, ppos, lse, y_own = ctx.saved_tensors
+        graph, heads, slope, p, seed, base, block, d, stacked = ctx.cfg
+        if gout.stride(1) != 1:
+            gout = gout.contiguous()
+        gy = gout[:, block * d:(block + 1) * d] if stacked else gout
+        g, stats, ger = ops.han_hop_bwd_stats(ctx.y_block if stacked else y_own, bias, gy, outpos, ppos, lse, slope)
+        gx, gel = ops.han_hop_bwd_src(graph.rowptrT, graph.colT, graph.slotT, x, el, er, g, stats, slope, p, seed, base)
+        gb = g.sum(0) if (bias is not None and ctx.needs_input_grad[3]) else None
+        # (towards the earlier hops of the same buffer: each reads only its own block, so the gradient goes on as it is -- the
+        #  wrapper admits no other producer of an ``out`` that requires grad)
+        return gx, gel, ger, gb, None, None, None, None, (gout if (stacked and ctx.needs_input_grad[8]) else None), None
+
+
+def han_gat_propagate(x: Tensor, el: Tensor, er: Tensor, graph, heads: int, negative_slope: float = 0.2, bias: Optional[Tensor] = None,
+                      attn_drop: float = 0.0, out: Optional[Tensor] = None, block: int = 0) -> Tensor:
+    """One HAN attention hop (DGL 0.7.1 ``GATConv``'s message passing + bias + ELU) over ``graph`` (a ``han.MetapathGraph``: ``n``
+    nodes, edges source -> target, duplicates allowed, every node with an incoming edge): with ``e_j = leaky_relu(el[s_j, h] +
+    er[t, h])``, ``p_j`` its softmax over the edges into ``t`` (no epsilon) and ``a_j = p_j * keep_j / (1 - attn_drop)``,
+    ``y[t, h] = elu(sum_j a_j x[s_j, h] + bias[h])``.  ``x`` [n, heads * C], ``el`` / ``er`` [n, heads]; ``keep_j`` is the library's
+    hash mask on (the edge's slot in the target-major CSR, head) -- :func:`han_edge_keep` returns it.  With ``out`` ([n, >= (block +
+    1) * heads * C], row-major) the result is written into its column block ``block`` and ``out`` itself is returned: the stacked
+    [n, M, heads * C] tensor of the HAN layer is filled hop by hop without a ``torch.stack`` copy.  ``out`` is a plain buffer (no
+    grad) or the result of earlier calls of this function into OTHER blocks of it; every block is written once and left alone until
+    the backward has run.  Differentiable in ``x``, ``el``, ``er`` and ``bias``."""
+    _lib.require_device(x, el, er)
+    if out is not None and out.requires_grad and type(out.grad_fn).__name__ != "_HanGatPropagateBackward":
+        raise ValueError("han_gat_propagate: out must be a buffer that does not require grad, or the result of an earlier "
+                         "han_gat_propagate into another of its blocks (the overwritten block would need a zero gradient)")
+    if el.dtype != torch.float32 or er.dtype != torch.float32:
+        el, er = el.float(), er.float()
+    return _HanGatPropagate.apply(x, el, er, bias, graph, int(heads), float(negative_slope), float(attn_drop), out, int(block))
+
+
+def han_edge_keep(graph, heads: int, p: float, seed: int) -> Tensor:
+    """The hop's per-(edge, head) factor ``keep / (1 - p)`` for host seed ``seed``, [nnz, heads] in the order of the caller's edge
+    list (``graph.src`` / ``graph.dst``)."""
+    from . import dense
+    k = dense.dropout_scale((graph.nnz, int(heads)), p, seed, graph.rowptr.device)      # indexed by target-major slot
+    out = torch.empty_like(k)
+    out[graph.perm.long()] = k
+    return out
+
+
+class _SemanticAttention(torch.autograd.Function):
+    """``out[n] = sum_m softmax_m(mean_n q . tanh(W1 z[n, m] + b1)) z[n, m]``: the 128-wide hidden lives in registers, forward and
+    backward (recomputed there).  Saved: ``z``, the parameters and ``{w, beta}``."""
+
+    @staticmethod
+    def forward(ctx, z, W1, b1, q):
+        out, wbeta = ops.han_sem_fwd(z, W1, b1, q)
+        ctx.save_for_backward(z, W1, b1, q, wbeta)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        z, W1, b1, q, wbeta = ctx.saved_tensors
+        gz, gW1, gb1, gq = ops.han_sem_bwd(z, W1, b1, q, wbeta, gout)
+        return gz, gW1, gb1, gq.view_as(q)
+
+
+def semantic_attention(z: Tensor, W1: Tensor, b1: Tensor, q: Tensor) -> Tensor:
+    """HAN's semantic attention (reference DGL_HAN/model.py ``SemanticAttention.forward``) over stacked metapath embeddings ``z``
+    [N, M, D] (contiguous): ``s[n, m] = q . tanh(W1 z[n, m] + b1)``, ``beta = softmax_m(mean_n s[n, m])``, result ``sum_m beta_m
+    z[n, m]`` [N, D].  ``W1`` [128, D], ``b1`` [128], ``q`` [128] (or [1, 128]).  Built for hidden 128, D <= 128, M <= 32.
+    Differentiable in all four."""
+    _lib.require_device(z, W1, b1, q)
+    return _SemanticAttention.apply(z, W1, b1, q)

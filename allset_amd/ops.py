@@ -988,3 +988,138 @@ def hypergcn_e2v(csr_v: CSR, colx: Tensor, pq: Tensor, dinv: Tensor, selfc: Tens
                                               ptr(dinv), ptr(selfc), ptr(x), _ld(x), ptr(bias), HYPERGCN_ACTS[act], float(p), int(seed),
                                               ptr(seed_base), ptr(y), max(d, 1), n_v, d, stream_of(dev)), "allset_hypergcn_e2v")
     return y
+
+
+# ---- HAN baseline: the DGL-style attention hop and the semantic attention (csrc/han.hip) ---------------------------------------------
+HAN_SEM_HIDDEN, HAN_SEM_MAX_WIDTH, HAN_SEM_MAX_PATHS = 128, 128, 32
+
+
+def _pitch(t: Tensor, what: str) -> int:
+    """Row pitch of a 2-D view whose rows are contiguous (a column block of a wider row-major buffer is one)."""
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise _lib.AllSetHipError(f"{what}: rows must be contiguous (got strides {tuple(t.stride())})")
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1], 1)
+
+
+def han_hop_fwd(rowptr: Tensor, col: Tensor, x: Tensor, el: Tensor, er: Tensor, heads: int, slope: float, bias: Optional[Tensor],
+                p_att: float, seed: int, seed_base: Optional[Tensor], y: Tensor, want_grad: bool):
+    """One HAN attention hop over a target-major CSR into ``y`` (a [n, H*C] view with contiguous rows, e.g. a column block of the
+    stacked buffer): ``(outpos, ppos, lse)``; ``outpos`` / ``ppos`` only with ``want_grad``."""
+    dev = require_device(rowptr, col, x, el, er, bias, y)
+    for t, what in ((x, "x"), (el, "el"), (er, "er"), (bias, "bias"), (y, "y")):
+        if t is not None:
+            _f32(t, f"han_hop_fwd {what}")
+    x, el, er = _rowmajor(x), el.contiguous(), er.contiguous()
+    n, d = x.shape
+    H = int(heads)
+    if H < 1 or d % H != 0 or d == 0:
+        raise _lib.AllSetHipError(f"han_hop_fwd: width {d} does not split into {H} heads")
+    if tuple(el.shape) != (n, H) or tuple(er.shape) != (n, H) or tuple(y.shape) != (n, d) or rowptr.numel() != n + 1:
+        raise _lib.AllSetHipError(f"han_hop_fwd: el {tuple(el.shape)} / er {tuple(er.shape)} / y {tuple(y.shape)} / rowptr "
+                                  f"{rowptr.numel()} against {n} nodes of width {d}, {H} heads")
+    if bias is not None and bias.numel() != d:
+        raise _lib.AllSetHipError(f"han_hop_fwd: bias has {bias.numel()} entries for width {d}")
+    bias = bias.contiguous() if bias is not None else None
+    lse = torch.empty((n, H), dtype=torch.float32, device=dev)
+    outpos = torch.empty((n, d), dtype=torch.float32, device=dev) if want_grad else None
+    ppos = torch.empty((n, H), dtype=torch.float32, device=dev) if want_grad else None
+    nnz = col.numel()
+    algo = nnz * (4 * d + 4 * H + 4) + (n + 1) * 4 + n * (4 * d + 12 * H) + (n * (4 * d + 4 * H) if want_grad else 0)
+    with on_device(dev), _timed("han_hop_fwd", dev, algo):
+        check(_lib.load().allset_han_hop_fwd(nnz, ptr(rowptr), ptr(col), ptr(el), ptr(er), ptr(x), _ld(x), float(slope), ptr(bias),
+                                             float(p_att), int(seed), ptr(seed_base), ptr(y), _pitch(y, "han_hop_fwd y"), ptr(outpos), d,
+                                             ptr(ppos), ptr(lse), n, H, d // H, stream_of(dev)), "allset_han_hop_fwd")
+    return outpos, ppos, lse
+
+
+def han_hop_bwd_stats(y: Tensor, bias: Optional[Tensor], gy: Tensor, outpos: Tensor, ppos: Tensor, lse: Tensor, slope: float):
+    """``(g [n, H*C] = gy * elu'(y), stats [n, H, 2] = {lse, <out, g>}, ger [n, H])``; ``y`` and ``gy`` may be column blocks."""
+    dev = require_device(y, bias, gy, outpos, ppos, lse)
+    for t in (y, gy, outpos, ppos, lse):
+        _f32(t, "han_hop_bwd_stats")
+    n, d = y.shape
+    H = lse.shape[1]
+    if tuple(gy.shape) != (n, d) or tuple(outpos.shape) != (n, d):
+        raise _lib.AllSetHipError(f"han_hop_bwd_stats: gy {tuple(gy.shape)} / outpos {tuple(outpos.shape)} against y {tuple(y.shape)}")
+    g = torch.empty((n, d), dtype=torch.float32, device=dev)
+    stats = torch.empty((n, H, 2), dtype=torch.float32, device=dev)
+    ger = torch.empty((n, H), dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("han_hop_bwd_stats", dev, 5 * n * d * 4 + n * H * 16):
+        check(_lib.load().allset_han_hop_bwd_stats(ptr(y), _pitch(y, "han_hop_bwd_stats y"), ptr(bias), ptr(gy),
+                                                   _pitch(gy, "han_hop_bwd_stats gy"), ptr(outpos), d, ptr(ppos), ptr(lse), float(slope),
+                                                   ptr(g), d, ptr(stats), ptr(ger), n, H, d // H, stream_of(dev)),
+              "allset_han_hop_bwd_stats")
+    return g, stats, ger
+
+
+def han_hop_bwd_src(rowptrT: Tensor, colT: Tensor, slotT: Tensor, x: Tensor, el: Tensor, er: Tensor, g: Tensor, stats: Tensor,
+                    slope: float, p_att: float, seed: int, seed_base: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """``(gx [n, H*C], gel [n, H])`` in one gather pass over the source-major CSR; ``slotT`` regenerates the forward's edge mask."""
+    dev = require_device(rowptrT, colT, slotT, x, el, er, g, stats)
+    for t in (x, el, er, g, stats):
+        _f32(t, "han_hop_bwd_src")
+    x, g, el, er, stats = _rowmajor(x), _rowmajor(g), el.contiguous(), er.contiguous(), stats.contiguous()
+    n, d = x.shape
+    H = er.shape[1]
+    if (tuple(g.shape) != (n, d) or rowptrT.numel() != n + 1 or slotT.numel() != colT.numel() or tuple(stats.shape) != (n, H, 2)
+            or tuple(el.shape) != (n, H)):
+        raise _lib.AllSetHipError(f"han_hop_bwd_src: g {tuple(g.shape)} / rowptrT {rowptrT.numel()} / slotT {slotT.numel()} against "
+                                  f"{n} nodes of width {d}, {colT.numel()} edges")
+    gx = torch.empty((n, d), dtype=torch.float32, device=dev)
+    gel = torch.empty((n, H), dtype=torch.float32, device=dev)
+    nnz = colT.numel()
+    with on_device(dev), _timed("han_hop_bwd_src", dev, nnz * (4 * d + 12 * H + 8) + (n + 1) * 4 + n * (8 * d + 8 * H)):
+        check(_lib.load().allset_han_hop_bwd_src(nnz, ptr(rowptrT), ptr(colT), ptr(slotT), ptr(el), ptr(er), ptr(x), _ld(x), ptr(g),
+                                                 _ld(g), ptr(stats), float(slope), float(p_att), int(seed), ptr(seed_base), ptr(gx), d,
+                                                 ptr(gel), n, H, d // H, stream_of(dev)), "allset_han_hop_bwd_src")
+    return gx, gel
+
+
+def _han_sem_blocks(N: int, M: int) -> int:
+    nb = c_int64_t(0)
+    check(_lib.load().allset_han_sem_blocks(N, M, byref(nb)), "allset_han_sem_blocks")
+    return nb.value
+
+
+def han_sem_fwd(z: Tensor, W1: Tensor, b1: Tensor, q: Tensor) -> Tuple[Tensor, Tensor]:
+    """``(out [N, D], wbeta [2, M] = {w, beta})`` from ``z`` [N, M, D] (contiguous), ``W1`` [128, D], ``b1`` [128], ``q`` [128]."""
+    dev = require_device(z, W1, b1, q)
+    for t in (z, W1, b1, q):
+        _f32(t, "han_sem_fwd")
+    if z.dim() != 3 or not z.is_contiguous():
+        raise _lib.AllSetHipError(f"han_sem_fwd: z must be a contiguous [N, M, D] tensor (got {tuple(z.shape)}, strides {tuple(z.stride())})")
+    N, M, D = z.shape
+    hidden = W1.shape[0]
+    if tuple(W1.shape) != (hidden, D) or b1.numel() != hidden or q.numel() != hidden:
+        raise _lib.AllSetHipError(f"han_sem_fwd: W1 {tuple(W1.shape)} / b1 {b1.numel()} / q {q.numel()} against width {D}")
+    W1, b1, q = W1.contiguous(), b1.contiguous(), q.contiguous()
+    part = torch.empty((_han_sem_blocks(N, M), M), dtype=torch.float32, device=dev)
+    wbeta = torch.empty((2, M), dtype=torch.float32, device=dev)
+    out = torch.empty((N, D), dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("han_sem_fwd", dev, 2 * 4 * N * M * D + 4 * N * D):
+        check(_lib.load().allset_han_sem_fwd(ptr(z), ptr(W1), ptr(b1), ptr(q), ptr(part), ptr(wbeta), ptr(out), N, M, D, hidden,
+                                             stream_of(dev)), "allset_han_sem_fwd")
+    return out, wbeta
+
+
+def han_sem_bwd(z: Tensor, W1: Tensor, b1: Tensor, q: Tensor, wbeta: Tensor, gout: Tensor):
+    """``(gz [N, M, D], gW1 [128, D], gb1 [128], gq [128])``; the hidden is recomputed, parameter gradients by block reduction."""
+    dev = require_device(z, W1, b1, q, wbeta, gout)
+    for t in (z, W1, b1, q, wbeta, gout):
+        _f32(t, "han_sem_bwd")
+    N, M, D = z.shape
+    hidden = W1.shape[0]
+    if tuple(gout.shape) != (N, D) or tuple(wbeta.shape) != (2, M) or not wbeta.is_contiguous() or not z.is_contiguous():
+        raise _lib.AllSetHipError(f"han_sem_bwd: gout {tuple(gout.shape)} / wbeta {tuple(wbeta.shape)} against z {tuple(z.shape)}")
+    W1, b1, q, gout = W1.contiguous(), b1.contiguous(), q.contiguous(), gout.contiguous()
+    nb = _han_sem_blocks(N, M)
+    P = hidden * D + 2 * hidden
+    part = torch.empty((nb, M), dtype=torch.float32, device=dev)
+    gsm = torch.empty((M,), dtype=torch.float32, device=dev)
+    gz = torch.empty((N, M, D), dtype=torch.float32, device=dev)
+    ppart = torch.empty((nb, P), dtype=torch.float32, device=dev)
+    gparams = torch.empty((P,), dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("han_sem_bwd", dev, 3 * 4 * N * M * D + 2 * 4 * N * D + nb * P * 4):
+        check(_lib.load().allset_han_sem_bwd(ptr(z), ptr(W1), ptr(b1), ptr(q), ptr(wbeta), ptr(gout), ptr(part), ptr(gsm), ptr(gz),
+                                             ptr(ppart), ptr(gparams), N, M, D, hidden, stream_of(dev)), "allset_han_sem_bwd")
+    return gz, gparams[:hidden * D].view(hidden, D), gparams[hidden * D:hidden * D + hidden], gparams[hidden * D + hidden:]

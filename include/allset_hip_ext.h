@@ -909,6 +909,54 @@ int allset_unignn_v2e_att_fwd(int variant, int64_t nnz, const int32_t* row_order
                               const float* s, const float* x, int64_t ldx, const float* att, float* xe, int64_t ldxe, float* ae,
                               int64_t n_t, int64_t n_s, int64_t H, int64_t C, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * HAN baseline (reference DGL_HAN/model.py): the DGL-style attention hop of one metapath graph and the semantic attention over
+ * the stacked metapath embeddings.  Added under ABI 15, additions only; detect with allset_han_supported() (returns 1).  fp32,
+ * row-major, wave 64, no atomics: every sum has a fixed order and results are bit-identical from run to run.
+ *
+ * allset_han_hop_fwd over a target-major CSR of n nodes (a multigraph: duplicate edges are separate slots), H heads of C channels,
+ * H <= 64, H * C <= 512 (ALLSET_ERR_UNSUPPORTED beyond); x f32[n, H*C] (pitch ldx), el / er f32[n, H] dense:
+ *   e_j = leaky_relu(el[col[j],h] + er[t,h], slope);  p_j = softmax over the row (no epsilon);  a_j = p_j * keep_j / (1 - p_att)
+ *   y[t,h,:] = elu(sum_j a_j x[col[j],h,:] + bias[h,:])        (bias f32[H*C] or NULL; y pitch ldy: a column block of a wider buffer)
+ * keep_j: the library's hash dropout on element index j * H + h (j = the edge's slot in THIS CSR), seed / seed_base as in
+ * allset_hconv_fwd; allset_relu_dropout_fwd on ones of shape [nnz, H] returns exactly these factors.  lse f32[n, H] = m + log l,
+ * always written.  outpos (f32[n, ldpos]) and ppos (f32[n, H]), both or neither: sum_{e_j > 0} a_j x_j and sum_{e_j > 0} p_j, what
+ * allset_han_hop_bwd_stats needs; NULL when no gradient will be asked for.
+ *
+ * allset_han_hop_bwd_stats: from gy (the gradient at y, pitch ldgy) writes g = gy * (y > 0 ? 1 : y + 1) (f32[n, ldg], the gradient
+ * at the aggregate: its column sums are the bias gradient), stats[t,h] = {lse, delta = <out, g>} (f32[n, H, 2], 8-byte aligned;
+ * out rebuilt from y and bias) and ger[t,h] = (1 - slope) (<outpos, g> - delta * ppos).
+ *
+ * allset_han_hop_bwd_src over the source-major CSR (rowptrT, colT = targets, slotT[j] = the target-major slot of entry j), one
+ * gather pass with the forward's p_att, seed, seed_base: gx[s,h,:] = sum_j a_j g[t_j,h,:] and
+ *   gel[s,h] = sum_j lrelu'(el[s,h] + er[t_j,h]) (a_j <x[s,h,:], g[t_j,h,:]> - p_j delta[t_j,h]).
+ *
+ * Semantic attention, z f32[N, M, D] dense, W1 f32[128, D], b1 f32[128], q f32[128]; built for hidden == 128, D <= 128, M <= 32
+ * (ALLSET_ERR_UNSUPPORTED otherwise).  allset_han_sem_blocks: B, the first dimension of the partial buffers below.
+ * allset_han_sem_fwd:  s[n,m] = q . tanh(W1 z[n,m,:] + b1) (the hidden never leaves the chip), w_m = mean_n s[n,m],
+ *   beta = softmax_m w, out[n,:] = sum_m beta_m z[n,m,:].  part f32[B, M] scratch; wbeta f32[2, M] = {w, beta}; out f32[N, D].
+ * allset_han_sem_bwd: from gout f32[N, D] and the forward's wbeta: gz f32[N, M, D] (beta_m gout[n] plus the term through w_m) and
+ *   gparams f32[128 * D + 256] = {gW1 [128, D], gb1 [128], gq [128]}.  part f32[B, M], gsm f32[M], ppart f32[B, 128 * D + 256]: scratch.
+ * ------------------------------------------------------------------------------------------- */
+int allset_han_supported(void);
+int allset_han_hop_fwd(int64_t nnz, const int32_t* rowptr, const int32_t* col, const float* el, const float* er, const float* x,
+                       int64_t ldx, float slope, const float* bias, float p_att, uint64_t seed, const uint64_t* seed_base, float* y,
+                       int64_t ldy, float* outpos, int64_t ldpos, float* ppos, float* lse, int64_t n, int64_t H, int64_t C,
+                       void* stream);
+int allset_han_hop_bwd_stats(const float* y, int64_t ldy, const float* bias, const float* gy, int64_t ldgy, const float* outpos,
+                             int64_t ldpos, const float* ppos, const float* lse, float slope, float* g, int64_t ldg, float* stats,
+                             float* ger, int64_t n, int64_t H, int64_t C, void* stream);
+int allset_han_hop_bwd_src(int64_t nnz, const int32_t* rowptrT, const int32_t* colT, const int32_t* slotT, const float* el,
+                           const float* er, const float* x, int64_t ldx, const float* g, int64_t ldg, const float* stats, float slope,
+                           float p_att, uint64_t seed, const uint64_t* seed_base, float* gx, int64_t ldgx, float* gel, int64_t n,
+                           int64_t H, int64_t C, void* stream);
+int allset_han_sem_blocks(int64_t N, int64_t M, int64_t* blocks);
+int allset_han_sem_fwd(const float* z, const float* W1, const float* b1, const float* q, float* part, float* wbeta, float* out,
+                       int64_t N, int64_t M, int64_t D, int64_t hidden, void* stream);
+int allset_han_sem_bwd(const float* z, const float* W1, const float* b1, const float* q, const float* wbeta, const float* gout,
+                       float* part, float* gsm, float* gz, float* ppart, float* gparams, int64_t N, int64_t M, int64_t D,
+                       int64_t hidden, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
