@@ -265,6 +265,18 @@ SIGNATURES = {
     "allset_han_sem_blocks": [c_int64, c_int64, POINTER(c_int64)],
     "allset_han_sem_fwd": [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P],
     "allset_han_sem_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P],
+    # mini-batch HAN: the metapath random walk, the block construction and the bipartite attention hop (under ABI 15, additions
+    # only; detect with allset_han_sampling_supported)
+    "allset_han_sampling_supported": [],
+    "allset_han_walk": [c_int, _P, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, c_int64, c_uint64, c_uint64, _P, _P],
+    "allset_han_block_rows": [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P],
+    "allset_han_block_compact": [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P],
+    "allset_han_block_hop_fwd": [c_int64, _P, _P, _P, _P, _P, c_int64, c_float, _P, c_float, c_uint64, _P, _P, c_int64, _P, c_int64, _P,
+                                 _P, c_int64, c_int64, c_int64, c_int64, _P],
+    "allset_han_block_hop_bwd_stats": [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P, c_float, _P, c_int64, _P, _P, c_int64, c_int64,
+                                       c_int64, _P],
+    "allset_han_block_hop_bwd_src": [c_int64, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_float, c_float, c_uint64, _P, _P,
+                                     c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

@@ -1,0 +1,270 @@
+// Mini-batch HAN (reference DGL_HAN/train_sampling.py: HANSampler over DGL's RandomWalkNeighborSampler, then dgl.to_block) for
+// gfx950: the metapath random walk, the per-seed neighbour rows, the block's local relabelling, and the bipartite entry points of
+// the attention hop.
+//
+// ---- the walk ----------------------------------------------------------------------------------------------------------------
+// Nodes are the "appended" id space n = n_v + n_e (vertices, then hyperedges).  A metapath is two hops over the BINARISED incidence:
+// CSR A (n_a rows -> ids of the other kind) then CSR B (back).  VEV: A = vertex -> hyperedges, B = hyperedge -> vertices, id_base 0;
+// EVE: A = hyperedge -> vertices, B = vertex -> hyperedges, id_base n_v.  A seed outside [id_base, id_base + n_a) or with an empty
+// row has no out-edge: the walk terminates and its endpoint is -1 (DGL writes -1 too).  Such a seed is never dereferenced.
+//   one lane per (seed, walk): four dependent loads (rowptrA, colA, rowptrB, colB) per lane and nothing else -- a pointer chase
+//   whose only lever is how many chases are in flight.  B * k lanes is 640 at the reference's defaults and 20 480 at B = 1024,
+//   k = 20: far fewer than the machine holds, so every walk gets its own lane, blocks of 4 waves spread over the CUs, and the
+//   cost is ONE chain latency (4 misses) whatever B is.  Rows are tiny (a hyperedge has a few members), so there is nothing to
+//   coalesce or stage in LDS.
+// Random numbers are counter-based, two rounds of common.h's pair_hash:
+//   key = (counter * golden + seed) ^ (metapath + 1) * odd constant;   ctr = ((GLOBAL seed-node id) * 64 + walk) * 2 + hop
+//   u32 = pair_hash(swap32(key), pair_hash(key, ctr))                   (the second round is a bijection of the first's 32 bits)
+// keyed on the seed NODE, not on its position in the batch: a node's walks are the same whatever batch it is in.
+// The uniform pick is multiply-shift, index = (u32 * degree) >> 32: every index is taken by floor(2^32 / degree) or one more of the
+// 2^32 values, so its probability is within degree / 2^32 (relative) of 1 / degree -- 2.4e-7 for a row of 1000.
+//
+// ---- block rows --------------------------------------------------------------------------------------------------------------
+// One wave per seed, one lane per walk (k <= 64): drop -1 and the seed itself, keep the first lane of every distinct endpoint, rank
+// the survivors by global id (two 64-step shuffle passes, no LDS), write them ascending into row b of a B x (k + 1) slab, then the
+// seed itself (the ONE self-loop) and -1 padding.  `extra` is the same slab with every seed-set member and the padding replaced by
+// INT32_MAX: sorted and uniqued it lists the block's non-seed source nodes.
+//
+// ---- compaction / relabelling ------------------------------------------------------------------------------------------------
+// One lane per slab entry: the block-local source id of a global id is its position in the seed list (binary search in the sorted
+// seeds, then the sort's permutation) or B + its rank among the sorted distinct non-seed nodes; written at rowptr[b] + i of the
+// target-major CSR together with the target b.  The row pointer is a prefix sum of the counts.
+//
+// ---- bipartite hop -----------------------------------------------------------------------------------------------------------
+// han.hip's hop kernels already index sources (x, el: through col) and targets (er, y, lse: by row) separately; only their entry
+// points tied the two row counts together.  allset_han_block_hop_* check the bipartite shapes and launch the same instantiations
+// through the existing entry points: forward and stats over n_dst target rows, the source pass over n_src source rows.
+#include <limits.h>
+
+#include "common.h"
+
+namespace allset {
+namespace han_sample {
+
+constexpr int kMaxWalks = 64;
+constexpr int kMaxHeads = 64;
+constexpr int kMaxWidth = 512;
+
+__device__ __forceinline__ uint32_t walk_hash(uint64_t key, uint32_t node, uint32_t walk, uint32_t hop) {
+  const int64_t ctr = (static_cast<int64_t>(node) * kMaxWalks + walk) * 2 + hop;
+  const uint32_t h = pair_hash(key, ctr);
+  return pair_hash((key >> 32) | (key << 32), static_cast<int64_t>(h));
+}
+
+__device__ __forceinline__ int uniform_pick(uint32_t h, int deg) {
+  return static_cast<int>((static_cast<uint64_t>(h) * static_cast<uint32_t>(deg)) >> 32);
+}
+
+__global__ __launch_bounds__(kBlock) void walk_kernel(
+    const int32_t* __restrict__ rpa, const int32_t* __restrict__ ca, const int32_t* __restrict__ rpb, const int32_t* __restrict__ cb,
+    int n_a, int n_b, int id_base, const int32_t* __restrict__ seeds, int B, int k, uint64_t key, int32_t* __restrict__ out) {
+  const int64_t tid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (tid >= static_cast<int64_t>(B) * k) return;
+  const int b = static_cast<int>(tid / k), w = static_cast<int>(tid % k);
+  const int s = seeds[b];
+  const int64_t loc = static_cast<int64_t>(s) - id_base;
+  int r = -1;
+  if (loc >= 0 && loc < n_a) {
+    const int a0 = rpa[loc], a1 = rpa[loc + 1];
+    if (a1 > a0) {
+      const int mid = ca[a0 + uniform_pick(walk_hash(key, static_cast<uint32_t>(s), w, 0), a1 - a0)];
+      if (mid >= 0 && mid < n_b) {
+        const int b0 = rpb[mid], b1 = rpb[mid + 1];
+        if (b1 > b0) r = cb[b0 + uniform_pick(walk_hash(key, static_cast<uint32_t>(s), w, 1), b1 - b0)] + id_base;
+      }
+    }
+  }
+  out[tid] = r;
+}
+
+// first index in sorted a[0, n) whose value is >= v
+__device__ __forceinline__ int lower_bound(const int32_t* __restrict__ a, int n, int v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kBlock) void block_rows_kernel(
+    const int32_t* __restrict__ endpoints, const int32_t* __restrict__ seeds, const int32_t* __restrict__ seeds_sorted, int B, int k,
+    int32_t* __restrict__ rows, int32_t* __restrict__ extra, int32_t* __restrict__ counts) {
+  const int b = static_cast<int>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+  if (b >= B) return;  // whole wave exits together
+  const int lane = lane_id();
+  const int s = seeds[b];
+  const int e = lane < k ? endpoints[static_cast<int64_t>(b) * k + lane] : -1;
+  const int valid = (e >= 0 && e != s) ? 1 : 0;
+  int first = valid;
+  for (int j = 0; j < kWave; ++j) {
+    const int ej = __shfl(e, j), vj = __shfl(valid, j);
+    if (vj && ej == e && j < lane) first = 0;
+  }
+  int rank = 0;
+  for (int j = 0; j < kWave; ++j) {
+    const int ej = __shfl(e, j), fj = __shfl(first, j);
+    if (fj && ej < e) ++rank;
+  }
+  const int cnt = __popcll(__ballot(first));
+  const int64_t base = static_cast<int64_t>(b) * (k + 1);
+  if (first) {
+    rows[base + rank] = e;
+    const int pos = lower_bound(seeds_sorted, B, e);
+    extra[base + rank] = (pos < B && seeds_sorted[pos] == e) ? INT32_MAX : e;
+  }
+  for (int p = cnt + lane; p <= k; p += kWave) {
+    rows[base + p] = p == cnt ? s : -1;
+    extra[base + p] = INT32_MAX;
+  }
+  if (lane == 0) counts[b] = cnt + 1;
+}
+
+__global__ __launch_bounds__(kBlock) void block_compact_kernel(
+    const int32_t* __restrict__ rows, const int32_t* __restrict__ counts, const int32_t* __restrict__ rowptr,
+    const int32_t* __restrict__ seeds_sorted, const int32_t* __restrict__ seed_perm, const int32_t* __restrict__ uniq, int n_extra,
+    int B, int k, int nnz, int32_t* __restrict__ col, int32_t* __restrict__ dst) {
+  const int64_t tid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (tid >= static_cast<int64_t>(B) * (k + 1)) return;
+  const int b = static_cast<int>(tid / (k + 1)), i = static_cast<int>(tid % (k + 1));
+  if (i >= counts[b]) return;
+  const int slot = rowptr[b] + i;
+  if (slot < 0 || slot >= nnz) return;
+  const int g = rows[tid];
+  const int pos = lower_bound(seeds_sorted, B, g);
+  int local;
+  if (pos < B && seeds_sorted[pos] == g) {
+    local = seed_perm[pos];
+  } else {
+    const int q = lower_bound(uniq, n_extra, g);
+    local = B + (q < n_extra ? q : max(n_extra - 1, 0));
+  }
+  col[slot] = local;
+  dst[slot] = b;
+}
+
+static int check_block(const char* who, int64_t n_dst, int64_t n_src, int64_t nnz) {
+  ALLSET_REQUIRE(n_dst >= 0 && n_src >= 0 && nnz >= 0, "%s: negative size", who);
+  ALLSET_REQUIRE(n_src < INT32_MAX && nnz < INT32_MAX, "%s: size exceeds int32", who);
+  ALLSET_REQUIRE(n_dst <= n_src, "%s: a block's targets are its first source rows (n_dst = %lld > n_src = %lld)", who,
+                 static_cast<long long>(n_dst), static_cast<long long>(n_src));
+  return ALLSET_OK;
+}
+
+static int check_heads(const char* who, int64_t H, int64_t C) {
+  ALLSET_REQUIRE(H >= 1 && C >= 1, "%s: heads/channels must be >= 1", who);
+  if (H > kMaxHeads || C > kMaxWidth || H * C > kMaxWidth) {
+    set_error("%s: heads=%lld x channels=%lld exceeds the built maximum (heads <= %d, heads * channels <= %d)", who,
+              static_cast<long long>(H), static_cast<long long>(C), kMaxHeads, kMaxWidth);
+    return ALLSET_ERR_UNSUPPORTED;
+  }
+  return ALLSET_OK;
+}
+
+static int check_batch(const char* who, int64_t B, int64_t k) {
+  ALLSET_REQUIRE(B >= 0 && k >= 1, "%s: need B >= 0 seeds and k >= 1 walks", who);
+  if (k > kMaxWalks) {
+    set_error("%s: %lld walks per seed exceeds the built maximum (%d)", who, static_cast<long long>(k), kMaxWalks);
+    return ALLSET_ERR_UNSUPPORTED;
+  }
+  ALLSET_REQUIRE(B * (k + 1) < INT32_MAX, "%s: size exceeds int32", who);
+  return ALLSET_OK;
+}
+
+static inline unsigned lane_grid(int64_t lanes) { return static_cast<unsigned>((lanes + kBlock - 1) / kBlock); }
+
+}  // namespace han_sample
+}  // namespace allset
+
+using namespace allset;
+using namespace allset::han_sample;
+
+extern "C" int allset_han_sampling_supported(void) { return 1; }
+
+extern "C" int allset_han_walk(int metapath, const int32_t* rowptr_a, const int32_t* col_a, const int32_t* rowptr_b,
+                               const int32_t* col_b, int64_t n_a, int64_t n_b, int64_t id_base, const int32_t* seeds, int64_t B,
+                               int64_t k, uint64_t seed, uint64_t counter, int32_t* endpoints, void* stream) {
+  clear_error();
+  ALLSET_REQUIRE(metapath >= 0 && metapath < 256, "han_walk: metapath index must be in [0, 256)");
+  int rc = check_batch("han_walk", B, k);
+  if (rc != ALLSET_OK) return rc;
+  ALLSET_REQUIRE(n_a >= 0 && n_b >= 0 && id_base >= 0 && id_base + n_a < INT32_MAX && n_b < INT32_MAX, "han_walk: sizes must fit int32");
+  if (B == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(rowptr_a && rowptr_b && seeds && endpoints, "han_walk: null rowptr/seeds/endpoints");
+  ALLSET_REQUIRE(col_a && col_b, "han_walk: null col");
+  const uint64_t key = (counter * 0x9E3779B97F4A7C15ULL + seed) ^ (static_cast<uint64_t>(metapath + 1) * 0xD1B54A32D192ED03ULL);
+  walk_kernel<<<lane_grid(B * k), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
+      rowptr_a, col_a, rowptr_b, col_b, static_cast<int>(n_a), static_cast<int>(n_b), static_cast<int>(id_base), seeds,
+      static_cast<int>(B), static_cast<int>(k), key, endpoints);
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
+}
+
+extern "C" int allset_han_block_rows(const int32_t* endpoints, const int32_t* seeds, const int32_t* seeds_sorted, int64_t B, int64_t k,
+                                     int32_t* rows, int32_t* extra, int32_t* counts, void* stream) {
+  clear_error();
+  int rc = check_batch("han_block_rows", B, k);
+  if (rc != ALLSET_OK) return rc;
+  if (B == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(endpoints && seeds && seeds_sorted && rows && extra && counts, "han_block_rows: null pointer");
+  block_rows_kernel<<<static_cast<unsigned>((B + kWavesPerBlock - 1) / kWavesPerBlock), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
+      endpoints, seeds, seeds_sorted, static_cast<int>(B), static_cast<int>(k), rows, extra, counts);
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
+}
+
+extern "C" int allset_han_block_compact(const int32_t* rows, const int32_t* counts, const int32_t* rowptr, const int32_t* seeds_sorted,
+                                        const int32_t* seed_perm, const int32_t* uniq, int64_t n_extra, int64_t B, int64_t k,
+                                        int64_t nnz, int32_t* col, int32_t* dst, void* stream) {
+  clear_error();
+  int rc = check_batch("han_block_compact", B, k);
+  if (rc != ALLSET_OK) return rc;
+  ALLSET_REQUIRE(n_extra >= 0 && n_extra <= B * k && nnz >= 0 && nnz <= B * (k + 1), "han_block_compact: n_extra / nnz outside the slab");
+  if (B == 0 || nnz == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(rows && counts && rowptr && seeds_sorted && seed_perm && col && dst, "han_block_compact: null pointer");
+  ALLSET_REQUIRE(n_extra == 0 || uniq, "han_block_compact: null uniq with n_extra > 0");
+  block_compact_kernel<<<lane_grid(B * (k + 1)), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
+      rows, counts, rowptr, seeds_sorted, seed_perm, uniq, static_cast<int>(n_extra), static_cast<int>(B), static_cast<int>(k),
+      static_cast<int>(nnz), col, dst);
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
+}
+
+extern "C" int allset_han_block_hop_fwd(int64_t nnz, const int32_t* rowptr, const int32_t* col, const float* el, const float* er,
+                                        const float* x, int64_t ldx, float slope, const float* bias, float p_att, uint64_t seed,
+                                        const uint64_t* seed_base, float* y, int64_t ldy, float* outpos, int64_t ldpos, float* ppos,
+                                        float* lse, int64_t n_dst, int64_t n_src, int64_t H, int64_t C, void* stream) {
+  clear_error();
+  int rc = check_block("han_block_hop_fwd", n_dst, n_src, nnz);
+  if (rc != ALLSET_OK) return rc;
+  rc = check_heads("han_block_hop_fwd", H, C);
+  if (rc != ALLSET_OK) return rc;
+  return allset_han_hop_fwd(nnz, rowptr, col, el, er, x, ldx, slope, bias, p_att, seed, seed_base, y, ldy, outpos, ldpos, ppos, lse,
+                            n_dst, H, C, stream);
+}
+
+extern "C" int allset_han_block_hop_bwd_stats(const float* y, int64_t ldy, const float* bias, const float* gy, int64_t ldgy,
+                                              const float* outpos, int64_t ldpos, const float* ppos, const float* lse, float slope,
+                                              float* g, int64_t ldg, float* stats, float* ger, int64_t n_dst, int64_t H, int64_t C,
+                                              void* stream) {
+  clear_error();
+  ALLSET_REQUIRE(n_dst >= 0 && n_dst < INT32_MAX, "han_block_hop_bwd_stats: n_dst must fit int32");
+  int rc = check_heads("han_block_hop_bwd_stats", H, C);
+  if (rc != ALLSET_OK) return rc;
+  return allset_han_hop_bwd_stats(y, ldy, bias, gy, ldgy, outpos, ldpos, ppos, lse, slope, g, ldg, stats, ger, n_dst, H, C, stream);
+}
+
+extern "C" int allset_han_block_hop_bwd_src(int64_t nnz, const int32_t* rowptrT, const int32_t* colT, const int32_t* slotT,
+                                            const float* el, const float* er, const float* x, int64_t ldx, const float* g, int64_t ldg,
+                                            const float* stats, float slope, float p_att, uint64_t seed, const uint64_t* seed_base,
+                                            float* gx, int64_t ldgx, float* gel, int64_t n_dst, int64_t n_src, int64_t H, int64_t C,
+                                            void* stream) {
+  clear_error();
+  int rc = check_block("han_block_hop_bwd_src", n_dst, n_src, nnz);
+  if (rc != ALLSET_OK) return rc;
+  rc = check_heads("han_block_hop_bwd_src", H, C);
+  if (rc != ALLSET_OK) return rc;
+  ALLSET_REQUIRE(nnz == 0 || n_dst > 0, "han_block_hop_bwd_src: edges into a block without targets");
+  return allset_han_hop_bwd_src(nnz, rowptrT, colT, slotT, el, er, x, ldx, g, ldg, stats, slope, p_att, seed, seed_base, gx, ldgx, gel,
+                                n_src, H, C, stream);
+}

@@ -1024,3 +1024,64 @@ def semantic_attention(z: Tensor, W1: Tensor, b1: Tensor, q: Tensor) -> Tensor:
     Differentiable in all four."""
     _lib.require_device(z, W1, b1, q)
     return _SemanticAttention.apply(z, W1, b1, q)
+
+
+# ---- mini-batch HAN: the attention hop over a bipartite block (csrc/han_sample.hip) ---------------------------------------------------
+class _HanBlockPropagate(torch.autograd.Function):
+    """:class:`_HanGatPropagate` over a bipartite block (``han_sampling.Block``): ``x`` / ``el`` have ``n_src`` rows, ``er`` and the
+    result ``n_dst``.  The same kernels, the same saved tensors, the same stacked-buffer rule."""
+
+    @staticmethod
+    def forward(ctx, x, el, er, bias, blk, heads, slope, p, out, block):
+        from . import dense
+        n_src, d = x.shape
+        n_dst = blk.n_dst
+        if n_src != blk.n_src or er.shape[0] != n_dst:
+            raise _lib.AllSetHipError(f"han_block_propagate: x has {n_src} rows and er {er.shape[0]}, the block has {blk.n_src} source "
+                                      f"and {n_dst} target nodes")
+        seed = dense._draw_seed() if p > 0.0 else 0
+        base = dense._seed_base() if p > 0.0 else None
+        want = any(ctx.needs_input_grad[:4])
+        if out is None:
+            ret = torch.empty((n_dst, d), dtype=torch.float32, device=x.device)
+            y = ret
+        else:
+            if out.dim() != 2 or out.shape[0] != n_dst or out.shape[1] < (block + 1) * d or out.stride(1) != 1 or out.dtype != torch.float32:
+                raise _lib.AllSetHipError(f"han_block_propagate: out {tuple(out.shape)} cannot hold block {block} of width {d} for {n_dst} rows")
+            ctx.mark_dirty(out)
+            ret = out
+            y = out.detach()[:, block * d:(block + 1) * d]
+        outpos, ppos, lse = ops.han_block_hop_fwd(blk.rowptr, blk.col, x, el, er, heads, slope, bias, p, seed, base, y, want)
+        ctx.save_for_backward(x, el, er, bias, outpos, ppos, lse, ret if out is None else None)
+        ctx.y_block = y if out is not None else None
+        ctx.cfg = (blk, heads, slope, p, seed, base, block, d, out is not None)
+        return ret
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        x, el, er, bias, outpos, ppos, lse, y_own = ctx.saved_tensors
+        blk, heads, slope, p, seed, base, block, d, stacked = ctx.cfg
+        if gout.stride(1) != 1:
+            gout = gout.contiguous()
+        gy = gout[:, block * d:(block + 1) * d] if stacked else gout
+        g, stats, ger = ops.han_block_hop_bwd_stats(ctx.y_block if stacked else y_own, bias, gy, outpos, ppos, lse, slope)
+        gx, gel = ops.han_block_hop_bwd_src(blk.rowptrT, blk.colT, blk.slotT, x, el, er, g, stats, slope, p, seed, base)
+        gb = g.sum(0) if (bias is not None and ctx.needs_input_grad[3]) else None
+        return gx, gel, ger, gb, None, None, None, None, (gout if (stacked and ctx.needs_input_grad[8]) else None), None
+
+
+def han_block_propagate(x: Tensor, el: Tensor, er: Tensor, blk, heads: int, negative_slope: float = 0.2, bias: Optional[Tensor] = None,
+                        attn_drop: float = 0.0, out: Optional[Tensor] = None, block: int = 0) -> Tensor:
+    """:func:`han_gat_propagate` over a bipartite block ``blk`` (a ``han_sampling.Block``: ``n_src`` source nodes of which the first
+    ``n_dst`` are the targets, edges source -> target in both CSR orientations): ``x`` [n_src, heads * C], ``el`` [n_src, heads],
+    ``er`` [n_dst, heads]; the result has ``n_dst`` rows, ``y[t, h] = elu(sum_j a_j x[s_j, h] + bias[h])`` with ``a_j`` the softmax
+    over the edges into ``t`` times the hash mask on (target-major slot, head).  ``out`` / ``block``: the stacked [n_dst, M * heads *
+    C] buffer, as there.  Differentiable in ``x``, ``el``, ``er`` and ``bias``."""
+    _lib.require_device(x, el, er)
+    if out is not None and out.requires_grad and type(out.grad_fn).__name__ != "_HanBlockPropagateBackward":
+        raise ValueError("han_block_propagate: out must be a buffer that does not require grad, or the result of an earlier "
+                         "han_block_propagate into another of its blocks (the overwritten block would need a zero gradient)")
+    if el.dtype != torch.float32 or er.dtype != torch.float32:
+        el, er = el.float(), er.float()
+    return _HanBlockPropagate.apply(x, el, er, bias, blk, int(heads), float(negative_slope), float(attn_drop), out, int(block))

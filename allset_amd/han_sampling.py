@@ -1,0 +1,423 @@
+"""Mini-batch HAN of the reference's results table (``src/DGL_HAN/train_sampling.py``) on the HIP path.
+
+The reference samples on CPU ``DataLoader`` workers through DGL: per seed ``k`` metapath random walks
+(``RandomWalkNeighborSampler(num_traversals=1, termination_prob=0, num_random_walks=k, num_neighbors=k)``), the distinct endpoints as
+neighbours, self-loops removed and exactly one added back, ``dgl.to_block`` with the seeds first.  Here the incidence, the features and
+the labels stay on the device and the sampler is three HIP kernels (``csrc/han_sample.hip``: the walk, the per-seed rows, the
+relabelling) around one torch sort; the GAT hop runs over the bipartite block (``functional.han_block_propagate``).
+
+Node ids are the "appended" space full-batch HAN uses: vertices ``0..n_v-1``, hyperedges ``n_v..n_v+n_e-1``.  ``['Vs_E', 'E_Vs']`` (VEV)
+leaves only vertex ids, ``['Es_V', 'V_Es']`` (EVE) only hyperedge ids; a walk from any other node terminates and contributes nothing, so
+for the labelled seeds (vertices) the EVE block is the self-loops alone -- the reference's behaviour, kept.
+
+Orderings chosen here (DGL's are hash-table orders): a target's neighbours ascending by global id with the self-loop last; the block's
+source nodes = the seeds in the given order, then the other distinct nodes ascending.  Random numbers are counter-based, keyed on
+``(seed, step counter, metapath, global seed node, walk, hop)``: a node's neighbours do not depend on the batch it is in.
+
+Reference quirks kept: ``evaluate`` samples ``2 k`` walks and returns the LAST batch's loss (which ``EarlyStopping`` then consumes);
+``HAN.forward`` hands the same blocks to every layer, so only ``len(num_heads) == 1`` can work -- more raises ``ValueError``.
+"""
+from __future__ import annotations
+
+import argparse
+import time
+from types import SimpleNamespace
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib, dense, ops
+from .functional import han_block_propagate, semantic_attention
+from .han import EarlyStopping, SemanticAttention, _first, node_features, rand_train_test_idx, score
+from .incidence import Incidence
+
+Tensor = torch.Tensor
+INT32_MAX = 2 ** 31 - 1
+METAPATHS = {('Vs_E', 'E_Vs'): 0, ('Es_V', 'V_Es'): 1}
+DEFAULT_METAPATHS = [['Vs_E', 'E_Vs'], ['Es_V', 'V_Es']]
+
+
+def metapath_index(metapath) -> int:
+    """0 for VEV (``['Vs_E', 'E_Vs']``, ``'VEV'`` or 0), 1 for EVE (``['Es_V', 'V_Es']``, ``'EVE'`` or 1)."""
+    if isinstance(metapath, str) and metapath in ('VEV', 'EVE'):
+        return 0 if metapath == 'VEV' else 1
+    if isinstance(metapath, (int, np.integer)) and int(metapath) in (0, 1):
+        return int(metapath)
+    try:
+        return METAPATHS[tuple(metapath)]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown metapath {metapath!r}: ['Vs_E', 'E_Vs'] (VEV) and ['Es_V', 'V_Es'] (EVE) are built") from None
+
+
+# --------------------------------------------------------------------------------------------------
+# sampler
+# --------------------------------------------------------------------------------------------------
+
+class MetapathWalker:
+    """The binarised (vertex, hyperedge) incidence of ``data`` as both CSRs on the device, built once: ``v2e`` (row = vertex) and
+    ``e2v`` (row = hyperedge) are the two orientations of one :class:`Incidence`.  ``data.edge_index`` holds the incidences with
+    hyperedge ids starting at ``e_base``; ``data.n_x`` vertices, ``data.num_hyperedges`` hyperedges."""
+
+    def __init__(self, data, e_base: int = 0):
+        n_v, n_e = _first(data.n_x), _first(data.num_hyperedges)
+        ei = data.edge_index
+        _lib.require_device(ei)
+        v, e = ei[0], ei[1] - int(e_base)
+        if ei.numel() and (int(v.min()) < 0 or int(v.max()) >= n_v or int(e.min()) < 0 or int(e.max()) >= n_e):
+            raise ValueError(f"MetapathWalker: incidences outside {n_v} vertices x {n_e} hyperedges (hyperedge ids start at e_base = {e_base})")
+        if n_v + n_e > INT32_MAX:
+            raise ValueError(f"MetapathWalker: {n_v + n_e} nodes: node ids are int32")
+        key = torch.unique(v * max(n_e, 1) + e)                       # binarise (the reference's .nonzero(): duplicates count once)
+        pairs = torch.stack([key // max(n_e, 1), key % max(n_e, 1)])
+        inc = Incidence.from_edge_index(pairs, n_src=n_v, n_dst=n_e)
+        self.n_v, self.n_e, self.n = n_v, n_e, n_v + n_e
+        self.v2e, self.e2v = inc.by_src, inc.by_dst
+        self.device = ei.device
+
+    def orientation(self, mp: int):
+        """``(CSR A, CSR B, id_base)`` of metapath ``mp``."""
+        return (self.v2e, self.e2v, 0) if mp == 0 else (self.e2v, self.v2e, self.n_v)
+
+
+def _seeds_on_device(walker: MetapathWalker, seeds, check_dups: bool) -> Tensor:
+    """int32[B] on the walker's device.  A host list / CPU tensor is range-checked (and checked for duplicates) on the host for free;
+    a device tensor is taken as it is -- out-of-range ids there are nodes without out-edges to the walk."""
+    if torch.is_tensor(seeds) and seeds.is_cuda:
+        return seeds.to(torch.int32).contiguous().view(-1)
+    host = np.asarray(seeds.cpu() if torch.is_tensor(seeds) else seeds).reshape(-1)
+    if host.size and host.dtype.kind not in "iu":
+        raise ValueError(f"seeds must be integer node ids (got {host.dtype})")
+    host = host.astype(np.int64)
+    if host.size and (host.min() < 0 or host.max() >= walker.n):
+        raise ValueError(f"seeds outside [0, {walker.n}): {int(host.min())}..{int(host.max())}")
+    if check_dups and np.unique(host).size != host.size:
+        raise ValueError("duplicate seeds: a block's target nodes are distinct (dgl.to_block raises too)")
+    return torch.from_numpy(host.astype(np.int32)).to(walker.device)
+
+
+def random_walk_endpoints(walker: MetapathWalker, metapath, seeds, num_walks: int, seed: int, counter: int) -> Tensor:
+    """The raw walks: int64[B, num_walks] endpoints in global ids, -1 for a walk that terminated (a seed without out-edges in this
+    metapath).  A pure function of its arguments."""
+    mp = metapath_index(metapath)
+    if not 1 <= int(num_walks) <= ops.HAN_MAX_WALKS:
+        raise ValueError(f"num_walks must be in [1, {ops.HAN_MAX_WALKS}] (got {num_walks})")
+    s32 = _seeds_on_device(walker, seeds, check_dups=False)
+    a, b, base = walker.orientation(mp)
+    return ops.han_walk(mp, a, b, base, s32, int(num_walks), seed, counter).long()
+
+
+class Block:
+    """A bipartite block, DGL's ``to_block`` result: ``n_src`` source nodes (``src_ids`` int64 global ids, the ``n_dst`` targets
+    first) and edges source -> target in block-local ids.  ``src`` / ``dst`` int64[nnz]: the edge list; ``rowptr`` / ``col``:
+    target-major CSR (a slot there is the edge's identity for the attention dropout), ``perm``: slot -> edge-list position;
+    ``rowptrT`` / ``colT`` / ``slotT``: source-major CSR and the target-major slot of each of its entries, as in
+    ``han.MetapathGraph``."""
+
+    def __init__(self, n_dst, n_src, src_ids, src, dst, rowptr, col, perm, rowptrT, colT, slotT):
+        self.n_dst, self.n_src, self.nnz = int(n_dst), int(n_src), int(col.numel())
+        self.src_ids, self.src, self.dst = src_ids, src, dst
+        self.rowptr, self.col, self.perm = rowptr, col, perm
+        self.rowptrT, self.colT, self.slotT = rowptrT, colT, slotT
+
+    @staticmethod
+    def from_edges(src: Tensor, dst: Tensor, n_src: int, n_dst: int, src_ids: Optional[Tensor] = None) -> "Block":
+        """From a block-local edge list on the device (any order, duplicates kept)."""
+        _lib.require_device(src, dst)
+        if n_dst > n_src:
+            raise ValueError(f"a block's targets are its first source nodes: n_dst = {n_dst} > n_src = {n_src}")
+        src, dst = src.long().contiguous(), dst.long().contiguous()
+        inc = Incidence.from_edge_index(torch.stack([src, dst]), n_src=n_src, n_dst=n_dst)
+        if src_ids is None:
+            src_ids = torch.arange(n_src, dtype=torch.int64, device=src.device)
+        return Block(n_dst, n_src, src_ids, src, dst, inc.by_dst.rowptr, inc.by_dst.col, inc.by_dst.perm, inc.by_src.rowptr,
+                     inc.by_src.col, inc.pos_dst_of_src())
+
+    def srcdata_nid(self) -> Tensor:
+        return self.src_ids
+
+
+class HANSampler:
+    """``HANSampler(g, metapath_list, num_neighbors)`` of the reference with the device-resident walker in ``g``'s place and an
+    explicit ``seed``.  Every :meth:`sample_blocks` call takes the next step counter (or the one given)."""
+
+    def __init__(self, walker: MetapathWalker, metapath_list, num_neighbors: int, seed: int = 0):
+        if not 1 <= int(num_neighbors) <= ops.HAN_MAX_WALKS:
+            raise ValueError(f"num_neighbors must be in [1, {ops.HAN_MAX_WALKS}] (got {num_neighbors}): the walk kernel is built for "
+                             f"at most {ops.HAN_MAX_WALKS} walks per seed")
+        self.walker, self.num_neighbors, self.seed = walker, int(num_neighbors), int(seed)
+        self.metapaths = [metapath_index(m) for m in metapath_list]
+        self.counter = 0
+
+    def sample_blocks(self, seeds, counter: Optional[int] = None):
+        """``(seeds, [Block per metapath])``.  One host read-back per call (every block's edge and node counts, together)."""
+        w = self.walker
+        s32 = _seeds_on_device(w, seeds, check_dups=True)
+        if counter is None:
+            counter = self.counter
+            self.counter += 1
+        B, k, dev = s32.numel(), self.num_neighbors, w.device
+        sorted_seeds, order = torch.sort(s32)
+        seed_perm = order.to(torch.int32)
+        dup = (sorted_seeds[1:] == sorted_seeds[:-1]).any().to(torch.int64).view(1) if B > 1 else torch.zeros(1, dtype=torch.int64, device=dev)
+        slab = B * (k + 1)
+        staged, sizes = [], [dup]
+        for mp in self.metapaths:
+            a, b, base = w.orientation(mp)
+            ends = ops.han_walk(mp, a, b, base, s32, k, self.seed, counter)
+            rows, extra, counts = ops.han_block_rows(ends, s32, sorted_seeds)
+            rowptr = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+            rowptr[1:] = torch.cumsum(counts, 0)
+            # the distinct non-seed nodes, ascending: one sort of the slab, first occurrences scattered to their rank (slot `slab` of
+            # the buffer collects everything else)
+            flat = torch.sort(extra.view(-1)).values
+            first = flat < INT32_MAX
+            first[1:] &= flat[1:] != flat[:-1]
+            rank = torch.cumsum(first, 0)
+            uniq = torch.empty(slab + 1, dtype=torch.int32, device=dev)
+            uniq[torch.where(first, rank - 1, slab)] = flat
+            staged.append((rows, counts, rowptr, uniq))
+            sizes += [rowptr[-1:].long(), rank[-1:] if slab else torch.zeros(1, dtype=torch.int64, device=dev)]
+        host = torch.cat(sizes).tolist()                                # the one read-back
+        if host[0]:
+            raise ValueError("duplicate seeds: a block's target nodes are distinct (dgl.to_block raises too)")
+        blocks = []
+        seeds64 = s32.long()
+        for i, (rows, counts, rowptr, uniq) in enumerate(staged):
+            nnz, n_extra = int(host[1 + 2 * i]), int(host[2 + 2 * i])
+            col, dst = ops.han_block_compact(rows, counts, rowptr, sorted_seeds, seed_perm, uniq, n_extra, nnz)
+            n_src = B + n_extra
+            # source-major orientation: a stable sort of the slots by source id
+            colT_src, slots = torch.sort(col, stable=True)
+            rowptrT = torch.searchsorted(colT_src, torch.arange(n_src + 1, dtype=torch.int32, device=dev)).to(torch.int32)
+            slotT = slots.to(torch.int32)
+            colT = dst[slots]
+            src_ids = torch.cat([seeds64, uniq[:n_extra].long()])
+            blocks.append(Block(B, n_src, src_ids, col.long(), dst.long(), rowptr, col, torch.arange(nnz, dtype=torch.int32, device=dev),
+                                rowptrT, colT, slotT))
+        return seeds, blocks
+
+
+def load_subtensors(blocks: Sequence[Block], features: Tensor) -> List[Tensor]:
+    """The feature rows of every block's source nodes."""
+    return [features[b.src_ids] for b in blocks]
+
+
+# --------------------------------------------------------------------------------------------------
+# model (reference DGL_HAN/train_sampling.py; GATConv: dgl 0.7.1 nn/pytorch/conv/gatconv.py on a block)
+# --------------------------------------------------------------------------------------------------
+
+class GATConv(nn.Module):
+    """DGL 0.7.1 ``GATConv`` on a block, as mini-batch HAN uses it (``allow_zero_in_degree=True`` is accepted: every target of a
+    sampled block has its self-loop): ``fs = fc(feat_drop(h_src))``, ``el`` from all ``n_src`` rows, ``er`` from the first ``n_dst``.
+    ``state_dict`` keys and shapes are the full-batch ``han.GATConv``'s."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0., attn_drop=0., negative_slope=0.2, residual=False,
+                 activation=None, allow_zero_in_degree=False, bias=True):
+        super().__init__()
+        if residual or not bias:
+            raise ValueError("GATConv: residual / bias=False are not built (HAN uses neither)")
+        if activation is not F.elu:
+            raise ValueError("GATConv: the HIP hop is built with HAN's activation, F.elu")
+        self._num_heads, self._in_feats, self._out_feats = num_heads, in_feats, out_feats
+        self._allow_zero_in_degree = bool(allow_zero_in_degree)
+        self.fc = nn.Linear(in_feats, out_feats * num_heads, bias=False)
+        self.attn_l = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.attn_r = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.feat_drop, self.attn_drop, self.negative_slope = float(feat_drop), float(attn_drop), float(negative_slope)
+        self.bias = nn.Parameter(torch.empty(num_heads * out_feats))
+        self.activation = activation
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain('relu')
+        nn.init.xavier_normal_(self.fc.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn_l, gain=gain)
+        nn.init.xavier_normal_(self.attn_r, gain=gain)
+        nn.init.constant_(self.bias, 0)
+
+    def forward(self, block: Block, feat: Tensor, out: Optional[Tensor] = None, col_block: int = 0) -> Tensor:
+        """[n_dst, H, C] -- or, with ``out``, the stacked buffer itself with column block ``col_block`` filled."""
+        H, C = self._num_heads, self._out_feats
+        if feat.shape[0] != block.n_src:
+            raise ValueError(f"GATConv: {feat.shape[0]} feature rows for a block of {block.n_src} source nodes")
+        h = dense.hash_dropout(feat, self.feat_drop, self.training)
+        fs = dense.linear(h, self.fc.weight, None)
+        f3 = fs.view(-1, H, C)
+        el = (f3 * self.attn_l).sum(-1)
+        er = (f3[:block.n_dst] * self.attn_r).sum(-1)
+        y = han_block_propagate(fs, el, er, block, H, self.negative_slope, self.bias, self.attn_drop if self.training else 0.0, out,
+                                col_block)
+        return y if out is not None else y.view(-1, H, C)
+
+
+class HANLayer(nn.Module):
+    def __init__(self, num_metapath, in_size, out_size, layer_num_heads, dropout):
+        super().__init__()
+        self.gat_layers = nn.ModuleList()
+        for _ in range(num_metapath):
+            self.gat_layers.append(GATConv(in_size, out_size, layer_num_heads, dropout, dropout, activation=F.elu,
+                                           allow_zero_in_degree=True))
+        self.semantic_attention = SemanticAttention(in_size=out_size * layer_num_heads)
+        self.num_metapath = num_metapath
+
+    def forward(self, block_list, h_list) -> Tensor:
+        M = len(block_list)
+        if M != len(h_list) or M > len(self.gat_layers):
+            raise ValueError(f"HANLayer: {M} blocks, {len(h_list)} feature tensors, {len(self.gat_layers)} metapaths")
+        n_dst = block_list[0].n_dst
+        if any(b.n_dst != n_dst for b in block_list):
+            raise ValueError("HANLayer: the blocks of one batch share their target nodes")
+        d = self.gat_layers[0]._num_heads * self.gat_layers[0]._out_feats
+        z = torch.empty((n_dst, M * d), dtype=torch.float32, device=h_list[0].device)   # the reference's torch.stack(..., dim=1)
+        for i, blk in enumerate(block_list):
+            z = self.gat_layers[i](blk, h_list[i], out=z, col_block=i)
+        return self.semantic_attention(z.view(n_dst, M, d))
+
+
+class HAN(nn.Module):
+    def __init__(self, num_metapath, in_size, hidden_size, out_size, num_heads, dropout):
+        super().__init__()
+        self.layers = nn.ModuleList()
+        self.layers.append(HANLayer(num_metapath, in_size, hidden_size, num_heads[0], dropout))
+        for l in range(1, len(num_heads)):
+            self.layers.append(HANLayer(num_metapath, hidden_size * num_heads[l - 1], hidden_size, num_heads[l], dropout))
+        self.predict = nn.Linear(hidden_size * num_heads[-1], out_size)
+
+    def forward(self, g, h) -> Tensor:
+        if len(self.layers) != 1:
+            raise ValueError("mini-batch HAN is single-layer: the reference hands the same blocks (and the blocks' input features) to "
+                             f"every layer, which cannot work for len(num_heads) = {len(self.layers)} > 1")
+        h = self.layers[0](g, h)
+        return dense.linear(h, self.predict.weight, self.predict.bias)
+
+
+# --------------------------------------------------------------------------------------------------
+# driver (reference DGL_HAN/train_sampling.py)
+# --------------------------------------------------------------------------------------------------
+
+def _batches(ids: Tensor, batch_size: int):
+    return [ids[i:i + batch_size] for i in range(0, ids.numel(), batch_size)]
+
+
+def evaluate(model, g, metapath_list, num_neighbors, features, labels, val_nid, loss_fcn, batch_size, seed: int = 0, counter: int = 0):
+    """The reference's ``evaluate``: ``2 * num_neighbors`` walks, batches in order, the predictions of all batches concatenated for
+    the scores -- and the loss of the LAST batch alone returned (the reference's quirk; ``EarlyStopping`` consumes it)."""
+    model.eval()
+    sampler = HANSampler(g, metapath_list, num_neighbors=num_neighbors * 2, seed=seed)
+    logits_all, labels_all = [], []
+    loss = None
+    with torch.no_grad():
+        for step, ids in enumerate(_batches(val_nid, batch_size)):
+            seeds, blocks = sampler.sample_blocks(ids, counter=counter + step)
+            logits = model(blocks, load_subtensors(blocks, features))
+            batch_labels = labels[ids]
+            loss = loss_fcn(logits, batch_labels)
+            logits_all.append(logits)
+            labels_all.append(batch_labels)
+    if loss is None:
+        raise ValueError("evaluate: no nodes to evaluate on")
+    return (loss,) + score(torch.cat(logits_all), torch.cat(labels_all))
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser('mini-batch HAN')
+    p.add_argument('-s', '--seed', type=int, default=1, help='Random seed')
+    p.add_argument('--batch_size', type=int, default=32)
+    p.add_argument('--num_neighbors', type=int, default=20)
+    p.add_argument('--lr', type=float, default=0.001)
+    p.add_argument('--hidden_units', type=int, default=8)
+    p.add_argument('--dropout', type=float, default=0.6)
+    p.add_argument('--weight_decay', type=float, default=0.001)
+    p.add_argument('--num_epochs', type=int, default=100)
+    p.add_argument('--patience', type=int, default=10)
+    p.add_argument('--dataset', type=str, default='synthetic', help="'synthetic' or a dataset name train.py loads (with "
+                   "--raw_data_dir / --processed_data)")
+    p.add_argument('--runs', type=int, default=20)
+    p.add_argument('--cuda', type=int, default=0)
+    p.add_argument('--train_prop', type=float, default=0.5)
+    p.add_argument('--valid_prop', type=float, default=0.25)
+    p.add_argument('--feature_noise', type=float, default=1)
+    # additions of this driver: where train.py's loaders find a named dataset
+    p.add_argument('--raw_data_dir', default=None)
+    p.add_argument('--processed_data', default=None)
+    return p
+
+
+def setup(args: dict) -> dict:
+    args['num_heads'] = [8]
+    np.random.seed(args['seed'])
+    torch.manual_seed(args['seed'])
+    args['device'] = f"cuda:{args['cuda']}"
+    return args
+
+
+def load_data(args: dict):
+    """``(walker, features, labels, num_classes)`` on ``args['device']``."""
+    from . import train
+    from .preprocessing import ExtractV2E
+    targs = SimpleNamespace(dname=args['dataset'], raw_data_dir=args.get('raw_data_dir'), processed_data=args.get('processed_data'),
+                            feature_noise=str(args['feature_noise']), seed=args['seed'])
+    data = ExtractV2E(train.load_data(targs))
+    data = data.to(args['device'])
+    features, labels = node_features(data)
+    return MetapathWalker(data, e_base=_first(data.n_x)), features, labels, int(targs.num_classes)
+
+
+def main(args: dict) -> dict:
+    walker, features, labels, num_classes = load_data(args)
+    metapath_list = DEFAULT_METAPATHS
+    k, bs = args['num_neighbors'], args['batch_size']
+    if 2 * k > ops.HAN_MAX_WALKS:
+        raise ValueError(f"--num_neighbors {k}: evaluation samples twice as many walks and the kernel is built for {ops.HAN_MAX_WALKS}")
+    history = {'acc': [], 'micro_f1': [], 'macro_f1': [], 'time': [], 'train_loss': []}
+    shuffle = torch.Generator().manual_seed(args['seed'])
+    for run in range(args['runs']):
+        split = rand_train_test_idx(labels, args['train_prop'], args['valid_prop'])
+        train_nid, val_nid, test_nid = split['train'], split['valid'], split['test']
+        sample_seed = args['seed'] * 1000003 + run
+        sampler = HANSampler(walker, metapath_list, k, seed=sample_seed)
+        model = HAN(num_metapath=len(metapath_list), in_size=features.shape[1], hidden_size=args['hidden_units'], out_size=num_classes,
+                    num_heads=args['num_heads'], dropout=args['dropout']).to(args['device'])
+        stopper = EarlyStopping(patience=args['patience'])
+        loss_fn = torch.nn.CrossEntropyLoss()
+        optimizer = torch.optim.Adam(model.parameters(), lr=args['lr'], weight_decay=args['weight_decay'])
+        start = time.time()
+        epoch_losses = []
+        eval_counter = 1 << 40                                         # evaluation draws from its own range of step counters
+        for epoch in range(args['num_epochs']):
+            model.train()
+            perm = torch.randperm(train_nid.numel(), generator=shuffle).to(train_nid.device)       # DataLoader(shuffle=True)
+            losses = []
+            for ids in _batches(train_nid[perm], bs):
+                seeds, blocks = sampler.sample_blocks(ids)
+                logits = model(blocks, load_subtensors(blocks, features))
+                loss = loss_fn(logits, labels[ids])
+                optimizer.zero_grad()
+                loss.backward()
+                optimizer.step()
+                losses.append(loss.detach())
+            epoch_losses.append(float(torch.stack(losses).mean()))
+            val_loss, val_acc, _, _ = evaluate(model, walker, metapath_list, k, features, labels, val_nid, loss_fn, bs, sample_seed,
+                                               eval_counter)
+            eval_counter += 1 << 20
+            if stopper.step(float(val_loss), val_acc, model):
+                break
+        stopper.load_checkpoint(model)
+        _, test_acc, test_micro, test_macro = evaluate(model, walker, metapath_list, k, features, labels, test_nid, loss_fn, bs,
+                                                       sample_seed, eval_counter)
+        history['acc'].append(100 * test_acc)
+        history['micro_f1'].append(100 * test_micro)
+        history['macro_f1'].append(100 * test_macro)
+        history['train_loss'].append(epoch_losses)
+        history['time'].append(time.time() - start)
+    print(f">> Final test acc: {np.mean(history['acc']):.2f}, std: {np.std(history['acc']):.2f}; "
+          f"test marco f1: {np.mean(history['macro_f1']):.2f}, std: {np.std(history['macro_f1']):.2f}")
+    print(f">> Train time per run: {np.mean(history['time']):.2f}, std: {np.std(history['time']):.2f}")
+    return history
+
+
+if __name__ == '__main__':
+    main(setup(build_parser().parse_args().__dict__))

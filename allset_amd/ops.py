@@ -1123,3 +1123,145 @@ def han_sem_bwd(z: Tensor, W1: Tensor, b1: Tensor, q: Tensor, wbeta: Tensor, gou
         check(_lib.load().allset_han_sem_bwd(ptr(z), ptr(W1), ptr(b1), ptr(q), ptr(wbeta), ptr(gout), ptr(part), ptr(gsm), ptr(gz),
                                              ptr(ppart), ptr(gparams), N, M, D, hidden, stream_of(dev)), "allset_han_sem_bwd")
     return gz, gparams[:hidden * D].view(hidden, D), gparams[hidden * D:hidden * D + hidden], gparams[hidden * D + hidden:]
+
+
+# ---- mini-batch HAN: the metapath random walk, the block construction and the bipartite hop (csrc/han_sample.hip) ----------------------
+HAN_MAX_WALKS = 64
+
+
+def _i32(t: Tensor, what: str) -> Tensor:
+    if t.dtype != torch.int32:
+        raise _lib.AllSetHipError(f"{what}: int32 required (got {t.dtype})")
+    return t.contiguous()
+
+
+def han_walk(metapath: int, csr_a: CSR, csr_b: CSR, id_base: int, seeds: Tensor, k: int, seed: int, counter: int) -> Tensor:
+    """``k`` two-hop walks per seed over CSR ``csr_a`` then ``csr_b`` (the binarised incidence in the metapath's orientation):
+    endpoints int32[B, k] in global ids, -1 where the walk terminates.  ``seeds`` int32[B] global ids."""
+    dev = require_device(csr_a.rowptr, csr_a.col, csr_b.rowptr, csr_b.col, seeds)
+    seeds = _i32(seeds, "han_walk seeds")
+    B, k = seeds.numel(), int(k)
+    if csr_a.n_cols != csr_b.n_rows or csr_b.n_cols != csr_a.n_rows:
+        raise _lib.AllSetHipError(f"han_walk: CSR A {csr_a.n_rows} x {csr_a.n_cols} and CSR B {csr_b.n_rows} x {csr_b.n_cols} are not "
+                                  "the two orientations of one incidence")
+    out = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    with on_device(dev), _timed("han_walk", dev, B * max(k, 0) * 20 + B * 4):
+        check(_lib.load().allset_han_walk(int(metapath), ptr(csr_a.rowptr), ptr(csr_a.col), ptr(csr_b.rowptr), ptr(csr_b.col),
+                                          csr_a.n_rows, csr_b.n_rows, int(id_base), ptr(seeds), B, k,
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF, ptr(out), stream_of(dev)),
+              "allset_han_walk")
+    return out
+
+
+def han_block_rows(endpoints: Tensor, seeds: Tensor, seeds_sorted: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(rows, extra, counts)``: per seed the distinct endpoints ascending, then the self-loop, then -1 (int32[B, k + 1]); the same
+    with seed-set members and padding as INT32_MAX; the row lengths."""
+    dev = require_device(endpoints, seeds, seeds_sorted)
+    endpoints, seeds, seeds_sorted = _i32(endpoints, "han_block_rows"), _i32(seeds, "han_block_rows"), _i32(seeds_sorted, "han_block_rows")
+    if endpoints.dim() != 2 or endpoints.shape[0] != seeds.numel() or seeds_sorted.numel() != seeds.numel():
+        raise _lib.AllSetHipError(f"han_block_rows: endpoints {tuple(endpoints.shape)} against {seeds.numel()} seeds")
+    B, k = endpoints.shape
+    rows = torch.empty((B, k + 1), dtype=torch.int32, device=dev)
+    extra = torch.empty((B, k + 1), dtype=torch.int32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    with on_device(dev), _timed("han_block_rows", dev, B * (k + 2 * (k + 1) + 2) * 4):
+        check(_lib.load().allset_han_block_rows(ptr(endpoints), ptr(seeds), ptr(seeds_sorted), B, k, ptr(rows), ptr(extra), ptr(counts),
+                                                stream_of(dev)), "allset_han_block_rows")
+    return rows, extra, counts
+
+
+def han_block_compact(rows: Tensor, counts: Tensor, rowptr: Tensor, seeds_sorted: Tensor, seed_perm: Tensor, uniq: Tensor, n_extra: int,
+                      nnz: int) -> Tuple[Tensor, Tensor]:
+    """``(col, dst)`` int32[nnz]: the target-major CSR's block-local source ids and the target of every slot."""
+    dev = require_device(rows, counts, rowptr, seeds_sorted, seed_perm, uniq)
+    for t in (rows, counts, rowptr, seeds_sorted, seed_perm, uniq):
+        _i32(t, "han_block_compact")
+    B, k = rows.shape[0], rows.shape[1] - 1
+    if (not rows.is_contiguous() or counts.numel() != B or rowptr.numel() != B + 1 or seeds_sorted.numel() != B or seed_perm.numel() != B
+            or uniq.numel() < n_extra):
+        raise _lib.AllSetHipError(f"han_block_compact: rows {tuple(rows.shape)} / counts {counts.numel()} / rowptr {rowptr.numel()} / "
+                                  f"uniq {uniq.numel()} for {n_extra} non-seed nodes")
+    col = torch.empty((nnz,), dtype=torch.int32, device=dev)
+    dst = torch.empty((nnz,), dtype=torch.int32, device=dev)
+    with on_device(dev), _timed("han_block_compact", dev, B * (k + 1) * 4 + nnz * 8):
+        check(_lib.load().allset_han_block_compact(ptr(rows), ptr(counts.contiguous()), ptr(rowptr.contiguous()), ptr(seeds_sorted.contiguous()),
+                                                   ptr(seed_perm.contiguous()), ptr(uniq.contiguous()), int(n_extra), B, k, int(nnz), ptr(col),
+                                                   ptr(dst), stream_of(dev)), "allset_han_block_compact")
+    return col, dst
+
+
+def han_block_hop_fwd(rowptr: Tensor, col: Tensor, x: Tensor, el: Tensor, er: Tensor, heads: int, slope: float, bias: Optional[Tensor],
+                      p_att: float, seed: int, seed_base: Optional[Tensor], y: Tensor, want_grad: bool):
+    """:func:`han_hop_fwd` over a bipartite block: ``x`` [n_src, H*C], ``el`` [n_src, H], ``er`` [n_dst, H], ``y`` [n_dst, H*C] (a view
+    with contiguous rows); ``col`` holds block-local source ids."""
+    dev = require_device(rowptr, col, x, el, er, bias, y)
+    for t, what in ((x, "x"), (el, "el"), (er, "er"), (bias, "bias"), (y, "y")):
+        if t is not None:
+            _f32(t, f"han_block_hop_fwd {what}")
+    x, el, er = _rowmajor(x), el.contiguous(), er.contiguous()
+    n_src, d = x.shape
+    n_dst = rowptr.numel() - 1
+    H = int(heads)
+    if H < 1 or d % H != 0 or d == 0:
+        raise _lib.AllSetHipError(f"han_block_hop_fwd: width {d} does not split into {H} heads")
+    if n_dst < 0 or tuple(el.shape) != (n_src, H) or tuple(er.shape) != (n_dst, H) or tuple(y.shape) != (n_dst, d):
+        raise _lib.AllSetHipError(f"han_block_hop_fwd: el {tuple(el.shape)} / er {tuple(er.shape)} / y {tuple(y.shape)} / rowptr "
+                                  f"{rowptr.numel()} against {n_src} source rows of width {d}, {H} heads")
+    if bias is not None and bias.numel() != d:
+        raise _lib.AllSetHipError(f"han_block_hop_fwd: bias has {bias.numel()} entries for width {d}")
+    bias = bias.contiguous() if bias is not None else None
+    lse = torch.empty((n_dst, H), dtype=torch.float32, device=dev)
+    outpos = torch.empty((n_dst, d), dtype=torch.float32, device=dev) if want_grad else None
+    ppos = torch.empty((n_dst, H), dtype=torch.float32, device=dev) if want_grad else None
+    nnz = col.numel()
+    algo = nnz * (4 * d + 4 * H + 4) + (n_dst + 1) * 4 + n_dst * (4 * d + 12 * H) + (n_dst * (4 * d + 4 * H) if want_grad else 0)
+    with on_device(dev), _timed("han_block_hop_fwd", dev, algo):
+        check(_lib.load().allset_han_block_hop_fwd(nnz, ptr(rowptr), ptr(col), ptr(el), ptr(er), ptr(x), _ld(x), float(slope), ptr(bias),
+                                                   float(p_att), int(seed), ptr(seed_base), ptr(y), _pitch(y, "han_block_hop_fwd y"),
+                                                   ptr(outpos), d, ptr(ppos), ptr(lse), n_dst, n_src, H, d // H, stream_of(dev)),
+              "allset_han_block_hop_fwd")
+    return outpos, ppos, lse
+
+
+def han_block_hop_bwd_stats(y: Tensor, bias: Optional[Tensor], gy: Tensor, outpos: Tensor, ppos: Tensor, lse: Tensor, slope: float):
+    """:func:`han_hop_bwd_stats` over a block's ``n_dst`` target rows."""
+    dev = require_device(y, bias, gy, outpos, ppos, lse)
+    for t in (y, gy, outpos, ppos, lse):
+        _f32(t, "han_block_hop_bwd_stats")
+    n, d = y.shape
+    H = lse.shape[1]
+    if tuple(gy.shape) != (n, d) or tuple(outpos.shape) != (n, d):
+        raise _lib.AllSetHipError(f"han_block_hop_bwd_stats: gy {tuple(gy.shape)} / outpos {tuple(outpos.shape)} against y {tuple(y.shape)}")
+    g = torch.empty((n, d), dtype=torch.float32, device=dev)
+    stats = torch.empty((n, H, 2), dtype=torch.float32, device=dev)
+    ger = torch.empty((n, H), dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("han_block_hop_bwd_stats", dev, 5 * n * d * 4 + n * H * 16):
+        check(_lib.load().allset_han_block_hop_bwd_stats(ptr(y), _pitch(y, "han_block_hop_bwd_stats y"), ptr(bias), ptr(gy),
+                                                         _pitch(gy, "han_block_hop_bwd_stats gy"), ptr(outpos), d, ptr(ppos), ptr(lse),
+                                                         float(slope), ptr(g), d, ptr(stats), ptr(ger), n, H, d // H, stream_of(dev)),
+              "allset_han_block_hop_bwd_stats")
+    return g, stats, ger
+
+
+def han_block_hop_bwd_src(rowptrT: Tensor, colT: Tensor, slotT: Tensor, x: Tensor, el: Tensor, er: Tensor, g: Tensor, stats: Tensor,
+                          slope: float, p_att: float, seed: int, seed_base: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """:func:`han_hop_bwd_src` over a block: ``(gx [n_src, H*C], gel [n_src, H])``; ``g`` / ``stats`` / ``er`` have ``n_dst`` rows."""
+    dev = require_device(rowptrT, colT, slotT, x, el, er, g, stats)
+    for t in (x, el, er, g, stats):
+        _f32(t, "han_block_hop_bwd_src")
+    x, g, el, er, stats = _rowmajor(x), _rowmajor(g), el.contiguous(), er.contiguous(), stats.contiguous()
+    n_src, d = x.shape
+    n_dst, H = er.shape
+    if (tuple(g.shape) != (n_dst, d) or rowptrT.numel() != n_src + 1 or slotT.numel() != colT.numel() or tuple(stats.shape) != (n_dst, H, 2)
+            or tuple(el.shape) != (n_src, H)):
+        raise _lib.AllSetHipError(f"han_block_hop_bwd_src: g {tuple(g.shape)} / rowptrT {rowptrT.numel()} / slotT {slotT.numel()} against "
+                                  f"{n_src} source and {n_dst} target rows of width {d}, {colT.numel()} edges")
+    gx = torch.empty((n_src, d), dtype=torch.float32, device=dev)
+    gel = torch.empty((n_src, H), dtype=torch.float32, device=dev)
+    nnz = colT.numel()
+    with on_device(dev), _timed("han_block_hop_bwd_src", dev, nnz * (4 * d + 12 * H + 8) + (n_src + 1) * 4 + n_src * (8 * d + 8 * H)):
+        check(_lib.load().allset_han_block_hop_bwd_src(nnz, ptr(rowptrT), ptr(colT), ptr(slotT), ptr(el), ptr(er), ptr(x), _ld(x), ptr(g),
+                                                       _ld(g), ptr(stats), float(slope), float(p_att), int(seed), ptr(seed_base), ptr(gx),
+                                                       d, ptr(gel), n_dst, n_src, H, d // H, stream_of(dev)),
+              "allset_han_block_hop_bwd_src")
+    return gx, gel

@@ -957,6 +957,54 @@ int allset_han_sem_bwd(const float* z, const float* W1, const float* b1, const f
                        float* part, float* gsm, float* gz, float* ppart, float* gparams, int64_t N, int64_t M, int64_t D,
                        int64_t hidden, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mini-batch HAN (reference DGL_HAN/train_sampling.py): the metapath random-walk neighbour sampler, the block construction and the
+ * attention hop over a bipartite block.  Added under ABI 15, additions only; detect with allset_han_sampling_supported() (returns 1).
+ * int32 ids, wave 64, no atomics; every result is a pure function of its arguments.
+ *
+ * allset_han_walk: k <= 64 two-hop walks per seed (ALLSET_ERR_UNSUPPORTED beyond) over the binarised incidence: CSR A (n_a rows,
+ * columns in [0, n_b)), then CSR B (n_b rows, columns in [0, n_a)).  seeds int32[B] are GLOBAL node ids; a seed's row in A is
+ * seed - id_base, the endpoint written is (column of B) + id_base.  endpoints int32[B, k]; -1 where the walk terminates: a seed
+ * outside [id_base, id_base + n_a) or with an empty row (nothing is read for it).  Each hop takes one uniformly random entry of the
+ * row: index = (u32 * degree) >> 32, whose probability is within degree / 2^32 (relative) of 1 / degree.  u32 is two rounds of the
+ * library's counter hash keyed on (seed, counter, metapath, global id of the seed node, walk index, hop) -- NOT on the seed's
+ * position in the batch: a node's walks are the same in every batch.
+ *
+ * allset_han_block_rows: per seed, the distinct endpoints other than -1 and the seed itself, ascending by global id, then the seed
+ * (its one self-loop), then -1 padding, in row b of rows int32[B, k + 1]; counts int32[B] (self-loop included).  seeds_sorted
+ * int32[B] = the seeds ascending.  extra int32[B, k + 1]: the same entries with members of the seed set and the padding replaced
+ * by INT32_MAX (sorted and uniqued by the caller: the block's non-seed source nodes).
+ *
+ * allset_han_block_compact: rowptr int32[B + 1] = exclusive prefix sum of counts, nnz = rowptr[B]; seed_perm int32[B]: position in
+ * seeds of seeds_sorted[i]; uniq int32[n_extra]: the distinct non-seed source nodes ascending.  Writes the target-major CSR's
+ * col int32[nnz] (block-local source ids: seeds first in their given order, then uniq's order) and dst int32[nnz] (the target b).
+ *
+ * allset_han_block_hop_fwd / _bwd_stats / _bwd_src: allset_han_hop_fwd / _bwd_stats / _bwd_src over a bipartite block of n_src
+ * source rows and n_dst <= n_src target rows: x, el, gx, gel have n_src rows; er, y, outpos, ppos, lse, gy, g, stats, ger have
+ * n_dst rows; col holds source ids, colT target ids; the dropout key is the target-major slot, as there.  Same limits (H <= 64,
+ * H * C <= 512), same kernels: with n_src == n_dst the results are bit-identical to the square entry points'.
+ * ------------------------------------------------------------------------------------------- */
+int allset_han_sampling_supported(void);
+int allset_han_walk(int metapath, const int32_t* rowptr_a, const int32_t* col_a, const int32_t* rowptr_b, const int32_t* col_b,
+                    int64_t n_a, int64_t n_b, int64_t id_base, const int32_t* seeds, int64_t B, int64_t k, uint64_t seed,
+                    uint64_t counter, int32_t* endpoints, void* stream);
+int allset_han_block_rows(const int32_t* endpoints, const int32_t* seeds, const int32_t* seeds_sorted, int64_t B, int64_t k,
+                          int32_t* rows, int32_t* extra, int32_t* counts, void* stream);
+int allset_han_block_compact(const int32_t* rows, const int32_t* counts, const int32_t* rowptr, const int32_t* seeds_sorted,
+                             const int32_t* seed_perm, const int32_t* uniq, int64_t n_extra, int64_t B, int64_t k, int64_t nnz,
+                             int32_t* col, int32_t* dst, void* stream);
+int allset_han_block_hop_fwd(int64_t nnz, const int32_t* rowptr, const int32_t* col, const float* el, const float* er, const float* x,
+                             int64_t ldx, float slope, const float* bias, float p_att, uint64_t seed, const uint64_t* seed_base,
+                             float* y, int64_t ldy, float* outpos, int64_t ldpos, float* ppos, float* lse, int64_t n_dst,
+                             int64_t n_src, int64_t H, int64_t C, void* stream);
+int allset_han_block_hop_bwd_stats(const float* y, int64_t ldy, const float* bias, const float* gy, int64_t ldgy, const float* outpos,
+                                   int64_t ldpos, const float* ppos, const float* lse, float slope, float* g, int64_t ldg,
+                                   float* stats, float* ger, int64_t n_dst, int64_t H, int64_t C, void* stream);
+int allset_han_block_hop_bwd_src(int64_t nnz, const int32_t* rowptrT, const int32_t* colT, const int32_t* slotT, const float* el,
+                                 const float* er, const float* x, int64_t ldx, const float* g, int64_t ldg, const float* stats,
+                                 float slope, float p_att, uint64_t seed, const uint64_t* seed_base, float* gx, int64_t ldgx,
+                                 float* gel, int64_t n_dst, int64_t n_src, int64_t H, int64_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
