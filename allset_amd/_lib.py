@@ -277,6 +277,15 @@ SIGNATURES = {
                                        c_int64, _P],
     "allset_han_block_hop_bwd_src": [c_int64, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_float, c_float, c_uint64, _P, _P,
                                      c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P],
+    # hypergraph attention of HCHA's HypergraphConv(use_attention=True) (under ABI 15, additions only; detect with
+    # allset_hattn_supported)
+    "allset_hattn_supported": [],
+    "allset_hattn_coef": [c_int64, _P, _P, _P, _P, _P, _P, c_float, c_float, c_uint64, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, _P],
+    "allset_hattn_hop": [c_int64, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_float, c_uint64, _P, c_int, _P, c_int64, c_int64,
+                         c_int64, c_int64, c_int64, _P],
+    "allset_hattn_bwd_vertex": [c_int64, _P, _P, _P, _P, _P, _P, _P, _P, c_float, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P,
+                                _P, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P],
+    "allset_hattn_bwd_edge": [c_int64, _P, _P, _P, c_int64, c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

@@ -1,5 +1,6 @@
 """The hypergraph-convolution baselines of the reference behind its own module surface: ``HypergraphConv`` / ``HCHA`` (HGNN is
-HCHA with ``symdegnorm``) and ``HNHNConv`` / ``HNHN`` (reference layers.py:233-494, models.py:207-292).
+HCHA with ``symdegnorm``; with hypergraph attention: ``HypergraphAttentionConv``, ``functional.hattn_propagate``, csrc/hattn.hip) and
+``HNHNConv`` / ``HNHN`` (reference layers.py:233-494, models.py:207-292).
 
 Each conv is a Linear and two degree-scaled segment sums over the V-E incidence, V->E then E->V.  Both hops are one HIP kernel
 each (``functional.scaled_propagate``, csrc/hconv.hip) with the per-row scales, the bias, the activation and the dropout that
@@ -41,8 +42,8 @@ from torch.nn import Parameter
 
 from . import dense
 from ._lib import AllSetHipError
-from .functional import (HyperGCNStructure, gat_propagate, hypergcn_propagate, hypergcn_structure, initial_residual, pma_aggregate,
-                         scaled_propagate, unigat_edge, unigcn_hop, unignn_hop, unignn_row_tail, weighted_propagate)
+from .functional import (HyperGCNStructure, gat_propagate, hattn_propagate, hypergcn_propagate, hypergcn_structure, initial_residual,
+                         pma_aggregate, scaled_propagate, unigat_edge, unigcn_hop, unignn_hop, unignn_row_tail, weighted_propagate)
 from .incidence import Incidence, cached_incidence
 from .layers import _linear, glorot, zeros
 from .preprocessing import generate_norm_HCHA
@@ -58,9 +59,12 @@ def _incidence(x: Tensor, edge_index) -> Incidence:
     return cached_incidence(edge_index, n_src=x.shape[0])     # hyperedges: max(id) + 1 rows (reference layers.py:422-423)
 
 
-def _hcha_scales(data, x: Tensor, symdegnorm: bool):
-    """``(D, B)`` of ``data`` for this normalisation; computed once and attached to ``data`` when it has none (or the other kind)."""
-    if getattr(data, 'HCHA_D', None) is None or getattr(data, 'HCHA_symdegnorm', None) != bool(symdegnorm) \
+def _hcha_scales(data, x: Tensor, symdegnorm: bool, hyperedge_weight: Optional[Tensor] = None):
+    """``(D, B)`` of ``data`` for this normalisation; computed once and attached to ``data`` when it has none (or the other kind).
+    With ``hyperedge_weight`` they are always computed (the weighted degree belongs to the call, not to ``data``)."""
+    if hyperedge_weight is not None:
+        generate_norm_HCHA(data, symdegnorm, hyperedge_weight)
+    elif getattr(data, 'HCHA_D', None) is None or getattr(data, 'HCHA_symdegnorm', None) != bool(symdegnorm) \
             or data.HCHA_D.shape[0] != x.shape[0] or data.HCHA_D.device != x.device:
         generate_norm_HCHA(data, symdegnorm)
     return data.HCHA_D, data.HCHA_B
@@ -68,20 +72,34 @@ def _hcha_scales(data, x: Tensor, symdegnorm: bool):
 
 class HypergraphConv(nn.Module):
     """``X' = D^-1 H B^-1 H^T X Theta + bias`` (``symdegnorm``: ``D^-1/2 H B^-1 H^T D^-1/2 X Theta + bias``), reference
-    layers.py:318-494 without attention.  ``weight`` is [in, out] (not nn.Linear's layout) and glorot-initialised, ``bias`` zeros."""
+    layers.py:318-494 without attention.  ``weight`` is [in, out] (not nn.Linear's layout) and glorot-initialised, ``bias`` zeros.
+    ``use_attention=True`` still raises ``NotImplementedError`` on THIS class, as it always has: the attention half of the reference's
+    layer is :class:`HypergraphAttentionConv`, which shares this class's ``forward``."""
 
     def __init__(self, in_channels, out_channels, symdegnorm=False, use_attention=False, heads=1,
                  concat=True, negative_slope=0.2, dropout=0, bias=True, **kwargs):
         super().__init__()
         if use_attention:
-            raise NotImplementedError("HypergraphConv(use_attention=True) is not built (the reference's models never construct it)")
+            raise NotImplementedError("HypergraphConv(use_attention=True) is not built on this class: use HypergraphAttentionConv (the "
+                                      "reference layer's parameters and state_dict, the attention hops of csrc/hattn.hip)")
+        self._setup(in_channels, out_channels, symdegnorm, False, heads, concat, negative_slope, dropout, bias)
+
+    def _setup(self, in_channels, out_channels, symdegnorm, use_attention, heads, concat, negative_slope, dropout, bias):
         self.in_channels = in_channels
         self.out_channels = out_channels
-        self.use_attention = False
+        self.use_attention = bool(use_attention)
         self.symdegnorm = symdegnorm
-        self.heads = 1
-        self.concat = True
-        self.weight = Parameter(torch.empty(in_channels, out_channels))
+        if self.use_attention:
+            self.heads = heads
+            self.concat = concat
+            self.negative_slope = negative_slope
+            self.dropout = dropout
+            self.weight = Parameter(torch.empty(in_channels, heads * out_channels))
+            self.att = Parameter(torch.empty(1, heads, 2 * out_channels))
+        else:
+            self.heads = 1
+            self.concat = True
+            self.weight = Parameter(torch.empty(in_channels, out_channels))
         if bias and concat:
             self.bias = Parameter(torch.empty(heads * out_channels))
         elif bias and not concat:
@@ -92,45 +110,124 @@ class HypergraphConv(nn.Module):
 
     def reset_parameters(self):
         glorot(self.weight)
+        if self.use_attention:
+            glorot(self.att)
         zeros(self.bias)
 
-    def forward(self, x: Tensor, hyperedge_index, hyperedge_weight: Optional[Tensor] = None, *, scales=None,
+    def _check(self, n_v: int, n_e: int, hyperedge_weight, hyperedge_attr) -> None:
+        if hyperedge_weight is not None and (hyperedge_weight.dim() != 1 or hyperedge_weight.numel() != n_e):
+            raise ValueError(f"HypergraphConv: hyperedge_weight has shape {tuple(hyperedge_weight.shape)}, expected ({n_e},)")
+        if hyperedge_attr is None:
+            if self.use_attention and n_e > n_v:
+                raise ValueError(f"HypergraphConv: without hyperedge_attr the attention reads x[hyperedge id] (as the reference does), "
+                                 f"which needs n_e <= n_v; got n_e = {n_e} hyperedges and n_v = {n_v} vertices -- pass hyperedge_attr")
+        elif isinstance(hyperedge_attr, str):
+            if hyperedge_attr != 'mean':
+                raise ValueError(f"HypergraphConv: hyperedge_attr must be None, 'mean' or an [n_e, in_channels] tensor, got {hyperedge_attr!r}")
+        elif hyperedge_attr.dim() != 2 or tuple(hyperedge_attr.shape) != (n_e, self.in_channels):
+            raise ValueError(f"HypergraphConv: hyperedge_attr has shape {tuple(hyperedge_attr.shape)}, expected ({n_e}, {self.in_channels})")
+
+    def forward(self, x: Tensor, hyperedge_index, hyperedge_weight: Optional[Tensor] = None, hyperedge_attr=None, *, scales=None,
                 act: Optional[str] = None, p: float = 0.0) -> Tensor:
-        """``scales`` = ``(D, B)`` from ``preprocessing.generate_norm_HCHA`` (derived from ``hyperedge_index`` when None);
-        ``act`` / ``p``: the activation and dropout the model applies next, fused into the E->V launch."""
-        if hyperedge_weight is not None:
-            raise NotImplementedError("HypergraphConv: hyperedge weights other than ones are not built (the reference never passes any)")
-        inc = _incidence(x, hyperedge_index)
+        """``scales`` = ``(D, B)`` from ``preprocessing.generate_norm_HCHA`` (derived from ``hyperedge_index`` and
+        ``hyperedge_weight`` when None; the weight enters ``D`` only, so prebuilt scales already hold it); ``hyperedge_attr``: the
+        edge-side rows of the attention (ignored without it); ``act`` / ``p``: the activation and dropout the model applies next,
+        fused into the E->V launch."""
+        inc = None
+        if isinstance(hyperedge_index, Incidence) or x.is_cuda:
+            inc = _incidence(x, hyperedge_index)
+            n_e = inc.n_dst
+        else:
+            n_e = int(hyperedge_index[1].max()) + 1 if hyperedge_index.numel() > 0 else 0
+        self._check(x.shape[0], n_e, hyperedge_weight, hyperedge_attr)
+        if inc is None:
+            inc = _incidence(x, hyperedge_index)               # (refuses: there is no CPU path)
         if scales is None:
             if isinstance(hyperedge_index, Incidence):
                 raise ValueError("HypergraphConv: pass scales=(D, B) together with a prebuilt Incidence")
-            scales = _hcha_scales(SimpleNamespace(x=x, edge_index=hyperedge_index), x, self.symdegnorm)
+            scales = _hcha_scales(SimpleNamespace(x=x, edge_index=hyperedge_index), x, self.symdegnorm, hyperedge_weight)
+        elif hyperedge_weight is not None:
+            raise ValueError("HypergraphConv: scales=(D, B) already hold the hyperedge weights (generate_norm_HCHA(..., hyperedge_weight)); "
+                             "pass one or the other")
         D, B = scales
-        xw = dense.linear(x, self.weight.t(), None)          # x Theta: the [in, out] weight read transposed by the GEMM, no copy
-        if self.symdegnorm:
-            h = scaled_propagate(xw, inc, 'v2e', r=D, s=B)
+        if not self.use_attention:
+            xw = dense.linear(x, self.weight.t(), None)      # x Theta: the [in, out] weight read transposed by the GEMM, no copy
+            if self.symdegnorm:
+                h = scaled_propagate(xw, inc, 'v2e', r=D, s=B)
+            else:
+                h = scaled_propagate(xw, inc, 'v2e', s=B)
+            return scaled_propagate(h, inc, 'e2v', s=D, bias=self.bias, act=act, p=p)
+        H, C = self.heads, self.out_channels
+        n_v = x.shape[0]
+        att_v, att_e = self.att[:, :, :C], self.att[:, :, C:]
+        if hyperedge_attr is None or isinstance(hyperedge_attr, str):
+            z = dense.linear(x, self.weight.t(), None)
+            # 'mean': B H^T (X Theta) = (B H^T X) Theta, one hop on the transformed rows
+            ze = z[:n_e] if hyperedge_attr is None else scaled_propagate(z, inc, 'v2e', s=B)
         else:
-            h = scaled_propagate(xw, inc, 'v2e', s=B)
-        return scaled_propagate(h, inc, 'e2v', s=D, bias=self.bias, act=act, p=p)
+            zz = dense.linear(torch.cat([x, hyperedge_attr.to(x.dtype)], dim=0), self.weight.t(), None)    # one GEMM for both tables
+            z, ze = zz[:n_v], zz[n_v:]
+        av = (z.view(n_v, H, C) * att_v).sum(dim=-1)
+        ae = (ze.view(n_e, H, C) * att_e).sum(dim=-1)
+        p_attn = float(self.dropout) if self.training else 0.0
+        return hattn_propagate(z, av, ae, inc, H, D, B, self.negative_slope, self.concat, bias=self.bias, act=act, p_attn=p_attn, p=p)
 
     def __repr__(self):
         return "{}({}, {})".format(self.__class__.__name__, self.in_channels, self.out_channels)
 
 
+class HypergraphAttentionConv(HypergraphConv):
+    """The reference's ``HypergraphConv(use_attention=True)`` (layers.py:377-384, 426-434, 472-480): the same parameters and
+    ``state_dict`` (``weight`` [in, heads * out], ``att`` [1, heads, 2 * out] both glorot-initialised, ``bias`` zeros).  Every
+    incidence (v, e) carries the coefficient ``softmax_{e ni v}(leaky_relu(<[z_v | ze_e], att>))`` per head, with dropout ``dropout``
+    on it in training mode, and both hops are weighted by it (``functional.hattn_propagate``, csrc/hattn.hip); heads side by side
+    (``concat``) or averaged.  The edge-side rows ``ze``: the reference reads ``z[hyperedge id]`` -- vertex rows indexed by hyperedge
+    id -- which is what ``hyperedge_attr=None`` does (it needs no more hyperedges than vertices); ``hyperedge_attr`` = an [n_e, in]
+    tensor gives ``ze = hyperedge_attr Theta`` (the signature of later torch_geometric releases), ``hyperedge_attr='mean'`` the mean
+    of each hyperedge's member rows.  ``symdegnorm`` is refused: the reference multiplies ``D.unsqueeze(-1)`` [N, 1] into the
+    [N, heads, out] view of ``x`` there, which is malformed."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0, bias=True, symdegnorm=False,
+                 **kwargs):
+        nn.Module.__init__(self)
+        if symdegnorm:
+            raise ValueError("HypergraphAttentionConv: symdegnorm=True with attention is not defined: the reference scales the "
+                             "[N, heads, out] view of x by D.unsqueeze(-1) of shape [N, 1] there, which is malformed")
+        self._setup(in_channels, out_channels, False, True, heads, concat, negative_slope, dropout, bias)
+
+    def __repr__(self):
+        return "{}({}, {}, heads={})".format(self.__class__.__name__, self.in_channels, self.out_channels, self.heads)
+
+
 class HCHA(nn.Module):
     """Reference models.py:252-292: ``[in -> hidden] + [hidden -> hidden] x (L - 2) + [hidden -> classes]`` (two convs at L = 1),
-    ``elu`` and dropout between convs (fused into each conv's E->V launch), nothing after the last."""
+    ``elu`` and dropout between convs (fused into each conv's E->V launch), nothing after the last.
+
+    ``args.HCHA_use_attention`` (absent = off) switches every conv to hypergraph attention, wired as the reference wires its own
+    multi-head baseline CEGAT: the hidden convs with ``heads=args.heads, concat=True`` (the next conv reads ``heads * MLP_hidden``
+    columns), the last with ``heads=args.output_heads, concat=False``; ``args.HCHA_attn_drop`` (default 0) is the dropout on the
+    coefficients.  The edge-side rows are each hyperedge's mean member row (``hyperedge_attr='mean'``): the driver's self-loop
+    hyperedges make n_e > n_v, which the reference's ``x[hyperedge id]`` cannot index."""
 
     def __init__(self, args):
         super().__init__()
         self.num_layers = args.All_num_layers
         self.dropout = args.dropout
         self.symdegnorm = args.HCHA_symdegnorm
+        self.use_attention = bool(getattr(args, 'HCHA_use_attention', False))
         self.convs = nn.ModuleList()
-        self.convs.append(HypergraphConv(args.num_features, args.MLP_hidden, self.symdegnorm))
-        for _ in range(self.num_layers - 2):
-            self.convs.append(HypergraphConv(args.MLP_hidden, args.MLP_hidden, self.symdegnorm))
-        self.convs.append(HypergraphConv(args.MLP_hidden, args.num_classes, self.symdegnorm))
+        if not self.use_attention:
+            self.convs.append(HypergraphConv(args.num_features, args.MLP_hidden, self.symdegnorm))
+            for _ in range(self.num_layers - 2):
+                self.convs.append(HypergraphConv(args.MLP_hidden, args.MLP_hidden, self.symdegnorm))
+            self.convs.append(HypergraphConv(args.MLP_hidden, args.num_classes, self.symdegnorm))
+        else:
+            heads, out_heads = int(getattr(args, 'heads', 1)), int(getattr(args, 'output_heads', 1))
+            kw = dict(symdegnorm=self.symdegnorm, dropout=float(getattr(args, 'HCHA_attn_drop', 0.0)))
+            self.convs.append(HypergraphAttentionConv(args.num_features, args.MLP_hidden, heads=heads, **kw))
+            for _ in range(self.num_layers - 2):
+                self.convs.append(HypergraphAttentionConv(heads * args.MLP_hidden, args.MLP_hidden, heads=heads, **kw))
+            self.convs.append(HypergraphAttentionConv(heads * args.MLP_hidden, args.num_classes, heads=out_heads, concat=False, **kw))
 
     def reset_parameters(self):
         for conv in self.convs:
@@ -141,9 +238,10 @@ class HCHA(nn.Module):
         inc = _incidence(x, data.edge_index)
         scales = _hcha_scales(data, x, self.symdegnorm)
         p = float(self.dropout) if self.training else 0.0
+        attr = 'mean' if self.use_attention else None
         for conv in self.convs[:-1]:
-            x = conv(x, inc, scales=scales, act='elu', p=p)
-        return self.convs[-1](x, inc, scales=scales)
+            x = conv(x, inc, hyperedge_attr=attr, scales=scales, act='elu', p=p)
+        return self.convs[-1](x, inc, hyperedge_attr=attr, scales=scales)
 
 
 class CEGraph:

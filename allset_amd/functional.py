@@ -528,6 +528,80 @@ def gat_propagate(x: Tensor, al: Tensor, ar: Tensor, inc: Incidence, heads: int,
     return _GatPropagate.apply(x, al, ar, bias, inc, int(heads), float(negative_slope), bool(concat), act, float(p))
 
 
+# ---- hypergraph attention of HCHA's HypergraphConv(use_attention=True) (csrc/hattn.hip) --------------------------------------------
+class _HattnPropagate(torch.autograd.Function):
+    """Both hops of the attention conv under one coefficient: the coefficient launch (vertex-major softmax + coefficient dropout,
+    written in both CSR orders), the V->E hop, the E->V hop with the epilogue.  Backward: the epilogue's kernel (only when there is an
+    epilogue), the E->V hop's transpose over the hyperedge-major CSR, one vertex-major gather pass (the V->E hop's transpose, ``gav`` and
+    the per-incidence logit gradient), one segment sum for ``gae``.  Saved: ``z``, ``av``, ``ae``, the coefficients in both orders
+    ([nnz, H] each), ``m``, ``l``, the V->E hop's output and, with an epilogue, the output."""
+
+    @staticmethod
+    def forward(ctx, z, av, ae, bias, inc, heads, D, B, slope, concat, act, p_attn, p):
+        from . import dense
+        n_v, n_e = inc.n_src, inc.n_dst
+        if z.shape[0] != n_v or tuple(av.shape) != (n_v, heads) or tuple(ae.shape) != (n_e, heads):
+            raise _lib.AllSetHipError(f"hattn_propagate: z {tuple(z.shape)} / av {tuple(av.shape)} / ae {tuple(ae.shape)} against "
+                                      f"{n_v} vertices, {n_e} hyperedges and {heads} heads")
+        if D.numel() != n_v or B.numel() != n_e:
+            raise _lib.AllSetHipError(f"hattn_propagate: D has {D.numel()} entries for {n_v} vertices, B {B.numel()} for {n_e} hyperedges")
+        base = dense._seed_base() if (p_attn > 0.0 or p > 0.0) else None
+        seed_a = dense._draw_seed() if p_attn > 0.0 else 0          # (drawn first: the coefficient's mask, then the output's)
+        seed = dense._draw_seed() if p > 0.0 else 0
+        pos = inc.pos_dst_of_src()
+        a_v, a_e, m, l = ops.hattn_coef(inc.by_src, pos, av, ae, slope, p_attn, seed_a, base)
+        y_e = ops.hattn_hop(inc.by_dst, a_e, z, heads, n_e, s=B)
+        out = ops.hattn_hop(inc.by_src, a_v, y_e, heads, n_v, s=D, concat=concat, bias=bias, act=act, p=p, seed=seed, seed_base=base)
+        epi = act is not None or p > 0.0 or bias is not None
+        ctx.save_for_backward(z, av, ae, a_v, a_e, m, l, y_e, out if epi else None, D, B)
+        ctx.cfg = (inc, heads, slope, concat, act, p, seed, base, epi)
+        ctx.bias_param = bias
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        from . import dense
+        z, av, ae, a_v, a_e, m, l, y_e, out, D, B = ctx.saved_tensors
+        inc, heads, slope, concat, act, p, seed, base, epi = ctx.cfg
+        need_b = ctx.bias_param is not None and ctx.needs_input_grad[3]
+        gb = None
+        if epi:
+            g, part = ops.hconv_bwd_epi(gout, out, act, p, seed, base, want_bias=need_b)
+            if need_b:
+                # (inside dense.deferred_param_grads(): queued for the step's one batched reduction, and None here)
+                (gb,) = dense._defer_or_reduce(part, [(ctx.bias_param, 0, (out.shape[1],))], defer=True)
+        else:
+            g = gout
+        if not concat:
+            g = (g * (1.0 / heads)).repeat(1, heads)                   # the head mean's backward: g / H to every head
+        gy = ops.hattn_hop(inc.by_dst, a_e, g, heads, inc.n_dst, r=D)
+        gz, gav, ge_e = ops.hattn_bwd_vertex(inc.by_src, inc.pos_dst_of_src(), a_v, av, ae, m, l, slope, z, g, y_e, gy, D, B)
+        gae = ops.hattn_bwd_edge(inc.by_dst, ge_e, inc.n_dst)
+        return gz, gav, gae, gb, None, None, None, None, None, None, None, None, None
+
+
+def hattn_propagate(z: Tensor, av: Tensor, ae: Tensor, inc: Incidence, heads: int, D: Tensor, B: Tensor, negative_slope: float = 0.2,
+                    concat: bool = True, bias: Optional[Tensor] = None, act: Optional[str] = None, p_attn: float = 0.0,
+                    p: float = 0.0) -> Tensor:
+    """The two hops of the hypergraph attention conv (reference layers.py:426-476) over ``inc`` (sources = vertices, targets =
+    hyperedges).  With ``l_j = leaky_relu(av[v_j, h] + ae[e_j, h])``, ``alpha_j`` its softmax over the incidences OF VERTEX ``v_j``
+    (torch_geometric's, 1e-16 in the denominator) and ``a_j = alpha_j * keep_j / (1 - p_attn)``:
+    ``Y[e, h] = B[e] * sum_{j in e} a_j z[v_j, h]``, ``U[v, h] = D[v] * sum_{j ni v} a_j Y[e_j, h]``, and the result is
+    ``drop_p(act(U + bias))`` with the heads side by side (``concat``) or averaged.  ``z`` [n_v, heads * C]; ``av`` [n_v, heads] and
+    ``ae`` [n_e, heads] the per-row logit terms (``<z[v, h], att_v[h]>`` and ``<ze[e, h], att_e[h]>``: the edge-side table enters only
+    through ``ae``); ``D`` [n_v], ``B`` [n_e] constants.  ``keep`` is the library's hash mask on (position of the incidence in the edge
+    list ``inc`` was built from) * heads + head -- ``dense.dropout_scale((nnz, heads), p_attn, seed, device)`` rebuilds it; ``act``
+    None / 'relu' / 'elu'; ``p`` the dropout probability on the OUTPUT.  Differentiable in ``z``, ``av``, ``ae`` and ``bias``."""
+    if act not in ops.HCONV_ACTS:
+        raise ValueError(f"hattn_propagate: act must be None, 'relu' or 'elu', got {act!r}")
+    _lib.require_device(z, av, ae, D, B)
+    if av.dtype != torch.float32 or ae.dtype != torch.float32:
+        av, ae = av.float(), ae.float()
+    return _HattnPropagate.apply(z, av, ae, bias, inc, int(heads), D, B, float(negative_slope), bool(concat), act, float(p_attn),
+                                 float(p))
+
+
 # ---- UniGCNII: the E->V hop with GCNII's initial-residual step (csrc/unigcn.hip) ---------------------------------------------------
 class _GradSink:
     """Where the hops of one forward add their ``alpha * gXi`` in place: ``x0`` feeds every layer, its gradient is one buffer."""

@@ -721,6 +721,111 @@ def gat_bwd_src(csrT: CSR, x: Tensor, al: Tensor, ar: Tensor, g: Tensor, stats: 
     return gx, gal
 
 
+# ---- hypergraph attention of HCHA's HypergraphConv(use_attention=True) (csrc/hattn.hip) --------------------------------------------
+HATTN_MAX_HEADS, HATTN_MAX_WIDTH = 64, 512
+
+
+def hattn_coef(csr_v: CSR, pos: Tensor, av: Tensor, ae: Tensor, slope: float, p: float = 0.0, seed: int = 0,
+               seed_base: Optional[Tensor] = None):
+    """The attention coefficients over ``csr_v`` (rows = vertices, cols = hyperedges): ``(a_v, a_e, m, l)`` with ``a`` =
+    softmax over each vertex's incidences of ``leaky_relu(av[v] + ae[e])`` times the coefficient dropout's ``keep / (1 - p)`` (hash
+    mask keyed by edge-list position * H + head), f32[nnz, H] in ``csr_v``'s order and in the hyperedge-major order (``pos``: int32
+    position of each ``csr_v`` position in that CSR); ``m`` / ``l`` f32[n_v, H] the softmax statistics."""
+    dev = require_device(csr_v.rowptr, pos, av, ae)
+    _f32(av, "hattn_coef av")
+    _f32(ae, "hattn_coef ae")
+    av, ae = av.contiguous(), ae.contiguous()
+    n_v, H = av.shape
+    n_e = ae.shape[0]
+    nnz = csr_v.col.numel()
+    if ae.shape[1] != H or n_v > csr_v.n_rows or csr_v.n_cols > n_e or pos.numel() != nnz:
+        raise _lib.AllSetHipError(f"hattn_coef: av {tuple(av.shape)} / ae {tuple(ae.shape)} against a CSR of {csr_v.n_rows} x {csr_v.n_cols}")
+    a_v = torch.empty((nnz, H), dtype=torch.float32, device=dev)
+    a_e = torch.empty((nnz, H), dtype=torch.float32, device=dev)
+    m = torch.empty((n_v, H), dtype=torch.float32, device=dev)
+    l = torch.empty((n_v, H), dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("hattn_coef", dev, nnz * (8 + 12 * H) + (n_v + 1) * 4 + n_v * 12 * H):
+        check(_lib.load().allset_hattn_coef(nnz, ptr(csr_v.rowptr), ptr(csr_v.col), ptr(csr_v.perm), ptr(pos), ptr(av), ptr(ae),
+                                            float(slope), float(p), int(seed), ptr(seed_base), ptr(a_v), ptr(a_e), ptr(m), ptr(l), n_v,
+                                            n_e, H, stream_of(dev)), "allset_hattn_coef")
+    return a_v, a_e, m, l
+
+
+def hattn_hop(csr: CSR, w: Tensor, x: Tensor, heads: int, n_t: int, r: Optional[Tensor] = None, s: Optional[Tensor] = None,
+              concat: bool = True, bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0, seed: int = 0,
+              seed_base: Optional[Tensor] = None) -> Tensor:
+    """``agg[t, h] = s[t] * sum_{j in row t} w[j, h] * r[col_j] * x[col_j, h]`` over ``csr`` (``w`` f32[nnz, H] in its order), then
+    ``drop_p(act(agg + bias))`` with the heads side by side (``concat``) or averaged.  fp32 only."""
+    dev = require_device(csr.rowptr, w, x, r, s, bias)
+    for t, what in ((x, "x"), (w, "w"), (r, "r"), (s, "s"), (bias, "bias")):
+        if t is not None:
+            _f32(t, f"hattn_hop {what}")
+    x, w = _rowmajor(x), w.contiguous()
+    r = r.contiguous() if r is not None else None
+    s = s.contiguous() if s is not None else None
+    bias = bias.contiguous() if bias is not None else None
+    n_s, d = x.shape
+    H = int(heads)
+    if H < 1 or d % H != 0 or d == 0:
+        raise _lib.AllSetHipError(f"hattn_hop: width {d} does not split into {H} heads")
+    C = d // H
+    nnz = csr.col.numel()
+    width = d if concat else C
+    if tuple(w.shape) != (nnz, H):
+        raise _lib.AllSetHipError(f"hattn_hop: w {tuple(w.shape)} against ({nnz}, {H})")
+    if bias is not None and bias.numel() != width:
+        raise _lib.AllSetHipError(f"hattn_hop: bias has {bias.numel()} entries for width {width}")
+    if (r is not None and r.numel() < n_s) or (s is not None and s.numel() < n_t):
+        raise _lib.AllSetHipError("hattn_hop: r / s shorter than the rows they scale")
+    if n_t > csr.n_rows or csr.n_cols > n_s:
+        raise _lib.AllSetHipError(f"hattn_hop: CSR of {csr.n_rows} x {csr.n_cols} against {n_t} outputs / {n_s} gathered rows")
+    y = torch.empty((n_t, width), dtype=torch.float32, device=dev)
+    algo = nnz * (4 * d + 4 * H + 4 + (4 if r is not None else 0)) + (n_t + 1) * 4 + n_t * 4 * width
+    with on_device(dev), _timed("hattn_hop", dev, algo):
+        check(_lib.load().allset_hattn_hop(nnz, ptr(_gat_order(csr, n_t)), ptr(csr.rowptr), ptr(csr.col), ptr(w), ptr(r), ptr(s), ptr(x),
+                                           _ld(x), ptr(bias), HCONV_ACTS[act], float(p), int(seed), ptr(seed_base), 1 if concat else 0,
+                                           ptr(y), max(width, 1), n_t, n_s, H, C, stream_of(dev)), "allset_hattn_hop")
+    return y
+
+
+def hattn_bwd_vertex(csr_v: CSR, pos: Tensor, a_v: Tensor, av: Tensor, ae: Tensor, m: Tensor, l: Tensor, slope: float, z: Tensor,
+                     g: Tensor, y: Tensor, gy: Tensor, D: Tensor, B: Tensor):
+    """``(gz [n_v, H*C], gav [n_v, H], ge_e [nnz, H])``: the V->E hop's transpose, the gradient at ``av`` and the per-incidence
+    gradient at the pre-activation logit in hyperedge-major order, in one gather pass over ``csr_v`` (see csrc/hattn.hip)."""
+    dev = require_device(csr_v.rowptr, pos, a_v, av, ae, m, l, z, g, y, gy, D, B)
+    z, g, y, gy = _rowmajor(z), _rowmajor(g), _rowmajor(y), _rowmajor(gy)
+    n_v, d = z.shape
+    n_e = y.shape[0]
+    H = av.shape[1]
+    nnz = csr_v.col.numel()
+    if tuple(g.shape) != (n_v, d) or y.shape[1] != d or tuple(gy.shape) != (n_e, d) or n_v > csr_v.n_rows or csr_v.n_cols > n_e \
+            or tuple(a_v.shape) != (nnz, H) or D.numel() < n_v or B.numel() < n_e or d % H != 0:
+        raise _lib.AllSetHipError(f"hattn_bwd_vertex: z {tuple(z.shape)} / g {tuple(g.shape)} / y {tuple(y.shape)} / gy {tuple(gy.shape)} "
+                                  f"against a CSR of {csr_v.n_rows} x {csr_v.n_cols}")
+    gz = torch.empty((n_v, d), dtype=torch.float32, device=dev)
+    t = torch.empty((nnz, H), dtype=torch.float32, device=dev)
+    gav = torch.empty((n_v, H), dtype=torch.float32, device=dev)
+    ge_e = torch.empty((nnz, H), dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("hattn_bwd_vertex", dev, nnz * (8 * d + 12 * H + 16) + (n_v + 1) * 4 + n_v * (12 * d + 8 * H)):
+        check(_lib.load().allset_hattn_bwd_vertex(nnz, ptr(csr_v.rowptr), ptr(csr_v.col), ptr(pos), ptr(a_v), ptr(av.contiguous()),
+                                                  ptr(ae.contiguous()), ptr(m), ptr(l), float(slope), ptr(z), _ld(z), ptr(g), _ld(g),
+                                                  ptr(y), _ld(y), ptr(gy), _ld(gy), ptr(D.contiguous()), ptr(B.contiguous()), ptr(gz), d,
+                                                  ptr(t), ptr(gav), ptr(ge_e), n_v, n_e, H, d // H, stream_of(dev)),
+              "allset_hattn_bwd_vertex")
+    return gz, gav, ge_e
+
+
+def hattn_bwd_edge(csr_e: CSR, ge_e: Tensor, n_e: int) -> Tensor:
+    """``gae[e, h] = sum_{j in row e} ge_e[j, h]`` over the hyperedge-major CSR's own positions."""
+    dev = require_device(csr_e.rowptr, ge_e)
+    nnz, H = ge_e.shape
+    gae = torch.empty((n_e, H), dtype=torch.float32, device=dev)
+    with on_device(dev), _timed("hattn_bwd_edge", dev, nnz * 4 * H + (n_e + 1) * 4 + n_e * 4 * H):
+        check(_lib.load().allset_hattn_bwd_edge(nnz, ptr(csr_e.rowptr), ptr(ge_e), ptr(gae), n_e, H, stream_of(dev)),
+              "allset_hattn_bwd_edge")
+    return gae
+
+
 # ---- UniGCNII: the E->V hop with GCNII's initial-residual step (csrc/unigcn.hip) ---------------------------------------------------
 UNIGCN_MAX_WIDTH = 512
 

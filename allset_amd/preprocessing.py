@@ -19,6 +19,8 @@ reference may return (tests compare per-vertex multisets).
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 
 Tensor = torch.Tensor
@@ -221,13 +223,21 @@ def _inv0(t: Tensor) -> Tensor:
     return out
 
 
-def generate_norm_HCHA(data, symdegnorm: bool = False):
+def generate_norm_HCHA(data, symdegnorm: bool = False, hyperedge_weight: Optional[Tensor] = None):
     """The scales ``HypergraphConv.forward`` derives from ``hyperedge_index`` on every call (reference layers.py:438-470), once:
     ``data.HCHA_D`` [N] = 1 / deg(v) (``symdegnorm``: deg(v)^-1/2), ``data.HCHA_B`` [M] = 1 / |e|, inf -> 0, float32 as in the
-    reference; N = ``data.x`` rows (``data.n_x[0]`` without features), M = max hyperedge id + 1 after re-basing to 0."""
+    reference; N = ``data.x`` rows (``data.n_x[0]`` without features), M = max hyperedge id + 1 after re-basing to 0.  With
+    ``hyperedge_weight`` ([M]; None = ones) the degree is the weighted one, deg(v) = sum of ``w[e]`` over the hyperedges of ``v``; the
+    weight enters ``D`` only, as in the reference."""
     num_nodes = data.x.shape[0] if getattr(data, 'x', None) is not None else _first(data.n_x)
     v, e, N, M = _vertex_edge_ids(data.edge_index, num_nodes)
-    deg = torch.bincount(v, minlength=N).to(torch.float32)
+    if hyperedge_weight is None:
+        deg = torch.bincount(v, minlength=N).to(torch.float32)
+    else:
+        if hyperedge_weight.dim() != 1 or hyperedge_weight.numel() != M:
+            raise ValueError(f"generate_norm_HCHA: hyperedge_weight has shape {tuple(hyperedge_weight.shape)}, expected ({M},)")
+        w = hyperedge_weight.detach().to(device=v.device, dtype=torch.float32)
+        deg = torch.zeros(N, dtype=torch.float32, device=v.device).index_add_(0, v, w[e])
     size = torch.bincount(e, minlength=M).to(torch.float32)
     data.HCHA_D = _inv0(deg.pow(0.5) if symdegnorm else deg)
     data.HCHA_B = _inv0(size)

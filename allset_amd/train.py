@@ -22,6 +22,7 @@ preprocessing branch, the ``--UniGNN_*`` flags below, the default one-group Adam
     python -m allset_amd.train --method AllSetTransformer --dname synthetic --epochs 50 --runs 2 --heads 4 \\
         --MLP_hidden 128 --All_num_layers 1
     python -m allset_amd.train --method HCHA --dname synthetic --epochs 50 --runs 2      # HGNN: --method HGNN --HCHA_symdegnorm
+    python -m allset_amd.train --method HCHA --HCHA_use_attention --heads 2 --dname synthetic --epochs 50 --runs 2
     python -m allset_amd.train --method UniGCNII --dname synthetic --epochs 50 --runs 2 --All_num_layers 4
     python -m allset_amd.train --method HyperGCN --dname synthetic --epochs 50 --runs 2 --no-HyperGCN_fast
     python -m allset_amd.train --method UniGAT --dname synthetic --epochs 50 --runs 2 --heads 2
@@ -497,6 +498,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--output_heads', default=1, type=int)
     for flag in ('--HyperGCN_mediators', '--HyperGCN_fast', '--HCHA_symdegnorm', '--UniGNN_use-norm'):
         p.add_argument(flag, action='store_true')
+    # (HCHA's attention half, reference layers.py:426-434: heads as for CEGAT -- --heads on the hidden convs, --output_heads on the last)
+    p.add_argument('--HCHA_use_attention', action='store_true')
+    p.add_argument('--HCHA_attn_drop', default=0.0, type=float, help="dropout on the hypergraph attention coefficients")
     p.add_argument('--HNHN_alpha', default=-1.5, type=float)
     p.add_argument('--HNHN_beta', default=-0.5, type=float)
     p.add_argument('--HNHN_nonlinear_inbetween', default=True, type=bool)

@@ -1005,6 +1005,44 @@ int allset_han_block_hop_bwd_src(int64_t nnz, const int32_t* rowptrT, const int3
                                  float slope, float p_att, uint64_t seed, const uint64_t* seed_base, float* gx, int64_t ldgx,
                                  float* gel, int64_t n_dst, int64_t n_src, int64_t H, int64_t C, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Hypergraph attention of HCHA's HypergraphConv(use_attention=True) (csrc/hattn.hip): the attention coefficient is a softmax over the
+ * hyperedges of a VERTEX and weights both hops, V->E (grouped by hyperedge) and E->V (grouped by vertex).  Added under ABI 15,
+ * additions only; detect with allset_hattn_supported() (returns 1).  fp32, row-major.  H heads of C channels, H <= 64 and
+ * H * C <= 512 (ALLSET_ERR_UNSUPPORTED beyond).  No float atomics: results are bit-stable run to run.
+ *
+ * allset_hattn_coef over the vertex-major CSR (rowptr int32[n_v + 1], col = hyperedge ids, perm = edge-list position of each CSR
+ * position, pos = position of the same incidence in the hyperedge-major CSR): with l_j = leaky_relu(av[v, h] + ae[col_j, h], slope),
+ *   m[v, h] = max_j l_j (0 for an empty row), l[v, h] = sum_j exp(l_j - m),
+ *   a_j = exp(l_j - m) / (l + 1e-16) * keep_j / (1 - p), keep_j = the library's hash mask at index perm[j] * H + h (seed, seed_base as
+ *   everywhere), written to a_v f32[nnz, H] in this CSR's order and to a_e f32[nnz, H] in the hyperedge-major order (row pos[j]).
+ *
+ * allset_hattn_hop over either CSR (rows = outputs): agg[t, h, :] = s[t] * sum_j w[j, h] * r[col_j] * x[col_j, h, :], w f32[nnz, H] in
+ * the CSR's own order, r (per gathered row) and s (per output row) optional; concat != 0: y[t, :] = drop_p(act(agg[t, :] + bias[H*C]));
+ * concat == 0: y[t, :C] = drop_p(act(mean_h agg[t, h, :] + bias[C])).  act: ALLSET_HCONV_ACT_*; the dropout mask is indexed by
+ * t * (row width of y) + column, so allset_hconv_bwd_epi is this epilogue's backward.  row_order: optional processing order.
+ *
+ * allset_hattn_bwd_vertex over the vertex-major CSR, from g_u = the gradient at the E->V hop's pre-epilogue rows (f32[n_v, H*C]), the
+ * V->E hop's output y f32[n_e, H*C] and gy = the gradient at it (allset_hattn_hop over the hyperedge-major CSR with w = a_e, r = D):
+ *   gz[v, h, :] = sum_j a_v[j, h] * B[col_j] * gy[col_j, h, :],
+ *   gav[v, h] and ge_e f32[nnz, H] (hyperedge-major order): the gradient at av and, per incidence, at the pre-activation logit.
+ * t f32[nnz, H] is scratch.  allset_hattn_bwd_edge: gae[e, h] = sum of ge_e over row e of the hyperedge-major CSR.
+ * ------------------------------------------------------------------------------------------- */
+int allset_hattn_supported(void);
+int allset_hattn_coef(int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* perm, const int32_t* pos, const float* av,
+                      const float* ae, float slope, float p, uint64_t seed, const uint64_t* seed_base, float* a_v, float* a_e,
+                      float* m, float* l, int64_t n_v, int64_t n_e, int64_t H, void* stream);
+int allset_hattn_hop(int64_t nnz, const int32_t* row_order, const int32_t* rowptr, const int32_t* col, const float* w, const float* r,
+                     const float* s, const float* x, int64_t ldx, const float* bias, int act, float p, uint64_t seed,
+                     const uint64_t* seed_base, int concat, float* y, int64_t ldy, int64_t n_t, int64_t n_s, int64_t H, int64_t C,
+                     void* stream);
+int allset_hattn_bwd_vertex(int64_t nnz, const int32_t* rowptr, const int32_t* col, const int32_t* pos, const float* a_v,
+                            const float* av, const float* ae, const float* m, const float* l, float slope, const float* z, int64_t ldz,
+                            const float* g_u, int64_t ldg, const float* y, int64_t ldy, const float* gy, int64_t ldgy, const float* D,
+                            const float* B, float* gz, int64_t ldgz, float* t, float* gav, float* ge_e, int64_t n_v, int64_t n_e,
+                            int64_t H, int64_t C, void* stream);
+int allset_hattn_bwd_edge(int64_t nnz, const int32_t* rowptr, const float* ge_e, float* gae, int64_t n_e, int64_t H, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
