@@ -286,6 +286,12 @@ SIGNATURES = {
     "allset_hattn_bwd_vertex": [c_int64, _P, _P, _P, _P, _P, _P, _P, _P, c_float, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P,
                                 _P, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P],
     "allset_hattn_bwd_edge": [c_int64, _P, _P, _P, c_int64, c_int64, _P],
+    # metapath reachability of the heterogeneous HAN: the boolean sparse product (under ABI 15, additions only; detect with
+    # allset_spgemm_bool_bins)
+    "allset_spgemm_bool_bins": [POINTER(c_int64)],
+    "allset_spgemm_bool_workspace_bytes": [c_int64, POINTER(c_size_t)],
+    "allset_spgemm_bool_count": [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P],
+    "allset_spgemm_bool_fill": [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, c_size_t, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

@@ -3,7 +3,7 @@
 // ---- the attention hop -------------------------------------------------------------------------------------------------------
 // Over a target-major CSR of a multigraph (slot j of the CSR is the edge's identity; duplicates are separate slots), per head h:
 //   e_j        = leaky_relu(el[s_j,h] + er[t,h], slope)
-//   p_j        = exp(e_j - m) / l,  m = max_j e_j,  l = sum_j exp(e_j - m)                    (no epsilon; every row has an edge)
+//   p_j        = exp(e_j - m) / l,  m = max_j e_j,  l = sum_j exp(e_j - m)                    (no epsilon; a row without edges: out = 0)
 //   a_j        = p_j * k_j,  k_j = keep_j / (1 - p_att),  keep_j = hash(seed, j * H + h)     (the library's counter-hash dropout)
 //   out[t,h,:] = sum_j a_j x[s_j,h,:]
 //   y[t,h,:]   = elu(out[t,h,:] + bias[h,:])                                                   (alpha = 1)
@@ -143,7 +143,9 @@ __global__ __launch_bounds__(kBlock) void hop_fwd_kernel(
     }
 
     if (slot == 0 && active) {
-      const float inv = l > 0.f ? 1.f / l : 0.f;      // (a row without edges is refused when the graph is built)
+      // a row without edges (han_hetero's graphs allow one): acc = 0, inv = 0 -> y = elu(bias); lse = FLT_MAX, outpos = ppos = 0, so
+      // the stats pass gives ger = 0 and no edge ever reads its stats (tests/test_gpu_han_hetero.py)
+      const float inv = l > 0.f ? 1.f / l : 0.f;
       FVec<VEC> r;
 #pragma unroll
       for (int k = 0; k < VEC; ++k) r.v[k] = elu1(acc[k] * inv + (bias ? bias[c0 + k] : 0.f));

@@ -9,6 +9,8 @@ settings.  The per-metapath attention hops and the semantic attention are HIP ke
 
 Two choices are this project's, because the generator of the reference's ``*_raw.pickle`` files is not in its tree: hyperedge nodes
 get ZERO feature rows and label ``-1`` (so they are never in a split).  Reading those external pickles is out of scope.
+
+``--hetero`` is the reference's other mode (one typed graph, metapaths of edge types): ``allset_amd/han_hetero.py``; the loop below serves both.
 """
 from __future__ import annotations
 
@@ -292,6 +294,8 @@ def evaluate(model, gs, features, labels, mask, loss_func):
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser('HAN')
     p.add_argument('-s', '--seed', type=int, default=1, help='Random seed')
+    p.add_argument('--hetero', action='store_true', help="one typed graph and metapaths of edge types (allset_amd.han_hetero) instead "
+                   "of the hypergraph's VEV / EVE graphs")
     p.add_argument('--dataset', default='synthetic', help="'synthetic' or a dataset name train.py loads (with --raw_data_dir / "
                    "--processed_data)")
     p.add_argument('--runs', type=int, default=20)
@@ -318,7 +322,10 @@ def setup(args: dict) -> dict:
 
 
 def load_data(args: dict):
-    """``(gs, features, labels, num_classes)`` on ``args['device']``."""
+    """``(gs, features, labels, num_classes)`` on ``args['device']``; with ``--hetero``, ``gs`` is the typed graph itself."""
+    if args.get('hetero'):
+        from . import han_hetero
+        return han_hetero.load_data(args)
     from . import train
     from .preprocessing import ExtractV2E
     targs = SimpleNamespace(dname=args['dataset'], raw_data_dir=args.get('raw_data_dir'), processed_data=args.get('processed_data'),
@@ -340,8 +347,12 @@ def main(args: dict) -> dict:
         for k, idx in split.items():
             masks[k] = torch.zeros(num_nodes, dtype=torch.bool, device=features.device)
             masks[k][idx] = True
-        model = HAN(num_meta_paths=len(gs), in_size=features.shape[1], hidden_size=args['hidden_units'], out_size=num_classes,
-                    num_heads=args['num_heads'], dropout=args['dropout']).to(args['device'])
+        if args.get('hetero'):
+            from . import han_hetero
+            model = han_hetero.make_model(args, features.shape[1], num_classes).to(args['device'])
+        else:
+            model = HAN(num_meta_paths=len(gs), in_size=features.shape[1], hidden_size=args['hidden_units'], out_size=num_classes,
+                        num_heads=args['num_heads'], dropout=args['dropout']).to(args['device'])
         stopper = EarlyStopping(patience=args['patience'])
         loss_fcn = torch.nn.CrossEntropyLoss()
         optimizer = torch.optim.Adam(model.parameters(), lr=args['lr'], weight_decay=args['weight_decay'])

@@ -590,6 +590,52 @@ def clique_pairs(rowptr: Tensor, member: Tensor, edge_of: Tensor) -> Tensor:
     return keys
 
 
+def spgemm_bool_bins() -> Tuple[int, int, int, int]:
+    """The boolean product's row bins: ``(hash16 candidates, hash64 candidates, bitmap window columns, entries of an A row from which
+    every thread walks its own)`` -- see include/allset_hip_ext.h."""
+    out = (c_int64_t * 4)()
+    check(_lib.load().allset_spgemm_bool_bins(out), "allset_spgemm_bool_bins")
+    return tuple(int(v) for v in out)
+
+
+def spgemm_bool(rowptr_a: Tensor, col_a: Tensor, rowptr_b: Tensor, col_b: Tensor, n_c: int,
+                workspace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """``pattern(A B)`` of two int32 device CSRs (``A`` [n_a, n_b], ``B`` [n_b, n_c]; duplicates count once) as int32 CSR ``(rowptr
+    [n_a + 1], col [nnz_c])`` with strictly increasing columns in every row: count pass, scan, fill pass (csrc/metapath.hip).  Device
+    memory: the result, 8 bytes per row of ``A`` for the scan, and the workspace (``workspace``: a uint8 device tensor of at least
+    ``allset_spgemm_bool_workspace_bytes(n_a)`` bytes, allocated here when None) -- nothing grows with the candidate count.  One
+    host sync: the result's size."""
+    dev = require_device(rowptr_a, col_a, rowptr_b, col_b, workspace)
+    for t, what in ((rowptr_a, "rowptr_a"), (col_a, "col_a"), (rowptr_b, "rowptr_b"), (col_b, "col_b")):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise _lib.AllSetHipError(f"spgemm_bool: {what} must be a contiguous int32 vector (got {t.dtype} {tuple(t.shape)})")
+    n_a, n_b = rowptr_a.numel() - 1, rowptr_b.numel() - 1
+    if n_a < 0 or n_b < 0:
+        raise _lib.AllSetHipError("spgemm_bool: an empty rowptr (a CSR of n rows has n + 1 entries)")
+    lib = _lib.load()
+    need = c_size_t(0)
+    check(lib.allset_spgemm_bool_workspace_bytes(n_a, byref(need)), "allset_spgemm_bool_workspace_bytes")
+    if workspace is None:
+        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise _lib.AllSetHipError("spgemm_bool: workspace must be a contiguous uint8 tensor")
+    ws_bytes = workspace.numel()
+    cnt = torch.empty(n_a, dtype=torch.int32, device=dev)
+    nnz_a, nnz_b = col_a.numel(), col_b.numel()
+    with on_device(dev), _timed("spgemm_bool_count", dev, (n_a + n_b) * 4 + nnz_a * 4 + n_a * 4):
+        check(lib.allset_spgemm_bool_count(ptr(rowptr_a), ptr(col_a), ptr(rowptr_b), ptr(col_b), n_a, n_b, int(n_c), ptr(cnt),
+                                           ptr(workspace), ws_bytes, stream_of(dev)), "allset_spgemm_bool_count")
+    rowptr64 = torch.zeros(n_a + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(cnt, 0, dtype=torch.int64, out=rowptr64[1:])
+    nnz_c = int(rowptr64[-1])                                                  # one host sync: the output size
+    col = torch.empty(nnz_c if nnz_c <= 2 ** 31 - 1 else 0, dtype=torch.int32, device=dev)
+    rowptr = rowptr64.clamp_(max=2 ** 31 - 1).to(torch.int32)                  # (beyond int32 the fill refuses before reading it)
+    with on_device(dev), _timed("spgemm_bool_fill", dev, (n_a + n_b) * 4 + nnz_a * 4 + n_a * 4 + nnz_c * 4):
+        check(lib.allset_spgemm_bool_fill(ptr(rowptr_a), ptr(col_a), ptr(rowptr_b), ptr(col_b), n_a, n_b, int(n_c), ptr(rowptr), nnz_c,
+                                          ptr(col), ptr(workspace), ws_bytes, stream_of(dev)), "allset_spgemm_bool_fill")
+    return rowptr, col
+
+
 def gcn_norm(src: Tensor, dst: Tensor, m: Optional[Tensor], n: int) -> Tuple[Tensor, Tensor]:
     """torch_geometric 1.6.3 ``gcn_norm(edge_index, m, add_self_loops=True)`` for edges without self-loops, ids in [0, n):
     ``(edge_index int64[2, E + n] = [pairs | loops 0..n-1], w f32[E + n])``, ``w = deg^-1/2[src] * m * deg^-1/2[dst]``."""

@@ -96,3 +96,58 @@ def random_hypergraph(n_v: int, n_e: int, degree: float = 16, seed: int = 0, dev
     norm = torch.ones(edge_index.shape[1], dtype=torch.int64, device=device)
     return SimpleNamespace(edge_index=edge_index, norm=norm, n_v=n_v, n_e=n_e, nnz=int(edge_index.shape[1]),
                            seed=int(seed), dist=dist)
+
+
+def acm_like_hetero(n_papers: int = 3000, n_authors: int = 4000, n_fields: int = 30, num_classes: int = 3, num_features: int = 128,
+                    authors_per_paper: int = 3, orphan_fraction: float = 0.05, field_skew: float = 1.5, signal: float = 0.25,
+                    seed: int = 0, device="cuda") -> SimpleNamespace:
+    """A seeded ACM-shaped typed graph for the heterogeneous HAN (``han_hetero``): papers, authors and fields with the relations
+    ``pa`` / ``ap`` (paper - author, both directions) and ``pf`` / ``fp`` (paper - field).
+
+    Every paper has ONE field, drawn from ``P(f) ~ (f + 1) ** -field_skew`` within its class's share of the fields (so field sizes are
+    strongly skewed and PFP has hub rows: field 0 holds a large part of its class), and 1 .. ``2 * authors_per_paper - 1`` distinct
+    authors, mostly from its class's share of the authors -- except the ``orphan_fraction`` of the papers that have NO author: PAP has
+    zero-in-degree nodes.  Features are binary bag-of-words rows, a word being likelier (by ``signal``) inside its class's share of the
+    vocabulary; labels are on the papers.  Drawn on the host from ``numpy.random.default_rng(seed)``: the same graph on every device.
+
+    Returns ``SimpleNamespace(edges, num_nodes, features, labels, num_classes, orphans)``: ``edges`` maps ``(srctype, etype, dsttype)``
+    to ``(src, dst)`` int64 id tensors on ``device`` (the first argument of ``dgl.heterograph``), ``num_nodes`` maps a type to its
+    count, ``features`` f32 [n_papers, num_features], ``labels`` int64 [n_papers], ``orphans`` the number of author-less papers."""
+    import numpy as np
+    if min(n_papers, n_authors, n_fields, num_classes, num_features) < 1 or n_fields < num_classes or n_authors < num_classes:
+        raise ValueError("acm_like_hetero: every count must be >= 1, with at least one field and one author per class")
+    if not 0.0 <= orphan_fraction < 1.0:
+        raise ValueError("acm_like_hetero: orphan_fraction must be in [0, 1)")
+    rng = np.random.default_rng(int(seed))
+    labels = rng.integers(0, num_classes, size=n_papers)
+    # fields: class c owns fields c, c + num_classes, c + 2 num_classes, ...; a power law over the owned ones
+    field = np.empty(n_papers, dtype=np.int64)
+    for c in range(num_classes):
+        own = np.arange(c, n_fields, num_classes)
+        w = (np.arange(own.size) + 1.0) ** -float(field_skew)
+        idx = np.nonzero(labels == c)[0]
+        field[idx] = own[rng.choice(own.size, size=idx.size, p=w / w.sum())]
+    # authors: 1 .. 2 k - 1 per paper, 80 % from the class's share; orphans have none
+    orphan = rng.random(n_papers) < orphan_fraction
+    n_auth = np.where(orphan, 0, rng.integers(1, 2 * authors_per_paper, size=n_papers))
+    p_ids = np.repeat(np.arange(n_papers, dtype=np.int64), n_auth)
+    own_class = rng.random(p_ids.size) < 0.8
+    per = n_authors // num_classes
+    home = labels[p_ids] * per + rng.integers(0, per, size=p_ids.size)
+    a_ids = np.where(own_class, home, rng.integers(0, n_authors, size=p_ids.size)).astype(np.int64)
+    key = np.unique(p_ids * n_authors + a_ids)                                   # distinct authors within a paper
+    p_ids, a_ids = key // n_authors, key % n_authors
+    # bag of words
+    words = num_features // num_classes
+    prob = np.full((n_papers, num_features), 0.05)
+    for c in range(num_classes):
+        rows = np.nonzero(labels == c)[0]
+        prob[np.ix_(rows, np.arange(c * words, (c + 1) * words))] += float(signal)
+    feats = (rng.random((n_papers, num_features)) < prob).astype(np.float32)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device)
+    papers = np.arange(n_papers, dtype=np.int64)
+    edges = {("paper", "pa", "author"): (t(p_ids), t(a_ids)), ("author", "ap", "paper"): (t(a_ids), t(p_ids)),
+             ("paper", "pf", "field"): (t(papers), t(field)), ("field", "fp", "paper"): (t(field), t(papers))}
+    return SimpleNamespace(edges=edges, num_nodes={"paper": n_papers, "author": n_authors, "field": n_fields},
+                           features=torch.from_numpy(feats).to(device), labels=torch.from_numpy(labels.astype(np.int64)).to(device),
+                           num_classes=int(num_classes), orphans=int(orphan.sum()))

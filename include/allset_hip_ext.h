@@ -1043,6 +1043,31 @@ int allset_hattn_bwd_vertex(int64_t nnz, const int32_t* rowptr, const int32_t* c
                             int64_t H, int64_t C, void* stream);
 int allset_hattn_bwd_edge(int64_t nnz, const int32_t* rowptr, const float* ge_e, float* gae, int64_t n_e, int64_t H, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Metapath reachability of the heterogeneous HAN (reference DGL_HAN/main.py --hetero: dgl.metapath_reachable_graph), csrc/metapath.hip:
+ * the boolean sparse product C = pattern(A B).  Added under ABI 15, additions only; detect with allset_spgemm_bool_bins (returns
+ * ALLSET_OK).  A [n_a, n_b] and B [n_b, n_c] are int32 CSR on the device (rowptr int32[rows + 1], col int32[nnz]; duplicate entries
+ * allowed, they count once; ids in range -- an id outside its range is skipped, not dereferenced).  C is int32 CSR with STRICTLY
+ * INCREASING columns in every row, so it is unique and bit-identical from run to run.
+ *
+ * allset_spgemm_bool_count: cnt[i] = the number of distinct columns of row i of A B (int32[n_a]) and, in the workspace, the rows
+ *   binned by their candidate count sum_{k in A[i,:]} deg_B(k).  The caller scans cnt into rowptrC (exclusive, rowptrC[n_a] = nnz_c)
+ *   and reads nnz_c -- the only host synchronisation of the product, none happens in here.
+ * allset_spgemm_bool_fill: colC[rowptrC[i] .. rowptrC[i + 1]) = those columns, ascending; `workspace` as the count pass left it.
+ * No global memory is proportional to the candidate count (which may exceed 2^31 and is never checked): a row's column set lives in
+ * LDS -- a hash table for rows of at most bins[0] = 32 / bins[1] = 512 candidates, beyond that a bitmap over windows of bins[2] =
+ * 262144 columns, one pass per window; rows of A with at least bins[3] entries are walked one entry per thread.  The workspace is
+ * allset_spgemm_bool_workspace_bytes(n_a) = 16 + 12 n_a bytes, 4-byte aligned.  n_c > INT32_MAX (count) and nnz_c > INT32_MAX
+ * (fill) return ALLSET_ERR_INVALID_ARGUMENT with a message before anything is launched.
+ * ------------------------------------------------------------------------------------------- */
+int allset_spgemm_bool_bins(int64_t* bins /* [4] */);
+int allset_spgemm_bool_workspace_bytes(int64_t n_a, size_t* bytes);
+int allset_spgemm_bool_count(const int32_t* rowptrA, const int32_t* colA, const int32_t* rowptrB, const int32_t* colB, int64_t n_a,
+                             int64_t n_b, int64_t n_c, int32_t* cnt, void* workspace, size_t workspace_bytes, void* stream);
+int allset_spgemm_bool_fill(const int32_t* rowptrA, const int32_t* colA, const int32_t* rowptrB, const int32_t* colB, int64_t n_a,
+                            int64_t n_b, int64_t n_c, const int32_t* rowptrC, int64_t nnz_c, int32_t* colC, const void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
