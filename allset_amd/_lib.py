@@ -292,6 +292,11 @@ SIGNATURES = {
     "allset_spgemm_bool_workspace_bytes": [c_int64, POINTER(c_size_t)],
     "allset_spgemm_bool_count": [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P],
     "allset_spgemm_bool_fill": [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, c_size_t, _P],
+    # leave-one-out segmented sums: exclude-self aggregation without the expanded edge list (under ABI 15, additions only; detect
+    # with allset_loo_supported)
+    "allset_loo_supported": [c_int64],
+    "allset_loo_long_threshold": [],
+    "allset_loo_rows": [_P, _P, _P, c_int64, _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

@@ -16,7 +16,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
 from ._lib import MAX, MEAN, MIN, REDUCE_CODES, SUM
-from .incidence import Incidence
+from .incidence import Incidence, LeaveOneOutIncidence
 
 Tensor = torch.Tensor
 
@@ -169,6 +169,73 @@ def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None,
     else:
         w_dst, w_src = inc.weights(norm)
     return _SegReduce.apply(x, w_dst, w_src, inc, REDUCE_CODES[aggr])
+
+
+# ---- exclude-self Deep Sets aggregation over the UNEXPANDED incidence (csrc/loo.hip; DESIGN.md section 19) ------------------------
+def _loo_expand(x: Tensor, loo: LeaveOneOutIncidence, s_src: Optional[Tensor], s_seg: Optional[Tensor]) -> Tensor:
+    """[rows of vertices] -> [nnz]: row (e, i) = s_seg[e] * sum of the scaled rows of e's members other than the i-th."""
+    return ops.loo_rows(loo.e_rowptr, loo.e_col, x, s_src, s_seg, long_seg=loo.long_seg if loo.n_long else None, n_long=loo.n_long)
+
+
+def _loo_collect(y: Tensor, loo: LeaveOneOutIncidence, s_seg: Optional[Tensor], w_inc: Optional[Tensor], n_rows: int) -> Tensor:
+    """[nnz] -> [n_rows of vertices]: row v = sum over v's incidences (e, j) of w_inc * s_seg[e] * (sum of e's rows other than the j-th)."""
+    t = ops.loo_rows(loo.e_rowptr, None, y, None, s_seg, long_seg=loo.long_seg if loo.n_long else None, n_long=loo.n_long)
+    out, _ = ops.segreduce(SUM, loo.v_rowptr, loo.v_col, w_inc, t, n_rows)
+    return out
+
+
+class _LooV2E(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, loo: LeaveOneOutIncidence, f):
+        ctx.loo, ctx.f, ctx.n_rows = loo, f, x.shape[0]
+        return _loo_expand(x, loo, f.v2e_src, f.v2e_seg)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout: Tensor):
+        f = ctx.f
+        return _loo_collect(gout.contiguous(), ctx.loo, f.v2e_seg, f.v2e_src_inc, ctx.n_rows), None, None
+
+
+class _LooE2V(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y: Tensor, loo: LeaveOneOutIncidence, f):
+        ctx.loo, ctx.f = loo, f
+        return _loo_collect(y, loo, f.e2v_seg, f.e2v_row_inc, loo.n_dst)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout: Tensor):
+        f = ctx.f
+        return _loo_expand(gout.contiguous(), ctx.loo, f.e2v_row, f.e2v_seg), None, None
+
+
+def deepsets_aggregate_exclude_self(x: Tensor, loo: LeaveOneOutIncidence, direction: str, aggr: str = "add",
+                                    normtype: str = "all_one") -> Tensor:
+    """``deepsets_aggregate`` over the reference's exclude-self expansion (``preprocessing.expand_edge_index``: hyperedge e of size k as
+    k hyperedges ``e_i`` = e without its i-th member) computed from the UNEXPANDED incidence ``loo``:
+
+    ``direction='v2e'``: ``x`` [n_v, d] -> [nnz, d], row (e, i) = reduce over the members of e other than the i-th;
+    ``direction='e2v'``: ``x`` [nnz, d] -> [loo.n_dst, d], row v = reduce over every (e, i) with v in e and v not e's i-th member.
+
+    ``aggr`` add | sum | mean (over the expanded sizes / degrees); ``normtype`` all_one | deg_half_sym (what ``norm_contruction`` gives on
+    the expanded list).  A singleton hyperedge keeps its member, as in the reference.  Differentiable in ``x``; each direction's
+    backward is the other's forward.  max / min, bf16 storage and a per-expanded-incidence weight (LearnMask) are not built here and
+    raise ``NotImplementedError``: they keep the expansion path."""
+    if direction not in ("v2e", "e2v"):
+        raise ValueError(f"deepsets_aggregate_exclude_self: direction must be 'v2e' or 'e2v', got {direction!r}")
+    f = loo.factors(aggr, normtype)
+    _lib.require_device(x)
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f"exclude-self aggregation: float32 only (got {x.dtype}); bf16 storage keeps the expansion path "
+                                  "(preprocessing.expand_edge_index)")
+    if direction == "v2e":
+        if not (loo.n_dst <= x.shape[0] <= loo.n_v):
+            raise ValueError(f"vertex matrix has {x.shape[0]} rows; the incidence needs between {loo.n_dst} and {loo.n_v}")
+        return _LooV2E.apply(x, loo, f)
+    if x.shape[0] != loo.nnz:
+        raise ValueError(f"hyperedge-side matrix has {x.shape[0]} rows; the exclude-self incidence has {loo.nnz} (one per incidence)")
+    return _LooE2V.apply(x, loo, f)
 
 
 def _colocate(V: Tensor, heads: int) -> bool:

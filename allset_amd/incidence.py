@@ -15,7 +15,7 @@ Layout (all int32, device resident):
 from __future__ import annotations
 
 import weakref
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -172,6 +172,131 @@ class Incidence:
             self._wcache.clear()
             self._wcache[key] = (weakref.ref(norm), hit, probed)
         return hit
+
+
+class LeaveOneOutIncidence:
+    """The structure of the exclude-self aggregation over the UNEXPANDED V->E edge list.
+
+    The reference's ``expand_edge_index`` (preprocessing.py:22-144) turns hyperedge ``e`` of size k into k hyperedges ``e_i = e`` minus
+    its i-th member; here they are never listed.  Held instead (int32; built once, on the device of ``edge_index`` -- plain torch, so
+    a CPU tensor works too and is what the host tests use):
+
+      e_rowptr, e_col : hyperedge-major CSR, members in edge-list order.  Position p of it IS the 0-based id ``expand_edge_index`` gives
+                        the expanded hyperedge "(hyperedge of p) without the member at p".
+      v_rowptr, v_col : vertex-major CSR whose ``col`` is that position.
+      pos             : int64[nnz] position of each incidence of the caller's edge list.
+      sizes           : int64[n_e] hyperedge sizes;  row_size f32[n_e] = max(k - 1, 1), the expanded hyperedges' size;
+      vdeg            : f32[n_v] = sum_{e ni v} max(k_e - 1, 1), the expanded vertex degree.
+      long_seg        : ids of the hyperedges longer than ``ops.loo_long_threshold()`` (one workgroup each in the kernel).
+
+    ``n_v`` = rows of the vertex feature matrix; ``n_dst`` (fixed here) = (largest vertex id with an incidence) + 1 rows leave the
+    E->V direction, the reference's sizing rule as in ``Incidence.reversed()``.  A repeated (vertex, hyperedge) pair is refused: the
+    reference's dict overwrite makes it ill-defined, and the loaders coalesce such pairs away."""
+
+    def __init__(self, edge_index: Tensor, n_v: Optional[int] = None, e_base: int = 0, long_threshold: Optional[int] = None):
+        if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
+            raise ValueError(f"edge_index must be int64 [2, nnz], got {edge_index.dtype} {tuple(edge_index.shape)}")
+        dev = edge_index.device
+        v, e = edge_index[0].contiguous(), edge_index[1].contiguous() - int(e_base)
+        nnz = int(v.numel())
+        if nnz >= 2 ** 31 - 1:
+            raise ValueError(f"{nnz} incidences do not fit the int32 CSR")
+        if nnz > 0:                                   # one-time host syncs: id ranges (the kernels cannot report a bad id)
+            lo_v, hi_v, lo_e, hi_e = int(v.min()), int(v.max()), int(e.min()), int(e.max())
+        else:
+            lo_v = lo_e = 0
+            hi_v = hi_e = -1
+        if n_v is None:
+            n_v = hi_v + 1
+        if lo_v < 0 or hi_v >= n_v:
+            raise ValueError(f"vertex ids span [{lo_v}, {hi_v}] but n_v = {n_v}")
+        if lo_e < 0:
+            raise ValueError(f"hyperedge ids start at {lo_e + int(e_base)}, below e_base = {int(e_base)}")
+        n_e = hi_e + 1
+        if nnz > 0 and int(torch.unique(e * n_v + v).numel()) != nnz:
+            raise ValueError("duplicate (vertex, hyperedge) incidences: the exclude-self expansion is ill-defined for them "
+                             "(the reference's loaders coalesce the edge list)")
+        self.n_v, self.n_e, self.n_dst, self.nnz, self.device = int(n_v), int(n_e), hi_v + 1, nnz, dev
+        order_e = torch.argsort(e, stable=True)                       # members of a hyperedge in edge-list order
+        self.sizes = torch.bincount(e, minlength=n_e)
+        self.e_rowptr = _rowptr_of(self.sizes, dev)
+        self.e_col = v[order_e].to(torch.int32).contiguous()
+        self.pos = torch.empty(nnz, dtype=torch.int64, device=dev)
+        self.pos[order_e] = torch.arange(nnz, dtype=torch.int64, device=dev)
+        order_v = torch.argsort(v, stable=True)
+        self.v_rowptr = _rowptr_of(torch.bincount(v, minlength=self.n_v), dev)
+        self.v_col = self.pos[order_v].to(torch.int32).contiguous()
+        self._v_of_vpos = v[order_v]                                   # vertex of each vertex-major position
+        self.row_size = (self.sizes - 1).clamp(min=1).to(torch.float32)
+        # (exact: integer sums far below 2^53)
+        self.vdeg = torch.bincount(v, weights=self.row_size[e].double(), minlength=self.n_v).to(torch.float32) if nnz else \
+            torch.zeros(self.n_v, dtype=torch.float32, device=dev)
+        if long_threshold is None:
+            long_threshold = ops.loo_long_threshold()
+        self.long_seg = (self.sizes > long_threshold).nonzero().reshape(-1).to(torch.int32).contiguous()
+        self.n_long = int(self.long_seg.numel())
+        self.max_size = int(self.sizes.max()) if n_e > 0 else 0
+        self._factors: Dict[Tuple[str, str], Tuple] = {}
+
+    @staticmethod
+    def from_edge_index(edge_index: Tensor, n_v: Optional[int] = None, e_base: int = 0) -> "LeaveOneOutIncidence":
+        return LeaveOneOutIncidence(edge_index, n_v, e_base)
+
+    def factors(self, aggr: str, normtype: str):
+        """The :class:`LooFactors` of ``aggr`` (add | sum | mean) and ``normtype`` (all_one | deg_half_sym): what the reference
+        expresses as ``norm`` and ``aggr`` over the expanded list, as scale vectors (None where all ones).
+        ``norm_contruction('deg_half_sym')`` there is ``vdeg^-1/2[v] * row_size^-1/2[e_i]``, a product of a per-vertex and a
+        per-hyperedge factor (every e_i of one hyperedge has the same size); ``mean`` divides by the expanded hyperedge size (V->E) or
+        the expanded vertex degree (E->V).  So with a = vdeg^-1/2, b = row_size^-1/2 (ones under all_one):
+          V->E:  out[(e, i)] = b_e / |e_i| * sum_{j != i} a_{n_j} x[n_j]                         -> s_src = a, s_seg = b [/ row_size]
+          E->V:  out[v] = a_v / vdeg_v * sum_{e ni v} b_e * sum_{i != j(v, e)} y[(e, i)]         -> s_seg = b, w_v = a [/ vdeg] per incidence
+        and each direction's backward is the other's forward with the same vectors (functional.deepsets_aggregate_exclude_self)."""
+        key = (aggr, normtype)
+        hit = self._factors.get(key)
+        if hit is None:
+            if aggr not in ("add", "sum", "mean"):
+                raise NotImplementedError(f"exclude-self aggregation: aggr {aggr!r} is not built (add | sum | mean); max / min keep the "
+                                          "expansion path (preprocessing.expand_edge_index)")
+            if normtype not in ("all_one", "deg_half_sym"):
+                raise NotImplementedError(f"exclude-self aggregation: normtype {normtype!r} is not built (all_one | deg_half_sym)")
+            sym, mean = normtype == "deg_half_sym", aggr == "mean"
+            has = self.vdeg > 0                                        # (a vertex without incidence is never gathered; keep it finite)
+            a = torch.where(has, self.vdeg.pow(-0.5), torch.zeros_like(self.vdeg)) if sym else None
+            b = self.row_size.pow(-0.5) if sym else None
+            inv_deg = torch.where(has, 1.0 / self.vdeg.clamp(min=1), torch.zeros_like(self.vdeg))
+            v2e_seg = (b / self.row_size if sym else 1.0 / self.row_size) if mean else b
+            r = (a * inv_deg if sym else inv_deg) if mean else a       # per vertex, behind the vertex sum
+
+            def per_incidence(t):                                      # a row scale behind the vertex sum as segreduce weights
+                return t[self._v_of_vpos].contiguous() if t is not None else None
+            hit = self._factors[key] = LooFactors(a, v2e_seg, per_incidence(a), b, r, per_incidence(r))
+        return hit
+
+
+class LooDirection(NamedTuple):
+    """One direction of a :class:`LeaveOneOutIncidence`, as ``HalfNLHconv.forward`` takes it in place of an ``Incidence``."""
+    loo: LeaveOneOutIncidence
+    direction: str                   # 'v2e' | 'e2v'
+    normtype: str = "all_one"
+
+
+class LooFactors(NamedTuple):
+    """The scale vectors of one (aggr, normtype); None = ones.  V->E forward: ``loo_rows(s_src=v2e_src, s_seg=v2e_seg)``, its backward:
+    the vertex sum of ``loo_rows(s_seg=v2e_seg)`` weighted by ``v2e_src_inc``.  E->V forward: the vertex sum of ``loo_rows(s_seg=
+    e2v_seg)`` weighted by ``e2v_row_inc``, its backward: ``loo_rows(s_src=e2v_row, s_seg=e2v_seg)``."""
+    v2e_src: Optional[Tensor]        # f32[n_v]
+    v2e_seg: Optional[Tensor]        # f32[n_e]
+    v2e_src_inc: Optional[Tensor]    # f32[nnz], vertex-major order: v2e_src of the position's vertex
+    e2v_seg: Optional[Tensor]        # f32[n_e]
+    e2v_row: Optional[Tensor]        # f32[n_v]
+    e2v_row_inc: Optional[Tensor]    # f32[nnz], vertex-major order
+
+
+def _rowptr_of(counts: Tensor, dev) -> Tensor:
+    rowptr = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=dev)
+    if counts.numel():
+        rowptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
+    return rowptr
 
 
 # ---------------------------------------------------------------------------------------------

@@ -24,7 +24,7 @@ import torch.nn.functional as F
 
 from . import dense
 from . import functional as AF
-from .incidence import Incidence, cached_incidence
+from .incidence import Incidence, LooDirection, cached_incidence
 
 Tensor = torch.Tensor
 EdgeIndex = Union[Tensor, Incidence]
@@ -576,6 +576,20 @@ class HalfNLHconv(nn.Module):
         post = _post_dropout is not None
         if _pre_dropout and not (self.takes_pre_dropout(x) and (aggr is not None or self.attention)):
             raise ValueError("HalfNLHconv.forward(_pre_dropout=...) needs takes_pre_dropout(x)")
+        if isinstance(edge_index, LooDirection):
+            # exclude-self data kept unexpanded (preprocessing.exclude_self): leave-one-out sums over the plain incidence
+            if self.attention:
+                raise NotImplementedError("exclude-self data without the expansion is built for the Deep Sets conv only: the PMA conv "
+                                          "(attention=True, AllSetTransformer) needs a leave-one-out softmax; expand the edge list "
+                                          "with preprocessing.expand_edge_index instead")
+            if norm is not None and norm.requires_grad:
+                raise NotImplementedError("exclude-self data without the expansion takes no per-incidence weight (LearnMask is a parameter "
+                                          "per EXPANDED incidence); expand the edge list with preprocessing.expand_edge_index instead")
+            if aggr is None:
+                raise ValueError("aggr was not passed!")
+            x = self._mlp_act(self.f_enc, x, self.dropout, pre=_pre_dropout)
+            x = AF.deepsets_aggregate_exclude_self(x, edge_index.loo, edge_index.direction, aggr, edge_index.normtype)
+            return self._mlp_act(self.f_dec, x, _post_dropout if post else 0.0)
         if self.attention:
             if post and self.training:      # training: the conv's relu -> dropout rides in ln1's pass (PMA.tail)
                 return self.prop(x, edge_index, _post=float(_post_dropout), _pre=float(_pre_dropout))

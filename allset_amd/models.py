@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from torch.nn import Linear, Parameter
 
 from . import dense
-from .incidence import Incidence
+from .incidence import Incidence, LeaveOneOutIncidence, LooDirection
 from .layers import MLP, HalfNLHconv, relu_dropout
 
 
@@ -143,6 +143,25 @@ class SetGNN(nn.Module):
         self._inc_cache[key] = (weakref.ref(edge_index), (v2e, e2v))
         return v2e, e2v
 
+    def _loo_incidences(self, edge_index: torch.Tensor, n_v: int, normtype: str) -> Tuple[LooDirection, LooDirection]:
+        """The (V->E, E->V) pair for exclude-self data that kept its UNEXPANDED edge list (``preprocessing.exclude_self``): one
+        :class:`LeaveOneOutIncidence`, built on first sight of the tensor and cached exactly as ``_incidences`` caches the plain pair
+        (hyperedge ids re-based in place, as there)."""
+        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), n_v, "loo", normtype)
+        hit = self._inc_cache.get(key)
+        if hit is not None and hit[0]() is edge_index:
+            return hit[1]
+        if edge_index.numel() > 0:
+            cidx = int(edge_index[1].min())
+            if cidx != 0:
+                edge_index[1] -= cidx
+        loo = LeaveOneOutIncidence.from_edge_index(edge_index, n_v=n_v)
+        pair = (LooDirection(loo, "v2e", normtype), LooDirection(loo, "e2v", normtype))
+        self._inc_cache.clear()
+        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), n_v, "loo", normtype)
+        self._inc_cache[key] = (weakref.ref(edge_index), pair)
+        return pair
+
     def _prefetch_planes(self, x: torch.Tensor) -> None:
         """At dataset scale every launch is a link of the step's dependent chain: the fp16 plane images of all wide (256 / 512-wide)
         Linears of the convs -- W for the forward, W^T too when a backward will follow -- in one launch up front (dense.prefetch_wide_planes;
@@ -164,9 +183,17 @@ class SetGNN(nn.Module):
         """``data.x`` [n_V, F] float32, ``data.edge_index`` int64 [2, nnz] (row 0 vertex ids, row 1
         hyperedge ids), ``data.norm`` [nnz] per-incidence weights.  Returns vertex logits."""
         x, edge_index, norm = data.x, data.edge_index, data.norm
-        if self.LearnMask:
-            norm = self.Importance * norm
-        v2e, e2v = self._incidences(edge_index, x.shape[0])
+        if getattr(data, 'exclude_self', False):
+            # exclude-self data with its unexpanded edge list: leave-one-out sums (DESIGN.md section 19); the hyperedge-side
+            # activations have nnz rows, as in the expanded model, and the parameters are the expanded model's
+            if self.LearnMask:
+                raise NotImplementedError("LearnMask holds one weight per EXPANDED incidence: exclude-self data must be expanded "
+                                          "(preprocessing.expand_edge_index) for it")
+            v2e, e2v = self._loo_incidences(edge_index, x.shape[0], getattr(data, 'exclude_self_normtype', 'all_one'))
+        else:
+            if self.LearnMask:
+                norm = self.Importance * norm
+            v2e, e2v = self._incidences(edge_index, x.shape[0])
         self._prefetch_planes(x)
         if self.GPR:
             xs = [F.relu(self.MLP(x))]

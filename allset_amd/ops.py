@@ -636,6 +636,64 @@ def spgemm_bool(rowptr_a: Tensor, col_a: Tensor, rowptr_b: Tensor, col_b: Tensor
     return rowptr, col
 
 
+# ---- leave-one-out segmented sums: exclude-self aggregation without the expanded edge list (csrc/loo.hip) -------------------------
+def loo_supported(d: int) -> bool:
+    return bool(_lib.load().allset_loo_supported(int(d)))
+
+
+def loo_long_threshold() -> int:
+    """Segments longer than this are summed by a workgroup each (``long_seg`` of :func:`loo_rows` lists them)."""
+    return int(_lib.load().allset_loo_long_threshold())
+
+
+def loo_rows(rowptr: Tensor, col: Optional[Tensor], src: Tensor, s_src: Optional[Tensor] = None, s_seg: Optional[Tensor] = None,
+             long_seg: Optional[Tensor] = None, n_long: Optional[int] = None) -> Tensor:
+    """``out[p] = s_seg[g] * sum_{q in segment g, q != p} s_src[idx(q)] * src[idx(q)]`` for every position ``p`` of the CSR ``rowptr``
+    (int32[n_seg + 1]); a segment of one position keeps its own row.  ``idx(q) = col[q]`` (int32[nnz]), or ``q`` itself with
+    ``col=None`` (``src`` holds the nnz rows).  ``s_src`` f32[src rows] and ``s_seg`` f32[n_seg] are optional.  ``long_seg``: int32 ids
+    of the segments longer than :func:`loo_long_threshold` (``None``: each segment's length is looked at on the device); ``n_long=0``
+    with ``long_seg=None`` states there is none.  Returns f32 [nnz, d].  fp32 only, d % 4 == 0, d <= 512: anything else raises."""
+    dev = require_device(rowptr, col, src, s_src, s_seg, long_seg)
+    if src.dtype != torch.float32:
+        raise NotImplementedError(f"loo_rows: float32 only (got {src.dtype}); bf16 storage keeps the expansion path "
+                                  "(preprocessing.expand_edge_index)")
+    for t, what in ((rowptr, "rowptr"), (col, "col"), (long_seg, "long_seg")):
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
+            raise _lib.AllSetHipError(f"loo_rows: {what} must be a contiguous int32 vector (got {t.dtype} {tuple(t.shape)})")
+    for t, what in ((s_src, "s_src"), (s_seg, "s_seg")):
+        if t is not None:
+            _f32(t, f"loo_rows {what}")
+            if t.dim() != 1 or not t.is_contiguous():
+                raise _lib.AllSetHipError(f"loo_rows: {what} must be a contiguous vector")
+    src = _rowmajor(src)
+    n_src, d = src.shape
+    n_seg = rowptr.numel() - 1
+    if n_seg < 0:
+        raise _lib.AllSetHipError("loo_rows: an empty rowptr (a CSR of n segments has n + 1 entries)")
+    nnz = int(col.numel()) if col is not None else n_src
+    if s_src is not None and s_src.numel() < n_src:
+        raise _lib.AllSetHipError(f"loo_rows: s_src has {s_src.numel()} entries for {n_src} source rows")
+    if s_seg is not None and s_seg.numel() < n_seg:
+        raise _lib.AllSetHipError(f"loo_rows: s_seg has {s_seg.numel()} entries for {n_seg} segments")
+    if d > 0 and not loo_supported(d):
+        raise _lib.AllSetHipError(f"loo_rows: width {d} is not built (d % 4 == 0, d <= 512); there is no fallback")
+    if src.stride(0) % 4 != 0 or src.data_ptr() % 16 != 0:
+        src = src.contiguous()
+    if long_seg is not None:
+        n_long = int(long_seg.numel())
+    elif n_long is None:
+        n_long = -1
+    elif n_long != 0:
+        raise _lib.AllSetHipError("loo_rows: n_long without long_seg can only state 0")
+    out = torch.empty((nnz, d), dtype=torch.float32, device=dev)
+    algo = nnz * (2 * d * 4 + (4 if col is not None else 0) + (4 if s_src is not None else 0)) + (n_seg + 1) * 4
+    with on_device(dev), _timed("loo_rows", dev, algo):
+        check(_lib.load().allset_loo_rows(ptr(rowptr), ptr(col), ptr(src), _ld(src), ptr(s_src), ptr(s_seg), ptr(out), max(d, 1),
+                                          ptr(long_seg) if n_long > 0 else None, n_long, n_seg, n_src, nnz, d, stream_of(dev)),
+              "allset_loo_rows")
+    return out
+
+
 def gcn_norm(src: Tensor, dst: Tensor, m: Optional[Tensor], n: int) -> Tuple[Tensor, Tensor]:
     """torch_geometric 1.6.3 ``gcn_norm(edge_index, m, add_self_loops=True)`` for edges without self-loops, ids in [0, n):
     ``(edge_index int64[2, E + n] = [pairs | loops 0..n-1], w f32[E + n])``, ``w = deg^-1/2[src] * m * deg^-1/2[dst]``."""

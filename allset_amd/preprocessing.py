@@ -205,6 +205,39 @@ def expand_edge_index(data, edge_th=0):
     return data
 
 
+EXCLUDE_SELF_NORMTYPES = ('all_one', 'deg_half_sym')
+
+
+def exclude_self(data, normtype='all_one'):
+    """The exclude-self mode WITHOUT the expansion: ``data.edge_index`` (the V->E list, hyperedge ids from ``n_x``) stays as it is and
+    ``SetGNN`` (Deep Sets convs) computes what it would compute over ``expand_edge_index(data)`` with
+    ``norm_contruction(option=normtype)`` from leave-one-out sums over the plain incidence (incidence.LeaveOneOutIncidence,
+    csrc/loo.hip): O(nnz) incidences in memory and per pass instead of sum k (k - 1).  Sets ``data.exclude_self = True``,
+    ``data.exclude_self_normtype`` and ``data.norm`` = int64 ones of the unexpanded length (the normalisation of the expanded list is
+    applied inside the aggregation).  Refuses what the expansion would silently drop or what is ill-defined under it: hyperedge ids
+    outside ``[n_x, n_x + number of hyperedges)`` and repeated (vertex, hyperedge) pairs."""
+    if normtype not in EXCLUDE_SELF_NORMTYPES:
+        raise ValueError(f"exclude_self: normtype {normtype!r} is not built without the expansion ({' | '.join(EXCLUDE_SELF_NORMTYPES)})")
+    ei = data.edge_index
+    if ei.dim() != 2 or ei.shape[0] != 2 or ei.dtype != torch.int64:
+        raise ValueError(f"exclude_self: edge_index must be int64 [2, nnz], got {ei.dtype} {tuple(ei.shape)}")
+    num_nodes = _first(data.n_x)
+    num_edges = int(data.totedges) if hasattr(data, 'totedges') else _first(data.num_hyperedges)
+    if ei.shape[1] > 0:
+        v, e = ei[0], ei[1] - num_nodes
+        if int(v.min()) < 0 or int(v.max()) >= num_nodes:
+            raise ValueError(f"exclude_self: vertex ids span [{int(v.min())}, {int(v.max())}] but n_x = {num_nodes}")
+        if int(e.min()) < 0 or int(e.max()) >= num_edges:
+            raise ValueError(f"exclude_self: hyperedge ids span [{int(ei[1].min())}, {int(ei[1].max())}], outside "
+                             f"[{num_nodes}, {num_nodes + num_edges}) (expand_edge_index would drop them)")
+        if int(torch.unique(e * num_nodes + v).numel()) != ei.shape[1]:
+            raise ValueError("exclude_self: duplicate (vertex, hyperedge) incidences (coalesce the edge list first)")
+    data.exclude_self = True
+    data.exclude_self_normtype = normtype
+    data.norm = torch.ones_like(ei[0])
+    return data
+
+
 # ---- degree scales of the hypergraph-convolution baselines (HCHA / HGNN / HNHN) ---------------------------------------------------
 # Computed once, on the device the ids live on, from the [V; E] edge list (no dense incidence matrix); stored as attributes of
 # ``data``.  A reciprocal of zero is 0 (the reference's ``D[D == inf] = 0``); a power of zero with a negative exponent is inf, as in

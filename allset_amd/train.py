@@ -45,8 +45,9 @@ import torch.nn.functional as F
 from . import dense
 from ._lib import AllSetHipError
 from .models import SetGNN
-from .preprocessing import (Add_Self_Loops, ConstructH_pairs, ConstructV2V, ExtractV2E, expand_edge_index, generate_norm_HCHA,
-                            generate_norm_HNHN, generate_norm_UniGNN, norm_contruction, rebase_hyperedge_ids)
+from .preprocessing import (EXCLUDE_SELF_NORMTYPES, Add_Self_Loops, ConstructH_pairs, ConstructV2V, ExtractV2E, exclude_self,
+                            expand_edge_index, generate_norm_HCHA, generate_norm_HNHN, generate_norm_UniGNN, norm_contruction,
+                            rebase_hyperedge_ids)
 
 ALLSET_METHODS = ('AllSetTransformer', 'AllDeepSets')
 BASELINE_METHODS = ('HGNN', 'HCHA', 'HNHN')
@@ -493,6 +494,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--num_classes', default=0, type=int)
     p.add_argument('--feature_noise', default='1', type=str)
     p.add_argument('--exclude_self', action='store_true')
+    p.add_argument('--exclude_self_expand', action='store_true',
+                   help='with --exclude_self: always expand the edge list as the reference does (for comparison), also where the '
+                        'leave-one-out kernels would run (--method AllDeepSets)')
     p.add_argument('--PMA', action='store_true')
     p.add_argument('--heads', default=1, type=int)
     p.add_argument('--output_heads', default=1, type=int)
@@ -606,8 +610,25 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
     if args.add_self_loop:
         data = Add_Self_Loops(data)
     if args.exclude_self:
+        if exclude_self_path(args) == 'loo':                # the edge list stays unexpanded
+            return exclude_self(data, normtype=args.normtype)
         data = expand_edge_index(data)
     return norm_contruction(data, option=args.normtype)
+
+
+def exclude_self_path(args) -> str:
+    """How ``--exclude_self`` runs: ``'loo'`` -- leave-one-out sums over the unexpanded edge list (csrc/loo.hip) -- for
+    ``--method AllDeepSets`` with ``--normtype`` all_one / deg_half_sym, no LearnMask and aggregated widths the kernel is built for;
+    ``'expand'`` -- the reference's expansion (``expand_edge_index``), unchanged -- for everything else (AllSetTransformer, the flag's
+    default method, among it) and under ``--exclude_self_expand``."""
+    if getattr(args, 'exclude_self_expand', False) or args.method != 'AllDeepSets' or args.LearnMask:
+        return 'expand'
+    if args.normtype not in EXCLUDE_SELF_NORMTYPES:
+        return 'expand'
+    from . import ops
+    # what a Deep Sets conv aggregates: f_enc's output (MLP_hidden), or with MLP_num_layers = 0 (identities) its input
+    widths = {int(args.MLP_hidden)} if int(args.MLP_num_layers) > 0 else {int(args.MLP_hidden), int(args.num_features)}
+    return 'loo' if all(w > 0 and ops.loo_supported(w) for w in widths) else 'expand'
 
 
 def run(args) -> dict:

@@ -1068,6 +1068,28 @@ int allset_spgemm_bool_fill(const int32_t* rowptrA, const int32_t* colA, const i
                             int64_t n_b, int64_t n_c, const int32_t* rowptrC, int64_t nnz_c, int32_t* colC, const void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Leave-one-out segmented sums (csrc/loo.hip): the reference's --exclude_self mode (preprocessing.py:22-144 expand_edge_index, every
+ * hyperedge of size k as k hyperedges of size k - 1) without the expanded edge list.  Added under ABI 15, additions only; detect with
+ * allset_loo_supported(d) (1 for d % 4 == 0, 0 < d <= 512).  fp32, row-major, int32 CSR.  No atomics, no allocation, no sync.
+ *
+ * allset_loo_rows: for every position p of every segment g of the CSR (rowptr int32[n_seg + 1], rowptr[n_seg] == nnz), of k positions,
+ *   out[p, :] = s_seg[g] * sum_{q in g, q != p} s_src[idx(q)] * src[idx(q), :]     (k > 1)
+ *   out[p, :] = s_seg[g] * s_src[idx(p)] * src[idx(p), :]                          (k == 1: a singleton keeps its member)
+ * idx(q) = col[q], or q itself when col is NULL (the source rows are the nnz contiguous rows; n_src >= nnz).  s_src f32[n_src] and
+ * s_seg f32[n_seg] may be NULL (ones).  out f32[nnz, ldo]; an empty segment writes nothing.  src and out 16-byte aligned, lds and ldo
+ * multiples of 4, out distinct from src.  Every output is the sum of the k - 1 terms it names (an exclusive prefix plus an exclusive
+ * suffix, never "total minus own row"): its error is bounded relative to those terms.
+ * Segments longer than allset_loo_long_threshold() are summed by a workgroup each: long_seg int32[n_long] lists them (every one of
+ * them; a listed shorter one is skipped); n_long == 0 states that there is none (a longer one is then summed by one wave: correct, slow);
+ * n_long < 0: not known -- one workgroup per segment looks at its length (long_seg is not read).
+ * ------------------------------------------------------------------------------------------- */
+int allset_loo_supported(int64_t d);
+int allset_loo_long_threshold(void);
+int allset_loo_rows(const int32_t* rowptr, const int32_t* col, const float* src, int64_t lds, const float* s_src, const float* s_seg,
+                    float* out, int64_t ldo, const int32_t* long_seg, int64_t n_long, int64_t n_seg, int64_t n_src, int64_t nnz,
+                    int64_t d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
