@@ -297,6 +297,13 @@ SIGNATURES = {
     "allset_loo_supported": [c_int64],
     "allset_loo_long_threshold": [],
     "allset_loo_rows": [_P, _P, _P, c_int64, _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _P],
+    # leave-one-out softmax: the exclude-self PMA pooling without the expanded edge list (under ABI 15, additions only; detect with
+    # allset_loo_softmax_supported)
+    "allset_loo_softmax_supported": [c_int64, c_int64],
+    "allset_loo_softmax_fwd": [_P, _P, _P, _P, c_int64, c_float, _P, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int64,
+                               c_int64, _P],
+    "allset_loo_softmax_bwd": [_P, _P, _P, _P, c_int64, c_float, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P, c_int64,
+                               c_int64, c_int64, c_int64, c_int64, c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

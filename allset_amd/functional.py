@@ -428,6 +428,107 @@ def pma_attention_weights(alpha: Tensor, m: Tensor, l: Tensor, inc: Incidence, n
     return p
 
 
+# ---- exclude-self PMA pooling over the UNEXPANDED incidence (csrc/loo_softmax.hip; DESIGN.md section 20) ----------------------------
+def _loo_long(loo: LeaveOneOutIncidence) -> dict:
+    return dict(long_seg=loo.long_seg if loo.n_long else None, n_long=loo.n_long)
+
+
+class _LooSoftmaxV2E(torch.autograd.Function):
+    """[vertices] -> [nnz]: row (e, i) = the softmax pooling of e's members other than the i-th.  Backward: the per-position gradients
+    of the leave-one-out softmax, summed per vertex by ``segreduce`` over the vertex-major CSR (as ``_loo_collect`` does)."""
+
+    @staticmethod
+    def forward(ctx, V: Tensor, alpha: Tensor, loo: LeaveOneOutIncidence, heads: int, slope: float):
+        out, lse = ops.loo_softmax_fwd(loo.e_rowptr, loo.e_col, alpha, V, heads, slope, **_loo_long(loo))
+        ctx.loo, ctx.heads, ctx.slope = loo, heads, slope
+        ctx.save_for_backward(V, alpha, out, lse)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout: Tensor):
+        V, alpha, out, lse = ctx.saved_tensors
+        loo = ctx.loo
+        gV_pos, ga_pos = ops.loo_softmax_bwd(loo.e_rowptr, loo.e_col, alpha, V, ctx.heads, ctx.slope, out, lse, gout.contiguous(), None,
+                                             **_loo_long(loo))
+        gV, _ = ops.segreduce(SUM, loo.v_rowptr, loo.v_col, None, gV_pos, V.shape[0])
+        galpha, _ = ops.segreduce(SUM, loo.v_rowptr, loo.v_col, None, ga_pos, V.shape[0])
+        return gV, galpha, None, None, None
+
+
+class _LooSoftmaxStates(torch.autograd.Function):
+    """Stage 1 of E->V: the nnz contiguous hyperedge-side rows -> per position the normalised softmax state ``(o, L)`` of "every row of
+    its hyperedge but its own".  Takes both cotangents (stage 2, the ordinary pooling with logits ``L``, supplies them)."""
+
+    @staticmethod
+    def forward(ctx, V: Tensor, alpha: Tensor, loo: LeaveOneOutIncidence, heads: int, slope: float):
+        out, lse = ops.loo_softmax_fwd(loo.e_rowptr, None, alpha, V, heads, slope, **_loo_long(loo))
+        ctx.loo, ctx.heads, ctx.slope = loo, heads, slope
+        ctx.save_for_backward(V, alpha, out, lse)
+        ctx.set_materialize_grads(False)
+        return out, lse
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout: Optional[Tensor], glse: Optional[Tensor]):
+        if gout is None and glse is None:
+            return None, None, None, None, None
+        V, alpha, out, lse = ctx.saved_tensors
+        loo = ctx.loo
+        gout = torch.zeros_like(out) if gout is None else gout.contiguous()
+        gV, galpha = ops.loo_softmax_bwd(loo.e_rowptr, None, alpha, V, ctx.heads, ctx.slope, out, lse, gout,
+                                         glse.contiguous() if glse is not None else None, **_loo_long(loo))
+        return gV, galpha, None, None, None
+
+
+def pma_exclude_self_states(V: Tensor, alpha: Tensor, loo: LeaveOneOutIncidence, heads: int, negative_slope: float = 0.2
+                            ) -> Tuple[Tensor, Tensor]:
+    """Stage 1 of the exclude-self E->V pooling: ``V`` [nnz, heads*C], ``alpha`` [nnz, heads] (the hyperedge-side rows, one per
+    incidence) -> ``(o [nnz, heads*C], L [nnz, heads])``, per position the softmax pooling of the OTHER rows of its hyperedge and the
+    log of its normaliser.  Pooling ``o`` with logits ``L`` (slope 1) over ``loo.merge_incidence()`` completes the direction."""
+    _check_exclude_self_pma(V, alpha, heads)
+    if V.shape[0] != loo.nnz:
+        raise ValueError(f"hyperedge-side matrix has {V.shape[0]} rows; the exclude-self incidence has {loo.nnz} (one per incidence)")
+    return _LooSoftmaxStates.apply(V, alpha, loo, int(heads), float(negative_slope))
+
+
+def _check_exclude_self_pma(V: Tensor, alpha: Tensor, heads: int) -> None:
+    _lib.require_device(V, alpha)
+    if V.dtype != torch.float32 or alpha.dtype != torch.float32:
+        raise NotImplementedError(f"exclude-self PMA pooling: float32 only (got V {V.dtype}, alpha {alpha.dtype}); bf16 storage keeps the "
+                                  "expansion path (preprocessing.expand_edge_index)")
+    if V.dim() != 2 or alpha.dim() != 2 or alpha.shape[0] != V.shape[0] or alpha.shape[1] != heads:
+        raise ValueError(f"V must be [n, heads*C] and alpha [n, heads]; got {tuple(V.shape)} and {tuple(alpha.shape)} for {heads} heads")
+    if not ops.loo_softmax_supported(V.shape[1], heads):
+        raise _lib.AllSetHipError(f"exclude-self PMA pooling: d = {V.shape[1]} with {heads} heads is not built (heads 1 | 2 | 4 | 8, "
+                                  "(d / heads) % 4 == 0, d <= 512); expand the edge list with preprocessing.expand_edge_index instead")
+
+
+def pma_aggregate_exclude_self(V: Tensor, alpha: Tensor, loo: LeaveOneOutIncidence, direction: str, heads: int,
+                               negative_slope: float = 0.2) -> Tensor:
+    """``pma_aggregate`` over the reference's exclude-self expansion (``preprocessing.expand_edge_index``) computed from the UNEXPANDED
+    incidence ``loo`` (a leave-one-out softmax):
+
+    ``direction='v2e'``: ``V`` [n_v, heads*C], ``alpha`` [n_v, heads] -> [nnz, heads*C], row (e, i) = the pooling of e's members other
+    than the i-th;
+    ``direction='e2v'``: ``V`` [nnz, heads*C], ``alpha`` [nnz, heads] -> [loo.n_dst, heads*C], row v = the pooling of every (e, i) with v
+    in e and v not e's i-th member: per hyperedge the state of "all rows but v's own", then the merge of v's states (``pma_aggregate``
+    with the states' log-normalisers as logits).
+
+    A singleton hyperedge keeps its member, as in the reference.  Differentiable in ``V`` and ``alpha``.  fp32, heads 1 | 2 | 4 | 8,
+    C % 4 == 0, d <= 512; anything else raises (bf16 storage and LearnMask keep the expansion path)."""
+    if direction not in ("v2e", "e2v"):
+        raise ValueError(f"pma_aggregate_exclude_self: direction must be 'v2e' or 'e2v', got {direction!r}")
+    if direction == "v2e":
+        _check_exclude_self_pma(V, alpha, heads)
+        if not (loo.n_dst <= V.shape[0] <= loo.n_v):
+            raise ValueError(f"vertex matrix has {V.shape[0]} rows; the incidence needs between {loo.n_dst} and {loo.n_v}")
+        return _LooSoftmaxV2E.apply(V, alpha, loo, int(heads), float(negative_slope))
+    o, L = pma_exclude_self_states(V, alpha, loo, heads, negative_slope)
+    out, _, _ = pma_aggregate(o, L, loo.merge_incidence(), heads, 1.0)
+    return out
+
+
 # ---- degree-scaled propagate of the hypergraph-convolution baselines (HCHA / HGNN / HNHN; csrc/hconv.hip) ----------------------
 class _ScaledPropagate(torch.autograd.Function):
     """``y = drop_p(act(s * (H^T or H)(r * x) + bias))`` -- one kernel forward; backward: the epilogue's kernel (only when there is

@@ -242,6 +242,15 @@ class LeaveOneOutIncidence:
     def from_edge_index(edge_index: Tensor, n_v: Optional[int] = None, e_base: int = 0) -> "LeaveOneOutIncidence":
         return LeaveOneOutIncidence(edge_index, n_v, e_base)
 
+    def merge_incidence(self) -> Incidence:
+        """The vertex-major CSR as an :class:`Incidence` position -> vertex (``n_src`` = nnz, ``n_dst`` = this structure's): what the
+        second stage of the exclude-self PMA E->V direction pools over (functional.pma_aggregate_exclude_self).  Built on first use
+        (device tensors only) and kept."""
+        if getattr(self, "_merge_inc", None) is None:
+            pairs = torch.stack([self.v_col.long(), self._v_of_vpos])
+            self._merge_inc = Incidence.from_edge_index(pairs, n_src=self.nnz, n_dst=self.n_dst)
+        return self._merge_inc
+
     def factors(self, aggr: str, normtype: str):
         """The :class:`LooFactors` of ``aggr`` (add | sum | mean) and ``normtype`` (all_one | deg_half_sym): what the reference
         expresses as ``norm`` and ``aggr`` over the expanded list, as scale vectors (None where all ones).
@@ -278,6 +287,7 @@ class LooDirection(NamedTuple):
     loo: LeaveOneOutIncidence
     direction: str                   # 'v2e' | 'e2v'
     normtype: str = "all_one"
+    attention: bool = False          # the PMA conv may take it (preprocessing.exclude_self(..., attention=True))
 
 
 class LooFactors(NamedTuple):

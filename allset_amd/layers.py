@@ -499,23 +499,26 @@ class PMA(nn.Module):
                 and self.att_r.dtype == torch.float32
                 and dense.pma_tail_supported(pooled, self.heads * self.hidden, ff.lins[0].weight, ff.lins[1].weight))
 
-    def pool_tail(self, x_V: Tensor, alpha_r: Tensor, inc: Incidence, _post: Optional[float] = None):
-        """``tail(pool(x_V, alpha_r))`` plus the softmax statistics: ``(out [n_t, H*C], m, l)`` (reference layers.py:145-157)."""
+    def pool_tail(self, x_V: Tensor, alpha_r: Tensor, inc: Incidence, _post: Optional[float] = None, _slope: Optional[float] = None):
+        """``tail(pool(x_V, alpha_r))`` plus the softmax statistics: ``(out [n_t, H*C], m, l)`` (reference layers.py:145-157).
+        ``_slope`` (internal): the leaky-relu slope of the logits when it is not the layer's (1.0: logits taken as they are, the
+        merge of softmax states in ``forward_exclude_self``)."""
         H = self.heads
+        slope = self.negative_slope if _slope is None else float(_slope)
         hip = _on_hip(x_V) or (x_V.is_cuda and x_V.dtype == torch.bfloat16 and self.ln0.weight.dtype == torch.bfloat16
                                and self.att_r.dtype == torch.bfloat16)
         if _on_hip(x_V) and AF.pma_pool_ln0_supported(x_V, H) and self._tail_fused(x_V):
             ff = self.rFF
-            return AF.pma_pool_tail(x_V, alpha_r, inc, H, self.negative_slope, self.att_r, self.ln0.weight, self.ln0.bias, self.ln0.eps,
+            return AF.pma_pool_tail(x_V, alpha_r, inc, H, slope, self.att_r, self.ln0.weight, self.ln0.bias, self.ln0.eps,
                                     ff.lins[0].weight, ff.lins[0].bias, ff.lins[1].weight, ff.lins[1].bias, self.ln1.weight, self.ln1.bias,
                                     self.ln1.eps, _post is not None, float(_post or 0.0) if self.training else 0.0)
         if (hip and self.ln0.bias is not None and self.ln1.bias is not None and self.ln0.elementwise_affine
                 and AF.pma_pool_ln0_supported(x_V, H)):
             # pooling + seed add + ln0 as one autograd node: the pooling's backward statistics come out of ln0's backward pass
-            out, m, l = AF.pma_pool_ln0(x_V, alpha_r, inc, H, self.negative_slope, self.att_r, self.ln0.weight, self.ln0.bias,
+            out, m, l = AF.pma_pool_ln0(x_V, alpha_r, inc, H, slope, self.att_r, self.ln0.weight, self.ln0.bias,
                                         self.ln0.eps)
             return self.tail(out, _post, _ln0_done=True), m, l
-        out, m, l = AF.pma_aggregate(x_V, alpha_r, inc, H, self.negative_slope)
+        out, m, l = AF.pma_aggregate(x_V, alpha_r, inc, H, slope)
         return self.tail(out, _post), m, l
 
     def forward(self, x, edge_index: EdgeIndex, size=None, return_attention_weights=None, _post: Optional[float] = None,
@@ -528,6 +531,19 @@ class PMA(nn.Module):
         if isinstance(return_attention_weights, bool):
             alpha = AF.pma_attention_weights(alpha_r, m, l, inc, self.negative_slope)
             return out, (edge_index, alpha)
+        return out
+
+    def forward_exclude_self(self, x, loo_dir: LooDirection, _post: Optional[float] = None, _pre: float = 0.0):
+        """The layer over the reference's exclude-self expansion, from the UNEXPANDED incidence: project -> the
+        leave-one-out softmax pooling -> tail.  V->E: one output row per incidence.  E->V: per position the softmax state of its
+        hyperedge's other rows, then the ordinary pooling (+ tail, fused where ``pool_tail`` fuses it) merges each vertex's states."""
+        assert x.dim() == 2, 'Static graphs not supported in `GATConv`.'
+        loo, H = loo_dir.loo, self.heads
+        x_V, alpha_r = self.project(x, _pre)
+        if loo_dir.direction == "v2e":
+            return self.tail(AF.pma_aggregate_exclude_self(x_V, alpha_r, loo, "v2e", H, self.negative_slope), _post)
+        o, L = AF.pma_exclude_self_states(x_V, alpha_r, loo, H, self.negative_slope)
+        out, _, _ = self.pool_tail(o, L, loo.merge_incidence(), _post, _slope=1.0)
         return out
 
     def __repr__(self):
@@ -579,9 +595,19 @@ class HalfNLHconv(nn.Module):
         if isinstance(edge_index, LooDirection):
             # exclude-self data kept unexpanded (preprocessing.exclude_self): leave-one-out sums over the plain incidence
             if self.attention:
-                raise NotImplementedError("exclude-self data without the expansion is built for the Deep Sets conv only: the PMA conv "
-                                          "(attention=True, AllSetTransformer) needs a leave-one-out softmax; expand the edge list "
-                                          "with preprocessing.expand_edge_index instead")
+                if not edge_index.attention:
+                    raise NotImplementedError("exclude-self data without the expansion reaches the PMA conv (attention=True, "
+                                              "AllSetTransformer) only when asked for: preprocessing.exclude_self(data, normtype, "
+                                              "attention=True) takes the leave-one-out softmax; or expand the edge list with "
+                                              "preprocessing.expand_edge_index instead")
+                if norm is not None and norm.requires_grad:
+                    raise NotImplementedError("exclude-self data without the expansion takes no per-incidence weight (LearnMask is a "
+                                              "parameter per EXPANDED incidence); expand the edge list with "
+                                              "preprocessing.expand_edge_index instead")
+                if post and self.training:  # training: the conv's relu -> dropout rides in ln1's pass (PMA.tail)
+                    return self.prop.forward_exclude_self(x, edge_index, _post=float(_post_dropout), _pre=float(_pre_dropout))
+                x = self.prop.forward_exclude_self(x, edge_index, _pre=float(_pre_dropout))
+                return relu_dropout(x, _post_dropout, self.training) if post else x
             if norm is not None and norm.requires_grad:
                 raise NotImplementedError("exclude-self data without the expansion takes no per-incidence weight (LearnMask is a parameter "
                                           "per EXPANDED incidence); expand the edge list with preprocessing.expand_edge_index instead")

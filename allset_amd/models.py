@@ -143,11 +143,12 @@ class SetGNN(nn.Module):
         self._inc_cache[key] = (weakref.ref(edge_index), (v2e, e2v))
         return v2e, e2v
 
-    def _loo_incidences(self, edge_index: torch.Tensor, n_v: int, normtype: str) -> Tuple[LooDirection, LooDirection]:
+    def _loo_incidences(self, edge_index: torch.Tensor, n_v: int, normtype: str, attention: bool = False
+                        ) -> Tuple[LooDirection, LooDirection]:
         """The (V->E, E->V) pair for exclude-self data that kept its UNEXPANDED edge list (``preprocessing.exclude_self``): one
         :class:`LeaveOneOutIncidence`, built on first sight of the tensor and cached exactly as ``_incidences`` caches the plain pair
         (hyperedge ids re-based in place, as there)."""
-        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), n_v, "loo", normtype)
+        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), n_v, "loo", normtype, attention)
         hit = self._inc_cache.get(key)
         if hit is not None and hit[0]() is edge_index:
             return hit[1]
@@ -156,9 +157,11 @@ class SetGNN(nn.Module):
             if cidx != 0:
                 edge_index[1] -= cidx
         loo = LeaveOneOutIncidence.from_edge_index(edge_index, n_v=n_v)
-        pair = (LooDirection(loo, "v2e", normtype), LooDirection(loo, "e2v", normtype))
+        if attention and edge_index.is_cuda:
+            loo.merge_incidence()                                  # (its one-time host syncs happen here, not inside a captured forward)
+        pair = (LooDirection(loo, "v2e", normtype, attention), LooDirection(loo, "e2v", normtype, attention))
         self._inc_cache.clear()
-        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), n_v, "loo", normtype)
+        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), n_v, "loo", normtype, attention)
         self._inc_cache[key] = (weakref.ref(edge_index), pair)
         return pair
 
@@ -189,7 +192,8 @@ class SetGNN(nn.Module):
             if self.LearnMask:
                 raise NotImplementedError("LearnMask holds one weight per EXPANDED incidence: exclude-self data must be expanded "
                                           "(preprocessing.expand_edge_index) for it")
-            v2e, e2v = self._loo_incidences(edge_index, x.shape[0], getattr(data, 'exclude_self_normtype', 'all_one'))
+            v2e, e2v = self._loo_incidences(edge_index, x.shape[0], getattr(data, 'exclude_self_normtype', 'all_one'),
+                                            bool(getattr(data, 'exclude_self_attention', False)))
         else:
             if self.LearnMask:
                 norm = self.Importance * norm

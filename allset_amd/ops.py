@@ -694,6 +694,89 @@ def loo_rows(rowptr: Tensor, col: Optional[Tensor], src: Tensor, s_src: Optional
     return out
 
 
+# ---- leave-one-out softmax: the exclude-self PMA pooling without the expanded edge list (csrc/loo_softmax.hip) --------------------
+def loo_softmax_supported(d: int, heads: int) -> bool:
+    return bool(_lib.load().allset_loo_softmax_supported(int(d), int(heads)))
+
+
+def _loo_softmax_args(who: str, rowptr: Tensor, col: Optional[Tensor], alpha: Tensor, V: Tensor, heads: int, long_seg: Optional[Tensor],
+                      n_long: Optional[int], extra: Tuple[Optional[Tensor], ...] = ()):
+    """The checks both passes share; returns (device, V row-major and aligned, n_seg, n_src, nnz, d, n_long)."""
+    dev = require_device(rowptr, col, alpha, V, long_seg, *extra)
+    if V.dtype != torch.float32 or alpha.dtype != torch.float32:
+        raise NotImplementedError(f"{who}: float32 only (got V {V.dtype}, alpha {alpha.dtype}); bf16 storage keeps the expansion path "
+                                  "(preprocessing.expand_edge_index)")
+    for t, what in ((rowptr, "rowptr"), (col, "col"), (long_seg, "long_seg")):
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
+            raise _lib.AllSetHipError(f"{who}: {what} must be a contiguous int32 vector (got {t.dtype} {tuple(t.shape)})")
+    V = _rowmajor(V)
+    n_src, d = V.shape
+    heads = int(heads)
+    n_seg = rowptr.numel() - 1
+    if n_seg < 0:
+        raise _lib.AllSetHipError(f"{who}: an empty rowptr (a CSR of n segments has n + 1 entries)")
+    if heads < 1 or alpha.dim() != 2 or tuple(alpha.shape) != (n_src, heads):
+        raise _lib.AllSetHipError(f"{who}: alpha must be [{n_src}, {heads}] (one logit per source row and head), got {tuple(alpha.shape)}")
+    if d > 0 and not loo_softmax_supported(d, heads):
+        raise _lib.AllSetHipError(f"{who}: d = {d} with {heads} heads is not built (heads 1 | 2 | 4 | 8, (d / heads) % 4 == 0, d <= 512); "
+                                  "there is no fallback")
+    if V.stride(0) % 4 != 0 or V.data_ptr() % 16 != 0:
+        V = V.contiguous()
+    nnz = int(col.numel()) if col is not None else n_src
+    if long_seg is not None:
+        n_long = int(long_seg.numel())
+    elif n_long is None:
+        n_long = -1
+    elif n_long != 0:
+        raise _lib.AllSetHipError(f"{who}: n_long without long_seg can only state 0")
+    return dev, V, n_seg, n_src, nnz, d, n_long
+
+
+def loo_softmax_fwd(rowptr: Tensor, col: Optional[Tensor], alpha: Tensor, V: Tensor, heads: int, negative_slope: float = 0.2,
+                    long_seg: Optional[Tensor] = None, n_long: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """Leave-one-out softmax pooling: for every position ``p`` of every segment of the CSR ``rowptr`` and every head ``h``, with
+    ``a_q = leaky_relu(alpha[idx(q), h])``, ``out[p, h] = sum_{q != p} exp(a_q) V[idx(q), h] / Z_p`` and ``lse[p, h] = log Z_p``,
+    ``Z_p = sum_{q != p} exp(a_q)``; a segment of one position keeps its row (``out = V[idx(p)]``, ``lse = a_p``).  ``idx(q) =
+    col[q]``, or ``q`` itself with ``col=None``.  ``long_seg`` / ``n_long`` as for :func:`loo_rows`.  Returns ``(out f32[nnz, d], lse
+    f32[nnz, heads])``.  fp32, heads 1 | 2 | 4 | 8, (d / heads) % 4 == 0, d <= 512: anything else raises."""
+    dev, V, n_seg, n_src, nnz, d, n_long = _loo_softmax_args("loo_softmax_fwd", rowptr, col, alpha, V, heads, long_seg, n_long)
+    alpha = alpha.contiguous()
+    out = torch.empty((nnz, d), dtype=torch.float32, device=dev)
+    lse = torch.empty((nnz, int(heads)), dtype=torch.float32, device=dev)
+    algo = nnz * ((2 * d + 2 * int(heads)) * 4 + (4 if col is not None else 0)) + (n_seg + 1) * 4
+    with on_device(dev), _timed("loo_softmax_fwd", dev, algo):
+        check(_lib.load().allset_loo_softmax_fwd(ptr(rowptr), ptr(col), ptr(alpha), ptr(V), _ld(V), float(negative_slope), ptr(out),
+                                                 max(d, 1), ptr(lse), ptr(long_seg) if n_long > 0 else None, n_long, n_seg, n_src, nnz,
+                                                 d, int(heads), stream_of(dev)), "allset_loo_softmax_fwd")
+    return out, lse
+
+
+def loo_softmax_bwd(rowptr: Tensor, col: Optional[Tensor], alpha: Tensor, V: Tensor, heads: int, negative_slope: float, out: Tensor,
+                    lse: Tensor, gout: Tensor, glse: Optional[Tensor] = None, long_seg: Optional[Tensor] = None,
+                    n_long: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """The backward of :func:`loo_softmax_fwd` PER POSITION: ``(gV_pos f32[nnz, d], galpha_pos f32[nnz, heads])``, the gradients that
+    reach ``V[idx(q)]`` and ``alpha[idx(q)]`` through position ``q`` (with ``col`` the caller sums the positions of a source row).
+    ``out`` / ``lse``: the forward's results; ``gout`` [nnz, d] and ``glse`` [nnz, heads] (``None``: zeros) their cotangents."""
+    dev, V, n_seg, n_src, nnz, d, n_long = _loo_softmax_args("loo_softmax_bwd", rowptr, col, alpha, V, heads, long_seg, n_long,
+                                                             (out, lse, gout, glse))
+    H = int(heads)
+    for t, what, shape in ((out, "out", (nnz, d)), (gout, "gout", (nnz, d)), (lse, "lse", (nnz, H)), (glse, "glse", (nnz, H))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape):
+            raise _lib.AllSetHipError(f"loo_softmax_bwd: {what} must be float32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    alpha, out, gout, lse = alpha.contiguous(), out.contiguous(), gout.contiguous(), lse.contiguous()
+    glse = glse.contiguous() if glse is not None else None
+    gV = torch.empty((nnz, d), dtype=torch.float32, device=dev)
+    galpha = torch.empty((nnz, H), dtype=torch.float32, device=dev)
+    scratch = torch.empty((nnz, H, 2), dtype=torch.float32, device=dev)          # parked suffix states of runs longer than a tile
+    algo = nnz * ((4 * d + (4 if glse is not None else 3) * H) * 4 + (4 if col is not None else 0)) + (n_seg + 1) * 4
+    with on_device(dev), _timed("loo_softmax_bwd", dev, algo):
+        check(_lib.load().allset_loo_softmax_bwd(ptr(rowptr), ptr(col), ptr(alpha), ptr(V), _ld(V), float(negative_slope), ptr(out),
+                                                 max(d, 1), ptr(lse), ptr(gout), max(d, 1), ptr(glse), ptr(gV), max(d, 1), ptr(galpha),
+                                                 ptr(scratch), ptr(long_seg) if n_long > 0 else None, n_long, n_seg, n_src, nnz, d, H,
+                                                 stream_of(dev)), "allset_loo_softmax_bwd")
+    return gV, galpha
+
+
 def gcn_norm(src: Tensor, dst: Tensor, m: Optional[Tensor], n: int) -> Tuple[Tensor, Tensor]:
     """torch_geometric 1.6.3 ``gcn_norm(edge_index, m, add_self_loops=True)`` for edges without self-loops, ids in [0, n):
     ``(edge_index int64[2, E + n] = [pairs | loops 0..n-1], w f32[E + n])``, ``w = deg^-1/2[src] * m * deg^-1/2[dst]``."""

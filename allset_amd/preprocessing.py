@@ -208,13 +208,15 @@ def expand_edge_index(data, edge_th=0):
 EXCLUDE_SELF_NORMTYPES = ('all_one', 'deg_half_sym')
 
 
-def exclude_self(data, normtype='all_one'):
+def exclude_self(data, normtype='all_one', attention=False):
     """The exclude-self mode WITHOUT the expansion: ``data.edge_index`` (the V->E list, hyperedge ids from ``n_x``) stays as it is and
     ``SetGNN`` (Deep Sets convs) computes what it would compute over ``expand_edge_index(data)`` with
     ``norm_contruction(option=normtype)`` from leave-one-out sums over the plain incidence (incidence.LeaveOneOutIncidence,
     csrc/loo.hip): O(nnz) incidences in memory and per pass instead of sum k (k - 1).  Sets ``data.exclude_self = True``,
     ``data.exclude_self_normtype`` and ``data.norm`` = int64 ones of the unexpanded length (the normalisation of the expanded list is
-    applied inside the aggregation).  Refuses what the expansion would silently drop or what is ill-defined under it: hyperedge ids
+    applied inside the aggregation).  ``attention=True`` (sets ``data.exclude_self_attention``) lets the PMA convs of AllSetTransformer take
+    the data too -- a leave-one-out softmax (csrc/loo_softmax.hip; PMA ignores ``norm``, so ``normtype`` plays no part there);
+    without it a PMA conv refuses unexpanded data.  Refuses what the expansion would silently drop or what is ill-defined under it: hyperedge ids
     outside ``[n_x, n_x + number of hyperedges)`` and repeated (vertex, hyperedge) pairs."""
     if normtype not in EXCLUDE_SELF_NORMTYPES:
         raise ValueError(f"exclude_self: normtype {normtype!r} is not built without the expansion ({' | '.join(EXCLUDE_SELF_NORMTYPES)})")
@@ -234,6 +236,7 @@ def exclude_self(data, normtype='all_one'):
             raise ValueError("exclude_self: duplicate (vertex, hyperedge) incidences (coalesce the edge list first)")
     data.exclude_self = True
     data.exclude_self_normtype = normtype
+    data.exclude_self_attention = bool(attention)
     data.norm = torch.ones_like(ei[0])
     return data
 

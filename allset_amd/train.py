@@ -497,6 +497,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--exclude_self_expand', action='store_true',
                    help='with --exclude_self: always expand the edge list as the reference does (for comparison), also where the '
                         'leave-one-out kernels would run (--method AllDeepSets)')
+    p.add_argument('--exclude_self_loo_attention', action='store_true',
+                   help='with --exclude_self --method AllSetTransformer: keep the edge list unexpanded and pool with the leave-one-out '
+                        'softmax (DESIGN.md section 20) where it is built; without this flag the method expands, as before')
     p.add_argument('--PMA', action='store_true')
     p.add_argument('--heads', default=1, type=int)
     p.add_argument('--output_heads', default=1, type=int)
@@ -611,6 +614,8 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
         data = Add_Self_Loops(data)
     if args.exclude_self:
         if exclude_self_path(args) == 'loo':                # the edge list stays unexpanded
+            if args.method == 'AllSetTransformer':             # (PMA ignores norm: any --normtype)
+                return exclude_self(data, attention=True)
             return exclude_self(data, normtype=args.normtype)
         data = expand_edge_index(data)
     return norm_contruction(data, option=args.normtype)
@@ -619,9 +624,18 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
 def exclude_self_path(args) -> str:
     """How ``--exclude_self`` runs: ``'loo'`` -- leave-one-out sums over the unexpanded edge list (csrc/loo.hip) -- for
     ``--method AllDeepSets`` with ``--normtype`` all_one / deg_half_sym, no LearnMask and aggregated widths the kernel is built for;
-    ``'expand'`` -- the reference's expansion (``expand_edge_index``), unchanged -- for everything else (AllSetTransformer, the flag's
-    default method, among it) and under ``--exclude_self_expand``."""
-    if getattr(args, 'exclude_self_expand', False) or args.method != 'AllDeepSets' or args.LearnMask:
+    and, with ``--exclude_self_loo_attention``, for ``--method AllSetTransformer`` at the widths and head counts the leave-one-out
+    softmax is built for (csrc/loo_softmax.hip); ``'expand'`` -- the reference's expansion (``expand_edge_index``), unchanged -- for
+    everything else (AllSetTransformer without that flag, the default method, among it) and under ``--exclude_self_expand``."""
+    if getattr(args, 'exclude_self_expand', False) or args.LearnMask:
+        return 'expand'
+    if args.method == 'AllSetTransformer' and getattr(args, 'exclude_self_loo_attention', False):
+        # the PMA convs pool MLP_hidden-wide rows with args.heads heads and ignore norm (so any normtype); GPR keeps the expansion
+        if getattr(args, 'GPR', False):
+            return 'expand'
+        from . import ops
+        return 'loo' if ops.loo_softmax_supported(int(args.MLP_hidden), int(args.heads)) else 'expand'
+    if args.method != 'AllDeepSets':
         return 'expand'
     if args.normtype not in EXCLUDE_SELF_NORMTYPES:
         return 'expand'

@@ -1090,6 +1090,34 @@ int allset_loo_rows(const int32_t* rowptr, const int32_t* col, const float* src,
                     float* out, int64_t ldo, const int32_t* long_seg, int64_t n_long, int64_t n_seg, int64_t n_src, int64_t nnz,
                     int64_t d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Leave-one-out softmax (csrc/loo_softmax.hip): the PMA (AllSetTransformer) pooling over the exclude-self expansion without the
+ * expanded edge list.  Added under ABI 15, additions only; detect with allset_loo_softmax_supported(d, heads) (1 for heads in
+ * {1, 2, 4, 8}, (d / heads) % 4 == 0, 0 < d <= 512).  fp32, row-major, int32 CSR.  No atomics, no allocation, no sync.
+ *
+ * With a_q = leaky_relu(alpha[idx(q), h], slope), v_q = V[idx(q), h*C .. (h+1)*C), idx(q) = col[q] or q itself when col is NULL, for
+ * every position p of every segment of k positions and every head h:
+ *   out[p, h, :] = sum_{q != p} exp(a_q) v_q / Z_p,   lse[p, h] = log Z_p,   Z_p = sum_{q != p} exp(a_q)          (k > 1)
+ *   out[p, h, :] = v_p,   lse[p, h] = a_p                                                                         (k == 1)
+ * alpha f32[n_src, heads], lse f32[nnz, heads], both dense; V / out rows 16-byte aligned, leading dimensions multiples of 4.  Every
+ * result is built from the k - 1 terms it names and no exp is taken at a positive argument, however the logits are spread.
+ *
+ * allset_loo_softmax_bwd: from the forward's out / lse and the cotangents gout f32[nnz, ldg] and glse f32[nnz, heads] (NULL = zeros),
+ * PER POSITION (the caller sums the positions of a source row when col is given):
+ *   gV[q, h, :] = sum_{p != q} w_pq gout[p, h, :],     w_pq = exp(a_q - lse[p, h])
+ *   galpha[q, h] = leaky_relu'(alpha) * ( <gV[q, h], v_q> + sum_{p != q} w_pq (glse[p, h] - <gout[p, h], out[p, h]>) )
+ * scratch: f32[nnz, heads, 2], 8-byte aligned, overwritten.  gV may alias neither gout nor out.
+ * long_seg / n_long: as for allset_loo_rows (the same threshold, the same list).
+ * ------------------------------------------------------------------------------------------- */
+int allset_loo_softmax_supported(int64_t d, int64_t heads);
+int allset_loo_softmax_fwd(const int32_t* rowptr, const int32_t* col, const float* alpha, const float* V, int64_t ldv, float slope,
+                           float* out, int64_t ldo, float* lse, const int32_t* long_seg, int64_t n_long, int64_t n_seg,
+                           int64_t n_src, int64_t nnz, int64_t d, int64_t heads, void* stream);
+int allset_loo_softmax_bwd(const int32_t* rowptr, const int32_t* col, const float* alpha, const float* V, int64_t ldv, float slope,
+                           const float* out, int64_t ldo, const float* lse, const float* gout, int64_t ldg, const float* glse,
+                           float* gV, int64_t ldgv, float* galpha, float* scratch, const int32_t* long_seg, int64_t n_long,
+                           int64_t n_seg, int64_t n_src, int64_t nnz, int64_t d, int64_t heads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,9 @@ the median over the repeats, the spread their (max - min).  The ``loo_rows`` lau
 ``nnz * (2 * d * 4 + 4) + (n_seg + 1) * 4`` per pass (the second read of a long segment's rows is expected to hit cache).  Shapes:
 |V| = |E| = 250k with size-16 hyperedges, and the Zipf <= 4096 generator of ``allset_amd.synthetic`` at the largest size whose
 expansion fits (the expansion is skipped, and said to be, where it does not).  ``--counters``: one pass of each ``loo_rows`` form only,
-for a counters-only ``rocprofv3 --pmc`` run of this script."""
+for a counters-only ``rocprofv3 --pmc`` run of this script.  ``--attention [--heads 4]``: the same protocol and shapes for the PMA pooling
+-- ``pma_aggregate_exclude_self`` (the leave-one-out softmax of csrc/loo_softmax.hip) against ``pma_aggregate``
+over the expansion, with the ``loo_softmax_fwd`` / ``loo_softmax_bwd`` launches timed on their own."""
 from __future__ import annotations
 
 import argparse
@@ -24,7 +26,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from allset_amd import Incidence, LeaveOneOutIncidence, deepsets_aggregate, deepsets_aggregate_exclude_self, ops   # noqa: E402
+from allset_amd import (Incidence, LeaveOneOutIncidence, deepsets_aggregate, deepsets_aggregate_exclude_self, ops,  # noqa: E402
+                        pma_aggregate, pma_aggregate_exclude_self)
 from allset_amd import preprocessing as P                                                                          # noqa: E402
 from allset_amd.synthetic import random_hypergraph                                                                 # noqa: E402
 
@@ -44,7 +47,8 @@ def _pair_times(fn, iters: int):
     return statistics.median(ms)
 
 
-def measure(name: str, n_v: int, n_e: int, dist: str, degree: float, d: int, repeats: int, iters: int, dev) -> dict:
+def measure(name: str, n_v: int, n_e: int, dist: str, degree: float, d: int, repeats: int, iters: int, dev, heads: int = 0) -> dict:
+    """``heads`` > 0: the PMA pooling with that many heads instead of the Deep Sets sum."""
     hg = random_hypergraph(n_v, n_e, degree=degree, seed=0, device=dev, dist=dist, e_base=n_v)
     ei = hg.edge_index
     sizes = torch.bincount(ei[1] - n_v)
@@ -53,7 +57,17 @@ def measure(name: str, n_v: int, n_e: int, dist: str, degree: float, d: int, rep
     x = torch.randn(n_v, d, device=dev, requires_grad=True)
     G = torch.randn(loo.n_dst, d, device=dev)
 
+    if heads:
+        a_v = torch.randn(n_v, heads, device=dev, requires_grad=True)
+        a_e = torch.randn(loo.nnz, heads, device=dev, requires_grad=True)
+        loo.merge_incidence()
+
     def new_pair():
+        if heads:
+            y = pma_aggregate_exclude_self(x, a_v, loo, "v2e", heads)
+            out = pma_aggregate_exclude_self(y, a_e, loo, "e2v", heads)
+            torch.autograd.grad(out, (x, a_v, a_e), G)
+            return
         y = deepsets_aggregate_exclude_self(x, loo, "v2e", "add")
         out = deepsets_aggregate_exclude_self(y, loo, "e2v", "add")
         torch.autograd.grad(out, x, G)
@@ -69,6 +83,11 @@ def measure(name: str, n_v: int, n_e: int, dist: str, degree: float, d: int, rep
         del data, eie
 
         def old_pair():
+            if heads:
+                y, _, _ = pma_aggregate(x, a_v, inc, heads)
+                out, _, _ = pma_aggregate(y, a_e, rev, heads)
+                torch.autograd.grad(out, (x, a_v, a_e), G)
+                return
             y = deepsets_aggregate(x, inc, None, "add")
             out = deepsets_aggregate(y, rev, None, "add")
             torch.autograd.grad(out, x, G)
@@ -99,6 +118,14 @@ def measure(name: str, n_v: int, n_e: int, dist: str, degree: float, d: int, rep
         summ = timer.summary()
     finally:
         ops.set_kernel_timer(None)
+    if heads:
+        res["heads"] = heads
+        for kernel, per_row in (("loo_softmax_fwd", 2 * d + 2 * heads), ("loo_softmax_bwd", 4 * d + 4 * heads)):
+            k = summ[kernel]
+            algo = loo.nnz * (per_row * 4 + 2) + (loo.n_e + 1) * 4          # (col: 4 bytes in the V->E launch, none in the E->V one)
+            res.update({f"{kernel}_avg_ms": k["avg_ms"], f"{kernel}_calls_per_pair": k["calls"] / iters, f"{kernel}_algo_bytes": algo,
+                        f"{kernel}_roofline_fraction": algo / HBM_BYTES_PER_S / (k["avg_ms"] * 1e-3)})
+        return res
     k = summ["loo_rows"]
     algo = loo.nnz * (2 * d * 4 + 4) + (loo.n_e + 1) * 4
     res.update(loo_rows_avg_ms=k["avg_ms"], loo_rows_calls_per_pair=k["calls"] / iters, loo_rows_algo_bytes=algo,
@@ -127,18 +154,21 @@ def main() -> None:
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--d", type=int, default=128)
     ap.add_argument("--counters", action="store_true")
+    ap.add_argument("--attention", action="store_true", help="time the PMA pooling (leave-one-out softmax) instead of the Deep Sets sum")
+    ap.add_argument("--heads", type=int, default=4)
     args = ap.parse_args()
+    heads = args.heads if args.attention else 0
     if not torch.cuda.is_available():
         raise SystemExit("exclude_self_ablation: needs the GPU (nothing here is measured on a CPU)")
     dev = torch.device("cuda:0")
     if args.counters:
         counters_pass(args.d, dev)
         return
-    results = [measure("fixed16_250k", 250_000, 250_000, "fixed", 16, args.d, args.repeats, args.iters, dev)]
+    results = [measure("fixed16_250k", 250_000, 250_000, "fixed", 16, args.d, args.repeats, args.iters, dev, heads)]
     torch.cuda.empty_cache()
     # Zipf sizes up to 4096 (mean 16): one 4096-member hyperedge alone expands to 16.7M incidences
     for n in (250_000, 60_000, 15_000):
-        r = measure(f"zipf4096_{n // 1000}k", n, n, "zipf", 16, args.d, args.repeats, args.iters, dev)
+        r = measure(f"zipf4096_{n // 1000}k", n, n, "zipf", 16, args.d, args.repeats, args.iters, dev, heads)
         results.append(r)
         torch.cuda.empty_cache()
         if "expansion_ms" in r:
