@@ -46,10 +46,49 @@ void clear_error();
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// ---- launch helpers of the one-wave-per-CSR-row kernels ----------------------------------------------------------------------
+inline unsigned row_grid(int64_t rows) { return static_cast<unsigned>((rows + kWavesPerBlock - 1) / kWavesPerBlock); }
+
+// lanes per row: the smallest power of two >= d / vec, in [8, max_lpr]
+inline int pick_lpr(int64_t d, int vec = 4, int max_lpr = 64) {
+  const int64_t need = (d + vec - 1) / vec;
+  int lpr = 8;
+  while (lpr < need && lpr < max_lpr) lpr <<= 1;
+  return lpr;
+}
+
+// AUTO takes the short-row ("flat") kernel above this many target rows, at a mean degree below the bound (allset_segreduce_fwd_ex)
+constexpr int kFlatMinRows = 16384;
+constexpr double kFlatMaxMeanDegree = 6.0;
+
 // ---- device helpers ---------------------------------------------------------------------------
 #ifdef __HIPCC__
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
+
+// Butterfly reductions over the wave: every lane ends with the same value, bit-identical.
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// Segmented lane sum: `val` over the lanes [li, grp_end) of an LPR-lane row group (li = this lane's index in the group, grp_end
+// = the end of its head's lanes); the head's total is valid in the head's first lane.
+template <int LPR>
+__device__ __forceinline__ float head_group_reduce(float val, int li, int grp_end) {
+#pragma unroll
+  for (int off = LPR / 2; off > 0; off >>= 1) {
+    const float o = __shfl_down(val, off);
+    if (li + off < grp_end) val += o;
+  }
+  return val;
+}
 
 // The hardware dispatcher places workgroup b on XCD b % 8 (MI355X_MICROARCH.md "Workgroup dispatch").
 // Remap so that each XCD walks a CONTIGUOUS range of row-blocks: neighbouring CSR rows (which on
@@ -231,6 +270,12 @@ __device__ __forceinline__ uint32_t drop_threshold(float p) {
   if (t8 == floorf(t8)) return kDrop8 | static_cast<uint32_t>(t8);
 #endif
   return static_cast<uint32_t>(p * 65536.0f);
+}
+// drop_threshold() for entry points that resolve the threshold on the host and pass it to their kernels.  The two MUST agree: masks
+// drawn by a kernel of one kind are regenerated by kernels of the other (dense.dropout_scale against the attention hops).
+inline uint32_t host_drop_threshold(float p) {
+  const float t8 = p * 256.0f;
+  return (t8 == floorf(t8)) ? (kDrop8 | static_cast<uint32_t>(t8)) : static_cast<uint32_t>(p * 65536.0f);
 }
 __device__ __forceinline__ float keep_scale(uint64_t seed, int64_t idx, uint32_t thr, float inv_keep) {
   if (thr & kDrop8) {

@@ -203,17 +203,6 @@ __global__ __launch_bounds__(kBlock) void hop_bwd_stats_kernel(
   }
 }
 
-// Sum `val` over the lanes [li - q, grp_end) of this lane's head inside its LPR-lane row group; valid in the head's first lane.
-template <int LPR>
-__device__ __forceinline__ float head_group_reduce(float val, int li, int grp_end) {
-#pragma unroll
-  for (int off = LPR / 2; off > 0; off >>= 1) {
-    const float o = __shfl_down(val, off);
-    if (li + off < grp_end) val += o;
-  }
-  return val;
-}
-
 template <int VEC, int LPR>
 __global__ __launch_bounds__(kBlock) void hop_bwd_src_kernel(
     const int32_t* __restrict__ rowptrT, const int32_t* __restrict__ colT, const int32_t* __restrict__ slotT,
@@ -602,20 +591,6 @@ __global__ __launch_bounds__(kBlock) void sem_reduce_kernel(const float* __restr
   float v = 0.f;
   for (int b = 0; b < nb; ++b) v += ppart[static_cast<int64_t>(b) * P + i];
   out[i] = v;
-}
-
-static inline unsigned row_grid(int64_t rows) { return static_cast<unsigned>((rows + kWavesPerBlock - 1) / kWavesPerBlock); }
-
-static inline int pick_lpr(int64_t d, int vec) {           // smallest power of two >= d / vec, in [8, 64]
-  const int64_t need = (d + vec - 1) / vec;
-  int lpr = 8;
-  while (lpr < need && lpr < 64) lpr <<= 1;
-  return lpr;
-}
-
-static inline uint32_t host_drop_threshold(float p) {      // drop_threshold() of common.h on the host
-  const float t8 = p * 256.0f;
-  return (t8 == floorf(t8)) ? (kDrop8 | static_cast<uint32_t>(t8)) : static_cast<uint32_t>(p * 65536.0f);
 }
 
 static int check_dims(const char* who, int64_t n, int64_t nnz, int64_t H, int64_t C) {

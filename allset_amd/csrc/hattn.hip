@@ -64,17 +64,6 @@ __device__ __forceinline__ float epilogue1(const Epi& e, float v, int64_t row, i
   return v;
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // One wavefront per vertex; lanes stride the vertex's incidences, heads in turn.
 __global__ __launch_bounds__(kBlock) void hattn_coef_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int32_t* __restrict__ perm,
@@ -368,13 +357,6 @@ __global__ __launch_bounds__(kBlock) void hattn_bwd_edge_kernel(const int32_t* _
     sum = wave_sum(sum);
     if (lane == 0) gae[static_cast<int64_t>(row) * H + h] = sum;
   }
-}
-
-static inline unsigned row_grid(int64_t rows) { return static_cast<unsigned>((rows + kWavesPerBlock - 1) / kWavesPerBlock); }
-
-static inline uint32_t host_drop_threshold(float p) {      // drop_threshold() of common.h on the host
-  const float t8 = p * 256.0f;
-  return (t8 == floorf(t8)) ? (kDrop8 | static_cast<uint32_t>(t8)) : static_cast<uint32_t>(p * 65536.0f);
 }
 
 static int check_dims(const char* who, int64_t n_a, int64_t n_b, int64_t nnz, int64_t H, int64_t C) {

@@ -268,18 +268,7 @@ __global__ __launch_bounds__(kBlock) void hconv_bwd_epi_kernel(
   }
 }
 
-constexpr double kFlatMaxMeanDegree = 6.0;
-constexpr int kFlatMinRows = 16384;
 constexpr int64_t kEpiMaxSlabs = 256;
-
-static inline unsigned row_grid(int64_t rows) { return static_cast<unsigned>((rows + kWavesPerBlock - 1) / kWavesPerBlock); }
-
-static inline int pick_lpr(int64_t d) {           // smallest power of two >= d / 4, in [8, 64]
-  const int64_t need = (d + 3) / 4;
-  int lpr = 8;
-  while (lpr < need && lpr < 64) lpr <<= 1;
-  return lpr;
-}
 
 template <int VEC, int LPR>
 static void launch_fwd(int sc, unsigned grid, hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* r,

@@ -417,18 +417,6 @@ __global__ __launch_bounds__(kBlock) void e2v_flat_kernel(const int32_t* __restr
   while (cur_row < r_end) flush();                                 // last row and trailing empty rows
 }
 
-constexpr double kFlatMaxMeanDegree = 6.0;
-constexpr int kFlatMinRows = 16384;
-
-static inline unsigned row_grid(int64_t rows) { return static_cast<unsigned>((rows + kWavesPerBlock - 1) / kWavesPerBlock); }
-
-static inline int pick_lpr(int64_t d) {           // smallest power of two >= d / 4, in [8, 64]
-  const int64_t need = (d + 3) / 4;
-  int lpr = 8;
-  while (lpr < need && lpr < 64) lpr <<= 1;
-  return lpr;
-}
-
 static inline int pick_group(int64_t nnz, int64_t rows) {   // lanes per CSR row of the structure kernels
   const double mean = rows > 0 ? static_cast<double>(nnz) / static_cast<double>(rows) : 0.0;
   return mean <= 8.0 ? 8 : (mean <= 32.0 ? 16 : 64);

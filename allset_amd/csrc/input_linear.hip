@@ -22,12 +22,6 @@
 
 namespace allset {
 
-__device__ __forceinline__ float wave_sum(float v) {      // butterfly: every lane ends with the same sum, bit-identical
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 template <int NS>
 __global__ __launch_bounds__(kBlock) void xhat_rows_kernel(const float* __restrict__ x, int64_t ldx, int64_t n, int d, float eps,
                                                            float p_pre, uint64_t seed, const uint64_t* __restrict__ seed_base,

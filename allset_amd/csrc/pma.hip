@@ -26,17 +26,6 @@ constexpr int kPmaUnroll = 8;
 constexpr int kMaxHeads = 256;   // per-wave LDS accumulators for the per-head scalars of the backward
 constexpr float kSoftmaxEps = 1e-16f;   // torch_geometric.utils.softmax denominator guard [external]
 
-// Sum `val` over the lanes [grp_start, grp_end) of this lane's LPR-lane row group; valid in lane grp_start.
-template <int LPR>
-__device__ __forceinline__ float head_group_reduce(float val, int li, int grp_end) {
-#pragma unroll
-  for (int off = LPR / 2; off > 0; off >>= 1) {
-    const float o = __shfl_down(val, off);
-    if (li + off < grp_end) val += o;
-  }
-  return val;
-}
-
 template <typename T, int VEC, int LPR>
 __global__ __launch_bounds__(kBlock) void pma_fwd_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ alpha, int64_t lda,
@@ -535,15 +524,6 @@ __global__ __launch_bounds__(kBlock) void pma_bwd_src_flat_kernel(
     }
   }
   while (cur_row < r_end) flush();
-}
-
-static inline unsigned row_grid(int64_t rows) { return static_cast<unsigned>((rows + kWavesPerBlock - 1) / kWavesPerBlock); }
-
-static inline int pick_lpr(int64_t d, int vec) {
-  const int64_t need = (d + vec - 1) / vec;
-  int lpr = 8;
-  while (lpr < need && lpr < 64) lpr <<= 1;
-  return lpr;
 }
 
 #define ALLSET_PMA_DISPATCH_T(KERNEL, T, WIDE, GRID, ST, ...)                                \

@@ -135,7 +135,6 @@ __global__ __launch_bounds__(kBlock) void segreduce_kernel(
 // stream: the rows' rowptr entries arrive in one load (lane i holds rowptr[r0+i]), the column ids of consecutive rows
 // are contiguous in the CSR and arrive LPR at a time, the gathers of a batch are in flight together regardless of row
 // boundaries, and a row is flushed (one coalesced store) whenever the stream crosses its end.  Slots never combine.
-constexpr int kFlatMinRows = 16384;   // AUTO: below this many target rows the one-group-per-row kernel (see allset_segreduce_fwd)
 constexpr int kFlatRows = 7;       // rows per slot; kFlatRows + 1 rowptr entries must fit in the smallest slot (8 lanes)
 
 template <typename T, int VEC, int LPR, bool WEIGHTED>
@@ -392,16 +391,6 @@ __global__ __launch_bounds__(kBlock) void sddmm_rowdot_vec_kernel(
 
 // ---- host-side dispatch ------------------------------------------------------------------------
 
-static inline unsigned row_grid(int64_t rows) { return static_cast<unsigned>((rows + kWavesPerBlock - 1) / kWavesPerBlock); }
-
-// lanes-per-row for the 16-byte path: smallest power of two >= d/vec, in [8, 64]
-static inline int pick_lpr(int64_t d, int vec = 4, int max_lpr = 64) {
-  const int64_t need = (d + vec - 1) / vec;
-  int lpr = 8;
-  while (lpr < need && lpr < max_lpr) lpr <<= 1;
-  return lpr;
-}
-
 template <typename T, int VEC, int LPR>
 static void launch_segreduce(int mode_ext, bool weighted, unsigned grid, hipStream_t st,
                              const int32_t* rowptr, const int32_t* col, const float* w, const T* x,
@@ -466,9 +455,6 @@ static void launch_segmax_bwd(bool weighted, unsigned grid, hipStream_t st, cons
 }  // namespace allset
 
 using namespace allset;
-
-// mean degree below which the short-row kernel is used (AUTO); see allset_segreduce_fwd_ex
-constexpr double kFlatMaxMeanDegree = 6.0;
 
 static int segreduce_impl(int reduce, int dtype, int variant, int64_t nnz_hint, const int32_t* row_order,
                           const int32_t* rowptr, const int32_t* col,

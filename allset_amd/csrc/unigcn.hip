@@ -197,16 +197,6 @@ __global__ __launch_bounds__(kBlock) void unigcn_flat_kernel(
   while (cur_row < r_end) flush();                                 // last row and trailing empty rows
 }
 
-constexpr double kFlatMaxMeanDegree = 6.0;
-constexpr int kFlatMinRows = 16384;
-
-static inline int pick_lpr(int64_t d) {           // smallest power of two >= d / 4, in [8, 64]
-  const int64_t need = (d + 3) / 4;
-  int lpr = 8;
-  while (lpr < need && lpr < 64) lpr <<= 1;
-  return lpr;
-}
-
 template <int LPR, int NCH>
 static void launch_rows(hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* xe, int64_t ldxe, const Tail& tl,
                         float* xi, int64_t ldxi, int n_t, int d, const int32_t* row_order) {

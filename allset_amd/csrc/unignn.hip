@@ -112,18 +112,6 @@ struct VertexTail {
   }
 };
 
-// Sum `val` over the lanes [li, grp_end) of this lane's head inside its LPR-lane row group; valid in the head's first lane
-// (gat.hip's segmented lane sum).
-template <int LPR>
-__device__ __forceinline__ float head_group_reduce(float val, int li, int grp_end) {
-#pragma unroll
-  for (int off = LPR / 2; off > 0; off >>= 1) {
-    const float o = __shfl_down(val, off);
-    if (li + off < grp_end) val += o;
-  }
-  return val;
-}
-
 // K2's row finish: the per-hyperedge scale, the row store and the H per-head dot products with att.
 struct EdgeLogit {
   const float* s;         // per output row, or NULL (= ones)
@@ -300,16 +288,6 @@ __global__ __launch_bounds__(kBlock) void unignn_flat_kernel(
     }
   }
   while (cur_row < r_end) flush();                                 // last row and trailing empty rows
-}
-
-constexpr double kFlatMaxMeanDegree = 6.0;
-constexpr int kFlatMinRows = 16384;
-
-static inline int pick_lpr(int64_t d) {           // smallest power of two >= d / 4, in [8, 64]
-  const int64_t need = (d + 3) / 4;
-  int lpr = 8;
-  while (lpr < need && lpr < 64) lpr <<= 1;
-  return lpr;
 }
 
 template <int LPR, int NCH, class Finish>

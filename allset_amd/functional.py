@@ -1161,19 +1161,19 @@ def unignn_row_tail(a: Tensor, skip: Optional[Tensor] = None, use_norm: bool = F
 
 
 # ---- HAN baseline: the DGL-style attention hop and the semantic attention (csrc/han.hip) ---------------------------------------------
-class _HanGatPropagate(torch.autograd.Function):
+class _HanPropagate(torch.autograd.Function):
     """``y = elu(sum_j softmax_j(lrelu(el[s_j] + er[t])) * keep_j / (1 - p) * x[s_j] + bias)`` -- one kernel forward, written into
     column block ``block`` of ``out`` when one is given (``out`` is then returned, marked dirty).  Backward: one pass over the target
     rows (elu', the softmax statistics, the whole of ``ger``), one gather pass over the source-major CSR (``gx``, ``gel``) that
     regenerates the edge mask from the seed.  Saved: ``x``, ``el``, ``er``, the positive-logit part of the aggregate (``outpos``
-    [n, H*C], ``ppos`` [n, H]) and ``lse``; ``y`` is read back where it was written."""
+    [n, H*C], ``ppos`` [n, H]) and ``lse``; ``y`` is read back where it was written.  ``graph`` is a ``han.MetapathGraph`` or a
+    ``han_sampling.Block`` (both carry the two CSR orientations): ``x`` / ``el`` / ``gx`` / ``gel`` have one row per source node,
+    ``er`` and everything else one per target node (``n``); the callers below have checked both counts against ``graph``."""
 
     @staticmethod
     def forward(ctx, x, el, er, bias, graph, heads, slope, p, out, block):
         from . import dense
-        n, d = x.shape
-        if n != graph.n:
-            raise _lib.AllSetHipError(f"han_gat_propagate: x has {n} rows, the graph has {graph.n} nodes")
+        n, d = er.shape[0], x.shape[1]
         seed = dense._draw_seed() if p > 0.0 else 0
         base = dense._seed_base() if p > 0.0 else None
         want = any(ctx.needs_input_grad[:4])
@@ -1182,7 +1182,7 @@ class _HanGatPropagate(torch.autograd.Function):
             y = ret
         else:
             if out.dim() != 2 or out.shape[0] != n or out.shape[1] < (block + 1) * d or out.stride(1) != 1 or out.dtype != torch.float32:
-                raise _lib.AllSetHipError(f"han_gat_propagate: out {tuple(out.shape)} cannot hold block {block} of width {d} for {n} rows")
+                raise _lib.AllSetHipError(f"HAN hop: out {tuple(out.shape)} cannot hold block {block} of width {d} for {n} rows")
             ctx.mark_dirty(out)
             ret = out
             y = out.detach()[:, block * d:(block + 1) * d]
@@ -1220,15 +1220,22 @@ def han_gat_propagate(x: Tensor, el: Tensor, er: Tensor, graph, heads: int, nega
     hash mask on (the edge's slot in the target-major CSR, head) -- :func:`han_edge_keep` returns it.  With ``out`` ([n, >= (block +
     1) * heads * C], row-major) the result is written into its column block ``block`` and ``out`` itself is returned: the stacked
     [n, M, heads * C] tensor of the HAN layer is filled hop by hop without a ``torch.stack`` copy.  ``out`` is a plain buffer (no
-    grad) or the result of earlier calls of this function into OTHER blocks of it; every block is written once and left alone until
-    the backward has run.  Differentiable in ``x``, ``el``, ``er`` and ``bias``."""
+    grad) or the result of earlier calls of this function (or of :func:`han_block_propagate`: the two share one autograd Function,
+    and the row counts still have to agree) into OTHER blocks of it; every block is written once and left alone until the backward
+    has run.  Differentiable in ``x``, ``el``, ``er`` and ``bias``."""
+    if x.shape[0] != graph.n:
+        raise _lib.AllSetHipError(f"han_gat_propagate: x has {x.shape[0]} rows, the graph has {graph.n} nodes")
+    return _han_propagate("han_gat_propagate", x, el, er, graph, heads, negative_slope, bias, attn_drop, out, block)
+
+
+def _han_propagate(who, x, el, er, graph, heads, negative_slope, bias, attn_drop, out, block) -> Tensor:
     _lib.require_device(x, el, er)
-    if out is not None and out.requires_grad and type(out.grad_fn).__name__ != "_HanGatPropagateBackward":
-        raise ValueError("han_gat_propagate: out must be a buffer that does not require grad, or the result of an earlier "
-                         "han_gat_propagate into another of its blocks (the overwritten block would need a zero gradient)")
+    if out is not None and out.requires_grad and type(out.grad_fn).__name__ != "_HanPropagateBackward":
+        raise ValueError(f"{who}: out must be a buffer that does not require grad, or the result of an earlier han_gat_propagate / "
+                         "han_block_propagate into another of its blocks (the overwritten block would need a zero gradient)")
     if el.dtype != torch.float32 or er.dtype != torch.float32:
         el, er = el.float(), er.float()
-    return _HanGatPropagate.apply(x, el, er, bias, graph, int(heads), float(negative_slope), float(attn_drop), out, int(block))
+    return _HanPropagate.apply(x, el, er, bias, graph, int(heads), float(negative_slope), float(attn_drop), out, int(block))
 
 
 def han_edge_keep(graph, heads: int, p: float, seed: int) -> Tensor:
@@ -1269,50 +1276,6 @@ def semantic_attention(z: Tensor, W1: Tensor, b1: Tensor, q: Tensor) -> Tensor:
 
 
 # ---- mini-batch HAN: the attention hop over a bipartite block (csrc/han_sample.hip) ---------------------------------------------------
-class _HanBlockPropagate(torch.autograd.Function):
-    """:class:`_HanGatPropagate` over a bipartite block (``han_sampling.Block``): ``x`` / ``el`` have ``n_src`` rows, ``er`` and the
-    result ``n_dst``.  The same kernels, the same saved tensors, the same stacked-buffer rule."""
-
-    @staticmethod
-    def forward(ctx, x, el, er, bias, blk, heads, slope, p, out, block):
-        from . import dense
-        n_src, d = x.shape
-        n_dst = blk.n_dst
-        if n_src != blk.n_src or er.shape[0] != n_dst:
-            raise _lib.AllSetHipError(f"han_block_propagate: x has {n_src} rows and er {er.shape[0]}, the block has {blk.n_src} source "
-                                      f"and {n_dst} target nodes")
-        seed = dense._draw_seed() if p > 0.0 else 0
-        base = dense._seed_base() if p > 0.0 else None
-        want = any(ctx.needs_input_grad[:4])
-        if out is None:
-            ret = torch.empty((n_dst, d), dtype=torch.float32, device=x.device)
-            y = ret
-        else:
-            if out.dim() != 2 or out.shape[0] != n_dst or out.shape[1] < (block + 1) * d or out.stride(1) != 1 or out.dtype != torch.float32:
-                raise _lib.AllSetHipError(f"han_block_propagate: out {tuple(out.shape)} cannot hold block {block} of width {d} for {n_dst} rows")
-            ctx.mark_dirty(out)
-            ret = out
-            y = out.detach()[:, block * d:(block + 1) * d]
-        outpos, ppos, lse = ops.han_block_hop_fwd(blk.rowptr, blk.col, x, el, er, heads, slope, bias, p, seed, base, y, want)
-        ctx.save_for_backward(x, el, er, bias, outpos, ppos, lse, ret if out is None else None)
-        ctx.y_block = y if out is not None else None
-        ctx.cfg = (blk, heads, slope, p, seed, base, block, d, out is not None)
-        return ret
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gout):
-        x, el, er, bias, outpos, ppos, lse, y_own = ctx.saved_tensors
-        blk, heads, slope, p, seed, base, block, d, stacked = ctx.cfg
-        if gout.stride(1) != 1:
-            gout = gout.contiguous()
-        gy = gout[:, block * d:(block + 1) * d] if stacked else gout
-        g, stats, ger = ops.han_block_hop_bwd_stats(ctx.y_block if stacked else y_own, bias, gy, outpos, ppos, lse, slope)
-        gx, gel = ops.han_block_hop_bwd_src(blk.rowptrT, blk.colT, blk.slotT, x, el, er, g, stats, slope, p, seed, base)
-        gb = g.sum(0) if (bias is not None and ctx.needs_input_grad[3]) else None
-        return gx, gel, ger, gb, None, None, None, None, (gout if (stacked and ctx.needs_input_grad[8]) else None), None
-
-
 def han_block_propagate(x: Tensor, el: Tensor, er: Tensor, blk, heads: int, negative_slope: float = 0.2, bias: Optional[Tensor] = None,
                         attn_drop: float = 0.0, out: Optional[Tensor] = None, block: int = 0) -> Tensor:
     """:func:`han_gat_propagate` over a bipartite block ``blk`` (a ``han_sampling.Block``: ``n_src`` source nodes of which the first
@@ -1320,10 +1283,7 @@ def han_block_propagate(x: Tensor, el: Tensor, er: Tensor, blk, heads: int, nega
     ``er`` [n_dst, heads]; the result has ``n_dst`` rows, ``y[t, h] = elu(sum_j a_j x[s_j, h] + bias[h])`` with ``a_j`` the softmax
     over the edges into ``t`` times the hash mask on (target-major slot, head).  ``out`` / ``block``: the stacked [n_dst, M * heads *
     C] buffer, as there.  Differentiable in ``x``, ``el``, ``er`` and ``bias``."""
-    _lib.require_device(x, el, er)
-    if out is not None and out.requires_grad and type(out.grad_fn).__name__ != "_HanBlockPropagateBackward":
-        raise ValueError("han_block_propagate: out must be a buffer that does not require grad, or the result of an earlier "
-                         "han_block_propagate into another of its blocks (the overwritten block would need a zero gradient)")
-    if el.dtype != torch.float32 or er.dtype != torch.float32:
-        el, er = el.float(), er.float()
-    return _HanBlockPropagate.apply(x, el, er, bias, blk, int(heads), float(negative_slope), float(attn_drop), out, int(block))
+    if x.shape[0] != blk.n_src or er.shape[0] != blk.n_dst:
+        raise _lib.AllSetHipError(f"han_block_propagate: x has {x.shape[0]} rows and er {er.shape[0]}, the block has {blk.n_src} source "
+                                  f"and {blk.n_dst} target nodes")
+    return _han_propagate("han_block_propagate", x, el, er, blk, heads, negative_slope, bias, attn_drop, out, block)

@@ -1295,37 +1295,42 @@ def _pitch(t: Tensor, what: str) -> int:
 
 def han_hop_fwd(rowptr: Tensor, col: Tensor, x: Tensor, el: Tensor, er: Tensor, heads: int, slope: float, bias: Optional[Tensor],
                 p_att: float, seed: int, seed_base: Optional[Tensor], y: Tensor, want_grad: bool):
-    """One HAN attention hop over a target-major CSR into ``y`` (a [n, H*C] view with contiguous rows, e.g. a column block of the
-    stacked buffer): ``(outpos, ppos, lse)``; ``outpos`` / ``ppos`` only with ``want_grad``."""
+    """One HAN attention hop over a target-major CSR of ``n_dst`` rows whose ``col`` indexes ``n_src`` source rows (a bipartite
+    block: the targets are the first source nodes; the full graph is ``n_src == n_dst``): ``x`` [n_src, H*C], ``el`` [n_src, H],
+    ``er`` [n_dst, H], into ``y`` (a [n_dst, H*C] view with contiguous rows, e.g. a column block of the stacked buffer).  Returns
+    ``(outpos, ppos, lse)``; ``outpos`` / ``ppos`` only with ``want_grad``."""
     dev = require_device(rowptr, col, x, el, er, bias, y)
     for t, what in ((x, "x"), (el, "el"), (er, "er"), (bias, "bias"), (y, "y")):
         if t is not None:
             _f32(t, f"han_hop_fwd {what}")
     x, el, er = _rowmajor(x), el.contiguous(), er.contiguous()
-    n, d = x.shape
+    n_src, d = x.shape
+    n_dst = rowptr.numel() - 1
     H = int(heads)
     if H < 1 or d % H != 0 or d == 0:
         raise _lib.AllSetHipError(f"han_hop_fwd: width {d} does not split into {H} heads")
-    if tuple(el.shape) != (n, H) or tuple(er.shape) != (n, H) or tuple(y.shape) != (n, d) or rowptr.numel() != n + 1:
+    if n_dst < 0 or tuple(el.shape) != (n_src, H) or tuple(er.shape) != (n_dst, H) or tuple(y.shape) != (n_dst, d):
         raise _lib.AllSetHipError(f"han_hop_fwd: el {tuple(el.shape)} / er {tuple(er.shape)} / y {tuple(y.shape)} / rowptr "
-                                  f"{rowptr.numel()} against {n} nodes of width {d}, {H} heads")
+                                  f"{rowptr.numel()} against {n_src} source rows of width {d}, {H} heads")
     if bias is not None and bias.numel() != d:
         raise _lib.AllSetHipError(f"han_hop_fwd: bias has {bias.numel()} entries for width {d}")
     bias = bias.contiguous() if bias is not None else None
-    lse = torch.empty((n, H), dtype=torch.float32, device=dev)
-    outpos = torch.empty((n, d), dtype=torch.float32, device=dev) if want_grad else None
-    ppos = torch.empty((n, H), dtype=torch.float32, device=dev) if want_grad else None
+    lse = torch.empty((n_dst, H), dtype=torch.float32, device=dev)
+    outpos = torch.empty((n_dst, d), dtype=torch.float32, device=dev) if want_grad else None
+    ppos = torch.empty((n_dst, H), dtype=torch.float32, device=dev) if want_grad else None
     nnz = col.numel()
-    algo = nnz * (4 * d + 4 * H + 4) + (n + 1) * 4 + n * (4 * d + 12 * H) + (n * (4 * d + 4 * H) if want_grad else 0)
+    algo = nnz * (4 * d + 4 * H + 4) + (n_dst + 1) * 4 + n_dst * (4 * d + 12 * H) + (n_dst * (4 * d + 4 * H) if want_grad else 0)
     with on_device(dev), _timed("han_hop_fwd", dev, algo):
-        check(_lib.load().allset_han_hop_fwd(nnz, ptr(rowptr), ptr(col), ptr(el), ptr(er), ptr(x), _ld(x), float(slope), ptr(bias),
-                                             float(p_att), int(seed), ptr(seed_base), ptr(y), _pitch(y, "han_hop_fwd y"), ptr(outpos), d,
-                                             ptr(ppos), ptr(lse), n, H, d // H, stream_of(dev)), "allset_han_hop_fwd")
+        check(_lib.load().allset_han_block_hop_fwd(nnz, ptr(rowptr), ptr(col), ptr(el), ptr(er), ptr(x), _ld(x), float(slope), ptr(bias),
+                                                   float(p_att), int(seed), ptr(seed_base), ptr(y), _pitch(y, "han_hop_fwd y"),
+                                                   ptr(outpos), d, ptr(ppos), ptr(lse), n_dst, n_src, H, d // H, stream_of(dev)),
+              "allset_han_block_hop_fwd")
     return outpos, ppos, lse
 
 
 def han_hop_bwd_stats(y: Tensor, bias: Optional[Tensor], gy: Tensor, outpos: Tensor, ppos: Tensor, lse: Tensor, slope: float):
-    """``(g [n, H*C] = gy * elu'(y), stats [n, H, 2] = {lse, <out, g>}, ger [n, H])``; ``y`` and ``gy`` may be column blocks."""
+    """``(g [n_dst, H*C] = gy * elu'(y), stats [n_dst, H, 2] = {lse, <out, g>}, ger [n_dst, H])`` over the target rows; ``y`` and
+    ``gy`` may be column blocks."""
     dev = require_device(y, bias, gy, outpos, ppos, lse)
     for t in (y, gy, outpos, ppos, lse):
         _f32(t, "han_hop_bwd_stats")
@@ -1337,33 +1342,35 @@ def han_hop_bwd_stats(y: Tensor, bias: Optional[Tensor], gy: Tensor, outpos: Ten
     stats = torch.empty((n, H, 2), dtype=torch.float32, device=dev)
     ger = torch.empty((n, H), dtype=torch.float32, device=dev)
     with on_device(dev), _timed("han_hop_bwd_stats", dev, 5 * n * d * 4 + n * H * 16):
-        check(_lib.load().allset_han_hop_bwd_stats(ptr(y), _pitch(y, "han_hop_bwd_stats y"), ptr(bias), ptr(gy),
-                                                   _pitch(gy, "han_hop_bwd_stats gy"), ptr(outpos), d, ptr(ppos), ptr(lse), float(slope),
-                                                   ptr(g), d, ptr(stats), ptr(ger), n, H, d // H, stream_of(dev)),
-              "allset_han_hop_bwd_stats")
+        check(_lib.load().allset_han_block_hop_bwd_stats(ptr(y), _pitch(y, "han_hop_bwd_stats y"), ptr(bias), ptr(gy),
+                                                         _pitch(gy, "han_hop_bwd_stats gy"), ptr(outpos), d, ptr(ppos), ptr(lse),
+                                                         float(slope), ptr(g), d, ptr(stats), ptr(ger), n, H, d // H, stream_of(dev)),
+              "allset_han_block_hop_bwd_stats")
     return g, stats, ger
 
 
 def han_hop_bwd_src(rowptrT: Tensor, colT: Tensor, slotT: Tensor, x: Tensor, el: Tensor, er: Tensor, g: Tensor, stats: Tensor,
                     slope: float, p_att: float, seed: int, seed_base: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
-    """``(gx [n, H*C], gel [n, H])`` in one gather pass over the source-major CSR; ``slotT`` regenerates the forward's edge mask."""
+    """``(gx [n_src, H*C], gel [n_src, H])`` in one gather pass over the source-major CSR (``n_src`` rows; ``g`` / ``stats`` / ``er``
+    have ``n_dst`` rows); ``slotT`` regenerates the forward's edge mask."""
     dev = require_device(rowptrT, colT, slotT, x, el, er, g, stats)
     for t in (x, el, er, g, stats):
         _f32(t, "han_hop_bwd_src")
     x, g, el, er, stats = _rowmajor(x), _rowmajor(g), el.contiguous(), er.contiguous(), stats.contiguous()
-    n, d = x.shape
-    H = er.shape[1]
-    if (tuple(g.shape) != (n, d) or rowptrT.numel() != n + 1 or slotT.numel() != colT.numel() or tuple(stats.shape) != (n, H, 2)
-            or tuple(el.shape) != (n, H)):
+    n_src, d = x.shape
+    n_dst, H = er.shape
+    if (tuple(g.shape) != (n_dst, d) or rowptrT.numel() != n_src + 1 or slotT.numel() != colT.numel() or tuple(stats.shape) != (n_dst, H, 2)
+            or tuple(el.shape) != (n_src, H)):
         raise _lib.AllSetHipError(f"han_hop_bwd_src: g {tuple(g.shape)} / rowptrT {rowptrT.numel()} / slotT {slotT.numel()} against "
-                                  f"{n} nodes of width {d}, {colT.numel()} edges")
-    gx = torch.empty((n, d), dtype=torch.float32, device=dev)
-    gel = torch.empty((n, H), dtype=torch.float32, device=dev)
+                                  f"{n_src} source and {n_dst} target rows of width {d}, {colT.numel()} edges")
+    gx = torch.empty((n_src, d), dtype=torch.float32, device=dev)
+    gel = torch.empty((n_src, H), dtype=torch.float32, device=dev)
     nnz = colT.numel()
-    with on_device(dev), _timed("han_hop_bwd_src", dev, nnz * (4 * d + 12 * H + 8) + (n + 1) * 4 + n * (8 * d + 8 * H)):
-        check(_lib.load().allset_han_hop_bwd_src(nnz, ptr(rowptrT), ptr(colT), ptr(slotT), ptr(el), ptr(er), ptr(x), _ld(x), ptr(g),
-                                                 _ld(g), ptr(stats), float(slope), float(p_att), int(seed), ptr(seed_base), ptr(gx), d,
-                                                 ptr(gel), n, H, d // H, stream_of(dev)), "allset_han_hop_bwd_src")
+    with on_device(dev), _timed("han_hop_bwd_src", dev, nnz * (4 * d + 12 * H + 8) + (n_src + 1) * 4 + n_src * (8 * d + 8 * H)):
+        check(_lib.load().allset_han_block_hop_bwd_src(nnz, ptr(rowptrT), ptr(colT), ptr(slotT), ptr(el), ptr(er), ptr(x), _ld(x), ptr(g),
+                                                       _ld(g), ptr(stats), float(slope), float(p_att), int(seed), ptr(seed_base), ptr(gx),
+                                                       d, ptr(gel), n_dst, n_src, H, d // H, stream_of(dev)),
+              "allset_han_block_hop_bwd_src")
     return gx, gel
 
 
@@ -1480,80 +1487,3 @@ def han_block_compact(rows: Tensor, counts: Tensor, rowptr: Tensor, seeds_sorted
                                                    ptr(seed_perm.contiguous()), ptr(uniq.contiguous()), int(n_extra), B, k, int(nnz), ptr(col),
                                                    ptr(dst), stream_of(dev)), "allset_han_block_compact")
     return col, dst
-
-
-def han_block_hop_fwd(rowptr: Tensor, col: Tensor, x: Tensor, el: Tensor, er: Tensor, heads: int, slope: float, bias: Optional[Tensor],
-                      p_att: float, seed: int, seed_base: Optional[Tensor], y: Tensor, want_grad: bool):
-    """:func:`han_hop_fwd` over a bipartite block: ``x`` [n_src, H*C], ``el`` [n_src, H], ``er`` [n_dst, H], ``y`` [n_dst, H*C] (a view
-    with contiguous rows); ``col`` holds block-local source ids."""
-    dev = require_device(rowptr, col, x, el, er, bias, y)
-    for t, what in ((x, "x"), (el, "el"), (er, "er"), (bias, "bias"), (y, "y")):
-        if t is not None:
-            _f32(t, f"han_block_hop_fwd {what}")
-    x, el, er = _rowmajor(x), el.contiguous(), er.contiguous()
-    n_src, d = x.shape
-    n_dst = rowptr.numel() - 1
-    H = int(heads)
-    if H < 1 or d % H != 0 or d == 0:
-        raise _lib.AllSetHipError(f"han_block_hop_fwd: width {d} does not split into {H} heads")
-    if n_dst < 0 or tuple(el.shape) != (n_src, H) or tuple(er.shape) != (n_dst, H) or tuple(y.shape) != (n_dst, d):
-        raise _lib.AllSetHipError(f"han_block_hop_fwd: el {tuple(el.shape)} / er {tuple(er.shape)} / y {tuple(y.shape)} / rowptr "
-                                  f"{rowptr.numel()} against {n_src} source rows of width {d}, {H} heads")
-    if bias is not None and bias.numel() != d:
-        raise _lib.AllSetHipError(f"han_block_hop_fwd: bias has {bias.numel()} entries for width {d}")
-    bias = bias.contiguous() if bias is not None else None
-    lse = torch.empty((n_dst, H), dtype=torch.float32, device=dev)
-    outpos = torch.empty((n_dst, d), dtype=torch.float32, device=dev) if want_grad else None
-    ppos = torch.empty((n_dst, H), dtype=torch.float32, device=dev) if want_grad else None
-    nnz = col.numel()
-    algo = nnz * (4 * d + 4 * H + 4) + (n_dst + 1) * 4 + n_dst * (4 * d + 12 * H) + (n_dst * (4 * d + 4 * H) if want_grad else 0)
-    with on_device(dev), _timed("han_block_hop_fwd", dev, algo):
-        check(_lib.load().allset_han_block_hop_fwd(nnz, ptr(rowptr), ptr(col), ptr(el), ptr(er), ptr(x), _ld(x), float(slope), ptr(bias),
-                                                   float(p_att), int(seed), ptr(seed_base), ptr(y), _pitch(y, "han_block_hop_fwd y"),
-                                                   ptr(outpos), d, ptr(ppos), ptr(lse), n_dst, n_src, H, d // H, stream_of(dev)),
-              "allset_han_block_hop_fwd")
-    return outpos, ppos, lse
-
-
-def han_block_hop_bwd_stats(y: Tensor, bias: Optional[Tensor], gy: Tensor, outpos: Tensor, ppos: Tensor, lse: Tensor, slope: float):
-    """:func:`han_hop_bwd_stats` over a block's ``n_dst`` target rows."""
-    dev = require_device(y, bias, gy, outpos, ppos, lse)
-    for t in (y, gy, outpos, ppos, lse):
-        _f32(t, "han_block_hop_bwd_stats")
-    n, d = y.shape
-    H = lse.shape[1]
-    if tuple(gy.shape) != (n, d) or tuple(outpos.shape) != (n, d):
-        raise _lib.AllSetHipError(f"han_block_hop_bwd_stats: gy {tuple(gy.shape)} / outpos {tuple(outpos.shape)} against y {tuple(y.shape)}")
-    g = torch.empty((n, d), dtype=torch.float32, device=dev)
-    stats = torch.empty((n, H, 2), dtype=torch.float32, device=dev)
-    ger = torch.empty((n, H), dtype=torch.float32, device=dev)
-    with on_device(dev), _timed("han_block_hop_bwd_stats", dev, 5 * n * d * 4 + n * H * 16):
-        check(_lib.load().allset_han_block_hop_bwd_stats(ptr(y), _pitch(y, "han_block_hop_bwd_stats y"), ptr(bias), ptr(gy),
-                                                         _pitch(gy, "han_block_hop_bwd_stats gy"), ptr(outpos), d, ptr(ppos), ptr(lse),
-                                                         float(slope), ptr(g), d, ptr(stats), ptr(ger), n, H, d // H, stream_of(dev)),
-              "allset_han_block_hop_bwd_stats")
-    return g, stats, ger
-
-
-def han_block_hop_bwd_src(rowptrT: Tensor, colT: Tensor, slotT: Tensor, x: Tensor, el: Tensor, er: Tensor, g: Tensor, stats: Tensor,
-                          slope: float, p_att: float, seed: int, seed_base: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
-    """:func:`han_hop_bwd_src` over a block: ``(gx [n_src, H*C], gel [n_src, H])``; ``g`` / ``stats`` / ``er`` have ``n_dst`` rows."""
-    dev = require_device(rowptrT, colT, slotT, x, el, er, g, stats)
-    for t in (x, el, er, g, stats):
-        _f32(t, "han_block_hop_bwd_src")
-    x, g, el, er, stats = _rowmajor(x), _rowmajor(g), el.contiguous(), er.contiguous(), stats.contiguous()
-    n_src, d = x.shape
-    n_dst, H = er.shape
-    if (tuple(g.shape) != (n_dst, d) or rowptrT.numel() != n_src + 1 or slotT.numel() != colT.numel() or tuple(stats.shape) != (n_dst, H, 2)
-            or tuple(el.shape) != (n_src, H)):
-        raise _lib.AllSetHipError(f"han_block_hop_bwd_src: g {tuple(g.shape)} / rowptrT {rowptrT.numel()} / slotT {slotT.numel()} against "
-                                  f"{n_src} source and {n_dst} target rows of width {d}, {colT.numel()} edges")
-    gx = torch.empty((n_src, d), dtype=torch.float32, device=dev)
-    gel = torch.empty((n_src, H), dtype=torch.float32, device=dev)
-    nnz = colT.numel()
-    with on_device(dev), _timed("han_block_hop_bwd_src", dev, nnz * (4 * d + 12 * H + 8) + (n_src + 1) * 4 + n_src * (8 * d + 8 * H)):
-        check(_lib.load().allset_han_block_hop_bwd_src(nnz, ptr(rowptrT), ptr(colT), ptr(slotT), ptr(el), ptr(er), ptr(x), _ld(x), ptr(g),
-                                                       _ld(g), ptr(stats), float(slope), float(p_att), int(seed), ptr(seed_base), ptr(gx),
-                                                       d, ptr(gel), n_dst, n_src, H, d // H, stream_of(dev)),
-              "allset_han_block_hop_bwd_src")
-    return gx, gel

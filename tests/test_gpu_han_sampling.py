@@ -4,7 +4,7 @@ the endpoint distribution of the raw walks and the collision rate of two walk la
 5-sigma bound; the bipartite hop forward and backward against the float64 restatement of tests/han_sampling_oracle.py with the
 product's own attention-dropout factors; the whole model on the fixed blocks of tests/han_sampling_cases.py against the restatement
 AND the recorded reference at the suite's fp32 parity level, rtol = atol = 1e-4, in eval mode and in training mode (product masks);
-a square block against ``han_gat_propagate`` bit for bit; error paths (argument checks only); the driver twice, bit for bit, and its
+a square block against ``han_gat_propagate`` and a stacked buffer over a non-square block against separate calls, bit for bit; error paths (argument checks only); the driver twice, bit for bit, and its
 training loss over a short synthetic run.
 
 The leaky-relu kink: as in tests/test_gpu_han.py, every comparison asserts from the float64 restatement alone that the nearest
@@ -267,6 +267,34 @@ def test_square_block_is_bit_identical_to_the_full_batch_hop():
             res.append([y.detach()] + [t.grad for t in leaves])
         for a, b in zip(*res):
             assert torch.equal(a, b)
+
+
+def test_stacked_write_over_a_non_square_block_equals_separate_calls_bitwise():
+    """n_src = 5, n_dst = 3: the smallest shape at which a mix-up of the two row counts in the one autograd Function shows."""
+    from allset_amd.functional import han_block_propagate
+    from allset_amd.han_sampling import Block
+    H, C, n_src, n_dst = 2, 4, 5, 3
+    d = H * C
+    edges = [([0, 1, 2, 3, 4], [0, 1, 2, 0, 1]), ([0, 1, 2, 3, 4, 4], [0, 1, 2, 2, 0, 1])]
+    blks = [Block.from_edges(torch.tensor(s, device=DEV), torch.tensor(t, device=DEV), n_src, n_dst) for s, t in edges]
+    g = torch.Generator().manual_seed(0)
+    ins = [[torch.randn(*s, generator=g).to(DEV) for s in ((n_src, d), (n_src, H), (n_dst, H), (d,))] for _ in blks]
+    G = torch.randn(n_dst, 2 * d, generator=g).to(DEV)
+
+    def run(stacked):
+        leaves = [[t.clone().requires_grad_(True) for t in one] for one in ins]
+        if stacked:
+            z = torch.full((n_dst, 2 * d), float("nan"), device=DEV)
+            for i, (blk, (x, el, er, b)) in enumerate(zip(blks, leaves)):
+                z = han_block_propagate(x, el, er, blk, H, 0.2, b, 0.0, out=z, block=i)
+        else:
+            z = torch.cat([han_block_propagate(x, el, er, blk, H, 0.2, b, 0.0) for blk, (x, el, er, b) in zip(blks, leaves)], dim=1)
+        assert tuple(z.shape) == (n_dst, 2 * d)
+        (z * G).sum().backward()
+        return [z.detach()] + [t.grad for one in leaves for t in one]
+
+    for a, b in zip(run(True), run(False)):
+        assert torch.equal(a, b)
 
 
 def test_unbuilt_shapes_and_bad_arguments_are_errors():

@@ -302,7 +302,7 @@ def test_short_row_kernel_matches_row_per_wave_and_oracle(d, mean_deg, device):
         b, _ = ops.segreduce(0, csr.rowptr, csr.col, None, xb, n_t, variant=2)
         torch.testing.assert_close(b.float(), a.float(), rtol=2e-2, atol=2e-2)
     auto, _ = ops.segreduce(0, csr.rowptr, csr.col, None, x.to(device), n_t)          # auto picks by nnz / n_t and by n_t:
-    # the short-row kernel only above 16384 target rows (segreduce.hip kFlatMinRows; ops.CSR.variant)
+    # the short-row kernel only above 16384 target rows (common.h kFlatMinRows; ops.CSR.variant)
     assert csr.variant("segreduce", n_t) == 1
     expect, _ = ops.segreduce(0, csr.rowptr, csr.col, None, x.to(device), n_t, variant=1)
     torch.testing.assert_close(auto, expect, rtol=0, atol=0)

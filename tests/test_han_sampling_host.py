@@ -176,6 +176,19 @@ def test_entry_points_refuse_bad_arguments_before_any_launch():
     assert lib.allset_han_block_hop_bwd_stats(*s) not in (0, -1) and "exceeds the built maximum" in err()
     s[16] = 4
     assert lib.allset_han_block_hop_bwd_stats(*s) == -1 and "null" in err()
+    # the full-graph entry points behind them (Python reaches them through the block ones only; C callers directly)
+    z22 = [0] * 22
+    for fn, i_p in ((lib.allset_han_hop_fwd, 9), (lib.allset_han_hop_bwd_src, 12)):
+        a = list(z22); a[18], a[19], a[20] = 4, 2, 4                             # fine shapes, null pointers
+        assert fn(*a) == -1 and "null" in err()
+        a[20] = 512                                                              # H * C = 1024
+        assert fn(*a) not in (0, -1) and "exceeds the built maximum" in err()
+        a[20], a[i_p] = 4, 1.0                                                   # p_att = 1
+        assert fn(*a) == -1 and "dropout p" in err()
+    s[16] = 4
+    assert lib.allset_han_hop_bwd_stats(*s) == -1 and "null" in err()
+    s[16] = 512
+    assert lib.allset_han_hop_bwd_stats(*s) not in (0, -1) and "exceeds the built maximum" in err()
     assert ctypes.sizeof(ctypes.c_void_p) == 8
 
 
