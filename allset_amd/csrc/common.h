@@ -123,17 +123,6 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {   // {bf16
   asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
   return r;
 }
-// x0, x1 -> packed fp16 planes {hi half: x1, lo half: x0}: h = RN16(x), l = RN16(x - h) (x - h is exact in fp32; fp16 denormals are
-// produced and the f16 MFMA honours them) -- "fp16x3": (x s)(w t) = h h' + h l' + l h' + (l l' <= 2^-22, dropped); the operands must have
-// been scaled into fp16's window by a power of two (csrc/fused_bwd6.hip has the scheme and its error model)
-__device__ __forceinline__ void split2_f16c(float x0, float x1, uint32_t& ph, uint32_t& pl) {
-  float r0, r1;
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(ph) : "v"(x0), "v"(x1));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(ph), "v"(x0));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(ph), "v"(x1));
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(pl) : "v"(r0), "v"(r1));
-}
-
 __device__ __forceinline__ void split3_bf16(float x0, float x1, uint32_t& ph, uint32_t& pm, uint32_t& pl) {
   ph = cvt_pk_bf16(x0, x1);
   const float r0 = x0 - __uint_as_float(ph << 16), r1 = x1 - __uint_as_float(ph & 0xffff0000u);
@@ -238,6 +227,8 @@ __device__ __forceinline__ float leaky_relu(float x, float slope) { return x > 0
 // ---- dropout mask shared by every dense-tail kernel (forward kernels apply it, backward kernels regenerate it).
 // Counter-based: one 32-bit hash per PAIR (16 bits per element) or per QUAD (8 bits per element) of consecutive elements -- see
 // drop_threshold below for which.
+// xorshift-multiply-xorshift: the finaliser of every counter hash here (one 32-bit multiply)
+__device__ __forceinline__ uint32_t hash_mix(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; return x; }
 __device__ __forceinline__ uint32_t pair_hash(uint64_t seed, int64_t pair) {
   // A Weyl-scrambled counter keyed by the 64-bit seed, then one xorshift-multiply-xorshift round.  32-bit integer multiplies run
   // at a quarter of the vector rate on gfx950 and a dropout-bearing kernel hashes once per element pair, so the count matters:
@@ -247,9 +238,7 @@ __device__ __forceinline__ uint32_t pair_hash(uint64_t seed, int64_t pair) {
   // halves, between neighbouring pairs, between rows and between neighbouring seeds, and the balance of all 32 bits are the
   // same to within sampling noise.
   const uint32_t lo = static_cast<uint32_t>(pair), hi = static_cast<uint32_t>(static_cast<uint64_t>(pair) >> 32);
-  uint32_t x = (lo ^ static_cast<uint32_t>(seed)) * 0x9E3779B1U + __umul24(hi, 0x5EBCA7U) + static_cast<uint32_t>(seed >> 32);
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15;
-  return x;
+  return hash_mix((lo ^ static_cast<uint32_t>(seed)) * 0x9E3779B1U + __umul24(hi, 0x5EBCA7U) + static_cast<uint32_t>(seed >> 32));
 }
 // Seeds: entry points take a host-side 64-bit seed by value and, optionally, `seed_base`, a DEVICE pointer to a 64-bit
 // counter.  With a counter the effective seed is counter * golden-ratio + seed, read at kernel start -- so a captured

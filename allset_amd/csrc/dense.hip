@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace allset {
 
@@ -434,7 +435,6 @@ __global__ void relu_dropout_bwd_scalar_kernel(const float* __restrict__ gy, con
 // ---- weight gradient: gW[o][i] = sum_r ga[r][o] * u[r][i],  gb[o] = sum_r ga[r][o] -----------------------
 // Weight gradient.  Grid: x = 128x128 output macro-tile (o-block * tiles_i + i-block), y = split-K slice of the rows;
 // K (= rows) is consumed 32 rows per stage through LDS (wgrad_x6_kernel below).
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 constexpr int kWgTile = 128;
 constexpr int kWgRows = 32;
 
@@ -600,9 +600,6 @@ static inline int ln_lpr(int64_t d) {
 // 32-row stage: 18 fragment reads feed 48 MFMAs.  Two LDS buffers: the next stage's global loads are in flight under
 // this stage's MFMAs, and one wave's conversion overlaps the other wave's MFMAs on the same SIMD.
 constexpr int kWx6Block = 512;
-using bf16x8_t = __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16;
-using f32x4_t = __attribute__((ext_vector_type(4))) float;
-union WFrag { uint4 u; bf16x8_t v; };
 
 __device__ __forceinline__ int wx6_swz(int feat) { return (((feat >> 2) & 3) >> 1) * 3; }
 
@@ -730,9 +727,9 @@ __global__ __launch_bounds__(kWx6Block) void wgrad_x6_kernel(
   // MFMA side: wave tile 64 (o) x 32 (i); lane (j, g) reads piece g of feature row j of a 16-feature tile
   const int fj = lane & 15, fg = lane >> 4;
   const int ob = (wave >> 2) * 64, ib = (wave & 3) * 32;
-  f32x4_t acc[4][2];
+  f32x4 acc[4][2];
 #pragma unroll
-  for (int ot = 0; ot < 4; ++ot) { acc[ot][0] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc[ot][1] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
+  for (int ot = 0; ot < 4; ++ot) { acc[ot][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[ot][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   int a_off[4], b_off[2];
 #pragma unroll
   for (int ot = 0; ot < 4; ++ot) { const int f = ob + ot * 16 + fj; a_off[ot] = f * 16 + 4 * (fg ^ wx6_swz(f)); }
@@ -745,7 +742,7 @@ __global__ __launch_bounds__(kWx6Block) void wgrad_x6_kernel(
 
   auto mfma_stage = [&](int buf) {
     if (i_live) {
-      WFrag b[2][3];
+      Frag b[2][3];
 #pragma unroll
       for (int it = 0; it < 2; ++it)
 #pragma unroll
@@ -753,7 +750,7 @@ __global__ __launch_bounds__(kWx6Block) void wgrad_x6_kernel(
 #pragma unroll
       for (int ot = 0; ot < 4; ++ot) {
         if (!o_live[ot]) continue;
-        WFrag a[3];
+        Frag a[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) a[pl].u = *reinterpret_cast<const uint4*>(&sP[buf][0][pl][a_off[ot]]);
         acc[ot][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2].v, b[0][0].v, acc[ot][0], 0, 0, 0);
@@ -1077,21 +1074,21 @@ __global__ __launch_bounds__(kWx6Block) void wgrad_bf16_kernel(
 
   const int fj = lane & 15, fg = lane >> 4;
   const int ob = (wave >> 2) * 64, ib = (wave & 3) * 32;
-  f32x4_t acc[4][2];
+  f32x4 acc[4][2];
 #pragma unroll
-  for (int ot = 0; ot < 4; ++ot) { acc[ot][0] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc[ot][1] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
+  for (int ot = 0; ot < 4; ++ot) { acc[ot][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[ot][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   int a_off[4], b_off[2];
 #pragma unroll
   for (int ot = 0; ot < 4; ++ot) { const int f = ob + ot * 16 + fj; a_off[ot] = f * 16 + 4 * (fg ^ wx6_swz(f)); }
 #pragma unroll
   for (int it = 0; it < 2; ++it) { const int f = ib + it * 16 + fj; b_off[it] = f * 16 + 4 * (fg ^ wx6_swz(f)); }
   auto mfma_stage = [&](int buf) {
-    WFrag b0, b1;
+    Frag b0, b1;
     b0.u = *reinterpret_cast<const uint4*>(&sP[buf][1][b_off[0]]);
     b1.u = *reinterpret_cast<const uint4*>(&sP[buf][1][b_off[1]]);
 #pragma unroll
     for (int ot = 0; ot < 4; ++ot) {
-      WFrag a;
+      Frag a;
       a.u = *reinterpret_cast<const uint4*>(&sP[buf][0][a_off[ot]]);
       acc[ot][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b0.v, acc[ot][0], 0, 0, 0);
       acc[ot][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b1.v, acc[ot][1], 0, 0, 0);
@@ -1149,9 +1146,6 @@ __global__ __launch_bounds__(kWx6Block) void wgrad_bf16_kernel(
 // A 32-row stage of both operands is copied into LDS exactly as it lies in memory (16-byte pieces, row-major, 32-byte chunks
 // XOR-swizzled by the row) and the MFMA fragments -- 8 consecutive ROWS of one column -- come out of ds_read_b64_tr_b16
 // (hardware 4 x 4 transpose, see fused_bwd.hip): no row-pair packing, no VALU in the staging path at all.
-typedef short wv4s_t __attribute__((ext_vector_type(4)));
-typedef __bf16 wv2bf_t __attribute__((ext_vector_type(2)));
-union WTrFrag { uint4 u; bf16x8_t v; struct { wv4s_t lo, hi; } t; };
 
 template <int PITCH>
 __device__ __forceinline__ int wtr_off(int row, int cbyte) {
@@ -1255,66 +1249,60 @@ __global__ __launch_bounds__(kWx6Block) void wgrad_bf16_tr_kernel(
   const int sw = (fi >> 2) | ((fg & 1) << 2);
   const int ob = (wave >> 1) * (16 * OTN), ib = (wave & 1) * (16 * ITN);     // this wave's tile origin
   const int rowoff_a = (8 * fg + (fi >> 2)) * PA + 8 * (fi & 3), rowoff_b = (8 * fg + (fi >> 2)) * PB + 8 * (fi & 3);
-  f32x4_t acc[OTN][ITN];
+  f32x4 acc[OTN][ITN];
 #pragma unroll
   for (int ot = 0; ot < OTN; ++ot)
 #pragma unroll
-    for (int it = 0; it < ITN; ++it) acc[ot][it] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < ITN; ++it) acc[ot][it] = f32x4{0.f, 0.f, 0.f, 0.f};
   float gbs[OTN];
 #pragma unroll
   for (int ot = 0; ot < OTN; ++ot) gbs[ot] = 0.f;
-  const wv2bf_t ones = __builtin_bit_cast(wv2bf_t, 0x3f803f80u);
+  const bf16x2 ones = __builtin_bit_cast(bf16x2, 0x3f803f80u);
   // the auxiliary tile's ITN column tiles of this wave's I half are shared out over the four waves of that half (wave >> 1):
   // ITN / 4 accumulator tiles each, so that no wave carries 32 more registers
   static_assert(!AUX || ITN % 4 == 0, "auxiliary rows: ITN must be a multiple of 4");
   constexpr int XT = AUX ? ITN / 4 : 1;
   const int wo = __builtin_amdgcn_readfirstlane(wave >> 1);        // wave-uniform
-  f32x4_t accx[XT];
+  f32x4 accx[XT];
 #pragma unroll
-  for (int it = 0; it < XT; ++it) accx[it] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  for (int it = 0; it < XT; ++it) accx[it] = f32x4{0.f, 0.f, 0.f, 0.f};
   float gbx = 0.f;
 
-  auto tr_frag = [&](const uint8_t* p, int half) {
-    WTrFrag f;
-    f.t.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wv4s_t*)(p));
-    f.t.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wv4s_t*)(p + half));
-    return f;
-  };
   auto mfma_stage = [&](int buf) {
     const uint8_t* ba = sS + buf * (SA + SB + SX);
     const uint8_t* bb = ba + SA;
-    WTrFrag a[OTN];
+    Frag a[OTN];
 #pragma unroll
     for (int ot = 0; ot < OTN; ++ot) {
       const int chunk = (ob + ot * 16) / 16;
-      a[ot] = tr_frag(ba + rowoff_a + (((chunk ^ sw) & (PA / 32 - 1)) << 5), 4 * PA);
+      a[ot] = tr_frag2<Frag>(ba + rowoff_a + (((chunk ^ sw) & (PA / 32 - 1)) << 5), 4 * PA);
     }
-    WTrFrag ax;
+    Frag ax;
     ax.u = make_uint4(0u, 0u, 0u, 0u);
     if constexpr (AUX) {
       {
-        ax = tr_frag(bb + SB + (8 * fg + (fi >> 2)) * 32 + 8 * (fi & 3), 4 * 32);
+        ax = tr_frag2<Frag>(bb + SB + (8 * fg + (fi >> 2)) * 32 + 8 * (fi & 3), 4 * 32);
         if (wave == 0) {
-          gbx = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wv2bf_t, ax.u.x), ones, gbx, false);
-          gbx = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wv2bf_t, ax.u.y), ones, gbx, false);
-          gbx = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wv2bf_t, ax.u.z), ones, gbx, false);
-          gbx = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wv2bf_t, ax.u.w), ones, gbx, false);
+          gbx = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, ax.u.x), ones, gbx, false);
+          gbx = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, ax.u.y), ones, gbx, false);
+          gbx = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, ax.u.z), ones, gbx, false);
+          gbx = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, ax.u.w), ones, gbx, false);
         }
       }
     }
     if ((wave & 1) == 0 && part_b != nullptr) {
 #pragma unroll
       for (int ot = 0; ot < OTN; ++ot) {
-        gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wv2bf_t, a[ot].u.x), ones, gbs[ot], false);
-        gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wv2bf_t, a[ot].u.y), ones, gbs[ot], false);
-        gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wv2bf_t, a[ot].u.z), ones, gbs[ot], false);
-        gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wv2bf_t, a[ot].u.w), ones, gbs[ot], false);
+        gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a[ot].u.x), ones, gbs[ot], false);
+        gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a[ot].u.y), ones, gbs[ot], false);
+        gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a[ot].u.z), ones, gbs[ot], false);
+        gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a[ot].u.w), ones, gbs[ot], false);
       }
     }
 #pragma unroll
     for (int it = 0; it < ITN; ++it) {
       const int chunk = (ib + it * 16) / 16;
-      const WTrFrag b = tr_frag(bb + rowoff_b + (((chunk ^ sw) & (PB / 32 - 1)) << 5), 4 * PB);
+      const Frag b = tr_frag2<Frag>(bb + rowoff_b + (((chunk ^ sw) & (PB / 32 - 1)) << 5), 4 * PB);
 #pragma unroll
       for (int ot = 0; ot < OTN; ++ot) acc[ot][it] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ot].v, b.v, acc[ot][it], 0, 0, 0);
       if constexpr (AUX) {

@@ -28,27 +28,18 @@
 //     term are applied there in fp32, the four values are packed to bf16 once, leave through a 16 x 64 per-wave LDS slab
 //     as one 8-byte write and reach memory as whole 128-byte row segments.
 #include "common.h"
+#include "mfma.h"
 
 #include <stdint.h>
 #include <type_traits>
 
 namespace allset {
 
-using bf16x8_b = __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16;
-using f32x4_b = __attribute__((ext_vector_type(4))) float;
-union FragB { uint4 u; bf16x8_b v; };
 typedef unsigned swap2_t __attribute__((ext_vector_type(2)));
 
 constexpr int kBfBlock = 512;
 constexpr int kBfWaves = kBfBlock / kWave;
 constexpr int kSlabPitch = 36;                 // dwords per slab row: 32 of data (64 bf16) + 4 of padding (bank spread)
-
-// dword offset of 16-byte piece t of (k-quarter g, column j) inside the weight image
-template <int KQD, int GS>
-__device__ __forceinline__ int wimg_off(int g, int j, int t) {
-  constexpr int PIECES = KQD / 4, ROWS64 = (64 / KQD) > 0 ? (64 / KQD) : 1;
-  return g * GS + j * KQD + 4 * (t ^ ((j / ROWS64) % PIECES));
-}
 
 __device__ __forceinline__ uint32_t keep_where_positive(uint32_t v, uint32_t y) {
   // per 16-bit half: keep v where the bf16 in y is > 0 (relu output: +0 or positive, so "magnitude bits set" is the test
@@ -220,7 +211,7 @@ __global__ __launch_bounds__(kBfBlock) void linear_bf16_kernel(
     for (int i = 0; i < NPW; ++i) {
       const int idx = tid + i * kBfBlock;
       const int j = idx / (KD / 8), k0 = 8 * (idx % (KD / 8));
-      *reinterpret_cast<uint4*>(&sW[wimg_off<KQD, GS>(k0 / KQ, j, (k0 % KQ) / 8)]) = wreg[i];
+      *reinterpret_cast<uint4*>(&sW[plane_off<KQD, GS>(k0 / KQ, j, (k0 % KQ) / 8)]) = wreg[i];
     }
   } else {
     // W[o][i] (the layer's [out, in] weight), reduction over o: the image row of column i holds its 256 o-values, so the copy is
@@ -255,7 +246,7 @@ __global__ __launch_bounds__(kBfBlock) void linear_bf16_kernel(
             const uint32_t a = c < 2 ? ra.x : c < 4 ? ra.y : c < 6 ? ra.z : ra.w, bb = c < 2 ? rb.x : c < 4 ? rb.y : c < 6 ? rb.z : rb.w;
             d[m] = (c & 1) ? __builtin_amdgcn_perm(bb, a, 0x07060302u) : __builtin_amdgcn_perm(bb, a, 0x05040100u);
           }
-          *reinterpret_cast<uint4*>(&sW[wimg_off<KQD, GS>(gq, 8 * ib + c, tp)]) = make_uint4(d[0], d[1], d[2], d[3]);
+          *reinterpret_cast<uint4*>(&sW[plane_off<KQD, GS>(gq, 8 * ib + c, tp)]) = make_uint4(d[0], d[1], d[2], d[3]);
         }
       }
     }
@@ -339,23 +330,23 @@ __global__ __launch_bounds__(kBfBlock) void linear_bf16_kernel(
   // half the LDS reads -- left the matrix phase alone at 26.4 us against 28.6 and the whole launch 15 us SLOWER (the rows of the
   // next step can only be requested once both steps' fragments are consumed): the phase is MFMA issue + the fixed weight staging,
   // not LDS rate.  tools/linear_bf16_ablation.py, profiles/r06_bf16_linear_ablation.txt.)
-  auto matrix = [&](const uint32_t (&a)[KQD], f32x4_b (&acc)[NTILE]) {
+  auto matrix = [&](const uint32_t (&a)[KQD], f32x4 (&acc)[NTILE]) {
 #ifdef ALLSET_BF16_ABL_NOMFMA               // (ablation: no matrix phase -- the accumulators take the rows' bits so that they stay live)
 #pragma unroll
     for (int tl = 0; tl < NTILE; ++tl)
-      acc[tl] = f32x4_b{__uint_as_float(a[(2 * tl) % KQD]), __uint_as_float(a[(2 * tl + 1) % KQD]), __uint_as_float(a[(2 * tl + 7) % KQD]), 0.f};
+      acc[tl] = f32x4{__uint_as_float(a[(2 * tl) % KQD]), __uint_as_float(a[(2 * tl + 1) % KQD]), __uint_as_float(a[(2 * tl + 7) % KQD]), 0.f};
 #else
 #pragma unroll
-    for (int tl = 0; tl < NTILE; ++tl) acc[tl] = f32x4_b{0.f, 0.f, 0.f, 0.f};
+    for (int tl = 0; tl < NTILE; ++tl) acc[tl] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-      FragB fa;
+      Frag fa;
       fa.u = make_uint4(a[4 * t], a[4 * t + 1], a[4 * t + 2], a[4 * t + 3]);
 #pragma unroll
       for (int tl = 0; tl < NTILE; tl += 2) {       // two column tiles: two independent accumulator chains
-        FragB b0, b1;
-        b0.u = *reinterpret_cast<const uint4*>(&sW[wimg_off<KQD, GS>(g, tl * 16 + ri, t)]);
-        b1.u = *reinterpret_cast<const uint4*>(&sW[wimg_off<KQD, GS>(g, tl * 16 + 16 + ri, t)]);
+        Frag b0, b1;
+        b0.u = *reinterpret_cast<const uint4*>(&sW[plane_off<KQD, GS>(g, tl * 16 + ri, t)]);
+        b1.u = *reinterpret_cast<const uint4*>(&sW[plane_off<KQD, GS>(g, tl * 16 + 16 + ri, t)]);
         acc[tl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0.v, fa.v, acc[tl], 0, 0, 0);
         acc[tl + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1.v, fa.v, acc[tl + 1], 0, 0, 0);
       }
@@ -367,7 +358,7 @@ __global__ __launch_bounds__(kBfBlock) void linear_bf16_kernel(
   // neighbouring 16-lane rows, v_permlane32_swap the pairs -- so that lane (ri, g) ends up with the 16 consecutive columns
   // 64 hb + 16 g .. of row ri and a row leaves as whole 128-byte segments.  No LDS slab, no lgkmcnt round trips (the slab form,
   // -DALLSET_BF16_SLAB_EPILOGUE, cost 13 us of LDS waits per launch beside the stores themselves).
-  auto epilogue = [&](auto with_acc, f32x4_b (&acc)[NTILE], int64_t chunk, const uint2 (&accv)[decltype(with_acc)::value ? NTILE : 1], const float4& ga4) {
+  auto epilogue = [&](auto with_acc, f32x4 (&acc)[NTILE], int64_t chunk, const uint2 (&accv)[decltype(with_acc)::value ? NTILE : 1], const float4& ga4) {
     constexpr bool WITH_ACC = decltype(with_acc)::value;
     const int rh = rows_here(chunk);
 #ifdef ALLSET_BF16_ABL_NOEPI                // (ablation: no epilogue; one never-true store keeps the accumulators live)
@@ -543,7 +534,7 @@ __global__ __launch_bounds__(kBfBlock) void linear_bf16_kernel(
       }
     }
     const float4 ga4 = load_ga4(chunk);
-    f32x4_b acc[NTILE];
+    f32x4 acc[NTILE];
     matrix(a, acc);
     __builtin_amdgcn_sched_barrier(0);
     request(a, x, ldx, chunk + ahead * stride);

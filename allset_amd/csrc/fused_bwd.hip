@@ -25,52 +25,20 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace allset {
 
-using bf16x8m = __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16;
-using f32x4m = __attribute__((ext_vector_type(4))) float;
-using f32x16m = __attribute__((ext_vector_type(16))) float;
-typedef short v4s_t __attribute__((ext_vector_type(4)));
-typedef __bf16 v2bf_t __attribute__((ext_vector_type(2)));
-union FragM { uint4 u; bf16x8m v; struct { v4s_t lo, hi; } t; };
 constexpr int kMBlock = 256;
 constexpr int kMWaves = kMBlock / kWave;
 
-// dword offset of 16-byte piece t of (k-quarter g, column j) inside a W plane (same image as fused_mlp.hip)
-template <int KQD, int GS>
-__device__ __forceinline__ int mplane_off(int g, int j, int t) {
-  constexpr int PIECES = KQD / 4, ROWS64 = 64 / KQD;
-  return g * GS + j * KQD + 4 * (t ^ ((j / ROWS64) % PIECES));
-}
-
 // byte offset of (row, column byte) in a [16][PITCH bytes] row-major bf16 plane whose 64-byte chunks are XOR-swizzled by
-// the row: the four rows a transpose-read touches land in four different bank quarters.
+// the row: the four rows a transpose-read touches land in four different bank quarters.  (Not mfma.h swizzle256: any pitch, and
+// the 16-byte pieces inside a chunk stay in order.)
 template <int PITCH>
 __device__ __forceinline__ int img_off(int row, int colbyte) {
   constexpr int NCH = PITCH / 64;
   return row * PITCH + ((((colbyte >> 6) ^ row) & (NCH - 1)) << 6) + (colbyte & 63);
-}
-
-// sum over the 16 lanes of a DPP row (= the 16 lanes that share one matrix row in the row-major epilogue), result in
-// every lane; four VALU instructions with DPP operands instead of four LDS permutes with their address registers
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp_f<0xB1>(v);       // quad_perm [1,0,3,2]
-  v += dpp_f<0x4E>(v);       // quad_perm [2,3,0,1]
-  v += dpp_f<0x141>(v);      // row_half_mirror
-  v += dpp_f<0x140>(v);      // row_mirror
-  return v;
-}
-
-__device__ __forceinline__ bf16x8m tr_frag(const uint8_t* p, int half_stride) {
-  FragM f;
-  f.t.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_t*)(p));
-  f.t.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_t*)(p + half_stride));
-  return f.v;
 }
 
 template <int OD, int ID, bool HAS_LN, bool DROP_IN, bool RELU_IN, bool HAS_MASK, bool HAS_ACC>
@@ -118,7 +86,7 @@ __global__ __launch_bounds__(kMBlock) void fused_linear_bwd_all_kernel(
           uint32_t ph, pm, pl;
           split3_bf16(w0[it], w1[it], ph, pm, pl);
           const int e = o % OQ;
-          const int off = mplane_off<OQD, GS>(o / OQ, i, e / 8) + (e % 8) / 2;
+          const int off = plane_off<OQD, GS>(o / OQ, i, e / 8) + (e % 8) / 2;
           sWh[off] = ph; sWm[off] = pm; sWl[off] = pl;
         }
       }
@@ -147,7 +115,8 @@ __global__ __launch_bounds__(kMBlock) void fused_linear_bwd_all_kernel(
   // them) are therefore NOT loop invariants kept in registers: every phase of the row loop re-derives the few it needs from an
   // opaque copy of the lane id (a handful of integer instructions per 16-row chunk); hoisted, they were spilled to scratch and
   // every reload drained the prefetch queue (one in-order vmcnt for loads, stores and scratch on gfx9).
-#define ALLSET_FRESH_LANE(name) int name = lane0; __asm__ volatile("" : "+v"(name))
+  // (not mfma.h ALLSET_FRESH_LANE: an opaque COPY of lane0, nothing recomputed)
+#define ALLSET_OPAQUE_LANE(name) int name = lane0; __asm__ volatile("" : "+v"(name))
 
   float4 dg[NH], db[NH];
 #pragma unroll
@@ -155,7 +124,7 @@ __global__ __launch_bounds__(kMBlock) void fused_linear_bwd_all_kernel(
   float gbs[OT];                                   // bias gradient: column ot*32 + (lane & 31), rows 8 (lane >> 5) .. +7 of every chunk
 #pragma unroll
   for (int ot = 0; ot < OT; ++ot) gbs[ot] = 0.f;
-  f32x16m gw[OT][IT];
+  f32x16 gw[OT][IT];
 #pragma unroll
   for (int ot = 0; ot < OT; ++ot)
 #pragma unroll
@@ -228,7 +197,7 @@ __global__ __launch_bounds__(kMBlock) void fused_linear_bwd_all_kernel(
   request_rows(chunk, lane0);
   for (; chunk < n_chunks; chunk += stride) {
     // ---- ga: epilogue mask of the forward, bf16 planes
-    ALLSET_FRESH_LANE(lane);
+    ALLSET_OPAQUE_LANE(lane);
     const int ri = lane & 15, g = lane >> 4, c4 = ri * 4;
     const int m_shift = (((g * OQ) % 64) / 4) & 7;
     // writer of ga (backward-data layout): row ri, columns g*OQ .. +OQ-1 = OQ*2 bytes inside one 64-byte chunk of the image
@@ -263,14 +232,14 @@ __global__ __launch_bounds__(kMBlock) void fused_linear_bwd_all_kernel(
     // ---- backward-data: gu = ga @ W on the bf16 matrix pipe (six of nine plane products)
     // B fragments (W planes, LDS) are fetched ONE block ahead by hand: two sets of six 16-byte fragments, so the matrix pipe
     // never waits on LDS and the register cost of the look-ahead is fixed (one wave per SIMD: nobody else hides it)
-    f32x4m acc[NTILE];
+    f32x4 acc[NTILE];
 #pragma unroll
-    for (int tl = 0; tl < NTILE; ++tl) acc[tl] = f32x4m{0.f, 0.f, 0.f, 0.f};
+    for (int tl = 0; tl < NTILE; ++tl) acc[tl] = f32x4{0.f, 0.f, 0.f, 0.f};
     constexpr int NBLK = T * (NTILE / 2);
-    FragM bw[2][6];
+    Frag bw[2][6];
     // fragment address of (k-quarter g, column tl*16 + ri, k-step t) = wb_base + 4 (t ^ wb_swz) + tl * 16 * OQD dwords: the
     // swizzle term does not depend on the column tile (16 columns are a whole number of swizzle periods), so a k-step needs
-    // ONE address register and the tiles are immediate offsets -- spelled out because the generic mplane_off() form made the
+    // ONE address register and the tiles are immediate offsets -- spelled out because the generic plane_off() form made the
     // compiler hoist 2 x 16 per-block addresses out of the row loop and spill them
     int xo[T];
 #pragma unroll
@@ -278,7 +247,7 @@ __global__ __launch_bounds__(kMBlock) void fused_linear_bwd_all_kernel(
       xo[t] = wb_base + 4 * (t ^ wb_swz);
       __asm__ volatile("" : "+v"(xo[t]));             // opaque: one register per k-step, everything else immediates
     }
-    auto load_b = [&](FragM (&b)[6], int blk) {
+    auto load_b = [&](Frag (&b)[6], int blk) {
       const int t = blk / (NTILE / 2), tl = 2 * (blk % (NTILE / 2));
       const uint32_t* p = sW + xo[t] + tl * 16 * OQD;
       b[0].u = *reinterpret_cast<const uint4*>(p);
@@ -288,8 +257,8 @@ __global__ __launch_bounds__(kMBlock) void fused_linear_bwd_all_kernel(
       b[4].u = *reinterpret_cast<const uint4*>(p + 16 * OQD + 4 * GS);
       b[5].u = *reinterpret_cast<const uint4*>(p + 16 * OQD + 8 * GS);
     };
-    FragM fa[2][3];                                     // A fragments of k-step t: [t & 1][h, m, l]
-    auto load_a = [&](FragM (&a)[3], int t) {
+    Frag fa[2][3];                                     // A fragments of k-step t: [t & 1][h, m, l]
+    auto load_a = [&](Frag (&a)[3], int t) {
       a[0].u = *reinterpret_cast<const uint4*>(reg + 0 * PLA + wa_off + 16 * t);
       a[1].u = *reinterpret_cast<const uint4*>(reg + 1 * PLA + wa_off + 16 * t);
       a[2].u = *reinterpret_cast<const uint4*>(reg + 2 * PLA + wa_off + 16 * t);
@@ -305,8 +274,8 @@ __global__ __launch_bounds__(kMBlock) void fused_linear_bwd_all_kernel(
       const int t = blk / (NTILE / 2), tl = 2 * (blk % (NTILE / 2));
       if (blk + 1 < NBLK) load_b(bw[(blk + 1) & 1], blk + 1);
       if (tl == NTILE - 2 && t + 1 < T) load_a(fa[(t + 1) & 1], t + 1);
-      const FragM &fa_h = fa[t & 1][0], &fa_m = fa[t & 1][1], &fa_l = fa[t & 1][2];
-      const FragM (&b)[6] = bw[blk & 1];
+      const Frag &fa_h = fa[t & 1][0], &fa_m = fa[t & 1][1], &fa_l = fa[t & 1][2];
+      const Frag (&b)[6] = bw[blk & 1];
       acc[tl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_l.v, b[0].v, acc[tl], 0, 0, 0);
       acc[tl + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_l.v, b[3].v, acc[tl + 1], 0, 0, 0);
       acc[tl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_h.v, b[2].v, acc[tl], 0, 0, 0);
@@ -436,30 +405,30 @@ __global__ __launch_bounds__(kMBlock) void fused_linear_bwd_all_kernel(
     // reads of the image; the bias gradient falls out of them (sum of the planes = ga exactly; v_dot2c with ones)
     // Transpose-reader: 16-lane group q4 -> k-half kh = q4 >> 1, column half ch = q4 & 1 of a 32-column tile; lane i of the group
     // supplies the address of row 8 kh + (i >> 2) [+4 for the second read], 4 columns at 4 (i & 3).
-    ALLSET_FRESH_LANE(lane_w);
+    ALLSET_OPAQUE_LANE(lane_w);
     const int q4 = lane_w >> 4, tr_r = (lane_w & 15) >> 2, tr_row = 8 * (q4 >> 1) + tr_r, tr_in = 32 * (q4 & 1) + 8 * (lane_w & 3);
     int ta_off[OT], tb_off[IT];
 #pragma unroll
     for (int t = 0; t < OT; ++t) ta_off[t] = tr_row * PA + (((t ^ tr_r) & (PA / 64 - 1)) << 6) + tr_in;
 #pragma unroll
     for (int t = 0; t < IT; ++t) tb_off[t] = tr_row * PB + (((t ^ tr_r) & (PB / 64 - 1)) << 6) + tr_in;
-    bf16x8m wa[OT][3];
+    bf16x8 wa[OT][3];
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot)
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) wa[ot][pl] = tr_frag(reg + pl * PLA + ta_off[ot], 4 * PA);
+      for (int pl = 0; pl < 3; ++pl) wa[ot][pl] = tr_frag2<bf16x8>(reg + pl * PLA + ta_off[ot], 4 * PA);
     __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the image is overwritten next (one wave: in-order LDS)
     {
-      const v2bf_t ones = __builtin_bit_cast(v2bf_t, 0x3f803f80u);
+      const bf16x2 ones = __builtin_bit_cast(bf16x2, 0x3f803f80u);
 #pragma unroll
       for (int ot = 0; ot < OT; ++ot)
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
-          FragM f; f.v = wa[ot][pl];
-          gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2bf_t, f.u.x), ones, gbs[ot], false);
-          gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2bf_t, f.u.y), ones, gbs[ot], false);
-          gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2bf_t, f.u.z), ones, gbs[ot], false);
-          gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2bf_t, f.u.w), ones, gbs[ot], false);
+          Frag f; f.v = wa[ot][pl];
+          gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, f.u.x), ones, gbs[ot], false);
+          gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, f.u.y), ones, gbs[ot], false);
+          gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, f.u.z), ones, gbs[ot], false);
+          gbs[ot] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, f.u.w), ones, gbs[ot], false);
         }
     }
     // ---- u planes into the image: row it*4 + (lane>>4), columns hb*64 + c4 .. +3 (8 bytes a plane)
@@ -481,9 +450,9 @@ __global__ __launch_bounds__(kMBlock) void fused_linear_bwd_all_kernel(
     // ---- weight gradient: gW[o][i] += sum over the chunk's 16 rows of ga[r][o] u[r][i]; 32 x 32 tiles, K = 16 = the chunk
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
-      bf16x8m wb[3];
+      bf16x8 wb[3];
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) wb[pl] = tr_frag(reg + pl * PLB + tb_off[it], 4 * PB);
+      for (int pl = 0; pl < 3; ++pl) wb[pl] = tr_frag2<bf16x8>(reg + pl * PLB + tb_off[it], 4 * PB);
       // the six plane products of an i-tile, each over ALL o-tiles before the next: OT independent accumulator chains between
       // two MFMAs on the same accumulator (a 32x32x16 result is not ready for 16 passes; one wave per SIMD has no neighbour to
       // fill the gap, so two interleaved chains -- enough at two waves per SIMD -- leave the pipe waiting)

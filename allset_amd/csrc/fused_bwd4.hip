@@ -4,7 +4,7 @@
 // Why: tools/micro/mfma_valu_corun.hip -- an MFMA-only wave and a VALU-only wave on the same SIMD run concurrently (1000 us of
 // MFMAs + 570 us of v_fma finish in 1040 us), while two waves that are both in a matrix phase share the pipe and two waves
 // that are both in a vector phase share the issue port.  Every symmetric organisation of this kernel (one wave per SIMD,
-// fused_bwd.hip; pairs, fused_bwd2.hip; eight cooperating waves in lock-step phases, fused_bwd3.hip) measured
+// fused_bwd.hip; pairs; eight cooperating waves in lock-step phases -- docs/DESIGN_HISTORY.md 6a has the latter two) measured
 // vector time + matrix time (+ barrier skew): 0.47-0.64 ms per [1M,128] x [128,128] Linear.  With the roles split the two
 // kinds of work overlap BY CONSTRUCTION and the kernel costs max(vector, matrix) per stage.
 //
@@ -25,47 +25,18 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace allset {
 
-using bf16x8r = __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16;
-using f32x4r = __attribute__((ext_vector_type(4))) float;
-using f32x16r = __attribute__((ext_vector_type(16))) float;
-typedef short v4sr_t __attribute__((ext_vector_type(4)));
-union FragR { uint4 u; bf16x8r v; struct { v4sr_t lo, hi; } t; };
 constexpr int kRBlock = 512;
 constexpr int kRRows = 32;                     // rows per stage
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_fr(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row16_sum_r(float v) {     // sum over the 16 lanes of a DPP row, result in every lane of it
-  v += dpp_fr<0xB1>(v);
-  v += dpp_fr<0x4E>(v);
-  v += dpp_fr<0x141>(v);
-  v += dpp_fr<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ bf16x8r tr_frag2_r(const uint8_t* lo, const uint8_t* hi) {
-  FragR f;
-  f.t.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4sr_t*)(lo));
-  f.t.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4sr_t*)(hi));
-  return f.v;
-}
-// byte offset of (row, column byte) in a [rows][256 B] bf16 plane: 64-byte chunk XOR row & 3, 16-byte piece XOR (row >> 2) & 3
-// (fused_bwd3.hip: both the row-wise 16-byte fragment reads and the transpose reads are then conflict-free)
-__device__ __forceinline__ int img_off_r(int row, int colbyte) {
-  return row * 256 + ((((colbyte >> 6) ^ row) & 3) << 6) + (((((colbyte >> 4) & 3) ^ (row >> 2)) & 3) << 4) + (colbyte & 15);
-}
-__device__ __forceinline__ uint32_t hash_mix_r(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; return x; }
 #ifdef ALLSET_ABL4_NOBAR            // ablation builds only: timing without the barriers, results wrong
-#define ALLSET_ROLE_TICK() __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+#define ALLSET_TICK() ALLSET_TICK_NO_BARRIER()
 #else
-#define ALLSET_ROLE_TICK() __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+#define ALLSET_TICK() ALLSET_TICK_BARRIER()
 #endif
-#define ALLSET_FRESH_LANE_R(name) \
-  int name = static_cast<int>(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))); __asm__ volatile("" : "+v"(name))
 
 template <bool HAS_LN, bool DROP_IN, bool RELU_IN, bool HAS_MASK, bool HAS_ACC, bool HAS_AUX>
 __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
@@ -112,9 +83,9 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
   __syncthreads();
 #ifdef ALLSET_ABL4_TIMING          // diagnostic builds only: cycles per segment of waves 0 (vector) and 4 (matrix) of workgroup 0
   uint64_t tph[4] = {0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#define ALLSET_RMARK(k) do { const uint64_t tn = __builtin_readcyclecounter(); tph[k] += tn - tlast; tlast = tn; } while (0)
+#define ALLSET_MARK(k) ALLSET_PHASE_MARK(k)
 #else
-#define ALLSET_RMARK(k) do {} while (0)
+#define ALLSET_MARK(k) do {} while (0)
 #endif
 
   if (wave < 4) {
@@ -214,7 +185,7 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
           uint32_t h0, m0, l0, h1, m1, l1;
           split3_bf16(v.x, v.y, h0, m0, l0);
           split3_bf16(v.z, v.w, h1, m1, l1);
-          const int wo = img_off_r(lr, 128 * hb + 8 * c);
+          const int wo = swizzle256(lr, 128 * hb + 8 * c);
           *reinterpret_cast<uint2*>(img + 0 * PLANE + wo) = make_uint2(h0, h1);
           *reinterpret_cast<uint2*>(img + 1 * PLANE + wo) = make_uint2(m0, m1);
           *reinterpret_cast<uint2*>(img + 2 * PLANE + wo) = make_uint2(l0, l1);
@@ -268,13 +239,13 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
             // pair index of (row, column) = stage * 2048 + (lr * 128 + column) / 2: the lane's part is < 2048 -> an OR (common.h pair_hash)
             if (thr_in & kDrop8) {     // 8 bits per element: ONE hash for the lane's float4 (quad index = stage * 1024 + lane part)
               const uint32_t lo = stage_quad_lo | static_cast<uint32_t>((lr * ID + 64 * hb + 4 * c) >> 2);
-              const uint32_t h = hash_mix_r((lo ^ seed_lo) * 0x9E3779B1U + hi_term_q), t8 = thr_in & 0xffu;
+              const uint32_t h = hash_mix((lo ^ seed_lo) * 0x9E3779B1U + hi_term_q), t8 = thr_in & 0xffu;
               kp.x = (h & 0xffu) >= t8 ? keep_in : 0.f; kp.y = ((h >> 8) & 0xffu) >= t8 ? keep_in : 0.f;
               kp.z = ((h >> 16) & 0xffu) >= t8 ? keep_in : 0.f; kp.w = (h >> 24) >= t8 ? keep_in : 0.f;
             } else {
               const uint32_t lo = stage_pair_lo | static_cast<uint32_t>((lr * ID + 64 * hb + 4 * c) >> 1);
-              const uint32_t h0 = hash_mix_r((lo ^ seed_lo) * 0x9E3779B1U + hi_term);
-              const uint32_t h1 = hash_mix_r(((lo + 1u) ^ seed_lo) * 0x9E3779B1U + hi_term);
+              const uint32_t h0 = hash_mix((lo ^ seed_lo) * 0x9E3779B1U + hi_term);
+              const uint32_t h1 = hash_mix(((lo + 1u) ^ seed_lo) * 0x9E3779B1U + hi_term);
               kp.x = (h0 & 0xffffu) >= thr_in ? keep_in : 0.f; kp.y = (h0 >> 16) >= thr_in ? keep_in : 0.f;
               kp.z = (h1 & 0xffffu) >= thr_in ? keep_in : 0.f; kp.w = (h1 >> 16) >= thr_in ? keep_in : 0.f;
             }
@@ -307,7 +278,7 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
             uint32_t h0, m0, l0, h1, m1, l1;
             split3_bf16(u.x, u.y, h0, m0, l0);
             split3_bf16(u.z, u.w, h1, m1, l1);
-            const int wo = img_off_r(lr, 128 * hb + 8 * c);
+            const int wo = swizzle256(lr, 128 * hb + 8 * c);
             *reinterpret_cast<uint2*>(img + 0 * PLANE + wo) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(img + 1 * PLANE + wo) = make_uint2(m0, m1);
             *reinterpret_cast<uint2*>(img + 2 * PLANE + wo) = make_uint2(l0, l1);
@@ -364,7 +335,7 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
           }
         }
         float s1 = 0.f, s2 = 0.f;
-        if constexpr (HAS_LN) { s1 = row16_sum_r(a1) * inv_i; s2 = row16_sum_r(a2) * inv_i; }
+        if constexpr (HAS_LN) { s1 = row16_sum(a1) * inv_i; s2 = row16_sum(a2) * inv_i; }
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb) {
           float4 o = v[hb];
@@ -404,7 +375,7 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
             split3_bf16(u.x, u.y, h0, m0, l0);
             split3_bf16(u.z, u.w, h1, m1, l1);
             uint8_t* img = sU + (k % 2) * IMG;
-            const int wo = img_off_r(lr, 128 * hb + 8 * c);
+            const int wo = swizzle256(lr, 128 * hb + 8 * c);
             *reinterpret_cast<uint2*>(img + 0 * PLANE + wo) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(img + 1 * PLANE + wo) = make_uint2(m0, m1);
             *reinterpret_cast<uint2*>(img + 2 * PLANE + wo) = make_uint2(l0, l1);
@@ -418,8 +389,8 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
     request_gy(1, lane0, agS[1], amS[1]);
     request_x(1, lane0, xrS[1], stS[1], g4S[1]);
     S0(0, agS[0], amS[0]);
-    ALLSET_ROLE_TICK();
-    ALLSET_RMARK(3);
+    ALLSET_TICK();
+    ALLSET_MARK(3);
     // Two stages per trip: stage k lives in register set 0, stage k + 1 in set 1.  The trip has NO conditional half: the compiler's
     // s_waitcnt insertion takes the shortest path between a load and its use, and with "if (k + 1 < T) { second half }" inside the
     // loop that path skipped the half's 14 memory operations -- the first S2 of every trip then waited with vmcnt(3) / vmcnt(0),
@@ -428,30 +399,30 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
     for (; k + 1 < T; k += 2) {
       S0(k + 1, agS[1], amS[1]);
       S2a(k, xrS[0], stS[0], g4S[0]);
-      ALLSET_RMARK(0);
-      ALLSET_ROLE_TICK();
-      ALLSET_RMARK(1);
+      ALLSET_MARK(0);
+      ALLSET_TICK();
+      ALLSET_MARK(1);
       S2b(k);
-      ALLSET_RMARK(2);
-      ALLSET_ROLE_TICK();
-      ALLSET_RMARK(3);
+      ALLSET_MARK(2);
+      ALLSET_TICK();
+      ALLSET_MARK(3);
       if (k + 2 < T) S0(k + 2, agS[0], amS[0]);
       S2a(k + 1, xrS[1], stS[1], g4S[1]);
-      ALLSET_RMARK(0);
-      ALLSET_ROLE_TICK();
-      ALLSET_RMARK(1);
+      ALLSET_MARK(0);
+      ALLSET_TICK();
+      ALLSET_MARK(1);
       S2b(k + 1);
-      ALLSET_RMARK(2);
-      ALLSET_ROLE_TICK();
-      ALLSET_RMARK(3);
+      ALLSET_MARK(2);
+      ALLSET_TICK();
+      ALLSET_MARK(3);
     }
     if (k < T) {                            // odd stage count: the last stage, in set 0
       S2a(k, xrS[0], stS[0], g4S[0]);
-      ALLSET_ROLE_TICK();
+      ALLSET_TICK();
       S2b(k);
-      ALLSET_ROLE_TICK();
+      ALLSET_TICK();
     }
-    ALLSET_ROLE_TICK();                     // (the matrix waves' last weight-gradient step)
+    ALLSET_TICK();                     // (the matrix waves' last weight-gradient step)
     // ---- column sums held by the vector waves (dgamma, dbeta, bias gradient): the four row groups of a lane column fold first,
     // then the four waves through LDS in a fixed order
     {
@@ -499,7 +470,7 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
     // ---- this wave's slice of W as MFMA B fragments: column tile ct (16 columns 32 m + 16 ct + n), k-step t, plane pl;
     // lane (n = lane & 15, kg = lane >> 4) holds W[o = 32 kg + 8 t + j][column], j = 0..7 (k-order of fused_mlp.hip / fused_bwd.hip:
     // the input gradient is bit-identical to theirs)
-    FragR wq[2][4][3];
+    Frag wq[2][4][3];
     {
       const int nn = lane0 & 15, kg = lane0 >> 4;
 #pragma unroll
@@ -517,7 +488,7 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
           wq[ct][t][2].u = make_uint4(pl[0], pl[1], pl[2], pl[3]);
         }
     }
-    f32x16r gw[2][2];
+    f32x16 gw[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -528,29 +499,29 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
     // ---- S1(k): backward-data for this wave's 32 output columns of the stage's 32 rows: 2 row tiles x 2 column tiles = four
     // independent accumulator chains; the A fragments of step t + 1 are requested before step t's MFMAs
     auto S1 = [&](int64_t k) {
-      ALLSET_FRESH_LANE_R(lane);
+      ALLSET_FRESH_LANE(lane);
       const int ri = lane & 15, kg = lane >> 4;
       const uint8_t* img = sGA + (k % 3) * IMG;
-      auto load_a = [&](FragR (&f0)[3], FragR (&f1)[3], int t) {
-        const int o0 = img_off_r(ri, 64 * kg + 16 * t), o1 = img_off_r(16 + ri, 64 * kg + 16 * t);
+      auto load_a = [&](Frag (&f0)[3], Frag (&f1)[3], int t) {
+        const int o0 = swizzle256(ri, 64 * kg + 16 * t), o1 = swizzle256(16 + ri, 64 * kg + 16 * t);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
           f0[pl].u = *reinterpret_cast<const uint4*>(img + pl * PLANE + o0);
           f1[pl].u = *reinterpret_cast<const uint4*>(img + pl * PLANE + o1);
         }
       };
-      FragR fa0[2][3], fa1[2][3];
-      f32x4r acc[2][2];
+      Frag fa0[2][3], fa1[2][3];
+      f32x4 acc[2][2];
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4r{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
       load_a(fa0[0], fa1[0], 0);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         if (t + 1 < 4) load_a(fa0[(t + 1) & 1], fa1[(t + 1) & 1], t + 1);
-        const FragR (&a0)[3] = fa0[t & 1];
-        const FragR (&a1)[3] = fa1[t & 1];
+        const Frag (&a0)[3] = fa0[t & 1];
+        const Frag (&a1)[3] = fa1[t & 1];
 #ifndef ALLSET_ABL4_NOMFMA
         constexpr int PA_[6] = {2, 0, 1, 1, 0, 0}, PB_[6] = {0, 2, 1, 0, 1, 0};     // l.h, h.l, m.m, m.h, h.m, h.h
 #pragma unroll
@@ -575,21 +546,21 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
     };
     // ---- S3(k): weight gradient, this wave's 64 x 64 tile of gW; K = the stage's 32 rows in two steps of 16; A = ga^T, B = u
     auto S3 = [&](int64_t k) {
-      ALLSET_FRESH_LANE_R(lane_w);
+      ALLSET_FRESH_LANE(lane_w);
       const uint8_t* ia = sGA + (k % 3) * IMG;
       const uint8_t* iu = sU + (k % 2) * IMG;
       const int q4 = lane_w >> 4, tr_r = (lane_w & 15) >> 2, tr_row = 8 * (q4 >> 1) + tr_r, tr_in = 32 * (q4 & 1) + 8 * (lane_w & 3);
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
-        bf16x8r wa[2][3], wb[2][3];
+        bf16x8 wa[2][3], wb[2][3];
 #pragma unroll
         for (int tl = 0; tl < 2; ++tl) {
-          const int a_lo = img_off_r(16 * kb + tr_row, 64 * (2 * oh + tl) + tr_in), a_hi = img_off_r(16 * kb + tr_row + 4, 64 * (2 * oh + tl) + tr_in);
-          const int b_lo = img_off_r(16 * kb + tr_row, 64 * (2 * ih + tl) + tr_in), b_hi = img_off_r(16 * kb + tr_row + 4, 64 * (2 * ih + tl) + tr_in);
+          const int a_lo = swizzle256(16 * kb + tr_row, 64 * (2 * oh + tl) + tr_in), a_hi = swizzle256(16 * kb + tr_row + 4, 64 * (2 * oh + tl) + tr_in);
+          const int b_lo = swizzle256(16 * kb + tr_row, 64 * (2 * ih + tl) + tr_in), b_hi = swizzle256(16 * kb + tr_row + 4, 64 * (2 * ih + tl) + tr_in);
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl) {
-            wa[tl][pl] = tr_frag2_r(ia + pl * PLANE + a_lo, ia + pl * PLANE + a_hi);
-            wb[tl][pl] = tr_frag2_r(iu + pl * PLANE + b_lo, iu + pl * PLANE + b_hi);
+            wa[tl][pl] = tr_frag2<bf16x8>(ia + pl * PLANE + a_lo, ia + pl * PLANE + a_hi);
+            wb[tl][pl] = tr_frag2<bf16x8>(iu + pl * PLANE + b_lo, iu + pl * PLANE + b_hi);
           }
         }
 #ifndef ALLSET_ABL4_NOMFMA
@@ -602,27 +573,27 @@ __global__ __launch_bounds__(kRBlock, 2) void fused_linear_bwd_roles_kernel(
           gw[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[1][PA_[pr]], wb[1][PB_[pr]], gw[1][1], 0, 0, 0);
         }
 #else
-        { FragR f; f.v = wa[0][0]; FragR g2; g2.v = wb[1][1]; FragR g3; g3.v = wa[1][2]; FragR g4; g4.v = wb[0][2];
+        { Frag f; f.v = wa[0][0]; Frag g2; g2.v = wb[1][1]; Frag g3; g3.v = wa[1][2]; Frag g4; g4.v = wb[0][2];
           gw[0][0][0] += __builtin_bit_cast(float, f.u.x ^ g2.u.y ^ g3.u.z ^ g4.u.w); }
 #endif
         __builtin_amdgcn_sched_barrier(0);
       }
     };
 
-    ALLSET_ROLE_TICK();
-    ALLSET_RMARK(3);
+    ALLSET_TICK();
+    ALLSET_MARK(3);
     for (int64_t k = 0; k < T; ++k) {
       S1(k);
-      ALLSET_RMARK(0);
-      ALLSET_ROLE_TICK();
-      ALLSET_RMARK(1);
+      ALLSET_MARK(0);
+      ALLSET_TICK();
+      ALLSET_MARK(1);
       if (k >= 1) S3(k - 1);
-      ALLSET_RMARK(2);
-      ALLSET_ROLE_TICK();
-      ALLSET_RMARK(3);
+      ALLSET_MARK(2);
+      ALLSET_TICK();
+      ALLSET_MARK(3);
     }
     S3(T - 1);
-    ALLSET_ROLE_TICK();
+    ALLSET_TICK();
     // ---- the workgroup's gW partial: each matrix wave its 64 x 64 tile
     {
       const int lane = lane0;

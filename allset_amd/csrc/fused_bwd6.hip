@@ -36,86 +36,27 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace allset {
 
-using f16x8s = __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16;
-using f32x4s = __attribute__((ext_vector_type(4))) float;
-using f32x16s = __attribute__((ext_vector_type(16))) float;
-typedef short v4ss_t __attribute__((ext_vector_type(4)));
-union FragS { uint4 u; f16x8s v; struct { v4ss_t lo, hi; } t; };
 constexpr int kSBlock = 768;
 constexpr int kSRows = 32;                     // rows per stage
 constexpr int kSVWaves = 8;
 constexpr int kSTop = 13;                      // a scaled row's largest element lies in [2^13, 2^14)
 constexpr int kSEMin = 20;                     // floor of the biased row exponent (rows below 2^-107 are treated as that small)
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_fs(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row16_sum_s(float v) {     // sum over the 16 lanes of a DPP row, result in every lane of it
-  v += dpp_fs<0xB1>(v);
-  v += dpp_fs<0x4E>(v);
-  v += dpp_fs<0x141>(v);
-  v += dpp_fs<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ float row16_max_s(float v) {     // max over the 16 lanes of a DPP row (v >= 0)
-  v = fmaxf(v, dpp_fs<0xB1>(v));
-  v = fmaxf(v, dpp_fs<0x4E>(v));
-  v = fmaxf(v, dpp_fs<0x141>(v));
-  v = fmaxf(v, dpp_fs<0x140>(v));
-  return v;
-}
-__device__ __forceinline__ float amax4_s(float4 a, float m) {
+// max(|a.x|, |a.y|, |a.z|, |a.w|, m) in plain fmaxf / fabsf (wgrad_f16.hip wf_amax4 is the v_max3_f32 asm form)
+__device__ __forceinline__ float amax4(float4 a, float m) {
   return fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))), m);
 }
-// 2^(field - 127) for a biased exponent field in [0, 254] (0 -> 0.0)
-__device__ __forceinline__ float pow2_field_s(int field) { return __uint_as_float(static_cast<uint32_t>(field) << 23); }
-// x0, x1 -> packed fp16 planes {hi half: x1, lo half: x0}: h = RN16(x), l = RN16(x - h) (x - h is exact in fp32)
-__device__ __forceinline__ void split2_f16(float x0, float x1, uint32_t& ph, uint32_t& pl) {
-  float r0, r1;
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(ph) : "v"(x0), "v"(x1));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(ph), "v"(x0));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(ph), "v"(x1));
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(pl) : "v"(r0), "v"(r1));
-}
-__device__ __forceinline__ f16x8s tr_frag2_s(const uint8_t* lo, const uint8_t* hi) {
-  FragS f;
-  f.t.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4ss_t*)(lo));
-  f.t.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4ss_t*)(hi));
-  return f.v;
-}
-// LDS byte offsets as 32-bit integers (address space 3 kept: a round trip through a generic pointer turns the reads into flat loads)
-using lds_u8_s = __attribute__((address_space(3))) uint8_t;
-__device__ __forceinline__ uint32_t lds_off_s(const void* p) {
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_u8_s*)(p)));
-}
-typedef uint32_t u32x4_s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 lds_read16_s(uint32_t off) {
-  const u32x4_s v = *reinterpret_cast<const __attribute__((address_space(3))) u32x4_s*>(static_cast<uintptr_t>(off));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ f16x8s tr_frag2_off_s(uint32_t lo, uint32_t hi) {
-  FragS f;
-  f.t.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<__attribute__((address_space(3))) v4ss_t*>(static_cast<uintptr_t>(lo)));
-  f.t.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<__attribute__((address_space(3))) v4ss_t*>(static_cast<uintptr_t>(hi)));
-  return f.v;
-}
-// byte offset of (row, column byte) in a [rows][256 B] 16-bit plane (fused_bwd4.hip img_off_r: conflict-free for both the row-wise
-// 16-byte fragment reads and the transpose reads)
-__device__ __forceinline__ int img_off_s(int row, int colbyte) {
-  return row * 256 + ((((colbyte >> 6) ^ row) & 3) << 6) + (((((colbyte >> 4) & 3) ^ (row >> 2)) & 3) << 4) + (colbyte & 15);
-}
-__device__ __forceinline__ uint32_t hash_mix_s(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; return x; }
+// 2^(field - 127) for a biased exponent field in [0, 254] (0 -> 0.0), no branch (wgrad_f16.hip wf_pow2 also maps fields < 0 to 0.0)
+__device__ __forceinline__ float pow2_field(int field) { return __uint_as_float(static_cast<uint32_t>(field) << 23); }
 #ifdef ALLSET_ABL6_NOBAR            // ablation builds only (tools/bwd_f16x3_ablation.py): timing without the barriers, results wrong
-#define ALLSET_S_TICK() __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+#define ALLSET_TICK() ALLSET_TICK_NO_BARRIER()
 #else
-#define ALLSET_S_TICK() __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+#define ALLSET_TICK() ALLSET_TICK_BARRIER()
 #endif
-#define ALLSET_FRESH_LANE_S(name) \
-  int name = static_cast<int>(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))); __asm__ volatile("" : "+v"(name))
 
 // PT (round 6, the PMA tail's first rFF Linear; reference layers.py:153-157): this Linear's input is out = ln0(pooled + att_r) and out
 // ALSO feeds the residual add in front of ln1, so the gradient of out is (this Linear's input gradient) + (the residual branch's gs).
@@ -188,9 +129,9 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
   __syncthreads();
 #ifdef ALLSET_ABL6_TIMING          // diagnostic builds only: cycles per segment of waves 0 (vector) and 8 (matrix) of workgroup 0
   uint64_t tph[4] = {0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#define ALLSET_SMARK(k) do { const uint64_t tn = __builtin_readcyclecounter(); tph[k] += tn - tlast; tlast = tn; } while (0)
+#define ALLSET_MARK(k) ALLSET_PHASE_MARK(k)
 #else
-#define ALLSET_SMARK(k) do {} while (0)
+#define ALLSET_MARK(k) do {} while (0)
 #endif
   // The window of u.  Row r of u is written as u 2^(140 + e_r - Q): e_r = the biased exponent of ga's row, eu_r = a biased exponent
   // with |u[r, :]| < 2^(eu_r - 126), q_r = e_r + eu_r, Q = the largest q_r the workgroup has met -- so u' < 2^14, and ga' u' = ga u
@@ -329,15 +270,15 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
               const uint64_t stage_quad = static_cast<uint64_t>(stage) * (R * OD / 4);
               const uint32_t hi_term = __umul24(static_cast<uint32_t>(stage_quad >> 32), 0x5EBCA7U) + static_cast<uint32_t>(seed2 >> 32);
               const uint32_t lo = static_cast<uint32_t>(stage_quad) | static_cast<uint32_t>((lr * OD + 64 * hb + 4 * c) >> 2);
-              const uint32_t h = hash_mix_s((lo ^ static_cast<uint32_t>(seed2)) * 0x9E3779B1U + hi_term), t8 = thr2 & 0xffu;
+              const uint32_t h = hash_mix((lo ^ static_cast<uint32_t>(seed2)) * 0x9E3779B1U + hi_term), t8 = thr2 & 0xffu;
               kp = make_float4((h & 0xffu) >= t8 ? keep2 : 0.f, ((h >> 8) & 0xffu) >= t8 ? keep2 : 0.f,
                                ((h >> 16) & 0xffu) >= t8 ? keep2 : 0.f, (h >> 24) >= t8 ? keep2 : 0.f);
             } else {
               const uint64_t stage_pair = static_cast<uint64_t>(stage) * (R * OD / 2);
               const uint32_t hi_term = __umul24(static_cast<uint32_t>(stage_pair >> 32), 0x5EBCA7U) + static_cast<uint32_t>(seed2 >> 32);
               const uint32_t lo = static_cast<uint32_t>(stage_pair) | static_cast<uint32_t>((lr * OD + 64 * hb + 4 * c) >> 1);
-              const uint32_t h0 = hash_mix_s((lo ^ static_cast<uint32_t>(seed2)) * 0x9E3779B1U + hi_term);
-              const uint32_t h1 = hash_mix_s(((lo + 1u) ^ static_cast<uint32_t>(seed2)) * 0x9E3779B1U + hi_term);
+              const uint32_t h0 = hash_mix((lo ^ static_cast<uint32_t>(seed2)) * 0x9E3779B1U + hi_term);
+              const uint32_t h1 = hash_mix(((lo + 1u) ^ static_cast<uint32_t>(seed2)) * 0x9E3779B1U + hi_term);
               kp = make_float4((h0 & 0xffffu) >= thr2 ? keep2 : 0.f, (h0 >> 16) >= thr2 ? keep2 : 0.f,
                                (h1 & 0xffffu) >= thr2 ? keep2 : 0.f, (h1 >> 16) >= thr2 ? keep2 : 0.f);
             }
@@ -357,7 +298,7 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
           a1 += (gh1[hb].x + gh1[hb].y) + (gh1[hb].z + gh1[hb].w);
           a2 = fmaf(gh1[hb].x, xh[hb].x, fmaf(gh1[hb].y, xh[hb].y, fmaf(gh1[hb].z, xh[hb].z, fmaf(gh1[hb].w, xh[hb].w, a2))));
         }
-        const float s1 = row16_sum_s(a1) * (1.f / 128.f), s2r = row16_sum_s(a2) * (1.f / 128.f);
+        const float s1 = row16_sum(a1) * (1.f / 128.f), s2r = row16_sum(a2) * (1.f / 128.f);
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb) {
           const float4 o = make_float4(rstd * (gh1[hb].x - s1 - xh[hb].x * s2r), rstd * (gh1[hb].y - s1 - xh[hb].y * s2r),
@@ -385,18 +326,18 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
           v[hb].x = valid ? v[hb].x : 0.f; v[hb].y = valid ? v[hb].y : 0.f; v[hb].z = valid ? v[hb].z : 0.f; v[hb].w = valid ? v[hb].w : 0.f;
           gbv[hb].x += v[hb].x; gbv[hb].y += v[hb].y; gbv[hb].z += v[hb].z; gbv[hb].w += v[hb].w;
         }
-        amax = amax4_s(v[hb], amax);
+        amax = amax4(v[hb], amax);
       }
-      amax = row16_max_s(amax) * (HAS_MASK ? keep_out : 1.f);
+      amax = row16_max(amax) * (HAS_MASK ? keep_out : 1.f);
       const int e = min(max(static_cast<int>(__float_as_uint(amax) >> 23), kSEMin), 254);
       eNext = e;
-      const float sa = pow2_field_s(254 + kSTop - e) * (HAS_MASK ? keep_out : 1.f);        // row max -> [2^13, 2^14); ga = gy keep_out under the mask
+      const float sa = pow2_field(254 + kSTop - e) * (HAS_MASK ? keep_out : 1.f);        // row max -> [2^13, 2^14); ga = gy keep_out under the mask
 #pragma unroll
       for (int hb = 0; hb < 2; ++hb) {
         uint32_t h0, l0, h1, l1;
         split2_f16(v[hb].x * sa, v[hb].y * sa, h0, l0);
         split2_f16(v[hb].z * sa, v[hb].w * sa, h1, l1);
-        const int wo = img_off_s(lr, 128 * hb + 8 * c);
+        const int wo = swizzle256(lr, 128 * hb + 8 * c);
         *reinterpret_cast<uint2*>(img + 0 * PLANE + wo) = make_uint2(h0, h1);
         *reinterpret_cast<uint2*>(img + 1 * PLANE + wo) = make_uint2(l0, l1);
       }
@@ -431,7 +372,7 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
           // pair index of (row, column) = stage * 2048 + (lr * 128 + column) / 2: the lane's part is < 2048 -> an OR (common.h pair_hash)
           if (thr_in & kDrop8) {     // 8 bits per element: ONE hash for the lane's float4 (quad index = stage * 1024 + lane part)
             const uint32_t lo = stage_quad_lo | static_cast<uint32_t>((lr * ID + 64 * hb + 4 * c) >> 2);
-            const int h = static_cast<int>(hash_mix_s((lo ^ seed_lo) * 0x9E3779B1U + hi_term_q));
+            const int h = static_cast<int>(hash_mix((lo ^ seed_lo) * 0x9E3779B1U + hi_term_q));
             const uint32_t t8 = thr_in & 0xffu;
             if (t8 == 128u) {        // (uniform) p = 0.5, the reference's default: keep iff the byte's top bit is set -- one instruction per element
               km = make_int4(__builtin_amdgcn_sbfe(h, 7, 1), __builtin_amdgcn_sbfe(h, 15, 1), __builtin_amdgcn_sbfe(h, 23, 1), h >> 31);
@@ -441,8 +382,8 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
             }
           } else {
             const uint32_t lo = stage_pair_lo | static_cast<uint32_t>((lr * ID + 64 * hb + 4 * c) >> 1);
-            const uint32_t h0 = hash_mix_s((lo ^ seed_lo) * 0x9E3779B1U + hi_term);
-            const uint32_t h1 = hash_mix_s(((lo + 1u) ^ seed_lo) * 0x9E3779B1U + hi_term);
+            const uint32_t h0 = hash_mix((lo ^ seed_lo) * 0x9E3779B1U + hi_term);
+            const uint32_t h1 = hash_mix(((lo + 1u) ^ seed_lo) * 0x9E3779B1U + hi_term);
             km = make_int4((h0 & 0xffffu) >= thr_in ? -1 : 0, (h0 >> 16) >= thr_in ? -1 : 0, (h1 & 0xffffu) >= thr_in ? -1 : 0, (h1 >> 16) >= thr_in ? -1 : 0);
           }
         }
@@ -460,16 +401,16 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
         if constexpr (HAS_LN) xh = make_float4((t.x - mean) * rstd, (t.y - mean) * rstd, (t.z - mean) * rstd, (t.w - mean) * rstd);
         // (a row past the end re-reads the last row: its xhat is finite and meets ga = 0, gu = 0 and fu = 0 wherever it is used)
         xhK[hb] = xh;
-        if constexpr (!HAS_LN) uamax = amax4_s(xh, uamax);
+        if constexpr (!HAS_LN) uamax = amax4(xh, uamax);
         else if (affine) {
           const float4 gm = *reinterpret_cast<const float4*>(&sG[64 * hb + 4 * c]), bt = *reinterpret_cast<const float4*>(&sB[64 * hb + 4 * c]);
-          uamax = amax4_s(make_float4(fmaf(xh.x, gm.x, bt.x), fmaf(xh.y, gm.y, bt.y), fmaf(xh.z, gm.z, bt.z), fmaf(xh.w, gm.w, bt.w)), uamax);
+          uamax = amax4(make_float4(fmaf(xh.x, gm.x, bt.x), fmaf(xh.y, gm.y, bt.y), fmaf(xh.z, gm.z, bt.z), fmaf(xh.w, gm.w, bt.w)), uamax);
         }
       }
       if constexpr (RELU_IN) __asm__ volatile("" : "+v"(xbK));     // (packed here, not at its use)
       // eu_r, q_r = e_r + eu_r, and the wave's largest q_r -> its slot of the stage (all lanes store the same word)
       if (HAS_LN && !affine) quK = eUc;
-      else quK = min(max(static_cast<int>(__float_as_uint(row16_max_s(uamax) * keep_in) >> 23) + 1, kSEMin), 254);     // |u| < 2^(eu - 126)
+      else quK = min(max(static_cast<int>(__float_as_uint(row16_max(uamax) * keep_in) >> 23) + 1, kSEMin), 254);     // |u| < 2^(eu - 126)
       {
         const int q = eCur + quK;
         const int qw = max(max(__builtin_amdgcn_readlane(q, 0), __builtin_amdgcn_readlane(q, 16)),
@@ -486,9 +427,9 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
       const int nrows = rows_left(stage);
       const bool live = lr < nrows;
       Erun = max(Erun, stage_emax(k));
-      const float inv_sa = pow2_field_s(eCur - kSTop) * keep_in;  // undoes the row scale of ga (the wave's W scale is undone by S1); x the dropout's 1 / keep
+      const float inv_sa = pow2_field(eCur - kSTop) * keep_in;  // undoes the row scale of ga (the wave's W scale is undone by S1); x the dropout's 1 / keep
       const int ffield = 267 + eCur - Erun;
-      const float fu = pow2_field_s(live ? max(ffield, 0) : 0) * keep_in;     // (a dead row's u is 0: its xhat is, but beta is not)
+      const float fu = pow2_field(live ? max(ffield, 0) : 0) * keep_in;     // (a dead row's u is 0: its xhat is, but beta is not)
       float4 gam[2], v[2];
       float a1 = 0.f, a2 = 0.f;
       // gx = acc_in + ...: a second gradient branch of the same tensor, summed here (may alias gx: each element is read and written
@@ -525,7 +466,7 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
         }
       }
       float s1 = 0.f, s2 = 0.f;
-      if constexpr (HAS_LN) { s1 = row16_sum_s(a1) * inv_i; s2 = row16_sum_s(a2) * inv_i; }
+      if constexpr (HAS_LN) { s1 = row16_sum(a1) * inv_i; s2 = row16_sum(a2) * inv_i; }
       const float rstd = rstdK;
       const float ptSd = PT ? 1.f / rstd : 0.f, ptMean = PT ? meanK : 0.f;
       float ptDot[2] = {0.f, 0.f};
@@ -570,7 +511,7 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
         uint32_t h0, l0, h1, l1;
         split2_f16(u.x * fu, u.y * fu, h0, l0);
         split2_f16(u.z * fu, u.w * fu, h1, l1);
-        const int wo = img_off_s(lr, 128 * hb + 8 * c);
+        const int wo = swizzle256(lr, 128 * hb + 8 * c);
         *reinterpret_cast<uint2*>(img + 0 * PLANE + wo) = make_uint2(h0, h1);
         *reinterpret_cast<uint2*>(img + 1 * PLANE + wo) = make_uint2(l0, l1);
       }
@@ -578,10 +519,10 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
         // per head: the lanes of a head are pt_g consecutive lanes of the DPP row (both column halves together when there is one head)
         float d0 = ptDot[0], d1 = ptDot[1];
         if (pt_g >= 32) { d0 += d1; d1 = d0; }
-        if (pt_g >= 2) { d0 += dpp_fs<0xB1>(d0); d1 += dpp_fs<0xB1>(d1); }
-        if (pt_g >= 4) { d0 += dpp_fs<0x4E>(d0); d1 += dpp_fs<0x4E>(d1); }
-        if (pt_g >= 8) { d0 += dpp_fs<0x141>(d0); d1 += dpp_fs<0x141>(d1); }
-        if (pt_g >= 16) { d0 += dpp_fs<0x140>(d0); d1 += dpp_fs<0x140>(d1); }
+        if (pt_g >= 2) { d0 += dpp_row<0xB1>(d0); d1 += dpp_row<0xB1>(d1); }
+        if (pt_g >= 4) { d0 += dpp_row<0x4E>(d0); d1 += dpp_row<0x4E>(d1); }
+        if (pt_g >= 8) { d0 += dpp_row<0x141>(d0); d1 += dpp_row<0x141>(d1); }
+        if (pt_g >= 16) { d0 += dpp_row<0x140>(d0); d1 += dpp_row<0x140>(d1); }
         const int64_t row = stage * R + lr;
         const bool w0 = live && (pt_g >= 32 ? c == 0 : (c % pt_g) == 0), w1 = live && pt_g < 32 && (c % pt_g) == 0;
         // empty target: never gathered; exp(a - FLT_MAX) = 0 (the convention of pma_bwd_stats_kernel, csrc/pma.hip)
@@ -601,38 +542,38 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
     request_x(1, xrS[1], stS[1]);
     S0(0, agS[0], amS[0], sgS[0], s2S[0]);
     eCur = eNext;
-    ALLSET_S_TICK();
+    ALLSET_TICK();
     // Two stages per trip: stage k lives in register set 0, stage k + 1 in set 1; no conditional half inside the trip (fused_bwd4.hip:
     // the compiler's s_waitcnt insertion); an odd last stage is peeled off.
     int64_t k = 0;
-    ALLSET_SMARK(3);
+    ALLSET_MARK(3);
     for (; k + 1 < T; k += 2) {
       S0(k + 1, agS[1], amS[1], sgS[1], s2S[1]);
       S2a(k, xrS[0], stS[0]);
-      ALLSET_SMARK(0);
-      ALLSET_S_TICK();
-      ALLSET_SMARK(1);
+      ALLSET_MARK(0);
+      ALLSET_TICK();
+      ALLSET_MARK(1);
       S2b(k);
-      ALLSET_SMARK(2);
-      ALLSET_S_TICK();
-      ALLSET_SMARK(3);
+      ALLSET_MARK(2);
+      ALLSET_TICK();
+      ALLSET_MARK(3);
       if (k + 2 < T) S0(k + 2, agS[0], amS[0], sgS[0], s2S[0]);
       S2a(k + 1, xrS[1], stS[1]);
-      ALLSET_SMARK(0);
-      ALLSET_S_TICK();
-      ALLSET_SMARK(1);
+      ALLSET_MARK(0);
+      ALLSET_TICK();
+      ALLSET_MARK(1);
       S2b(k + 1);
-      ALLSET_SMARK(2);
-      ALLSET_S_TICK();
-      ALLSET_SMARK(3);
+      ALLSET_MARK(2);
+      ALLSET_TICK();
+      ALLSET_MARK(3);
     }
     if (k < T) {                            // odd stage count: the last stage, in set 0
       S2a(k, xrS[0], stS[0]);
-      ALLSET_S_TICK();
+      ALLSET_TICK();
       S2b(k);
-      ALLSET_S_TICK();
+      ALLSET_TICK();
     }
-    ALLSET_S_TICK();                        // (the matrix waves' last weight-gradient step)
+    ALLSET_TICK();                        // (the matrix waves' last weight-gradient step)
     // ---- column sums held by the vector waves (dgamma, dbeta, bias gradient): the four row groups of a lane column fold first,
     // then the eight waves through LDS in a fixed order
 #pragma unroll
@@ -659,7 +600,7 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
     // ---- this wave's slice of W (32 columns 32 m + 16 ct + nn) as MFMA B fragments: column tile ct, k-step t; lane (nn = lane & 15,
     // kg = lane >> 4) holds W[o = 32 kg + 8 t + j][column], j = 0..7, scaled so that the slice's largest element lies in
     // [2^13, 2^14).  The h plane stays in 32 registers; the l plane is used once per k-step and lives in LDS, fragment by fragment.
-    FragS wq[2][4];
+    Frag wq[2][4];
     float inv_sw;
     uint4* wl = reinterpret_cast<uint4*>(sWL) + m * (2 * 4 * 64) + lane0;        // [m][ct][t][lane]
     {
@@ -678,8 +619,8 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
 #pragma unroll
       for (int off = 1; off < 64; off <<= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
       const int ew = __builtin_amdgcn_readfirstlane(min(max(static_cast<int>(__float_as_uint(amax) >> 23), kSEMin), 254));
-      const float sw = pow2_field_s(254 + kSTop - ew);
-      inv_sw = pow2_field_s(ew - kSTop);
+      const float sw = pow2_field(254 + kSTop - ew);
+      inv_sw = pow2_field(ew - kSTop);
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -691,7 +632,7 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
           wl[(ct * 4 + t) * 64] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
         }
     }
-    f32x16s gw[2][2];
+    f32x16 gw[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -704,59 +645,59 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
     // independent accumulator chains; the A fragments of step t + 1 are requested before step t's MFMAs
     // LDS addresses: every fragment address of a stage is ONE per-lane base (kept in a register) XOR a constant in the swizzle's
     // chunk / piece bits, plus an immediate (row tile, plane, 16-row step) and the image buffer's offset -- a handful of vector
-    // instructions per stage where the generic img_off_s arithmetic cost ~130 (the matrix waves are the critical role, and each of
+    // instructions per stage where the generic swizzle256 arithmetic cost ~130 (the matrix waves are the critical role, and each of
     // their vector instructions queues behind two vector waves on the same SIMD).
     //   S1: row ri (+16), column byte 64 kg + 16 t:  base1 ^ (t << 4);   rows +16: + 4096 (same swizzle class)
     //   S3: row 16 kb + tr_row + 4 hi, column byte 64 (2 o + tl) + tr_in:  base3 ^ (tl << 6) ^ (hi << 4), + 4096 kb + 1024 hi
-    const int base1 = img_off_s(lane0 & 15, 64 * (lane0 >> 4));
+    const int base1 = swizzle256(lane0 & 15, 64 * (lane0 >> 4));
     int base3a, base3b, base_gu;
     {
       const int q4 = lane0 >> 4, tr_r = (lane0 & 15) >> 2, tr_row = 8 * (q4 >> 1) + tr_r, tr_in = 32 * (q4 & 1) + 8 * (lane0 & 3);
-      base3a = img_off_s(tr_row, 64 * (2 * oh) + tr_in);
-      base3b = img_off_s(tr_row, 64 * (2 * ih) + tr_in);
+      base3a = swizzle256(tr_row, 64 * (2 * oh) + tr_in);
+      base3b = swizzle256(tr_row, 64 * (2 * ih) + tr_in);
       base_gu = (4 * (lane0 >> 4) * SPG + 32 * m + (lane0 & 15)) * 4;
     }
     auto S1 = [&](int64_t k, int b3) {
-      const uint32_t img = lds_off_s(sGA) + static_cast<uint32_t>(b3 * IMG + base1);
-      auto load_a = [&](FragS (&f0)[2], FragS (&f1)[2], FragS (&fl)[2], int t) {
+      const uint32_t img = lds_off(sGA) + static_cast<uint32_t>(b3 * IMG + base1);
+      auto load_a = [&](Frag (&f0)[2], Frag (&f1)[2], Frag (&fl)[2], int t) {
         const uint32_t pa = img ^ static_cast<uint32_t>(t << 4);
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
-          f0[pl].u = lds_read16_s(pa + pl * PLANE);
-          f1[pl].u = lds_read16_s(pa + pl * PLANE + 16 * 256);
+          f0[pl].u = lds_read16(pa + pl * PLANE);
+          f1[pl].u = lds_read16(pa + pl * PLANE + 16 * 256);
         }
         fl[0].u = wl[(0 * 4 + t) * 64];
         fl[1].u = wl[(1 * 4 + t) * 64];
       };
-      FragS fa0[2][2], fa1[2][2], fwl[2][2];
-      f32x4s acc[2][2];
+      Frag fa0[2][2], fa1[2][2], fwl[2][2];
+      f32x4 acc[2][2];
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4s{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
       load_a(fa0[0], fa1[0], fwl[0], 0);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         if (t + 1 < 4) load_a(fa0[(t + 1) & 1], fa1[(t + 1) & 1], fwl[(t + 1) & 1], t + 1);
-        const FragS (&a0)[2] = fa0[t & 1];
-        const FragS (&a1)[2] = fa1[t & 1];
-        const FragS (&bl)[2] = fwl[t & 1];
+        const Frag (&a0)[2] = fa0[t & 1];
+        const Frag (&a1)[2] = fa1[t & 1];
+        const Frag (&bl)[2] = fwl[t & 1];
         // l.h, h.l, h.h
 #ifdef ALLSET_ABL6_NOMFMA
         acc[0][0][0] += __builtin_bit_cast(float, a0[0].u.x ^ a0[1].u.y ^ bl[0].u.z ^ bl[1].u.w); acc[1][0][0] += __builtin_bit_cast(float, a1[0].u.x ^ a1[1].u.y);
 #else
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[1].v, wq[0][t].v, acc[0][0], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[1].v, wq[0][t].v, acc[1][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[1].v, wq[1][t].v, acc[0][1], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[1].v, wq[1][t].v, acc[1][1], 0, 0, 0);
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[0].v, bl[0].v, acc[0][0], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[0].v, bl[0].v, acc[1][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[0].v, bl[1].v, acc[0][1], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[0].v, bl[1].v, acc[1][1], 0, 0, 0);
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[0].v, wq[0][t].v, acc[0][0], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[0].v, wq[0][t].v, acc[1][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[0].v, wq[1][t].v, acc[0][1], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[0].v, wq[1][t].v, acc[1][1], 0, 0, 0);
+        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[1].h, wq[0][t].h, acc[0][0], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[1].h, wq[0][t].h, acc[1][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[1].h, wq[1][t].h, acc[0][1], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[1].h, wq[1][t].h, acc[1][1], 0, 0, 0);
+        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[0].h, bl[0].h, acc[0][0], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[0].h, bl[0].h, acc[1][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[0].h, bl[1].h, acc[0][1], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[0].h, bl[1].h, acc[1][1], 0, 0, 0);
+        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[0].h, wq[0][t].h, acc[0][0], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[0].h, wq[0][t].h, acc[1][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[0].h, wq[1][t].h, acc[0][1], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[0].h, wq[1][t].h, acc[1][1], 0, 0, 0);
 #endif
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -773,7 +714,7 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
     auto S3 = [&](int64_t k, int b3, int b2) {
       const int Ek = stage_emax(k);
       if (Ek > Erun) {                            // a larger row exponent: bring the accumulated sum to the new scale (exact)
-        const float f = pow2_field_s(max(127 - (Ek - Erun), 0));
+        const float f = pow2_field(max(127 - (Ek - Erun), 0));
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -782,22 +723,22 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
             for (int q = 0; q < 16; ++q) gw[a][b][q] *= f;
         Erun = Ek;
       }
-      const uint32_t ia = lds_off_s(sGA) + static_cast<uint32_t>(b3 * IMG + base3a), iu = lds_off_s(sU) + static_cast<uint32_t>(b2 * IMG + base3b);
+      const uint32_t ia = lds_off(sGA) + static_cast<uint32_t>(b3 * IMG + base3a), iu = lds_off(sU) + static_cast<uint32_t>(b2 * IMG + base3b);
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
-        f16x8s wa[2][2], wb[2][2];
+        f16x8 wa[2][2], wb[2][2];
 #pragma unroll
         for (int tl = 0; tl < 2; ++tl) {
           const uint32_t a_lo = (ia ^ static_cast<uint32_t>(tl << 6)) + kb * 4096, a_hi = (ia ^ static_cast<uint32_t>((tl << 6) | 16)) + kb * 4096 + 1024;
           const uint32_t b_lo = (iu ^ static_cast<uint32_t>(tl << 6)) + kb * 4096, b_hi = (iu ^ static_cast<uint32_t>((tl << 6) | 16)) + kb * 4096 + 1024;
 #pragma unroll
           for (int pl = 0; pl < 2; ++pl) {
-            wa[tl][pl] = tr_frag2_off_s(a_lo + pl * PLANE, a_hi + pl * PLANE);
-            wb[tl][pl] = tr_frag2_off_s(b_lo + pl * PLANE, b_hi + pl * PLANE);
+            wa[tl][pl] = tr_frag2_off<f16x8>(a_lo + pl * PLANE, a_hi + pl * PLANE);
+            wb[tl][pl] = tr_frag2_off<f16x8>(b_lo + pl * PLANE, b_hi + pl * PLANE);
           }
         }
 #ifdef ALLSET_ABL6_NOMFMA
-        { FragS f; f.v = wa[0][0]; FragS g2; g2.v = wb[1][1]; FragS g3; g3.v = wa[1][1]; FragS g4; g4.v = wb[0][0];
+        { Frag f; f.h = wa[0][0]; Frag g2; g2.h = wb[1][1]; Frag g3; g3.h = wa[1][1]; Frag g4; g4.h = wb[0][0];
           gw[0][0][0] += __builtin_bit_cast(float, f.u.x ^ g2.u.y ^ g3.u.z ^ g4.u.w); }
 #else
         constexpr int PA_[3] = {1, 0, 0}, PB_[3] = {0, 1, 0};     // l.h, h.l, h.h
@@ -813,27 +754,27 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
       }
     };
 
-    ALLSET_S_TICK();
-    ALLSET_SMARK(3);
+    ALLSET_TICK();
+    ALLSET_MARK(3);
     int c3 = 0, p3 = 2, c2 = 0;                   // k % 3, (k - 1) % 3, k % 2 without the divisions
     for (int64_t k = 0; k < T; ++k) {
       S1(k, c3);
-      ALLSET_SMARK(0);
-      ALLSET_S_TICK();
-      ALLSET_SMARK(1);
+      ALLSET_MARK(0);
+      ALLSET_TICK();
+      ALLSET_MARK(1);
       if (k >= 1) S3(k - 1, p3, c2 ^ 1);
-      ALLSET_SMARK(2);
-      ALLSET_S_TICK();
-      ALLSET_SMARK(3);
+      ALLSET_MARK(2);
+      ALLSET_TICK();
+      ALLSET_MARK(3);
       p3 = c3; c3 = c3 == 2 ? 0 : c3 + 1; c2 ^= 1;
     }
     S3(T - 1, p3, c2 ^ 1);
-    ALLSET_S_TICK();
+    ALLSET_TICK();
     // ---- the workgroup's gW partial: each matrix wave its 64 x 64 tile; the accumulators hold gW 2^(kSTop + 267 - Erun)
     {
       const int X = Erun - 267 - kSTop;           // in [-240, 228]: applied as two factors
       const int X1 = X >> 1, X2 = X - X1;
-      const float f1 = pow2_field_s(127 + X1), f2 = pow2_field_s(127 + X2);
+      const float f1 = pow2_field(127 + X1), f2 = pow2_field(127 + X2);
       float* pw = part_w + static_cast<int64_t>(blockIdx.x) * pstride_w;
 #pragma unroll
       for (int a = 0; a < 2; ++a)

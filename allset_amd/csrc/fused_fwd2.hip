@@ -28,49 +28,20 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace allset {
 
-using bf16x8f = __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16;
-using f16x8f = __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16;
-using f32x4f = __attribute__((ext_vector_type(4))) float;
-union FragF { uint4 u; bf16x8f v; f16x8f h; };
-// fp16x3 (fused_bwd6.hip has the scheme): x0, x1 -> packed fp16 planes h = RN16(x), l = RN16(x - h)
-__device__ __forceinline__ void split2_f16_f(float x0, float x1, uint32_t& ph, uint32_t& pl) {
-  float r0, r1;
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(ph) : "v"(x0), "v"(x1));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(ph), "v"(x0));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(ph), "v"(x1));
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(pl) : "v"(r0), "v"(r1));
-}
 constexpr int kF2Block = 768;
 constexpr int kF2Rows = 32;                    // rows per stage
 constexpr int kF2VWaves = 8;
 constexpr int kF2Sets = 4;                     // register sets of prefetched rows per vector wave
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_ff(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row16_sum_f(float v) {     // sum over the 16 lanes of a DPP row, result in every lane of it
-  v += dpp_ff<0xB1>(v);
-  v += dpp_ff<0x4E>(v);
-  v += dpp_ff<0x141>(v);
-  v += dpp_ff<0x140>(v);
-  return v;
-}
-// byte offset of (row, column byte) in a [rows][256 B] bf16 plane (fused_bwd4.hip img_off_r: conflict-free 16-byte fragment reads)
-__device__ __forceinline__ int img_off_f(int row, int colbyte) {
-  return row * 256 + ((((colbyte >> 6) ^ row) & 3) << 6) + (((((colbyte >> 4) & 3) ^ (row >> 2)) & 3) << 4) + (colbyte & 15);
-}
-__device__ __forceinline__ uint32_t hash_mix_f(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; return x; }
 #ifdef ALLSET_ABL5_NOBAR            // ablation builds only (tools/fwd_roles_ablation.py): timing without the barriers, results wrong
-#define ALLSET_F2_TICK() __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+#define ALLSET_TICK() ALLSET_TICK_NO_BARRIER()
 #else
-#define ALLSET_F2_TICK() __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+#define ALLSET_TICK() ALLSET_TICK_BARRIER()
 #endif
-#define ALLSET_FRESH_LANE_F(name) \
-  int name = static_cast<int>(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))); __asm__ volatile("" : "+v"(name))
 
 // XM ("extra mode", round 5 -- the PMA tail of reference layers.py:153-157 folded into its two rFF Linears, fp16x3 only):
 //   1  prologue = LayerNorm(x + colb) (ln0 with the seed add riding in it), whose OUTPUT is also written to `uo` (the residual
@@ -153,9 +124,9 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
   }
 #ifdef ALLSET_ABL5_TIMING          // diagnostic builds only: cycles per segment of waves 0 (vector) and 8 (matrix) of workgroup 0
   uint64_t tph[4] = {0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#define ALLSET_FMARK(k) do { const uint64_t tn = __builtin_readcyclecounter(); tph[k] += tn - tlast; tlast = tn; } while (0)
+#define ALLSET_MARK(k) ALLSET_PHASE_MARK(k)
 #else
-#define ALLSET_FMARK(k) do {} while (0)
+#define ALLSET_MARK(k) do {} while (0)
 #endif
 
   if (wave < kF2VWaves) {
@@ -220,15 +191,15 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
         const uint64_t stage_quad = static_cast<uint64_t>(stage) * (R * KD / 4);
         const uint32_t hi_term = __umul24(static_cast<uint32_t>(stage_quad >> 32), 0x5EBCA7U) + static_cast<uint32_t>(seed >> 32);
         const uint32_t lo = static_cast<uint32_t>(stage_quad) | static_cast<uint32_t>((lr * KD + 64 * hb + 4 * c) >> 2);
-        const uint32_t h = hash_mix_f((lo ^ sl) * 0x9E3779B1U + hi_term), t8 = thr & 0xffu;
+        const uint32_t h = hash_mix((lo ^ sl) * 0x9E3779B1U + hi_term), t8 = thr & 0xffu;
         return make_float4((h & 0xffu) >= t8 ? keep : 0.f, ((h >> 8) & 0xffu) >= t8 ? keep : 0.f,
                            ((h >> 16) & 0xffu) >= t8 ? keep : 0.f, (h >> 24) >= t8 ? keep : 0.f);
       }
       const uint64_t stage_pair = static_cast<uint64_t>(stage) * (R * KD / 2);
       const uint32_t hi_term = __umul24(static_cast<uint32_t>(stage_pair >> 32), 0x5EBCA7U) + static_cast<uint32_t>(seed >> 32);
       const uint32_t lo = static_cast<uint32_t>(stage_pair) | static_cast<uint32_t>((lr * KD + 64 * hb + 4 * c) >> 1);
-      const uint32_t h0 = hash_mix_f((lo ^ sl) * 0x9E3779B1U + hi_term);
-      const uint32_t h1 = hash_mix_f(((lo + 1u) ^ sl) * 0x9E3779B1U + hi_term);
+      const uint32_t h0 = hash_mix((lo ^ sl) * 0x9E3779B1U + hi_term);
+      const uint32_t h1 = hash_mix(((lo + 1u) ^ sl) * 0x9E3779B1U + hi_term);
       return make_float4((h0 & 0xffffu) >= thr ? keep : 0.f, (h0 >> 16) >= thr ? keep : 0.f,
                          (h1 & 0xffffu) >= thr ? keep : 0.f, (h1 >> 16) >= thr ? keep : 0.f);
     };
@@ -252,7 +223,7 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
         }
       }
       if constexpr (HAS_LN) {
-        const float s = row16_sum_f(((t[0].x + t[0].y) + (t[0].z + t[0].w)) + ((t[1].x + t[1].y) + (t[1].z + t[1].w)));
+        const float s = row16_sum(((t[0].x + t[0].y) + (t[0].z + t[0].w)) + ((t[1].x + t[1].y) + (t[1].z + t[1].w)));
         const float mean = s * inv_k;
         float q2 = 0.f;
 #pragma unroll
@@ -260,7 +231,7 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
           t[hb].x -= mean; t[hb].y -= mean; t[hb].z -= mean; t[hb].w -= mean;
           q2 = fmaf(t[hb].x, t[hb].x, fmaf(t[hb].y, t[hb].y, fmaf(t[hb].z, t[hb].z, fmaf(t[hb].w, t[hb].w, q2))));
         }
-        const float rstd = rsqrtf(row16_sum_f(q2) * inv_k + eps);
+        const float rstd = rsqrtf(row16_sum(q2) * inv_k + eps);
         if (live && c == 0) *reinterpret_cast<float2*>(stats + (stage * R + lr) * 2) = make_float2(mean, rstd);
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb) {
@@ -280,7 +251,7 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float4 w0 = *reinterpret_cast<const float4*>(&sAuxW[j * KD + 4 * c]), w1 = *reinterpret_cast<const float4*>(&sAuxW[j * KD + 64 + 4 * c]);
-          s4[j] = row16_sum_f(fmaf(t[0].x, w0.x, fmaf(t[0].y, w0.y, fmaf(t[0].z, w0.z, t[0].w * w0.w))) +
+          s4[j] = row16_sum(fmaf(t[0].x, w0.x, fmaf(t[0].y, w0.y, fmaf(t[0].z, w0.z, t[0].w * w0.w))) +
                               fmaf(t[1].x, w1.x, fmaf(t[1].y, w1.y, fmaf(t[1].z, w1.z, t[1].w * w1.w))));
         }
         if (live && c == 0)
@@ -293,8 +264,8 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb)
           amax = fmaxf(fmaxf(fmaxf(fabsf(t[hb].x), fabsf(t[hb].y)), fmaxf(fabsf(t[hb].z), fabsf(t[hb].w))), amax);
-        amax = fmaxf(amax, dpp_ff<0xB1>(amax)); amax = fmaxf(amax, dpp_ff<0x4E>(amax));
-        amax = fmaxf(amax, dpp_ff<0x141>(amax)); amax = fmaxf(amax, dpp_ff<0x140>(amax));
+        amax = fmaxf(amax, dpp_row<0xB1>(amax)); amax = fmaxf(amax, dpp_row<0x4E>(amax));
+        amax = fmaxf(amax, dpp_row<0x141>(amax)); amax = fmaxf(amax, dpp_row<0x140>(amax));
         const int e = min(max(static_cast<int>(__float_as_uint(amax * keep_in) >> 23), 20), 254);
         eC = eB; eB = eA; eA = e;
         rsc = __uint_as_float(static_cast<uint32_t>(254 + 13 - e) << 23);       // the row's largest element -> [2^13, 2^14)
@@ -306,11 +277,11 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
           t[hb].x *= kp.x; t[hb].y *= kp.y; t[hb].z *= kp.z; t[hb].w *= kp.w;
         }
         if constexpr (ROWSC || XM == 1) { t[hb].x *= rsc; t[hb].y *= rsc; t[hb].z *= rsc; t[hb].w *= rsc; }
-        const int wo = img_off_f(lr, 128 * hb + 8 * c);
+        const int wo = swizzle256(lr, 128 * hb + 8 * c);
         if constexpr (F16) {
           uint32_t h0, l0, h1, l1;
-          split2_f16_f(t[hb].x, t[hb].y, h0, l0);
-          split2_f16_f(t[hb].z, t[hb].w, h1, l1);
+          split2_f16(t[hb].x, t[hb].y, h0, l0);
+          split2_f16(t[hb].z, t[hb].w, h1, l1);
           *reinterpret_cast<uint2*>(img + 0 * PLANE + wo) = make_uint2(h0, h1);
           *reinterpret_cast<uint2*>(img + 1 * PLANE + wo) = make_uint2(l0, l1);
         } else {
@@ -356,7 +327,7 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
           sv[hb] = make_float4(resR[hb].x + vv[hb].x, resR[hb].y + vv[hb].y, resR[hb].z + vv[hb].z, resR[hb].w + vv[hb].w);
           a1 += (sv[hb].x + sv[hb].y) + (sv[hb].z + sv[hb].w);
         }
-        const float mean = row16_sum_f(a1) * (1.f / 128.f);
+        const float mean = row16_sum(a1) * (1.f / 128.f);
         float q2 = 0.f;
         float4 cv[2];
 #pragma unroll
@@ -364,7 +335,7 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
           cv[hb] = make_float4(sv[hb].x - mean, sv[hb].y - mean, sv[hb].z - mean, sv[hb].w - mean);
           q2 = fmaf(cv[hb].x, cv[hb].x, fmaf(cv[hb].y, cv[hb].y, fmaf(cv[hb].z, cv[hb].z, fmaf(cv[hb].w, cv[hb].w, q2))));
         }
-        const float rstd = rsqrtf(row16_sum_f(q2) * (1.f / 128.f) + eps);
+        const float rstd = rsqrtf(row16_sum(q2) * (1.f / 128.f) + eps);
         if (live) {
           if (c == 0) *reinterpret_cast<float2*>(stats + (stage * R + lr) * 2) = make_float2(mean, rstd);
           char* ub = reinterpret_cast<char*>(uo + stage * R * lduo) + static_cast<uint32_t>(lr) * static_cast<uint32_t>(lduo) * 4u + 16u * c;
@@ -421,12 +392,12 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
     for (int q = 0; q < kF2Sets; ++q) request_x(q, xrS[q]);
     request_res(0);
     S0(0, xrS[0]);
-    ALLSET_F2_TICK();
+    ALLSET_TICK();
     S0(1, xrS[1]);                               // tick 0 (stage 1 may be a re-run of the last stage: never consumed)
-    ALLSET_F2_TICK();
+    ALLSET_TICK();
     // ticks 1 .. T - 1, four per trip (stage t + 1 lives in register set (t + 1) % 4); the last 1..3 ticks are peeled off: a
     // conditional part inside the trip makes hipcc wait vmcnt(0) at the loop header (DESIGN.md 6a''')
-#define ALLSET_F2_FULL_TICK(tt, set) do { ALLSET_FMARK(3); S0((tt) + 1, xrS[set]); ALLSET_FMARK(0); E((tt) - 1, eC); ALLSET_FMARK(1); ALLSET_F2_TICK(); ALLSET_FMARK(2); } while (0)
+#define ALLSET_F2_FULL_TICK(tt, set) do { ALLSET_MARK(3); S0((tt) + 1, xrS[set]); ALLSET_MARK(0); E((tt) - 1, eC); ALLSET_MARK(1); ALLSET_TICK(); ALLSET_MARK(2); } while (0)
     int64_t t = 1;
     for (; t + 3 < T; t += 4) {
       ALLSET_F2_FULL_TICK(t, 2);
@@ -444,7 +415,7 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
     const int m = wave - kF2VWaves;
     // this wave's slice of W^T as MFMA B fragments: output columns 32 m + 16 ct + nn, k-step t, plane pl; lane (nn = lane & 15,
     // kg = lane >> 4) holds W[column][k = 32 kg + 8 t + j], j = 0..7 (the k-order of fused_linear_fwd_x6_kernel)
-    FragF wq[2][4][F16 ? 2 : 3];
+    Frag wq[2][4][F16 ? 2 : 3];
     float inv_s = 1.f;                           // (fp16x3: undoes the slice's W scale and 2^Su on the way to the output tile)
     if constexpr (F16) {
       const int nn = lane0 & 15, kg = lane0 >> 4;
@@ -472,10 +443,10 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
         for (int tt = 0; tt < 4; ++tt) {
           const float4 a = wa[ct][tt], b = wb[ct][tt];
           uint32_t ph[4], pl[4];
-          split2_f16_f(a.x * sw, a.y * sw, ph[0], pl[0]);
-          split2_f16_f(a.z * sw, a.w * sw, ph[1], pl[1]);
-          split2_f16_f(b.x * sw, b.y * sw, ph[2], pl[2]);
-          split2_f16_f(b.z * sw, b.w * sw, ph[3], pl[3]);
+          split2_f16(a.x * sw, a.y * sw, ph[0], pl[0]);
+          split2_f16(a.z * sw, a.w * sw, ph[1], pl[1]);
+          split2_f16(b.x * sw, b.y * sw, ph[2], pl[2]);
+          split2_f16(b.z * sw, b.w * sw, ph[3], pl[3]);
           wq[ct][tt][0].u = make_uint4(ph[0], ph[1], ph[2], ph[3]);
           wq[ct][tt][1].u = make_uint4(pl[0], pl[1], pl[2], pl[3]);
         }
@@ -498,31 +469,31 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
         }
     }
     auto S1 = [&](int64_t k) {
-      ALLSET_FRESH_LANE_F(lane);
+      ALLSET_FRESH_LANE(lane);
       const int ri = lane & 15, kg = lane >> 4;
       const uint8_t* img = sX + (k & 1) * IMG;
       float* ty = sY + (k & 1) * (R * SPY);
       constexpr int NP = F16 ? 2 : 3;
-      auto load_a = [&](FragF (&f0)[3], FragF (&f1)[3], int tt) {
-        const int o0 = img_off_f(ri, 64 * kg + 16 * tt), o1 = img_off_f(16 + ri, 64 * kg + 16 * tt);
+      auto load_a = [&](Frag (&f0)[3], Frag (&f1)[3], int tt) {
+        const int o0 = swizzle256(ri, 64 * kg + 16 * tt), o1 = swizzle256(16 + ri, 64 * kg + 16 * tt);
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl) {
           f0[pl].u = *reinterpret_cast<const uint4*>(img + pl * PLANE + o0);
           f1[pl].u = *reinterpret_cast<const uint4*>(img + pl * PLANE + o1);
         }
       };
-      FragF fa0[2][3], fa1[2][3];
-      f32x4f acc[2][2];
+      Frag fa0[2][3], fa1[2][3];
+      f32x4 acc[2][2];
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4f{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
       load_a(fa0[0], fa1[0], 0);
 #pragma unroll
       for (int tt = 0; tt < 4; ++tt) {
         if (tt + 1 < 4) load_a(fa0[(tt + 1) & 1], fa1[(tt + 1) & 1], tt + 1);
-        const FragF (&a0)[3] = fa0[tt & 1];
-        const FragF (&a1)[3] = fa1[tt & 1];
+        const Frag (&a0)[3] = fa0[tt & 1];
+        const Frag (&a1)[3] = fa1[tt & 1];
         constexpr int PA_[6] = {2, 0, 1, 1, 0, 0}, PB_[6] = {0, 2, 1, 0, 1, 0};     // l.h, h.l, m.m, m.h, h.m, h.h
 #ifdef ALLSET_ABL5_NOMFMA
         acc[0][0][0] += __builtin_bit_cast(float, a0[0].u.x ^ a0[1].u.y ^ a0[2].u.z); acc[1][0][0] += __builtin_bit_cast(float, a1[0].u.x ^ a1[1].u.y ^ a1[2].u.z);
@@ -560,13 +531,13 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
 #pragma unroll
           for (int r = 0; r < 4; ++r) ty[(16 * rt + 4 * kg + r) * SPY + 32 * m + 16 * ct + ri] = F16 ? acc[rt][ct][r] * inv_s : acc[rt][ct][r];
     };
-    ALLSET_F2_TICK();
+    ALLSET_TICK();
     for (int64_t k = 0; k < T; ++k) {
-      ALLSET_FMARK(3);
+      ALLSET_MARK(3);
       S1(k);
-      ALLSET_FMARK(0);
-      ALLSET_F2_TICK();
-      ALLSET_FMARK(2);
+      ALLSET_MARK(0);
+      ALLSET_TICK();
+      ALLSET_MARK(2);
     }
   }
 #ifdef ALLSET_ABL5_TIMING

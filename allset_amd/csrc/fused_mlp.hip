@@ -26,10 +26,10 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace allset {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 constexpr int kFusedBlock = 512;
 constexpr int kFusedWaves = kFusedBlock / kWave;
 
@@ -46,18 +46,8 @@ constexpr int kFusedWaves = kFusedBlock / kWave;
 //   * the accumulators (one column x 4 rows per lane) take one trip through the wave's LDS slab and leave as 16-byte
 //     stores of 4 consecutive columns (dword stores from the MFMA layout are issue-bound at ~5 B/clk/CU); bias / relu /
 //     dropout run on the row-major side, where one hash covers two neighbours.
-using bf16x8 = __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-union Frag8 { uint4 u; bf16x8 v; };
 constexpr int kX6Block = 512;
 constexpr int kX6Waves = kX6Block / kWave;
-
-// dword offset of 16-byte piece t of (k-quarter g, column j) inside a plane
-template <int KQD, int GS>
-__device__ __forceinline__ int plane_off(int g, int j, int t) {
-  constexpr int PIECES = KQD / 4, ROWS64 = 64 / KQD;
-  return g * GS + j * KQD + 4 * (t ^ ((j / ROWS64) % PIECES));
-}
 
 // Waves per workgroup (round 3): 12 = three per SIMD for the variants with a LayerNorm prologue -- their vector work (statistics,
 // normalisation, dropout hash, three-plane split, epilogue) is 7x the matrix pipe's issue slots, and a third wave per SIMD fills
@@ -242,14 +232,14 @@ __global__ __launch_bounds__(fwd_x6_waves<HAS_LN>() * kWave) void fused_linear_f
 #pragma unroll
     for (int t = 0; t < T; ++t) {
 #endif
-      Frag8 fa_h, fa_m, fa_l;
+      Frag fa_h, fa_m, fa_l;
       fa_h.u = make_uint4(ah[4 * t], ah[4 * t + 1], ah[4 * t + 2], ah[4 * t + 3]);
       fa_m.u = make_uint4(am[4 * t], am[4 * t + 1], am[4 * t + 2], am[4 * t + 3]);
       fa_l.u = make_uint4(al[4 * t], al[4 * t + 1], al[4 * t + 2], al[4 * t + 3]);
 #pragma unroll
       for (int tl = 0; tl < NTILE; tl += 2) {       // two column tiles: two independent accumulator chains
         const int o0 = plane_off<KQD, GS>(g, tl * 16 + ri, t), o1 = plane_off<KQD, GS>(g, tl * 16 + 16 + ri, t);
-        Frag8 b0h, b0m, b0l, b1h, b1m, b1l;
+        Frag b0h, b0m, b0l, b1h, b1m, b1l;
         b0h.u = *reinterpret_cast<const uint4*>(&sWh[o0]);
         b0m.u = *reinterpret_cast<const uint4*>(&sWm[o0]);
         b0l.u = *reinterpret_cast<const uint4*>(&sWl[o0]);
@@ -511,14 +501,14 @@ __global__ __launch_bounds__(kX6Block) void fused_linear_bwd_x6_kernel(
 #pragma unroll
     for (int t = 0; t < T; ++t) {
 #endif
-      Frag8 fa_h, fa_m, fa_l;
+      Frag fa_h, fa_m, fa_l;
       fa_h.u = make_uint4(ah[4 * t], ah[4 * t + 1], ah[4 * t + 2], ah[4 * t + 3]);
       fa_m.u = make_uint4(am[4 * t], am[4 * t + 1], am[4 * t + 2], am[4 * t + 3]);
       fa_l.u = make_uint4(al[4 * t], al[4 * t + 1], al[4 * t + 2], al[4 * t + 3]);
 #pragma unroll
       for (int tl = 0; tl < NTILE; tl += 2) {
         const int o0 = plane_off<OQD, GS>(g, tl * 16 + ri, t), o1 = plane_off<OQD, GS>(g, tl * 16 + 16 + ri, t);
-        Frag8 b0h, b0m, b0l, b1h, b1m, b1l;
+        Frag b0h, b0m, b0l, b1h, b1m, b1l;
         b0h.u = *reinterpret_cast<const uint4*>(&sWh[o0]);
         b0m.u = *reinterpret_cast<const uint4*>(&sWm[o0]);
         b0l.u = *reinterpret_cast<const uint4*>(&sWl[o0]);

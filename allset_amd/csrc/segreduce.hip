@@ -15,6 +15,7 @@
 // HBM-bound by construction: algorithmic bytes per launch are nnz*(4*d + 4) + (n_t+1)*4 + n_t*4*d
 // (SURVEY.md section 8(d3)); VALU work is one FMA per gathered element.
 #include "common.h"
+#include "mfma.h"     // dpp_row
 
 namespace allset {
 
@@ -319,16 +320,12 @@ __global__ __launch_bounds__(kBlock) void sddmm_rowdot_kernel(
 // of contiguous floats (lane li < kUnroll of slot s holds incidence j + li * NS + s).  The scalar kernel above -- a serial
 // loop over incidences with 4-byte loads, a 6-step shuffle reduction and a lane-0 store per incidence, nothing in flight --
 // ran at 0.3 of the gather roofline (3.25 ms per pass at 1M rows x 16 x 128 where segreduce moves the same rows in 1.19).
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
 template <int LPR>
 __device__ __forceinline__ float slot_sum(float v) {      // sum over the LPR lanes of a slot, result in every lane of it
-  v = dpp_add<0xB1>(v);                                   // quad_perm [1,0,3,2]
-  v = dpp_add<0x4E>(v);                                   // quad_perm [2,3,0,1]
-  v = dpp_add<0x141>(v);                                  // row_half_mirror: the other quad of the 8
-  if constexpr (LPR >= 16) v = dpp_add<0x140>(v);         // row_mirror: the other half of the 16
+  v += dpp_row<0xB1>(v);                                 // quad_perm [1,0,3,2]
+  v += dpp_row<0x4E>(v);                                 // quad_perm [2,3,0,1]
+  v += dpp_row<0x141>(v);                                // row_half_mirror: the other quad of the 8
+  if constexpr (LPR >= 16) v += dpp_row<0x140>(v);       // row_mirror: the other half of the 16
   if constexpr (LPR >= 32) v += __shfl_xor(v, 16);
   if constexpr (LPR >= 64) v += __shfl_xor(v, 32);
   return v;

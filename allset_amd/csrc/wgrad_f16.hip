@@ -29,13 +29,10 @@
 // stage's largest element); a gradient COLUMN that far below the others therefore loses low bits -- the contract of the 128-wide
 // one-pass backward (include/allset_hip_ext.h, "arithmetic").  ALLSET_ARITH_BF16X6 callers keep wgrad_x6_kernel.
 #include "common.h"
+#include "mfma.h"
 
 namespace allset {
 
-using f16x8w_t = __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16;
-using f32x16w_t = __attribute__((ext_vector_type(16))) float;
-typedef short wf_v4s_t __attribute__((ext_vector_type(4)));
-union WfFrag { uint4 u; f16x8w_t v; struct { wf_v4s_t lo, hi; } t; };
 constexpr int kWfBlock = 512;
 constexpr int kWfRows = 32;                          // rows per stage
 constexpr int kWfTO = 256, kWfTI = 128;              // the workgroup's tile of gW
@@ -53,7 +50,8 @@ struct WfArgs {
   int64_t n; int O, I, tiles_i; int64_t rows_per_slice; int n_slices;
 };
 
-// max over the 16 lanes of a DPP row (v >= 0, no NaN handling wanted: one v_max_f32_dpp per step)
+// max over the 16 lanes of a DPP row as inline asm (v >= 0, no NaN handling wanted: one v_max_f32_dpp per step, the s_nop are the
+// DPP hazard's wait states; mfma.h row16_max is the builtin form, with fmaxf's canonicalisation)
 __device__ __forceinline__ float wf_row16_max(float v) {
   asm volatile("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
                "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
@@ -61,34 +59,23 @@ __device__ __forceinline__ float wf_row16_max(float v) {
                "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\ts_nop 1" : "+v"(v));
   return v;
 }
-// max(|a.x|, |a.y|, |a.z|, |a.w|, m): two v_max3_f32 with |.| source modifiers (fmaxf / fabsf cost a canonicalising max each)
+// max(|a.x|, |a.y|, |a.z|, |a.w|, m): two v_max3_f32 with |.| source modifiers (fmaxf / fabsf -- fused_bwd6.hip amax4 -- cost a
+// canonicalising max each)
 __device__ __forceinline__ float wf_amax4(float4 a, float m) {
   asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a.x), "v"(a.y));
   asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a.z), "v"(a.w));
   return m;
 }
-using wf_lds_u8 = __attribute__((address_space(3))) uint8_t;
-__device__ __forceinline__ uint32_t wf_lds_off(const void* p) { return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((wf_lds_u8*)(p))); }
 // ds_max_u32 without the compiler's wave-reduction loop around an atomic on a uniform address (four lanes post per wave)
 __device__ __forceinline__ void wf_lds_max(uint32_t* p, uint32_t v) {
-  asm volatile("ds_max_u32 %0, %1" :: "v"(wf_lds_off(p)), "v"(v) : "memory");
+  asm volatile("ds_max_u32 %0, %1" :: "v"(lds_off(p)), "v"(v) : "memory");
 }
-// 2^(field - 127) for a biased exponent field; fields <= 0 give 0.0
+// 2^(field - 127) for a biased exponent field; fields <= 0 give 0.0 (a branch: fused_bwd6.hip pow2_field has none and needs field >= 0)
 __device__ __forceinline__ float wf_pow2(int field) { return field > 0 ? __uint_as_float(static_cast<uint32_t>(field) << 23) : 0.f; }
-// byte offset of (row, column byte) in a [32][256 B] 16-bit plane (fused_bwd6.hip img_off_s: conflict-free for the row-wise 8-byte
-// stores and for the transposing reads)
-__device__ __forceinline__ int wf_img_off(int row, int colbyte) {
-  return row * 256 + ((((colbyte >> 6) ^ row) & 3) << 6) + (((((colbyte >> 4) & 3) ^ (row >> 2)) & 3) << 4) + (colbyte & 15);
-}
-__device__ __forceinline__ f16x8w_t wf_tr_frag(uint32_t lo, uint32_t hi) {
-  WfFrag f;
-  f.t.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<__attribute__((address_space(3))) wf_v4s_t*>(static_cast<uintptr_t>(lo)));
-  f.t.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<__attribute__((address_space(3))) wf_v4s_t*>(static_cast<uintptr_t>(hi)));
-  return f.v;
-}
 
+// (not mfma.h's tick: __syncthreads(), the compiler's fence + barrier, which it may schedule around; the tick is opaque asm)
 #ifdef ALLSET_ABL_WF_NOBAR            // (ablation builds: timing only, results wrong)
-#define WF_SYNC() __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+#define WF_SYNC() ALLSET_TICK_NO_BARRIER()
 #else
 #define WF_SYNC() __syncthreads()
 #endif
@@ -228,7 +215,7 @@ __global__ __launch_bounds__(kWfBlock) void wgrad_f16_kernel(WfArgs g) {
   int Q = kWfEMin;                                                    // the largest stage exponent met so far (uniform over the workgroup)
   // dropout counter (element index / 4) of (row, block hb) = row * (I / 4) + i_base / 4 + 16 hb + c
   const uint32_t hp_lane = static_cast<uint32_t>(lr * (I / 4) + i_base / 4 + c);
-  const int wo0 = wf_img_off(lr, 8 * c), wo1 = wf_img_off(lr, 128 + 8 * c);     // column bytes 128 hb + 8 c of the lane's row
+  const int wo0 = swizzle256(lr, 8 * c), wo1 = swizzle256(lr, 128 + 8 * c);     // column bytes 128 hb + 8 c of the lane's row
 
   auto store_stage = [&](Stage& sg, int buf, int slot, int64_t r0) -> int {   // returns the Q this stage was scaled against
     const int e = min(max(static_cast<int>(__builtin_amdgcn_readfirstlane(static_cast<int>(sMax[slot])) >> 23), kWfEMin), 254);
@@ -242,8 +229,8 @@ __global__ __launch_bounds__(kWfBlock) void wgrad_f16_kernel(WfArgs g) {
     for (int hb = 0; hb < 4; ++hb) {
       const float4 a = sg.a[hb];
       uint32_t h0, l0, h1, l1;
-      split2_f16c(a.x * ks, a.y * ks, h0, l0);
-      split2_f16c(a.z * ks, a.w * ks, h1, l1);
+      split2_f16(a.x * ks, a.y * ks, h0, l0);
+      split2_f16(a.z * ks, a.w * ks, h1, l1);
       uint8_t* p = img + (hb >> 1) * kWfImg + ((hb & 1) ? wo1 : wo0);
       *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
       *reinterpret_cast<uint2*>(p + kWfPlane) = make_uint2(l0, l1);
@@ -269,8 +256,8 @@ __global__ __launch_bounds__(kWfBlock) void wgrad_f16_kernel(WfArgs g) {
         }
       }
       uint32_t h0, l0, h1, l1;
-      split2_f16c(t.x, t.y, h0, l0);
-      split2_f16c(t.z, t.w, h1, l1);
+      split2_f16(t.x, t.y, h0, l0);
+      split2_f16(t.z, t.w, h1, l1);
       uint8_t* p = img + 2 * kWfImg + (hb ? wo1 : wo0);
       *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
       *reinterpret_cast<uint2*>(p + kWfPlane) = make_uint2(l0, l1);
@@ -285,10 +272,10 @@ __global__ __launch_bounds__(kWfBlock) void wgrad_f16_kernel(WfArgs g) {
   uint32_t base_a, base_u;
   {
     const int q4 = lane >> 4, tr_row = 8 * (q4 >> 1) + ((lane & 15) >> 2), tr_in = 32 * (q4 & 1) + 8 * (lane & 3);
-    base_a = wf_lds_off(sP) + static_cast<uint32_t>((oh >> 1) * kWfImg + wf_img_off(tr_row, 64 * (2 * (oh & 1)) + tr_in));
-    base_u = wf_lds_off(sP) + static_cast<uint32_t>(2 * kWfImg + wf_img_off(tr_row, 64 * (2 * ih) + tr_in));
+    base_a = lds_off(sP) + static_cast<uint32_t>((oh >> 1) * kWfImg + swizzle256(tr_row, 64 * (2 * (oh & 1)) + tr_in));
+    base_u = lds_off(sP) + static_cast<uint32_t>(2 * kWfImg + swizzle256(tr_row, 64 * (2 * ih) + tr_in));
   }
-  f32x16w_t gw[2][2];
+  f32x16 gw[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -318,15 +305,15 @@ __global__ __launch_bounds__(kWfBlock) void wgrad_f16_kernel(WfArgs g) {
     const uint32_t ia = base_a + static_cast<uint32_t>(buf * kWfBuf), iu = base_u + static_cast<uint32_t>(buf * kWfBuf);
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      f16x8w_t wa[2][2], wb[2][2];
+      f16x8 wa[2][2], wb[2][2];
 #pragma unroll
       for (int tl = 0; tl < 2; ++tl) {
         const uint32_t a_lo = (ia ^ static_cast<uint32_t>(tl << 6)) + kb * 4096, a_hi = (ia ^ static_cast<uint32_t>((tl << 6) | 16)) + kb * 4096 + 1024;
         const uint32_t b_lo = (iu ^ static_cast<uint32_t>(tl << 6)) + kb * 4096, b_hi = (iu ^ static_cast<uint32_t>((tl << 6) | 16)) + kb * 4096 + 1024;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
-          wa[tl][pl] = wf_tr_frag(a_lo + pl * kWfPlane, a_hi + pl * kWfPlane);
-          wb[tl][pl] = wf_tr_frag(b_lo + pl * kWfPlane, b_hi + pl * kWfPlane);
+          wa[tl][pl] = tr_frag2_off<f16x8>(a_lo + pl * kWfPlane, a_hi + pl * kWfPlane);
+          wb[tl][pl] = tr_frag2_off<f16x8>(b_lo + pl * kWfPlane, b_hi + pl * kWfPlane);
         }
       }
       constexpr int PA_[3] = {1, 0, 0}, PB_[3] = {0, 1, 0};          // l.h, h.l, h.h
@@ -349,7 +336,7 @@ __global__ __launch_bounds__(kWfBlock) void wgrad_f16_kernel(WfArgs g) {
   int sl0 = 0, sl1 = 1, sl2 = 2;                                      // slots of stages k, k + 1, k + 2
 #ifdef ALLSET_ABL_WF_TIMING         // diagnostic builds only: cycles per segment of waves 0 and 4 of workgroup (0, 0)
   uint64_t tph[5] = {0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#define WF_MARK(k) do { const uint64_t tn = __builtin_readcyclecounter(); tph[k] += tn - tlast; tlast = tn; } while (0)
+#define WF_MARK(k) ALLSET_PHASE_MARK(k)
 #else
 #define WF_MARK(k) do {} while (0)
 #endif

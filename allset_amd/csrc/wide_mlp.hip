@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace allset {
 
@@ -25,9 +26,6 @@ constexpr int kGxBM = 128, kGxBN = 256, kGxKS = 32, kGxThreads = 512;
 // piece on rows {4-11}, and the 16 of them must land on the 16 distinct 16-byte slots of the 256-byte bank line.  Storing
 // piece p of row r at position p ^ h((r >> 2) & 3) with h = {0, 2, 3, 1} does exactly that (slot = 4 * (r & 3) + position).
 __host__ __device__ __forceinline__ int gx_swz(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }
-using bf16x8_t = __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16;
-using f32x4_t = __attribute__((ext_vector_type(4))) float;
-union GxFrag { uint4 u; bf16x8_t v; };
 
 // Where dword `at` of a K step's LDS slab of B (3 planes x 256 n x 32 k bf16 = 3072 pieces of 16 bytes; thread t of the
 // 512 copies pieces t, t + 512, ..., t + 2560) sits in the global image: the six pieces of one WAVE are adjacent (6 x 1 KB),
@@ -63,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void gemm_x6_planes_kernel(const float* __r
   }
 }
 
-// ---- the same weight in TWO fp16 planes ("fp16x3", common.h split2_f16c) -----------------------------------------------------------
+// ---- the same weight in TWO fp16 planes ("fp16x3", mfma.h split2_f16) ------------------------------------------------------------
 // Row n of B is scaled by 2^(140 - e_n), e_n = the biased exponent of its largest element (so that it lands in [2^13, 2^14)); the
 // inverse 2^(e_n - 140) per output column is stored behind the planes (float[n_pad]) and applied in the GEMM's epilogue.
 // ONE launch (round 6, second session: at dataset scale a step rebuilds ten plane images -- W and W^T of five wide Linears -- and the
@@ -88,7 +86,7 @@ __device__ __forceinline__ void gemm_f16_planes_row(const float* __restrict__ W,
       else { w0 = W[static_cast<int64_t>(n) * ldw + k]; w1 = W[static_cast<int64_t>(n) * ldw + k + 1]; }
     }
     uint32_t ph, pl;
-    split2_f16c(w0 * sc, w1 * sc, ph, pl);
+    split2_f16(w0 * sc, w1 * sc, ph, pl);
     const int ks = k / kGxKS, kk = k % kGxKS;
     const int64_t image = (static_cast<int64_t>(nt) * (K / kGxKS) + ks) * 2 * (kGxBN * kGxKS / 2);   // dwords
     const int at = nn * (kGxKS / 2) + (((kk >> 3) ^ gx_swz(nn)) << 2) + ((kk & 7) >> 1);
@@ -180,19 +178,10 @@ struct GxRow {
   float asc;               // fp16x3 without a LayerNorm prologue: the power of two this row's A elements are scaled by (its inverse goes
   bool ok;                 // to sRowInv for the epilogue)
 };
-using f16x8_t = __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16;
-union GxFragH { uint4 u; f16x8_t v; };
 // sum over the 64 lanes of a wave, the same value in every lane: DPP sums inside each row of 16 lanes, then the four row totals by
 // v_readlane (scalar registers) -- ~11 short-latency instructions where six __shfl_xor steps are six dependent ds_bpermute round trips
-template <int CTRL>
-__device__ __forceinline__ float gx_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
 __device__ __forceinline__ float gx_wave_sum(float v) {
-  v += gx_dpp<0xB1>(v);          // quad_perm [1,0,3,2]
-  v += gx_dpp<0x4E>(v);          // quad_perm [2,3,0,1]
-  v += gx_dpp<0x141>(v);         // row_half_mirror
-  v += gx_dpp<0x140>(v);         // row_mirror
+  v = row16_sum(v);
   const int b = __float_as_int(v);
   return (__int_as_float(__builtin_amdgcn_readlane(b, 0)) + __int_as_float(__builtin_amdgcn_readlane(b, 16))) +
          (__int_as_float(__builtin_amdgcn_readlane(b, 32)) + __int_as_float(__builtin_amdgcn_readlane(b, 48)));
@@ -364,10 +353,10 @@ __global__ __launch_bounds__(kGxThreads) void gemm_x6_kernel(
     uint4 h_, m_, l_;                                                                           \
     if constexpr (F16) {                                                                        \
       const float sc_ = mask_fold ? (ctx_).asc * inv_mask : (ctx_).asc;                         \
-      split2_f16c(e0 * sc_, e1 * sc_, h_.x, l_.x);                                              \
-      split2_f16c(e2 * sc_, e3 * sc_, h_.y, l_.y);                                              \
-      split2_f16c(e4 * sc_, e5 * sc_, h_.z, l_.z);                                              \
-      split2_f16c(e6 * sc_, e7 * sc_, h_.w, l_.w);                                              \
+      split2_f16(e0 * sc_, e1 * sc_, h_.x, l_.x);                                               \
+      split2_f16(e2 * sc_, e3 * sc_, h_.y, l_.y);                                               \
+      split2_f16(e4 * sc_, e5 * sc_, h_.z, l_.z);                                               \
+      split2_f16(e6 * sc_, e7 * sc_, h_.w, l_.w);                                               \
       sA[buf_][a_st] = h_;                                                                      \
       sA[buf_][kGxBM * 4 + a_st] = l_;                                                          \
       sB[buf_][tid] = pb0; sB[buf_][tid + kGxThreads] = pb1; sB[buf_][tid + 2 * kGxThreads] = pb2; \
@@ -395,26 +384,26 @@ __global__ __launch_bounds__(kGxThreads) void gemm_x6_kernel(
   // opposite order -- one multiplies out of the current buffers while the other splits and stores the next ones -- so the
   // matrix pipe and the VALU / LDS-store path are busy at the same time instead of taking turns.
   const bool mfma_first = wave < 4;
-  f32x4_t acc[4][4];
+  f32x4 acc[4][4];
 
   auto compute = [&](int buf) {
     if constexpr (F16) {
 #pragma unroll
       for (int rh = 0; rh < 2; ++rh) {
-        GxFragH a[2][2];
+        Frag a[2][2];
 #pragma unroll
         for (int r2 = 0; r2 < 2; ++r2)
 #pragma unroll
           for (int p = 0; p < 2; ++p) a[r2][p].u = sA[buf][p * kGxBM * 4 + a_at + (rh * 2 + r2) * 64];
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) {
-          GxFragH b[2];
+          Frag b[2];
 #pragma unroll
           for (int p = 0; p < 2; ++p) b[p].u = sB[buf][p * kGxBN * 4 + b_at + ct * 64];
 #define GX_MM16(X, Y, C) (kSwap ? __builtin_amdgcn_mfma_f32_16x16x32_f16(Y, X, C, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_f16(X, Y, C, 0, 0, 0))
 #define GX_MFMAH(PA, PB)                                                                                                  \
-  acc[rh * 2][ct] = GX_MM16(a[0][PA].v, b[PB].v, acc[rh * 2][ct]);                                                        \
-  acc[rh * 2 + 1][ct] = GX_MM16(a[1][PA].v, b[PB].v, acc[rh * 2 + 1][ct])
+  acc[rh * 2][ct] = GX_MM16(a[0][PA].h, b[PB].h, acc[rh * 2][ct]);                                                        \
+  acc[rh * 2 + 1][ct] = GX_MM16(a[1][PA].h, b[PB].h, acc[rh * 2 + 1][ct])
           GX_MFMAH(1, 0); GX_MFMAH(0, 1); GX_MFMAH(0, 0);              // l.h, h.l, h.h
 #undef GX_MFMAH
 #undef GX_MM16
@@ -423,14 +412,14 @@ __global__ __launch_bounds__(kGxThreads) void gemm_x6_kernel(
     } else {
 #pragma unroll
     for (int rh = 0; rh < 2; ++rh) {                                   // two row tiles at a time: 24 + 12 fragment registers
-      GxFrag a[2][3];
+      Frag a[2][3];
 #pragma unroll
       for (int r2 = 0; r2 < 2; ++r2)
 #pragma unroll
         for (int p = 0; p < 3; ++p) a[r2][p].u = sA[buf][p * kGxBM * 4 + a_at + (rh * 2 + r2) * 64];
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
-        GxFrag b[3];
+        Frag b[3];
 #pragma unroll
         for (int p = 0; p < 3; ++p) b[p].u = sB[buf][p * kGxBN * 4 + b_at + ct * 64];
         // smallest products first; consecutive MFMAs alternate between two accumulators
@@ -448,7 +437,7 @@ __global__ __launch_bounds__(kGxThreads) void gemm_x6_kernel(
 
 #ifdef ALLSET_ABL_GX_TIMING         // diagnostic builds only (tools/gemm_wide_ablation.py): cycles per segment of waves 0 and 4 of workgroup 0
   uint64_t tph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#define GX_MARK(k) do { const uint64_t tn = __builtin_readcyclecounter(); tph[k] += tn - tlast; tlast = tn; } while (0)
+#define GX_MARK(k) ALLSET_PHASE_MARK(k)
 #else
 #define GX_MARK(k) do {} while (0)
 #endif
@@ -504,7 +493,7 @@ __global__ __launch_bounds__(kGxThreads) void gemm_x6_kernel(
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+      for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
     GX_MARK(4);
     GX_STORE(cur, 0, 0);                                               // step 0 of this tile (loaded during the previous one)
     GX_MARK(1);
@@ -919,14 +908,14 @@ __global__ __launch_bounds__(kGrThreads) void gemm_f16_roles_kernel(
     __syncthreads();
   }
 #ifdef ALLSET_ABL_GR_NOBAR          // ablation builds only (tools/gemm_roles_ablation.py): timing without the barriers, results wrong
-#define GR_TICK() __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+#define GR_TICK() ALLSET_TICK_NO_BARRIER()
 #else
-#define GR_TICK() __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+#define GR_TICK() ALLSET_TICK_BARRIER()
 #endif
   const bool has_stats_out = epi.stats_out != nullptr;
 #ifdef ALLSET_ABL_GR_TIMING         // diagnostic builds only (tools/gemm_roles_ablation.py): cycles per segment of waves 0 (vector) and 8 (matrix) of workgroup 0
   uint64_t tph[4] = {0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#define GR_MARK(k) do { const uint64_t tn = __builtin_readcyclecounter(); tph[k] += tn - tlast; tlast = tn; } while (0)
+#define GR_MARK(k) ALLSET_PHASE_MARK(k)
 #else
 #define GR_MARK(k) do {} while (0)
 #endif
@@ -1053,10 +1042,10 @@ __global__ __launch_bounds__(kGrThreads) void gemm_f16_roles_kernel(
       }
       const float sc = mask_fold ? asc * inv_mask : asc;
       uint4 h, l;
-      split2_f16c(e[0] * sc, e[1] * sc, h.x, l.x);
-      split2_f16c(e[2] * sc, e[3] * sc, h.y, l.y);
-      split2_f16c(e[4] * sc, e[5] * sc, h.z, l.z);
-      split2_f16c(e[6] * sc, e[7] * sc, h.w, l.w);
+      split2_f16(e[0] * sc, e[1] * sc, h.x, l.x);
+      split2_f16(e[2] * sc, e[3] * sc, h.y, l.y);
+      split2_f16(e[4] * sc, e[5] * sc, h.z, l.z);
+      split2_f16(e[6] * sc, e[7] * sc, h.w, l.w);
       sA[buf][a_st] = h;
       sA[buf][kGxBM * 4 + a_st] = l;
       sB[buf][tid] = q0; sB[buf][tid + kGrVThreads] = q1; sB[buf][tid + 2 * kGrVThreads] = q2; sB[buf][tid + 3 * kGrVThreads] = q3;
@@ -1118,7 +1107,7 @@ __global__ __launch_bounds__(kGrThreads) void gemm_f16_roles_kernel(
     const int fr = lane & 15, fg = lane >> 4;
     const int sw = gx_swz(fr);
     const int a_at = (wr * 64 + fr) * 4 + (fg ^ sw), b_at = (wc * 64 + fr) * 4 + (fg ^ sw);
-    f32x4_t acc[4][4];
+    f32x4 acc[4][4];
     auto compute = [&](int buf) __attribute__((always_inline)) {
       // 128 registers per wave (16 waves per CU): 64 accumulators + the A fragments of two row tiles (16) + the B fragments of the
       // current and the NEXT column tile (16) -- requested one column tile ahead, explicitly: left to itself the scheduler hoists all of a
@@ -1127,7 +1116,7 @@ __global__ __launch_bounds__(kGrThreads) void gemm_f16_roles_kernel(
       const uint4* pb = &sB[buf][b_at];
 #pragma unroll
       for (int rh = 0; rh < 2; ++rh) {
-        GxFragH a[2][2], b[2][2];
+        Frag a[2][2], b[2][2];
 #pragma unroll
         for (int r2 = 0; r2 < 2; ++r2)
 #pragma unroll
@@ -1136,11 +1125,11 @@ __global__ __launch_bounds__(kGrThreads) void gemm_f16_roles_kernel(
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) {
           if (ct + 1 < 4) { b[(ct + 1) & 1][0].u = pb[(ct + 1) * 64]; b[(ct + 1) & 1][1].u = pb[kGxBN * 4 + (ct + 1) * 64]; }
-          const GxFragH (&bc)[2] = b[ct & 1];
+          const Frag (&bc)[2] = b[ct & 1];
           // operands swapped (the weight fragment is A): acc[rt][ct][q] = out[row fr][column 4 fg + q] of the 16 x 16 tile; l.h, h.l, h.h
 #define GR_MFMA(PA, PB)                                                                                                   \
-  acc[rh * 2][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bc[PB].v, a[0][PA].v, acc[rh * 2][ct], 0, 0, 0);               \
-  acc[rh * 2 + 1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bc[PB].v, a[1][PA].v, acc[rh * 2 + 1][ct], 0, 0, 0)
+  acc[rh * 2][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bc[PB].h, a[0][PA].h, acc[rh * 2][ct], 0, 0, 0);               \
+  acc[rh * 2 + 1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bc[PB].h, a[1][PA].h, acc[rh * 2 + 1][ct], 0, 0, 0)
 #ifdef ALLSET_ABL_GR_NOMFMA         // ablation builds only: the fragment reads stay, the MFMAs go
           acc[rh * 2][ct][0] += __builtin_bit_cast(float, bc[0].u.x ^ bc[1].u.y ^ a[0][0].u.z ^ a[0][1].u.w);
           acc[rh * 2 + 1][ct][0] += __builtin_bit_cast(float, bc[0].u.y ^ bc[1].u.x ^ a[1][0].u.z ^ a[1][1].u.w);
@@ -1240,7 +1229,7 @@ __global__ __launch_bounds__(kGrThreads) void gemm_f16_roles_kernel(
                 const float d0 = t.x - mu, d1 = t.y - mu, d2 = t.z - mu, d3 = t.w - mu;
                 a = fmaf(d0, d0, fmaf(d1, d1, fmaf(d2, d2, d3 * d3)));
               }
-              a += gx_dpp<0xB1>(a); a += gx_dpp<0x4E>(a); a += gx_dpp<0x141>(a); a += gx_dpp<0x140>(a);
+              a = row16_sum(a);
               if (c == 0) sS[rr * 4 + wc] = a;
             }
           __syncthreads();
@@ -1263,7 +1252,7 @@ __global__ __launch_bounds__(kGrThreads) void gemm_f16_roles_kernel(
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
       for (int ks = 0; ks < ksteps; ks += 2) {                         // (ksteps is even: the buffer index is a compile-time constant --
         GR_MARK(3);
         compute(0);                                                    //  behind a run-time parity the accumulators became loop phis with
