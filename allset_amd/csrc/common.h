@@ -253,19 +253,19 @@ __device__ __forceinline__ uint64_t resolve_seed(const uint64_t* base, uint64_t 
 //   any other p: 16 bits per element, one hash per PAIR (counter = idx >> 1), keep iff u16 >= p * 65536.
 // drop_threshold() returns the threshold with the resolution in bit 16 (kDrop8).
 constexpr uint32_t kDrop8 = 0x10000u;
-__device__ __forceinline__ uint32_t drop_threshold(float p) {
+// ONE definition for both sides: entry points that resolve the threshold on the host pass it to kernels whose masks are regenerated
+// by kernels that resolve it on the device (dense.dropout_scale and hconv_bwd_epi against the hop forwards).
+__host__ __device__ __forceinline__ uint32_t drop_threshold(float p) {
 #ifndef ALLSET_ABL_DROP16          // (ablation builds: the 16-bit form for every p)
   const float t8 = p * 256.0f;
   if (t8 == floorf(t8)) return kDrop8 | static_cast<uint32_t>(t8);
 #endif
   return static_cast<uint32_t>(p * 65536.0f);
 }
-// drop_threshold() for entry points that resolve the threshold on the host and pass it to their kernels.  The two MUST agree: masks
-// drawn by a kernel of one kind are regenerated by kernels of the other (dense.dropout_scale against the attention hops).
-inline uint32_t host_drop_threshold(float p) {
-  const float t8 = p * 256.0f;
-  return (t8 == floorf(t8)) ? (kDrop8 | static_cast<uint32_t>(t8)) : static_cast<uint32_t>(p * 65536.0f);
-}
+// the 8-bit form (p <= 0 included: 0 * 256 is integral) -- for launchers that pick a kernel by resolution
+__host__ __device__ __forceinline__ bool drop_is8(float p) { return (drop_threshold(p) & kDrop8) != 0; }
+// the scale of a kept element
+__host__ __device__ __forceinline__ float drop_inv_keep(float p) { return p > 0.f ? 1.f / (1.f - p) : 1.f; }
 __device__ __forceinline__ float keep_scale(uint64_t seed, int64_t idx, uint32_t thr, float inv_keep) {
   if (thr & kDrop8) {
     const uint32_t h = pair_hash(seed, idx >> 2);

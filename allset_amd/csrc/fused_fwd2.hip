@@ -587,12 +587,7 @@ int launch_fused_linear_fwd_roles(hipStream_t st, const float* x, int64_t ldx, c
   const int64_t blocks = (n + kF2Rows - 1) / kF2Rows;
   const unsigned grid = static_cast<unsigned>(blocks > 256 ? 256 : (blocks < 1 ? 1 : blocks));      // one persistent workgroup per CU
   // the dropout resolution is a function of p alone (common.h drop_threshold): 8 bits per element when p * 256 is an integer
-  auto is8 = [](float p) { const float t8 = p * 256.0f; return p <= 0.f || t8 == floorf(t8); };
-#ifdef ALLSET_ABL_DROP16          // (ablation builds: the 16-bit form for every p, common.h)
-  const bool d8 = false; (void)is8;
-#else
-  const bool d8 = is8(p_in) && is8(p_out);
-#endif
+  const bool d8 = drop_is8(p_in) && drop_is8(p_out);
   // fp16x3 arithmetic: behind a true LayerNorm prologue (its bound on the operand gives one scale per launch) and -- round 5 -- without
   // any norm (one scale per row, from the row's largest element); bf16x6 in the column-affine mode and on request (ALLSET_ARITH_BF16X6)
 #ifdef ALLSET_NO_F16X3

@@ -26,38 +26,22 @@
 #include <float.h>
 
 #include "common.h"
+#include "row_epilogue.h"
 
 namespace allset {
 namespace gat {
 
-enum { kActNone = 0, kActRelu = 1 };
 constexpr int kUnroll = 8;
 constexpr int kMaxHeads = 64;            // one lane group per head in the stats kernel
 constexpr int kMaxWidth = 512;           // H * C: the head-mean epilogue stages one row per wave in LDS
 constexpr float kSoftmaxEps = 1e-16f;    // torch_geometric.utils.softmax denominator guard
-
-struct Epi {
-  const float* bias;      // per output column, or NULL
-  int act;
-  float p;
-  uint64_t seed;          // resolved (seed_base folded in) at kernel start
-  uint32_t thr;
-  float inv_keep;
-};
-
-__device__ __forceinline__ float epilogue1(const Epi& e, float v, int64_t row, int c, int width) {
-  if (e.bias) v += e.bias[c];
-  if (e.act == kActRelu) v = fmaxf(v, 0.f);
-  if (e.p > 0.f) v *= keep_scale(e.seed, row * width + c, e.thr, e.inv_keep);
-  return v;
-}
 
 template <int VEC, int LPR, bool POS>
 __global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ al, const float* __restrict__ ar,
     const float* __restrict__ x, int64_t ldx, float slope, float* __restrict__ y, int64_t ldy, float* __restrict__ agg, int64_t lda,
     float* __restrict__ aggpos, int64_t ldp, float* __restrict__ ppos, float* __restrict__ m_out, float* __restrict__ l_out, int n_t,
-    int H, int C, int concat, const int32_t* __restrict__ row_order, Epi epi, const uint64_t* __restrict__ seed_base) {
+    int H, int C, int concat, const int32_t* __restrict__ row_order, RowEpi epi, const uint64_t* __restrict__ seed_base) {
   constexpr int NS = kWave / LPR;
   __shared__ float stage[kWavesPerBlock][kMaxWidth];               // head-mean form: the row's agg, one wave's worth
   const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
@@ -159,7 +143,10 @@ __global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
       }
       if (concat) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) r.v[k] = epilogue1(epi, r.v[k], row, c0 + k, d);
+        for (int k = 0; k < VEC; ++k) {
+          const int c = c0 + k;
+          r.v[k] = row_epilogue<false>(epi, r.v[k], c, [=] { return static_cast<int64_t>(row) * d + c; });
+        }
         store_vec<float, VEC>(y + static_cast<int64_t>(row) * ldy + c0, r);
       } else {
 #pragma unroll
@@ -174,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
     for (int c = lane; c < C; c += kWave) {
       float s = 0.f;
       for (int h = 0; h < H; ++h) s += stage[wave][h * C + c];
-      y[static_cast<int64_t>(row) * ldy + c] = epilogue1(epi, s * inv_h, row, c, C);
+      y[static_cast<int64_t>(row) * ldy + c] = row_epilogue<false>(epi, s * inv_h, c, [=] { return static_cast<int64_t>(row) * C + c; });
     }
   }
 }
@@ -382,7 +369,7 @@ extern "C" int allset_gat_fwd(int variant, int64_t nnz, const int32_t* row_order
   ALLSET_REQUIRE(ldx >= d && ldy >= dy && (!agg || ldagg >= d) && (!aggpos || ldpos >= d), "gat_fwd: leading dimension smaller than the row");
   const bool wide_ok = (C % 4 == 0) && (ldx % 4 == 0) && aligned16(x) && (!concat || (ldy % 4 == 0 && aligned16(y))) &&
                        (!agg || (ldagg % 4 == 0 && aligned16(agg))) && (!aggpos || (ldpos % 4 == 0 && aligned16(aggpos)));
-  Epi e{bias, act, p, seed, host_drop_threshold(p), p > 0.f ? 1.f / (1.f - p) : 1.f};
+  const RowEpi e = row_epi(bias, act, p, seed);
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = row_grid(n_t);
 #define ALLSET_GAT_FWD(VEC, LPR)                                                                                                   \

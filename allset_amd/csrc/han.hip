@@ -659,8 +659,8 @@ extern "C" int allset_han_hop_fwd(int64_t nnz, const int32_t* rowptr, const int3
   ALLSET_REQUIRE(ldx >= d && ldy >= d && (!outpos || ldpos >= d), "han_hop_fwd: leading dimension smaller than the row");
   const bool wide_ok = (C % 4 == 0) && (ldx % 4 == 0) && aligned16(x) && (ldy % 4 == 0) && aligned16(y) &&
                        (!outpos || (ldpos % 4 == 0 && aligned16(outpos)));
-  const uint32_t thr = host_drop_threshold(p_att);
-  const float inv_keep = p_att > 0.f ? 1.f / (1.f - p_att) : 1.f;
+  const uint32_t thr = drop_threshold(p_att);
+  const float inv_keep = drop_inv_keep(p_att);
   const int drop = p_att > 0.f ? 1 : 0;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = row_grid(n);
@@ -713,8 +713,8 @@ extern "C" int allset_han_hop_bwd_src(int64_t nnz, const int32_t* rowptrT, const
   ALLSET_REQUIRE(ldx >= d && ldg >= d && ldgx >= d, "han_hop_bwd_src: leading dimension smaller than H*C");
   ALLSET_REQUIRE((reinterpret_cast<uintptr_t>(stats) & 7u) == 0, "han_hop_bwd_src: stats must be 8-byte aligned");
   const bool wide_ok = (C % 4 == 0) && (ldx % 4 == 0) && (ldg % 4 == 0) && (ldgx % 4 == 0) && aligned16(x) && aligned16(g) && aligned16(gx);
-  const uint32_t thr = host_drop_threshold(p_att);
-  const float inv_keep = p_att > 0.f ? 1.f / (1.f - p_att) : 1.f;
+  const uint32_t thr = drop_threshold(p_att);
+  const float inv_keep = drop_inv_keep(p_att);
   const int drop = p_att > 0.f ? 1 : 0;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = row_grid(n);

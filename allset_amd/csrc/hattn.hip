@@ -31,11 +31,11 @@
 #include <float.h>
 
 #include "common.h"
+#include "row_epilogue.h"
 
 namespace allset {
 namespace hattn {
 
-enum { kActNone = 0, kActRelu = 1, kActElu = 2 };
 constexpr int kUnroll = 4;
 constexpr int kMaxHeads = 64;
 constexpr int kMaxWidth = 512;
@@ -46,23 +46,6 @@ struct Geo {
   int LH;     // lanes per head (power of two)
   int GW;     // lanes per incidence slot = Hp * LH (power of two, <= 64)
 };
-
-struct Epi {
-  const float* bias;      // per output column, or NULL
-  int act;
-  float p;
-  uint64_t seed;          // resolved (seed_base folded in) at kernel start
-  uint32_t thr;
-  float inv_keep;
-};
-
-__device__ __forceinline__ float epilogue1(const Epi& e, float v, int64_t row, int c, int width) {
-  if (e.bias) v += e.bias[c];
-  if (e.act == kActRelu) v = fmaxf(v, 0.f);
-  else if (e.act == kActElu) v = v > 0.f ? v : expm1f(v);
-  if (e.p > 0.f) v *= keep_scale(e.seed, row * width + c, e.thr, e.inv_keep);
-  return v;
-}
 
 // One wavefront per vertex; lanes stride the vertex's incidences, heads in turn.
 __global__ __launch_bounds__(kBlock) void hattn_coef_kernel(
@@ -103,7 +86,7 @@ template <int VEC, int NPL>
 __global__ __launch_bounds__(kBlock) void hattn_hop_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ w, const float* __restrict__ r,
     const float* __restrict__ s, const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy, int n_t, Geo g,
-    int concat, const int32_t* __restrict__ row_order, Epi epi, const uint64_t* __restrict__ seed_base) {
+    int concat, const int32_t* __restrict__ row_order, RowEpi epi, const uint64_t* __restrict__ seed_base) {
   const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
   const int slot_row = static_cast<int>(blk) * kWavesPerBlock + (threadIdx.x >> 6);
   if (slot_row >= n_t) return;  // whole wave exits together
@@ -189,7 +172,10 @@ __global__ __launch_bounds__(kBlock) void hattn_hop_kernel(
       if (on[k]) {
         FVec<VEC> o;
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) o.v[i] = epilogue1(epi, acc[k][i], row, cofs[k] + i, d);
+        for (int i = 0; i < VEC; ++i) {
+          const int c = cofs[k] + i;
+          o.v[i] = row_epilogue<true>(epi, acc[k][i], c, [=] { return static_cast<int64_t>(row) * d + c; });
+        }
         store_vec<float, VEC>(y + static_cast<int64_t>(row) * ldy + cofs[k], o);
       }
     }
@@ -200,7 +186,10 @@ __global__ __launch_bounds__(kBlock) void hattn_hop_kernel(
       if (on[k]) {
         FVec<VEC> o;
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) o.v[i] = epilogue1(epi, acc[k][i] * inv_h, row, cofs[k] + i, g.C);
+        for (int i = 0; i < VEC; ++i) {
+          const int c = cofs[k] + i;
+          o.v[i] = row_epilogue<true>(epi, acc[k][i] * inv_h, c, [=] { return static_cast<int64_t>(row) * g.C + c; });
+        }
         store_vec<float, VEC>(y + static_cast<int64_t>(row) * ldy + cofs[k], o);
       }
     }
@@ -423,7 +412,7 @@ extern "C" int allset_hattn_coef(int64_t nnz, const int32_t* rowptr, const int32
   ALLSET_REQUIRE(rowptr && av && m && l, "hattn_coef: null rowptr/av/m/l");
   ALLSET_REQUIRE(nnz == 0 || (col && perm && pos && ae && a_v && a_e), "hattn_coef: null col/perm/pos/ae/a_v/a_e with nnz > 0");
   hattn_coef_kernel<<<row_grid(n_v), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
-      rowptr, col, perm, pos, av, ae, slope, p, seed, seed_base, host_drop_threshold(p), p > 0.f ? 1.f / (1.f - p) : 1.f, a_v, a_e, m, l,
+      rowptr, col, perm, pos, av, ae, slope, p, seed, seed_base, drop_threshold(p), drop_inv_keep(p), a_v, a_e, m, l,
       static_cast<int>(n_v), static_cast<int>(H));
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
@@ -446,7 +435,7 @@ extern "C" int allset_hattn_hop(int64_t nnz, const int32_t* row_order, const int
   const bool wide_ok = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && aligned16(x) && aligned16(y);
   Geo g;
   const int npl = geometry(H, C, wide_ok ? 4 : 1, &g);
-  Epi e{bias, act, p, seed, host_drop_threshold(p), p > 0.f ? 1.f / (1.f - p) : 1.f};
+  const RowEpi e = row_epi(bias, act, p, seed);
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned grid = row_grid(n_t);
 #define ALLSET_HATTN_HOP(VEC, NPL)                                                                                               \

@@ -19,43 +19,27 @@
 // of the per-source r[col_j]: w is read in CSR order next to the column ids (one coalesced load per 64 incidences), so the
 // backward over the transposed CSR takes w permuted into that CSR's order, once per graph.
 #include "common.h"
+#include "row_epilogue.h"
 
 namespace allset {
 namespace hconv {
 
-enum { kActNone = 0, kActRelu = 1, kActElu = 2 };
 enum { kScNone = 0, kScR = 1, kScW = 2 };   // per-incidence scale: none, r[col_j] (per gathered row), w[j] (per CSR position)
 constexpr int kUnroll = 8;
 constexpr int kFlatRows = 7;          // rows per lane group in the short-row kernel (kFlatRows + 1 rowptr entries fit in 8 lanes)
 
 struct Epi {
   const float* s;         // per output row, or NULL
-  const float* bias;      // per column, or NULL
-  int act;
-  float p;
-  uint64_t seed;          // resolved (seed_base folded in) at kernel start
-  uint32_t thr;
-  float inv_keep;
+  RowEpi row;
 };
-
-__device__ __forceinline__ float act_fwd(float v, int act) {
-  if (act == kActRelu) return fmaxf(v, 0.f);
-  if (act == kActElu) return v > 0.f ? v : expm1f(v);
-  return v;
-}
 
 // epilogue of VEC consecutive columns c0.. of output row `row`
 template <int VEC>
 __device__ __forceinline__ void epilogue(const Epi& e, int row, int c0, int d, float (&acc)[VEC]) {
   const float sc = e.s ? e.s[row] : 1.f;
 #pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    float v = acc[k] * sc;
-    if (e.bias) v += e.bias[c0 + k];
-    v = act_fwd(v, e.act);
-    if (e.p > 0.f) v *= keep_scale(e.seed, static_cast<int64_t>(row) * d + c0 + k, e.thr, e.inv_keep);
-    acc[k] = v;
-  }
+  for (int k = 0; k < VEC; ++k)
+    acc[k] = row_epilogue<true>(e.row, acc[k] * sc, c0 + k, [=] { return static_cast<int64_t>(row) * d + c0 + k; });
 }
 
 template <int VEC>
@@ -66,23 +50,18 @@ __device__ __forceinline__ void store_row(float* __restrict__ y, int64_t ldy, in
   store_vec<float, VEC>(y + static_cast<int64_t>(row) * ldy + c0, o);
 }
 
-__device__ __forceinline__ Epi resolve(Epi e, const uint64_t* seed_base) {
-  e.seed = resolve_seed(seed_base, e.seed);
-  return e;
-}
-
 // SC: kScNone, kScR (r indexed by the gathered row id) or kScW (r is the weight stream, indexed by CSR position)
 template <int VEC, int LPR, int SC>
 __global__ __launch_bounds__(kBlock) void hconv_fwd_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ r,
     const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy, int n_t, int d,
-    const int32_t* __restrict__ row_order, Epi epi, const uint64_t* __restrict__ seed_base) {
+    const int32_t* __restrict__ row_order, Epi e, const uint64_t* __restrict__ seed_base) {
   constexpr int NS = kWave / LPR;
   const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
   const int slot_row = static_cast<int>(blk) * kWavesPerBlock + (threadIdx.x >> 6);
   if (slot_row >= n_t) return;  // whole wave exits together
   const int row = row_order ? row_order[slot_row] : slot_row;
-  const Epi e = resolve(epi, seed_base);
+  e.row.seed = resolve_seed(seed_base, e.row.seed);
   const int lane = lane_id();
   const int slot = lane / LPR, li = lane % LPR;
   const int start = rowptr[row], end = rowptr[row + 1];
@@ -148,7 +127,7 @@ __global__ __launch_bounds__(kBlock) void hconv_fwd_kernel(
 template <int LPR, int SC>
 __global__ __launch_bounds__(kBlock) void hconv_flat_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ r,
-    const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy, int n_t, int d, Epi epi,
+    const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy, int n_t, int d, Epi e,
     const uint64_t* __restrict__ seed_base) {
   constexpr int VEC = 4;
   constexpr int NS = kWave / LPR;
@@ -159,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void hconv_flat_kernel(
   const int64_t slot_global = (static_cast<int64_t>(blk) * kWavesPerBlock + (threadIdx.x >> 6)) * NS + slot;
   const int64_t r_begin64 = slot_global * kFlatRows;
   if (r_begin64 - static_cast<int64_t>(slot) * kFlatRows >= n_t) return;      // whole wave beyond the last row
-  const Epi e = resolve(epi, seed_base);
+  e.row.seed = resolve_seed(seed_base, e.row.seed);
   const int r_begin = static_cast<int>(min(r_begin64, static_cast<int64_t>(n_t)));
   const int r_end = min(r_begin + kFlatRows, n_t);
   const int c0 = li * VEC;
@@ -244,15 +223,7 @@ __global__ __launch_bounds__(kBlock) void hconv_bwd_epi_kernel(
       const float yv = y[row * ldy + c];
       float k = 1.f;
       if (p > 0.f) k = keep_scale(seed, row * d + c, thr, inv_keep);
-      float out;
-      if (act == kActRelu) {
-        out = yv > 0.f ? gv * k : 0.f;                             // (a select, as torch's relu backward: no 0 * NaN)
-      } else if (act == kActElu) {
-        const float a = yv * keep;
-        out = gv * k * (a > 0.f ? 1.f : a + 1.f);
-      } else {
-        out = gv * k;
-      }
+      const float out = row_epilogue_bwd(gv, yv, k, act, keep);
       g[row * ldo + c] = out;
       sum += out;
     }
@@ -315,13 +286,7 @@ static int hconv_fwd_impl(int sc, int variant, int64_t nnz, const int32_t* row_o
   ALLSET_REQUIRE(nnz == 0 || (col && x), "hconv_fwd: null col/x with nnz > 0");
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const bool vec4 = (d % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && aligned16(x) && aligned16(y);
-  const Epi e{s, bias, act, p, seed, 0u, p > 0.f ? 1.f / (1.f - p) : 1.f};
-  Epi ep = e;
-  {
-    // drop_threshold is a device function; the same formula on the host (p * 256 integral -> 8-bit form)
-    const float t8 = p * 256.0f;
-    ep.thr = (t8 == floorf(t8)) ? (kDrop8 | static_cast<uint32_t>(t8)) : static_cast<uint32_t>(p * 65536.0f);
-  }
+  const Epi ep{s, row_epi(bias, act, p, seed)};
   const int nt = static_cast<int>(n_t), di = static_cast<int>(d);
   const bool flat_ok = vec4 && d <= 256;
   const bool use_flat = flat_ok && (variant == 2 || (variant == 0 && nnz >= 0 && n_t > kFlatMinRows &&

@@ -26,11 +26,11 @@
 // of the last layer); anything else: ALLSET_ERR_UNSUPPORTED and the caller composes the hop from allset_hconv_fwd.
 // Algorithmic bytes: v2e nnz * (4d + 8) + (n_e + 1) * 4 + 12 n_e + 2 n_e * 4d;  e2v nnz * (4d + 4) + (n_v + 1) * 4 + 8 n_v + 2 n_v * 4d.
 #include "common.h"
+#include "row_epilogue.h"
 
 namespace allset {
 namespace hypergcn {
 
-enum { kActNone = 0, kActRelu = 1 };
 constexpr int kUnroll = 8;
 constexpr int kFlatRows = 7;
 constexpr int kMaxWidth = 256;
@@ -269,12 +269,7 @@ struct Tail {
   const float* selfc;     // per output row
   const float* x;         // the hop's input (the self term)
   int64_t ldx;
-  const float* bias;      // per column, or NULL
-  int act;
-  float p;
-  uint64_t seed;          // resolved (seed_base folded in) at kernel start
-  uint32_t thr;
-  float inv_keep;
+  RowEpi epi;
 };
 
 template <int VEC>
@@ -285,13 +280,8 @@ __device__ __forceinline__ void finish_row(const Tail& tl, int row, int c0, int 
   const FVec<VEC> xs = load_vec<float, VEC>(tl.x + static_cast<int64_t>(row) * tl.ldx + c0);
   FVec<VEC> o;
 #pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    float v = dv * fmaf(sc, xs.v[k], acc[k]);
-    if (tl.bias) v += tl.bias[c0 + k];
-    if (tl.act == kActRelu) v = fmaxf(v, 0.f);
-    if (tl.p > 0.f) v *= keep_scale(tl.seed, static_cast<int64_t>(row) * d + c0 + k, tl.thr, tl.inv_keep);
-    o.v[k] = v;
-  }
+  for (int k = 0; k < VEC; ++k)
+    o.v[k] = row_epilogue<false>(tl.epi, dv * fmaf(sc, xs.v[k], acc[k]), c0 + k, [=] { return static_cast<int64_t>(row) * d + c0 + k; });
   store_vec<float, VEC>(y + static_cast<int64_t>(row) * ldy + c0, o);
 }
 
@@ -305,7 +295,7 @@ __global__ __launch_bounds__(kBlock) void e2v_kernel(const int32_t* __restrict__
   const int slot_row = static_cast<int>(blk) * kWavesPerBlock + (threadIdx.x >> 6);
   if (slot_row >= n_v) return;  // whole wave exits together
   const int row = row_order ? row_order[slot_row] : slot_row;
-  tl.seed = resolve_seed(seed_base, tl.seed);
+  tl.epi.seed = resolve_seed(seed_base, tl.epi.seed);
   const int lane = lane_id();
   const int slot = lane / LPR, li = lane % LPR;
   const int start = rowptr[row], end = rowptr[row + 1];
@@ -363,7 +353,7 @@ __global__ __launch_bounds__(kBlock) void e2v_flat_kernel(const int32_t* __restr
   const int64_t slot_global = (static_cast<int64_t>(blk) * kWavesPerBlock + (threadIdx.x >> 6)) * NS + slot;
   const int64_t r_begin64 = slot_global * kFlatRows;
   if (r_begin64 - static_cast<int64_t>(slot) * kFlatRows >= n_v) return;      // whole wave beyond the last row
-  tl.seed = resolve_seed(seed_base, tl.seed);
+  tl.epi.seed = resolve_seed(seed_base, tl.epi.seed);
   const int r_begin = static_cast<int>(min(r_begin64, static_cast<int64_t>(n_v)));
   const int r_end = min(r_begin + kFlatRows, n_v);
   const int c0 = li * VEC;
@@ -581,12 +571,7 @@ extern "C" int allset_hypergcn_e2v(int variant, int64_t nnz, const int32_t* row_
   ALLSET_REQUIRE(ldx >= d && ldy >= d && ldpq >= d, "hypergcn_e2v: leading dimension smaller than d");
   ALLSET_REQUIRE(nnz == 0 || (colx && pq), "hypergcn_e2v: null colx/pq with nnz > 0");
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  Tail tl{dinv, selfc, x, ldx, bias, act, p, seed, 0u, p > 0.f ? 1.f / (1.f - p) : 1.f};
-  {
-    // drop_threshold is a device function; the same formula on the host (p * 256 integral -> 8-bit form)
-    const float t8 = p * 256.0f;
-    tl.thr = (t8 == floorf(t8)) ? (kDrop8 | static_cast<uint32_t>(t8)) : static_cast<uint32_t>(p * 65536.0f);
-  }
+  const Tail tl{dinv, selfc, x, ldx, row_epi(bias, act, p, seed)};
   const int nv = static_cast<int>(n_v), di = static_cast<int>(d), npq = static_cast<int>(n_pq);
   const bool use_flat = wc == 1 && (variant == 2 || (variant == 0 && n_v > kFlatMinRows &&
                                                      static_cast<double>(nnz) < kFlatMaxMeanDegree * static_cast<double>(n_v)));

@@ -34,18 +34,19 @@
 // Algorithmic bytes per launch, K1: nnz * (4d + 4) + (n_t + 1) * 4 + n_t * 4d, plus n_t * 4d for xs and n_t * 4 each for s and
 // t_out; K2: nnz * (4d + 4) + (n_t + 1) * 4 + n_t * (4d + 4H + 4) + 4d.
 #include "common.h"
+#include "row_epilogue.h"
 
 namespace allset {
 namespace unignn {
 
-enum { kActNone = 0, kActRelu = 1 };
 constexpr int kMaxWidth = 512;
 constexpr int kFlatRows = 7;          // rows per lane group in the short-row kernel (kFlatRows + 1 rowptr entries fit in 8 lanes)
 constexpr int kFlatUnroll = 8;
 
 // K1's row tail.  The LPR lanes that together hold row `row` call finish(): lane li has columns (ch * LPR + li) * 4 .. + 3 of the
 // gathered sum in acc[ch] (zeros beyond d).  Every lane of the group calls it (the norm is reduced across them); `writer`
-// lanes load the self term and store.
+// lanes load the self term and store.  Not row_epilogue.h's RowEpi / row_epilogue: the row is scaled by t, has no bias and masks a
+// quad with one keep_scale4; the activation and the threshold are the shared ones.
 struct VertexTail {
   const float* s;         // per output row, or NULL (= ones)
   const float* xs;        // self-term rows, or NULL
@@ -102,9 +103,7 @@ struct VertexTail {
         FVec<4> o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          float v = t * acc[ch][k];
-          if (act == kActRelu) v = fmaxf(v, 0.f);
-          o.v[k] = v * kk[k];
+          o.v[k] = row_act<false>(t * acc[ch][k], act) * kk[k];
         }
         store_vec<float, 4>(y + static_cast<int64_t>(row) * ldy + c0, o);
       }
@@ -368,10 +367,7 @@ extern "C" int allset_unignn_hop_fwd(int variant, int64_t nnz, const int32_t* ro
     set_error("unignn_hop_fwd: the short-row variant needs d <= 256");
     return ALLSET_ERR_UNSUPPORTED;
   }
-  // drop_threshold is a device function; the same formula on the host (p * 256 integral -> 8-bit form)
-  const float t8 = p * 256.0f;
-  const uint32_t thr = (t8 == floorf(t8)) ? (kDrop8 | static_cast<uint32_t>(t8)) : static_cast<uint32_t>(p * 65536.0f);
-  const VertexTail tl{s, xs, ldxs, c_dev, c, t_out, use_norm ? 1 : 0, act, p, seed, thr, p > 0.f ? 1.f / (1.f - p) : 1.f, y, ldy};
+  const VertexTail tl{s, xs, ldxs, c_dev, c, t_out, use_norm ? 1 : 0, act, p, seed, drop_threshold(p), drop_inv_keep(p), y, ldy};
   dispatch(variant, nnz, static_cast<hipStream_t>(stream), rowptr, col, xe, ldxe, tl, static_cast<int>(n_t), static_cast<int>(d),
            row_order, seed_base);
   ALLSET_LAUNCH_CHECK();

@@ -472,13 +472,7 @@ extern "C" int allset_wgrad_f16x3(const float* gy, int64_t ldg, const uint32_t* 
   a.rows_per_slice = rps; a.n_slices = static_cast<int>(n_slices);
   const dim3 grid(static_cast<unsigned>((O / kWfTO) * (I / kWfTI)), static_cast<unsigned>((n_slices + 7) / 8 * 8));
   // the dropout's resolution as common.h drop_threshold() chooses it: 8 bits per element iff p * 256 is an integer
-  const float t8 = p_in * 256.0f;
-#ifdef ALLSET_ABL_DROP16          // (ablation builds: the 16-bit form for every p, common.h)
-  const int drop = p_in > 0.f ? 2 : 0;
-  (void)t8;
-#else
-  const int drop = p_in > 0.f ? (t8 == floorf(t8) ? 1 : 2) : 0;
-#endif
+  const int drop = p_in > 0.f ? (drop_is8(p_in) ? 1 : 2) : 0;
 #define ALLSET_WF16(MKV) do { if (drop == 0) wgrad_f16_kernel<MKV, 0><<<grid, kWfBlock, 0, st>>>(a); \
     else if (drop == 1) wgrad_f16_kernel<MKV, 1><<<grid, kWfBlock, 0, st>>>(a); else wgrad_f16_kernel<MKV, 2><<<grid, kWfBlock, 0, st>>>(a); } while (0)
   if (mask != nullptr) ALLSET_WF16(2); else ALLSET_WF16(0);

@@ -59,6 +59,11 @@ def _seed_base() -> Optional[Tensor]:
     return _SeedSource.base
 
 
+def _seed_for(p: float):
+    """``(seed, seed_base)`` of one dropout site: a fresh draw, or ``(0, None)`` -- and nothing drawn -- without dropout."""
+    return (_draw_seed(), _seed_base()) if p > 0.0 else (0, None)
+
+
 class device_seed_counter:
     """Context manager: dropout sites inside draw their masks from ``counter`` (int64 device tensor, 1 element)."""
 
@@ -1047,8 +1052,7 @@ def hash_dropout(x: Tensor, p: float, training: bool) -> Tensor:
 class _LayerNormFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, relu_in, p):
-        seed = _draw_seed() if p > 0.0 else 0
-        base = _seed_base() if p > 0.0 else None
+        seed, base = _seed_for(p)
         y, stats = ln_fwd(x, gamma, beta, eps, relu_in, p, seed, base)
         ctx.save_for_backward(x, stats, gamma)
         ctx.cfg = (bool(relu_in), float(p), seed, base)
@@ -1070,10 +1074,10 @@ class _ReluDropout(torch.autograd.Function):
         _check_f32(x)
         x = x.contiguous()
         y = torch.empty_like(x)
-        seed = _draw_seed() if p > 0.0 else 0
+        seed, base = _seed_for(p)
         n = x.numel()
         with on_device(dev), _timed("relu_dropout_fwd", dev, 2 * n * 4):
-            check(_lib.load().allset_relu_dropout_fwd(ptr(x), p, seed, ptr(y), n, ptr(_seed_base() if p > 0.0 else None),
+            check(_lib.load().allset_relu_dropout_fwd(ptr(x), p, seed, ptr(y), n, ptr(base),
                                                       stream_of(dev)), "allset_relu_dropout_fwd")
         ctx.save_for_backward(y)
         ctx.p = float(p)
@@ -1450,8 +1454,7 @@ class _LayerNormRes(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, colb, res, gamma, beta, eps, relu_out, p):
-        seed = _draw_seed() if p > 0.0 else 0
-        base = _seed_base() if p > 0.0 else None
+        seed, base = _seed_for(p)
         cb = colb.reshape(-1) if colb is not None else None
         y, stats = ln_res_fwd(x, cb, res, gamma, beta, eps, relu_out, p, seed, base)
         ctx.save_for_backward(x, cb, res, stats, gamma, beta)
@@ -1552,8 +1555,7 @@ class _PmaResidualFF(torch.autograd.Function):
         words = activation_mask_words(out.shape[0], w2.shape[0])
         mask = torch.empty(words, dtype=torch.int32, device=out.device) if words > 0 else None
         z, _ = fused_linear_fwd(y1, w2, b2, None, None, 1e-5, True, 0.0, 0, True, 0.0, 0, None, mask)
-        seed = _draw_seed() if p > 0.0 else 0
-        base = _seed_base() if p > 0.0 else None
+        seed, base = _seed_for(p)
         y, stats = ln_res_fwd(out, None, z, gamma, beta, eps, relu_post, p, seed, base)
         ctx.save_for_backward(out, y1, z, mask, stats, w1, w2, gamma, beta)
         ctx.cfg = (bool(relu_post), float(p), seed, base, b1 is not None, b2 is not None)
@@ -1643,8 +1645,7 @@ def pma_tail_fwd(pooled: Tensor, cb: Tensor, g0, b0, eps0, w1, b1, w2, b2, g1, b
     y1, out, stats0 = fused_linear_fwd_ln_side(pooled, cb, g0, b0, eps0, w1, b1, False)
     words = activation_mask_words(pooled.shape[0], w2.shape[0])
     mask = torch.empty(words, dtype=torch.int32, device=pooled.device)
-    seed = _draw_seed() if p > 0.0 else 0
-    base = _seed_base() if p > 0.0 else None
+    seed, base = _seed_for(p)
     y, s, stats1 = fused_linear_fwd_res_ln(y1, True, w2, b2, True, out, g1, bt1, eps1, relu_post, p, seed, base, mask)
     return y, (pooled, cb, stats0, g0, b0, out, y1, mask, s, stats1, w1, w2, g1, bt1), (bool(relu_post), float(p), seed, base,
                                                                                        b1 is not None, b2 is not None)
@@ -2102,8 +2103,7 @@ class _PmaResidualFFBf16(torch.autograd.Function):
             h, _ = linear_bf16_fwd(out, w1, b1, True)
             z, _ = linear_bf16_fwd(h, w2, b2, True)
             mh = mz = None
-        seed = _draw_seed() if p > 0.0 else 0
-        base = _seed_base() if p > 0.0 else None
+        seed, base = _seed_for(p)
         y, stats = ln_res_fwd(out, None, z, gamma, beta, eps, relu_post, p, seed, base)
         ctx.save_for_backward(out, h, z, stats, w1, w2, gamma, beta, mh, mz)
         ctx.cfg = (bool(relu_post), float(p), seed, base, b1 is not None, b2 is not None)
@@ -2319,8 +2319,7 @@ class _SparseInputNormLinear(torch.autograd.Function):
         dev = x.device
         O, d = weight.shape
         n = x.shape[0]
-        seed = _draw_seed() if p_pre > 0.0 else 0
-        base = _seed_base() if p_pre > 0.0 else None
+        seed, base = _seed_for(p_pre)
         weight_c, gamma_c, beta_c = _rowmajor(weight), gamma.contiguous(), beta.contiguous()
         wt = torch.empty((d + 2, O), dtype=torch.float32, device=dev)
         y = torch.empty((n, O), dtype=torch.float32, device=dev)
@@ -2388,8 +2387,7 @@ class _SparsePmaProject(torch.autograd.Function):
         O1, d = w_v.shape
         H = w_a.shape[0]
         n = x.shape[0]
-        seed = _draw_seed() if p_pre > 0.0 else 0
-        base = _seed_base() if p_pre > 0.0 else None
+        seed, base = _seed_for(p_pre)
         w_v_c, w_a_c = _rowmajor(w_v), _rowmajor(w_a)
         pitch = int(lib.allset_sparse_linear_pitch(O1, H))
         wt = torch.empty((d + 1, pitch), dtype=torch.float32, device=dev)

@@ -530,6 +530,20 @@ def pma_aggregate_exclude_self(V: Tensor, alpha: Tensor, loo: LeaveOneOutInciden
 
 
 # ---- degree-scaled propagate of the hypergraph-convolution baselines (HCHA / HGNN / HNHN; csrc/hconv.hip) ----------------------
+def _epilogue_backward(gy, y, act, p, seed, base, epi, bias=None, need_b=False):
+    """Backward of a hop's row epilogue ``y = drop_p(act(v + bias))``: ``(g, gb)``, the gradients of ``v`` and -- with ``need_b`` -- of
+    the bias.  Without an epilogue ``gy`` passes through."""
+    if not epi:
+        return gy, None
+    from . import dense
+    g, part = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=need_b)
+    gb = None
+    if need_b:
+        # (inside dense.deferred_param_grads(): queued for the step's one batched reduction, and None here)
+        (gb,) = dense._defer_or_reduce(part, [(bias, 0, (y.shape[1],))], defer=True)
+    return g, gb
+
+
 class _ScaledPropagate(torch.autograd.Function):
     """``y = drop_p(act(s * (H^T or H)(r * x) + bias))`` -- one kernel forward; backward: the epilogue's kernel (only when there is
     an epilogue) and the same propagate kernel over the opposite CSR with ``r`` and ``s`` swapped.  ``r`` / ``s`` are constants."""
@@ -541,8 +555,7 @@ class _ScaledPropagate(torch.autograd.Function):
         n_t, n_s = (inc.n_dst, inc.n_src) if to_dst else (inc.n_src, inc.n_dst)
         if x.shape[0] != n_s:
             raise _lib.AllSetHipError(f"scaled_propagate: x has {x.shape[0]} rows, the incidence gathers from {n_s}")
-        seed = dense._draw_seed() if p > 0.0 else 0
-        base = dense._seed_base() if p > 0.0 else None
+        seed, base = dense._seed_for(p)
         y = ops.hconv_propagate(fwd, x, n_t, r, s, bias, act, p, seed, base)
         epi = act is not None or p > 0.0 or bias is not None
         ctx.save_for_backward(y if epi else None)
@@ -553,18 +566,10 @@ class _ScaledPropagate(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        from . import dense
         (y,) = ctx.saved_tensors
         bwd, n_s, r, s, act, p, seed, base, epi = ctx.cfg
         need_b = ctx.bias_param is not None and ctx.needs_input_grad[1]
-        gb = None
-        if epi:
-            g, part = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=need_b)
-            if need_b:
-                # (inside dense.deferred_param_grads(): queued for the step's one batched reduction, and None here)
-                (gb,) = dense._defer_or_reduce(part, [(ctx.bias_param, 0, (y.shape[1],))], defer=True)
-        else:
-            g = gy
+        g, gb = _epilogue_backward(gy, y, act, p, seed, base, epi, ctx.bias_param, need_b)
         gx = ops.hconv_propagate(bwd, g, n_s, r=s, s=r) if ctx.needs_input_grad[0] else None
         return gx, gb, None, None, None, None, None, None
 
@@ -579,8 +584,7 @@ class _WeightedPropagate(torch.autograd.Function):
         from . import dense
         if x.shape[0] != inc.n_src:
             raise _lib.AllSetHipError(f"weighted_propagate: x has {x.shape[0]} rows, the graph gathers from {inc.n_src}")
-        seed = dense._draw_seed() if p > 0.0 else 0
-        base = dense._seed_base() if p > 0.0 else None
+        seed, base = dense._seed_for(p)
         y = ops.hconv_propagate_w(inc.by_dst, x, inc.n_dst, w_dst, bias, act, p, seed, base)
         epi = act is not None or p > 0.0 or bias is not None
         ctx.save_for_backward(y if epi else None)
@@ -591,17 +595,10 @@ class _WeightedPropagate(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        from . import dense
         (y,) = ctx.saved_tensors
         inc, w_src, act, p, seed, base, epi = ctx.cfg
         need_b = ctx.bias_param is not None and ctx.needs_input_grad[1]
-        gb = None
-        if epi:
-            g, part = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=need_b)
-            if need_b:
-                (gb,) = dense._defer_or_reduce(part, [(ctx.bias_param, 0, (y.shape[1],))], defer=True)
-        else:
-            g = gy
+        g, gb = _epilogue_backward(gy, y, act, p, seed, base, epi, ctx.bias_param, need_b)
         gx = ops.hconv_propagate_w(inc.by_src, g, inc.n_src, w_src) if ctx.needs_input_grad[0] else None
         return gx, gb, None, None, None, None, None
 
@@ -646,8 +643,7 @@ class _GatPropagate(torch.autograd.Function):
         from . import dense
         if x.shape[0] != inc.n_src:
             raise _lib.AllSetHipError(f"gat_propagate: x has {x.shape[0]} rows, the graph gathers from {inc.n_src}")
-        seed = dense._draw_seed() if p > 0.0 else 0
-        base = dense._seed_base() if p > 0.0 else None
+        seed, base = dense._seed_for(p)
         want = any(ctx.needs_input_grad[:4])
         y, agg, aggpos, ppos, m, l = ops.gat_fwd(inc.by_dst, x, al, ar, heads, slope, inc.n_dst, concat, bias, act, p, seed, base,
                                                  want_grad=want)
@@ -660,18 +656,10 @@ class _GatPropagate(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        from . import dense
         x, al, ar, y, agg, aggpos, ppos, m, l = ctx.saved_tensors
         inc, heads, slope, concat, act, p, seed, base, epi = ctx.cfg
         need_b = ctx.bias_param is not None and ctx.needs_input_grad[3]
-        gb = None
-        if epi:
-            g, part = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=need_b)
-            if need_b:
-                # (inside dense.deferred_param_grads(): queued for the step's one batched reduction, and None here)
-                (gb,) = dense._defer_or_reduce(part, [(ctx.bias_param, 0, (y.shape[1],))], defer=True)
-        else:
-            g = gy
+        g, gb = _epilogue_backward(gy, y, act, p, seed, base, epi, ctx.bias_param, need_b)
         if concat:
             stats, gar = ops.gat_bwd_stats(g, aggpos, ppos, m, l, slope, y=y, bias=ctx.bias_param, p=p)
         else:
@@ -688,7 +676,7 @@ def gat_propagate(x: Tensor, al: Tensor, ar: Tensor, inc: Incidence, heads: int,
     ``agg[t, h] = sum_j p_j x[s_j, h]``; ``y = drop_p(act(agg + bias))`` with the heads side by side (``concat``) or averaged.
     ``x`` [n_src, heads * C], ``al`` [n_src, heads], ``ar`` [n_dst, heads]; ``act`` None / 'relu'; ``p`` the dropout probability on
     the OUTPUT (the library's hash mask).  Differentiable in ``x``, ``al``, ``ar`` and ``bias``."""
-    if act not in ops.GAT_ACTS:
+    if act not in ops.RELU_ACTS:
         raise ValueError(f"gat_propagate: act must be None or 'relu', got {act!r}")
     _lib.require_device(x, al, ar)
     if al.dtype != torch.float32 or ar.dtype != torch.float32:
@@ -713,11 +701,10 @@ class _HattnPropagate(torch.autograd.Function):
                                       f"{n_v} vertices, {n_e} hyperedges and {heads} heads")
         if D.numel() != n_v or B.numel() != n_e:
             raise _lib.AllSetHipError(f"hattn_propagate: D has {D.numel()} entries for {n_v} vertices, B {B.numel()} for {n_e} hyperedges")
-        base = dense._seed_base() if (p_attn > 0.0 or p > 0.0) else None
-        seed_a = dense._draw_seed() if p_attn > 0.0 else 0          # (drawn first: the coefficient's mask, then the output's)
-        seed = dense._draw_seed() if p > 0.0 else 0
+        seed_a, base_a = dense._seed_for(p_attn)                     # (drawn first: the coefficient's mask, then the output's)
+        seed, base = dense._seed_for(p)
         pos = inc.pos_dst_of_src()
-        a_v, a_e, m, l = ops.hattn_coef(inc.by_src, pos, av, ae, slope, p_attn, seed_a, base)
+        a_v, a_e, m, l = ops.hattn_coef(inc.by_src, pos, av, ae, slope, p_attn, seed_a, base_a)
         y_e = ops.hattn_hop(inc.by_dst, a_e, z, heads, n_e, s=B)
         out = ops.hattn_hop(inc.by_src, a_v, y_e, heads, n_v, s=D, concat=concat, bias=bias, act=act, p=p, seed=seed, seed_base=base)
         epi = act is not None or p > 0.0 or bias is not None
@@ -729,18 +716,10 @@ class _HattnPropagate(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
-        from . import dense
         z, av, ae, a_v, a_e, m, l, y_e, out, D, B = ctx.saved_tensors
         inc, heads, slope, concat, act, p, seed, base, epi = ctx.cfg
         need_b = ctx.bias_param is not None and ctx.needs_input_grad[3]
-        gb = None
-        if epi:
-            g, part = ops.hconv_bwd_epi(gout, out, act, p, seed, base, want_bias=need_b)
-            if need_b:
-                # (inside dense.deferred_param_grads(): queued for the step's one batched reduction, and None here)
-                (gb,) = dense._defer_or_reduce(part, [(ctx.bias_param, 0, (out.shape[1],))], defer=True)
-        else:
-            g = gout
+        g, gb = _epilogue_backward(gout, out, act, p, seed, base, epi, ctx.bias_param, need_b)
         if not concat:
             g = (g * (1.0 / heads)).repeat(1, heads)                   # the head mean's backward: g / H to every head
         gy = ops.hattn_hop(inc.by_dst, a_e, g, heads, inc.n_dst, r=D)
@@ -951,8 +930,7 @@ class _HyperGCNPropagate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, st, act, p, variant, fused):
         from . import dense
-        seed = dense._draw_seed() if p > 0.0 else 0
-        base = dense._seed_base() if p > 0.0 else None
+        seed, base = dense._seed_for(p)
         y = _hypergcn_apply(x, st, fused, bias, act, p, seed, base, variant)
         epi = act is not None or p > 0.0 or bias is not None
         ctx.save_for_backward(y if epi else None)
@@ -963,19 +941,11 @@ class _HyperGCNPropagate(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        from . import dense
         (y,) = ctx.saved_tensors
         st, act, p, seed, base, epi, variant, fused = ctx.cfg
         need_b = ctx.bias_param is not None and ctx.needs_input_grad[1]
-        gb = None
-        if epi:
-            g, part = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=need_b)
-            if need_b:
-                # (inside dense.deferred_param_grads(): queued for the step's one batched reduction, and None here)
-                (gb,) = dense._defer_or_reduce(part, [(ctx.bias_param, 0, (y.shape[1],))], defer=True)
-        else:
-            g = gy.contiguous()
-        gx = _hypergcn_apply(g, st, fused, variant=variant) if ctx.needs_input_grad[0] else None
+        g, gb = _epilogue_backward(gy, y, act, p, seed, base, epi, ctx.bias_param, need_b)
+        gx = _hypergcn_apply(g.contiguous(), st, fused, variant=variant) if ctx.needs_input_grad[0] else None
         return gx, gb, None, None, None, None, None
 
 
@@ -986,7 +956,7 @@ def hypergcn_propagate(x: Tensor, structure: HyperGCNStructure, bias: Optional[T
     dropout probability (the library's hash mask).  Differentiable in ``x`` and ``bias``.  ``variant``: kernel variant of the E->V
     pass (tests); ``fused``: None = the HIP hop where the width is built (``ops.hypergcn_hop_supported``) and the composition from
     ``hconv`` launches and torch ops otherwise; True insists on the HIP hop (an unbuilt width raises); False forces the composition."""
-    if act not in ops.HYPERGCN_ACTS:
+    if act not in ops.RELU_ACTS:
         raise ValueError(f"hypergcn_propagate: act must be None or 'relu', got {act!r}")
     _lib.require_device(x)
     if x.dtype != torch.float32:
@@ -1012,8 +982,7 @@ class _UniGNNHop(torch.autograd.Function):
         n_v = inc.n_src
         if xe.shape[0] != inc.n_dst:
             raise _lib.AllSetHipError(f"unignn_hop: xe has {xe.shape[0]} rows, the incidence has {inc.n_dst} hyperedges")
-        seed = dense._draw_seed() if p > 0.0 else 0
-        base = dense._seed_base() if p > 0.0 else None
+        seed, base = dense._seed_for(p)
         c = c_t.detach() if c_t is not None else c_f
         if ops.unignn_hop_supported(xe, xs):
             y, t = ops.unignn_hop_fwd(inc.by_src, xe, n_v, s, xs, c, use_norm, act, p, seed, base, variant)
@@ -1039,10 +1008,7 @@ class _UniGNNHop(torch.autograd.Function):
     def backward(ctx, gy):
         t, y, xs, c_t = ctx.saved_tensors
         inc, s, c_f, act, p, seed, base, epi = ctx.cfg
-        if epi:
-            g, _ = ops.hconv_bwd_epi(gy, y, act, p, seed, base, want_bias=False)
-        else:
-            g = gy.contiguous()
+        g = _epilogue_backward(gy, y, act, p, seed, base, epi)[0].contiguous()
         gxe = gxs = gc = None
         if ctx.needs_input_grad[0]:
             r = s if t is None else (t if s is None else s * t)
@@ -1064,7 +1030,7 @@ def unignn_hop(xe: Tensor, inc: Incidence, *, s: Optional[Tensor] = None, xs: Op
     [n_src, 1]) and ``xs`` [n_src, d] optional; ``c`` a float or a one-element device tensor (read on the device: a captured graph sees
     its current value); ``act`` None / 'relu'; ``p`` the dropout probability (the library's hash mask).  Device fp32 only.
     Differentiable in ``xe``, ``xs`` and a tensor ``c``.  ``variant``: kernel variant override (tests)."""
-    if act not in ops.UNIGNN_ACTS:
+    if act not in ops.RELU_ACTS:
         raise ValueError(f"unignn_hop: act must be None or 'relu', got {act!r}")
     c_t = c if torch.is_tensor(c) else None
     _lib.require_device(xe, xs, s, c_t)
@@ -1145,7 +1111,7 @@ def unignn_row_tail(a: Tensor, skip: Optional[Tensor] = None, use_norm: bool = F
     is the one-pass ``dense.relu_dropout``; otherwise the norm and the sum are torch ops over [N, d] and only the ``relu`` + dropout
     pass is the library's (no fused kernel for this tail yet: DESIGN.md section 14 lists the passes it leaves)."""
     from . import dense
-    if act not in ops.UNIGNN_ACTS:
+    if act not in ops.RELU_ACTS:
         raise ValueError(f"unignn_row_tail: act must be None or 'relu', got {act!r}")
     _lib.require_device(a, skip)
     if a.dtype != torch.float32 or (skip is not None and skip.dtype != torch.float32):
@@ -1174,8 +1140,7 @@ class _HanPropagate(torch.autograd.Function):
     def forward(ctx, x, el, er, bias, graph, heads, slope, p, out, block):
         from . import dense
         n, d = er.shape[0], x.shape[1]
-        seed = dense._draw_seed() if p > 0.0 else 0
-        base = dense._seed_base() if p > 0.0 else None
+        seed, base = dense._seed_for(p)
         want = any(ctx.needs_input_grad[:4])
         if out is None:
             ret = torch.empty((n, d), dtype=torch.float32, device=x.device)

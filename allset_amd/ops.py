@@ -497,7 +497,9 @@ def pma_merge_pack(out_loc: Tensor, m_loc: Tensor, l_loc: Tensor, m_glob: Tensor
 
 
 # ---- degree-scaled propagate of the hypergraph-convolution baselines (csrc/hconv.hip) -----------------------------------------
+# activation codes of the row epilogue (csrc/row_epilogue.h): the hops built with the elu branch (hconv, hattn), and the relu-only ones
 HCONV_ACTS = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "relu": _lib.ACT_RELU, "elu": _lib.ACT_ELU}
+RELU_ACTS = {k: v for k, v in HCONV_ACTS.items() if k != "elu"}
 
 
 def hconv_propagate(csr: CSR, x: Tensor, n_t: int, r: Optional[Tensor] = None, s: Optional[Tensor] = None,
@@ -818,7 +820,6 @@ def hconv_bwd_epi(gy: Tensor, y: Tensor, act: Optional[str], p: float, seed: int
 
 
 # ---- GAT attention hop of the clique-expansion baseline CEGAT (csrc/gat.hip) ----------------------------------------------------
-GAT_ACTS = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "relu": _lib.ACT_RELU}
 GAT_MAX_HEADS, GAT_MAX_WIDTH = 64, 512
 
 
@@ -861,7 +862,7 @@ def gat_fwd(csr: CSR, x: Tensor, al: Tensor, ar: Tensor, heads: int, slope: floa
         + (n_t * 4 * d if agg is not None else 0)
     with on_device(dev), _timed("gat_fwd", dev, algo):
         check(_lib.load().allset_gat_fwd(1, nnz, ptr(_gat_order(csr, n_t)), ptr(csr.rowptr), ptr(csr.col), ptr(al), ptr(ar), ptr(x),
-                                         _ld(x), float(slope), ptr(bias), GAT_ACTS[act], float(p), int(seed), ptr(seed_base),
+                                         _ld(x), float(slope), ptr(bias), RELU_ACTS[act], float(p), int(seed), ptr(seed_base),
                                          1 if concat else 0, ptr(y), max(width, 1), ptr(agg), d, ptr(aggpos), d, ptr(ppos), ptr(m),
                                          ptr(l), n_t, n_s, H, C, stream_of(dev)), "allset_gat_fwd")
     return y, agg, aggpos, ppos, m, l
@@ -1059,7 +1060,6 @@ def unigcn_hop_fwd(csr: CSR, xe: Tensor, x0: Tensor, n_t: int, degV: Optional[Te
 
 # ---- UniGNN: the E->V hop with the row tail, UniGAT's V->E hop with the attention logit (csrc/unignn.hip) ------------------------------
 UNIGNN_MAX_WIDTH = 512
-UNIGNN_ACTS = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "relu": _lib.ACT_RELU}
 
 
 def unignn_hop_supported(xe: Tensor, xs: Optional[Tensor] = None) -> bool:
@@ -1108,7 +1108,7 @@ def unignn_hop_fwd(csr: CSR, xe: Tensor, n_t: int, s: Optional[Tensor] = None, x
     with on_device(dev), _timed("unignn_hop_fwd", dev, algo):
         check(_lib.load().allset_unignn_hop_fwd(variant, nnz, ptr(order), ptr(csr.rowptr), ptr(csr.col), ptr(s), ptr(xe), _ld(xe),
                                                 ptr(xs), _ld(xs) if xs is not None else 0, 0.0 if c_dev is not None else float(c),
-                                                ptr(c_dev), int(bool(use_norm)), UNIGNN_ACTS[act], float(p), int(seed),
+                                                ptr(c_dev), int(bool(use_norm)), RELU_ACTS[act], float(p), int(seed),
                                                 ptr(seed_base), ptr(y), max(d, 1), ptr(t), n_t, n_s, d, stream_of(dev)),
               "allset_unignn_hop_fwd")
     return y, t
@@ -1160,7 +1160,6 @@ def unignn_v2e_att_fwd(csr: CSR, x: Tensor, n_t: int, s: Optional[Tensor], att: 
 # ---- HyperGCN: the on-device Laplacian approximation and its two-pass hop (csrc/hypergcn.hip) -----------------------------------------
 HYPERGCN_MAX_WIDTH = 256             # 16-byte lanes: multiples of 4 up to here
 HYPERGCN_MAX_SCALAR_WIDTH = 64       # one column per lane: any width up to here (the class counts of the last layer)
-HYPERGCN_ACTS = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "relu": _lib.ACT_RELU}
 
 
 def _rows16(*ts: Tensor) -> bool:
@@ -1277,7 +1276,7 @@ def hypergcn_e2v(csr_v: CSR, colx: Tensor, pq: Tensor, dinv: Tensor, selfc: Tens
     algo = nnz * (4 * d + 4) + (n_v + 1) * 4 + 8 * n_v + 2 * n_v * 4 * d
     with on_device(dev), _timed("hypergcn_e2v", dev, algo):
         check(_lib.load().allset_hypergcn_e2v(variant, nnz, ptr(order), ptr(csr_v.rowptr), ptr(colx), ptr(pq), _ld(pq), pq.shape[0],
-                                              ptr(dinv), ptr(selfc), ptr(x), _ld(x), ptr(bias), HYPERGCN_ACTS[act], float(p), int(seed),
+                                              ptr(dinv), ptr(selfc), ptr(x), _ld(x), ptr(bias), RELU_ACTS[act], float(p), int(seed),
                                               ptr(seed_base), ptr(y), max(d, 1), n_v, d, stream_of(dev)), "allset_hypergcn_e2v")
     return y
 

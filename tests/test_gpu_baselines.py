@@ -64,6 +64,7 @@ KERNEL_CASES = [
     (4, True, False, True, "relu", 0.0, "v2e"),
     (64, False, True, True, "elu", 0.5, "e2v"),
     (64, True, True, False, "relu", 0.5, "v2e"),
+    (64, False, True, True, "elu", 0.3, "e2v"),                        # p * 256 not an integer: the 16-bit mask
     (128, True, True, True, "elu", 0.0, "v2e"),
     (128, False, True, True, "relu", 0.5, "e2v"),
     (256, True, True, True, None, 0.5, "e2v"),

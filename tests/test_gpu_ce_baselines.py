@@ -93,7 +93,7 @@ def _graph(n, seed, long_rows):
 
 @pytest.mark.parametrize("d,act,p,long_rows", [(1, None, 0.0, ()), (3, "relu", 0.5, (70,)), (7, "relu", 0.0, (1500,)),
                                                (64, "relu", 0.5, (70, 1500)), (128, None, 0.0, (1100,)), (128, "relu", 0.5, ()),
-                                               (512, "relu", 0.5, (65, 2000))])
+                                               (512, "relu", 0.5, (65, 2000)), (64, "relu", 0.3, (70, 1500))])
 def test_weighted_propagate_vs_float64(monkeypatch, d, act, p, long_rows):
     from allset_amd import Incidence, dense
     from allset_amd.functional import weighted_propagate

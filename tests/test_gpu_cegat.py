@@ -41,7 +41,7 @@ N_HOP = 2500
 HOP_CASES = [(1, 1, True, None, 0.0, (), 0), (1, 7, True, "relu", 0.5, (70,), 0), (2, 3, True, "relu", 0.0, (1500,), 0),
              (4, 16, True, "relu", 0.5, (70, 1500), 1), (4, 32, True, None, 0.0, (1100,), 3), (8, 64, True, "relu", 0.5, (65, 2000), 1),
              (1, 128, True, "relu", 0.5, (), 0), (8, 16, True, None, 0.0, (70,), 3), (1, 5, False, None, 0.0, (70,), 1),
-             (2, 7, False, "relu", 0.5, (1500,), 1), (4, 6, False, "relu", 0.0, (), 0)]
+             (2, 7, False, "relu", 0.5, (1500,), 1), (4, 6, False, "relu", 0.0, (), 0), (4, 16, True, "relu", 0.3, (70, 1500), 1)]
 
 
 def hop_inputs(H, C, concat, long_rows, seed, n=N_HOP):

@@ -65,6 +65,7 @@ KERNEL_CASES = [
     (1, 1, True, None, 0.0, 0.0, False, False),
     (1, 64, False, "elu", 0.5, 0.5, True, True),
     (4, 16, True, "elu", 0.5, 0.0, True, False),
+    (4, 16, True, "elu", 0.3, 0.3, True, False),                       # p * 256 not an integer: the 16-bit mask, both sites
     (3, 5, False, None, 0.0, 0.5, False, False),
     (8, 32, True, "elu", 0.0, 0.5, False, False),
     (2, 128, False, None, 0.5, 0.0, True, False),
