@@ -304,6 +304,12 @@ SIGNATURES = {
                                c_int64, _P],
     "allset_loo_softmax_bwd": [_P, _P, _P, _P, c_int64, c_float, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P, c_int64,
                                c_int64, c_int64, c_int64, c_int64, c_int64, _P],
+    # CEGCN's GCN hop without the clique expansion: segmented exclusive scan + per-vertex collect (under ABI 15, additions only;
+    # detect with allset_scan_rows_supported)
+    "allset_scan_rows_supported": [c_int64],
+    "allset_scan_rows": [_P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, _P],
+    "allset_scan_collect": [_P, _P, _P, c_int64, _P, _P, c_int64, _P, _P, c_int, c_float, c_uint64, _P, _P, c_int64, c_int64, c_int64,
+                            c_int64, c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

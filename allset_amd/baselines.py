@@ -40,10 +40,11 @@ import torch
 import torch.nn as nn
 from torch.nn import Parameter
 
-from . import dense
+from . import dense, ops
 from ._lib import AllSetHipError
-from .functional import (HyperGCNStructure, gat_propagate, hattn_propagate, hypergcn_propagate, hypergcn_structure, initial_residual,
-                         pma_aggregate, scaled_propagate, unigat_edge, unigcn_hop, unignn_hop, unignn_row_tail, weighted_propagate)
+from .functional import (HyperGCNStructure, clique_propagate, gat_propagate, hattn_propagate, hypergcn_propagate, hypergcn_structure,
+                         initial_residual, pma_aggregate, scaled_propagate, unigat_edge, unigcn_hop, unignn_hop, unignn_row_tail,
+                         weighted_propagate)
 from .incidence import Incidence, cached_incidence
 from .layers import _linear, glorot, zeros
 from .preprocessing import generate_norm_HCHA
@@ -267,6 +268,43 @@ class CEGraph:
         return self.edge_index is edge_index and self.norm is norm and self.n == n
 
 
+class ImplicitCEGraph:
+    """The clique expansion a CEGCN forward propagates over, NOT materialised: from the V->E list ``edge_index``
+    (hyperedge ids anywhere, duplicates counting once) over ``n`` vertex rows it keeps, as int32 device tensors,
+
+    ``e_rowptr`` / ``e_col``: the hyperedge-major CSR, members ascending (``e_col`` = vertex);
+    ``v_rowptr`` / ``v_pos``: the vertex-major CSR whose columns are positions of the first;
+    ``long_seg`` / ``n_long``: the hyperedges longer than ``ops.loo_long_threshold()`` (a workgroup each in ``ops.scan_rows``);
+    ``deg`` (int64), ``dinv`` = ``deg^-1/2`` (float32 from the exact integer degree, inf -> 0), ``loop`` (bool: ``j < N``), ``N``,
+    ``r_self`` = ``loop * dinv`` -- what ``gcn_norm`` over the expansion would give (``preprocessing.clique_implicit_structure``).
+
+    O(nnz) index memory.  Holds strong references to every tensor a captured graph reads."""
+
+    def __init__(self, edge_index: Tensor, n: int):
+        if not edge_index.is_cuda:
+            raise AllSetHipError("the clique-expansion baselines run on ROCm device tensors (no CPU path)")
+        from .preprocessing import clique_implicit_structure
+        st = clique_implicit_structure(edge_index, int(n))
+        if int(st['e_rowptr'][-1]) >= 2 ** 31 - 1 or st['n'] >= 2 ** 31 - 1:
+            raise ValueError(f"ImplicitCEGraph: {int(st['e_rowptr'][-1])} incidences do not fit an int32-indexed CSR")
+        self.edge_index, self.norm, self.n = edge_index, None, int(n)
+        self.nnz, self.n_e, self.N = int(st['member'].numel()), st['n_e'], st['N']
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        self.e_rowptr, self.e_col = i32(st['e_rowptr']), i32(st['member'])
+        self.v_rowptr, self.v_pos = i32(st['v_rowptr']), i32(st['v_pos'])
+        size = st['e_rowptr'][1:] - st['e_rowptr'][:-1]
+        self.long_seg = i32((size > ops.loo_long_threshold()).nonzero().reshape(-1))
+        self.n_long = int(self.long_seg.numel())
+        self.deg, self.loop = st['deg'], st['loop']
+        dinv = st['deg'].to(torch.float32).pow(-0.5)
+        dinv[torch.isinf(dinv)] = 0
+        self.dinv = dinv.contiguous()
+        self.r_self = (self.dinv * self.loop.to(torch.float32)).contiguous()
+
+    def matches(self, edge_index: Tensor, norm: Optional[Tensor], n: int) -> bool:
+        return self.edge_index is edge_index and norm is None and self.n == n
+
+
 class GCNConv(nn.Module):
     """torch_geometric 1.6.3 ``GCNConv(in, out, normalize=False)`` as the reference's CEGCN builds it (models.py:94-108):
     ``out = propagate(x @ weight) + bias`` with messages from ``edge_index[0]`` into ``edge_index[1]`` scaled by the edge weight,
@@ -294,8 +332,12 @@ class GCNConv(nn.Module):
 
     def forward(self, x: Tensor, edge_index, edge_weight: Optional[Tensor] = None, *, act: Optional[str] = None,
                 p: float = 0.0) -> Tensor:
-        """``edge_index``: the [2, E] int64 edge list (with ``edge_weight``) or a prebuilt :class:`CEGraph`; ``act`` / ``p``: the
-        activation and dropout the model applies next, fused into the launch."""
+        """``edge_index``: the [2, E] int64 edge list (with ``edge_weight``), a prebuilt :class:`CEGraph`, or an
+        :class:`ImplicitCEGraph` (the same hop from prefix sums over the hyperedges, ``functional.clique_propagate``); ``act`` / ``p``:
+        the activation and dropout the model applies next, fused into the launch."""
+        if isinstance(edge_index, ImplicitCEGraph):
+            xw = dense.linear(x, self.weight.t(), None)
+            return clique_propagate(xw, edge_index, bias=self.bias, act=act, p=p)
         graph = edge_index if isinstance(edge_index, CEGraph) else CEGraph(edge_index, edge_weight, x.shape[0])
         xw = dense.linear(x, self.weight.t(), None)          # x @ weight: the [in, out] weight read transposed by the GEMM, no copy
         return weighted_propagate(xw, graph.inc, graph.w_dst, graph.w_src, bias=self.bias, act=act, p=p)
@@ -323,7 +365,7 @@ class CEGCN(nn.Module):
             self.normalizations.append(nn.BatchNorm1d(hid_dim) if bn else nn.Identity())
         self.convs.append(GCNConv(hid_dim, out_dim, normalize=False))
         self.dropout = dropout
-        self._graph: Optional[CEGraph] = None
+        self._graph = None                                   # a CEGraph, or an ImplicitCEGraph for ConstructV2V_implicit data
 
     def reset_parameters(self):
         for layer in self.convs:
@@ -332,11 +374,13 @@ class CEGCN(nn.Module):
             if not isinstance(normalization, nn.Identity):
                 normalization.reset_parameters()
 
-    def graph(self, data, x: Tensor) -> CEGraph:
+    def graph(self, data, x: Tensor):
         """The V2V graph of ``data``, built on first sight and kept (with the tensors it came from) for later forwards."""
         norm = getattr(data, 'norm', None)
-        if self._graph is None or not self._graph.matches(data.edge_index, norm, x.shape[0]):
-            self._graph = CEGraph(data.edge_index, norm, x.shape[0])
+        implicit = bool(getattr(data, 'clique_implicit', False))           # preprocessing.ConstructV2V_implicit: the V->E list itself
+        if self._graph is None or isinstance(self._graph, ImplicitCEGraph) != implicit \
+                or not self._graph.matches(data.edge_index, norm, x.shape[0]):
+            self._graph = ImplicitCEGraph(data.edge_index, x.shape[0]) if implicit else CEGraph(data.edge_index, norm, x.shape[0])
         return self._graph
 
     def forward(self, data):

@@ -616,6 +616,71 @@ def weighted_propagate(x: Tensor, inc: Incidence, w_dst: Optional[Tensor], w_src
     return _WeightedPropagate.apply(x, bias, inc, w_dst, w_src, act, float(p))
 
 
+class _CliquePropagate(torch.autograd.Function):
+    """The GCN hop over the clique expansion from prefix sums over the hyperedges (``graph``: a ``baselines.ImplicitCEGraph``).  Forward:
+    ``ops.scan_rows`` (exclusive prefix of ``dinv * x`` inside every hyperedge) and ``ops.scan_collect`` (sum over a vertex's positions,
+    the self-loop term, ``dinv``, the row epilogue).  Backward: the epilogue's kernel (only when there is an epilogue), then the same two
+    launches with the exclusive SUFFIX.  ``x`` arrives padded to a multiple of 4 columns; ``width`` is the logical width."""
+
+    @staticmethod
+    def forward(ctx, x, bias, graph, act, p, width):
+        from . import dense
+        seed, base = dense._seed_for(p)
+        long = dict(long_seg=graph.long_seg if graph.n_long else None, n_long=graph.n_long)
+        t = ops.scan_rows(graph.e_rowptr, graph.e_col, x, graph.dinv, reverse=False, **long)
+        y = ops.scan_collect(graph.v_rowptr, graph.v_pos, t, x, graph.r_self, graph.dinv, bias, act, p, seed, base, width=width)
+        y = y if width == y.shape[1] else y[:, :width]
+        epi = act is not None or p > 0.0 or bias is not None
+        ctx.save_for_backward(y if epi else None)
+        ctx.cfg = (graph, long, act, p, seed, base, epi, x.shape[1])
+        ctx.bias_param = bias
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        (y,) = ctx.saved_tensors
+        graph, long, act, p, seed, base, epi, d = ctx.cfg
+        need_b = ctx.bias_param is not None and ctx.needs_input_grad[1]
+        g, gb = _epilogue_backward(gy, y, act, p, seed, base, epi, ctx.bias_param, need_b)
+        gx = None
+        if ctx.needs_input_grad[0]:
+            g = _pad_columns(g, d)
+            t = ops.scan_rows(graph.e_rowptr, graph.e_col, g, graph.dinv, reverse=True, **long)
+            gx = ops.scan_collect(graph.v_rowptr, graph.v_pos, t, g, graph.r_self, graph.dinv)
+        return gx, gb, None, None, None, None
+
+
+def _pad_columns(x: Tensor, d: int) -> Tensor:
+    return x if x.shape[1] == d else torch.nn.functional.pad(x, (0, d - x.shape[1]))
+
+
+def clique_propagate(x: Tensor, graph, bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+    """One GCN hop over the clique expansion of a hypergraph WITHOUT the expansion: what
+    ``weighted_propagate`` computes over ``ConstructV2V`` + ``norm_contruction(TYPE='V2V')``,
+
+    ``y[j] = drop_p(act(dinv[j] * (sum_{e ni j} sum_{i in e, i < j} dinv[i] * x[i] + loop[j] * dinv[j] * x[j]) + bias))``,
+
+    from ``graph`` (a ``baselines.ImplicitCEGraph``): O(nnz * C) traffic, O(nnz) index memory.  ``act`` None / 'relu' / 'elu'; ``p`` the
+    dropout probability.  Differentiable in ``x`` and ``bias``.  fp32, any width 1 <= C <= 512 (a width that is no multiple of 4 is
+    padded with zero columns around the two launches); anything else raises -- there is no fallback."""
+    if act not in ops.HCONV_ACTS:
+        raise ValueError(f"clique_propagate: act must be None, 'relu' or 'elu', got {act!r}")
+    _lib.require_device(x, bias)
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f"clique_propagate: float32 only (got {x.dtype}); bf16 storage is not built -- use the explicit "
+                                  "expansion (preprocessing.ConstructV2V)")
+    if x.dim() != 2 or x.shape[0] != graph.n:
+        raise _lib.AllSetHipError(f"clique_propagate: x is {tuple(x.shape)}, the graph has {graph.n} vertex rows")
+    C = x.shape[1]
+    if not 1 <= C <= 512:
+        raise _lib.AllSetHipError(f"clique_propagate: width {C} is not built (1 <= C <= 512); there is no fallback -- use the explicit "
+                                  "expansion (preprocessing.ConstructV2V)")
+    if bias is not None and bias.numel() != C:
+        raise _lib.AllSetHipError(f"clique_propagate: bias has {bias.numel()} entries for width {C}")
+    return _CliquePropagate.apply(_pad_columns(x, (C + 3) // 4 * 4), bias, graph, act, float(p), C)
+
+
 def scaled_propagate(x: Tensor, inc: Incidence, direction: str, r: Optional[Tensor] = None, s: Optional[Tensor] = None,
                      bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0) -> Tensor:
     """One hop of a hypergraph convolution over ``inc`` (sources = vertices, targets = hyperedges):

@@ -696,6 +696,102 @@ def loo_rows(rowptr: Tensor, col: Optional[Tensor], src: Tensor, s_src: Optional
     return out
 
 
+# ---- CEGCN's GCN hop without the clique expansion: segmented exclusive scan + per-vertex collect (csrc/scan.hip) --------------------
+def scan_rows_supported(d: int) -> bool:
+    return bool(_lib.load().allset_scan_rows_supported(int(d)))
+
+
+def scan_rows(rowptr: Tensor, col: Optional[Tensor], src: Tensor, s_src: Optional[Tensor] = None, reverse: bool = False,
+              long_seg: Optional[Tensor] = None, n_long: Optional[int] = None) -> Tensor:
+    """``out[p] = sum_{q in p's segment, q before p (reverse: behind p)} s_src[idx(q)] * src[idx(q)]`` for every position ``p`` of the CSR
+    ``rowptr`` (int32[n_seg + 1]): an exclusive prefix (suffix) sum per segment, zeros where there is nothing in front (behind).
+    ``idx(q) = col[q]`` (int32[nnz]), or ``q`` itself with ``col=None``.  ``s_src`` f32[src rows] is optional.  ``long_seg`` /
+    ``n_long``: as for :func:`loo_rows` (the same threshold).  Returns f32 [nnz, d].  fp32 only, d % 4 == 0, d <= 512: anything else
+    raises."""
+    dev = require_device(rowptr, col, src, s_src, long_seg)
+    if src.dtype != torch.float32:
+        raise NotImplementedError(f"scan_rows: float32 only (got {src.dtype}); bf16 storage is not built")
+    for t, what in ((rowptr, "rowptr"), (col, "col"), (long_seg, "long_seg")):
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
+            raise _lib.AllSetHipError(f"scan_rows: {what} must be a contiguous int32 vector (got {t.dtype} {tuple(t.shape)})")
+    if s_src is not None:
+        _f32(s_src, "scan_rows s_src")
+        if s_src.dim() != 1 or not s_src.is_contiguous():
+            raise _lib.AllSetHipError("scan_rows: s_src must be a contiguous vector")
+    src = _rowmajor(src)
+    n_src, d = src.shape
+    n_seg = rowptr.numel() - 1
+    if n_seg < 0:
+        raise _lib.AllSetHipError("scan_rows: an empty rowptr (a CSR of n segments has n + 1 entries)")
+    nnz = int(col.numel()) if col is not None else n_src
+    if s_src is not None and s_src.numel() < n_src:
+        raise _lib.AllSetHipError(f"scan_rows: s_src has {s_src.numel()} entries for {n_src} source rows")
+    if d > 0 and not scan_rows_supported(d):
+        raise _lib.AllSetHipError(f"scan_rows: width {d} is not built (d % 4 == 0, d <= 512); there is no fallback")
+    if src.stride(0) % 4 != 0 or src.data_ptr() % 16 != 0:
+        src = src.contiguous()
+    if long_seg is not None:
+        n_long = int(long_seg.numel())
+    elif n_long is None:
+        n_long = -1
+    elif n_long != 0:
+        raise _lib.AllSetHipError("scan_rows: n_long without long_seg can only state 0")
+    out = torch.empty((nnz, d), dtype=torch.float32, device=dev)
+    algo = nnz * (2 * d * 4 + (4 if col is not None else 0) + (4 if s_src is not None else 0)) + (n_seg + 1) * 4
+    with on_device(dev), _timed("scan_rows", dev, algo):
+        check(_lib.load().allset_scan_rows(ptr(rowptr), ptr(col), ptr(src), _ld(src), ptr(s_src), ptr(out), max(d, 1),
+                                           ptr(long_seg) if n_long > 0 else None, n_long, int(bool(reverse)), n_seg, n_src, nnz, d,
+                                           stream_of(dev)), "allset_scan_rows")
+    return out
+
+
+def scan_collect(rowptr: Tensor, col: Tensor, t: Tensor, x: Optional[Tensor] = None, r_self: Optional[Tensor] = None,
+                 s: Optional[Tensor] = None, bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0, seed: int = 0,
+                 seed_base: Optional[Tensor] = None, width: Optional[int] = None) -> Tensor:
+    """``y[j] = drop_p(act(s[j] * (sum_{q in row j} t[col[q]] + r_self[j] * x[j]) + bias))`` over the CSR ``rowptr`` (int32[n + 1]) /
+    ``col`` (int32, rows of ``t``).  ``r_self`` / ``s`` f32[n] and ``bias`` f32[width] are optional.  ``width`` (default d): the columns
+    that carry the epilogue -- the dropout mask is that of an [n, width] matrix -- the d - width < 4 columns behind them are written
+    as zeros.  Returns f32 [n, d].  fp32 only, d % 4 == 0, d <= 512: anything else raises."""
+    dev = require_device(rowptr, col, t, x, r_self, s, bias)
+    _f32(t, "scan_collect")
+    for v, what in ((x, "x"), (r_self, "r_self"), (s, "s"), (bias, "bias")):
+        if v is not None:
+            _f32(v, f"scan_collect {what}")
+    for v, what in ((rowptr, "rowptr"), (col, "col")):
+        if v.dtype != torch.int32 or v.dim() != 1 or not v.is_contiguous():
+            raise _lib.AllSetHipError(f"scan_collect: {what} must be a contiguous int32 vector (got {v.dtype} {tuple(v.shape)})")
+    t = _rowmajor(t)
+    n_pos, d = t.shape
+    n = rowptr.numel() - 1
+    width = d if width is None else int(width)
+    if n < 0:
+        raise _lib.AllSetHipError("scan_collect: an empty rowptr (a CSR of n rows has n + 1 entries)")
+    if d > 0 and not scan_rows_supported(d):
+        raise _lib.AllSetHipError(f"scan_collect: width {d} is not built (d % 4 == 0, d <= 512); there is no fallback")
+    if (r_self is None) != (x is None):
+        raise _lib.AllSetHipError("scan_collect: give x and r_self together, or neither")
+    if x is not None:
+        x = _rowmajor(x)
+        if tuple(x.shape) != (n, d):
+            raise _lib.AllSetHipError(f"scan_collect: x is {tuple(x.shape)}, expected ({n}, {d})")
+        if x.stride(0) % 4 != 0 or x.data_ptr() % 16 != 0:
+            x = x.contiguous()
+    for v, what in ((r_self, "r_self"), (s, "s")):
+        if v is not None and (v.dim() != 1 or not v.is_contiguous() or v.numel() < n):
+            raise _lib.AllSetHipError(f"scan_collect: {what} must be a contiguous vector of at least {n} entries")
+    if bias is not None and (not bias.is_contiguous() or bias.numel() != width):
+        raise _lib.AllSetHipError(f"scan_collect: bias has {bias.numel()} entries for width {width}")
+    if t.stride(0) % 4 != 0 or t.data_ptr() % 16 != 0:
+        t = t.contiguous()
+    y = torch.empty((n, d), dtype=torch.float32, device=dev)
+    algo = col.numel() * (4 * d + 4) + (n + 1) * 4 + n * (4 * d + (4 * d + 4 if x is not None else 0) + (4 if s is not None else 0))
+    with on_device(dev), _timed("scan_collect", dev, algo):
+        check(_lib.load().allset_scan_collect(ptr(rowptr), ptr(col), ptr(t), _ld(t), ptr(r_self), ptr(x), _ld(x) if x is not None else 0,
+                                              ptr(s), ptr(bias), HCONV_ACTS[act], float(p), int(seed), ptr(seed_base), ptr(y),
+                                              max(d, 1), n, n_pos, d, width, stream_of(dev)), "allset_scan_collect")
+    return y
+
+
 # ---- leave-one-out softmax: the exclude-self PMA pooling without the expanded edge list (csrc/loo_softmax.hip) --------------------
 def loo_softmax_supported(d: int, heads: int) -> bool:
     return bool(_lib.load().allset_loo_softmax_supported(int(d), int(heads)))

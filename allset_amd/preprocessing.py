@@ -138,6 +138,77 @@ def ConstructV2V(data):
     return data
 
 
+def _dedup_by_hyperedge(edge_index: Tensor):
+    """``(e, v)`` of the distinct (vertex, hyperedge) pairs sorted by (hyperedge, vertex), hyperedge ids re-based to 0 -- the rows
+    ``ConstructV2V`` expands."""
+    v, e = edge_index[0].to(torch.int64), edge_index[1].to(torch.int64)
+    e = e - e.min()
+    n_v = int(v.max()) + 1
+    key = torch.unique(e * n_v + v)
+    return key // n_v, key % n_v
+
+
+def clique_implicit_structure(edge_index: Tensor, n: Optional[int] = None) -> dict:
+    """What the GCN hop over the clique expansion of the V->E list ``edge_index`` needs, WITHOUT the expansion (pure torch, any device;
+    all int64 unless noted).  With the distinct members of each hyperedge in ascending vertex order, one position per incidence:
+
+    ``e_rowptr`` [n_e + 1], ``member`` [nnz]: the hyperedge-major CSR (``member[p]`` = the vertex at position p);
+    ``rank`` [nnz]: the number of smaller members of p's hyperedge -- the pairs (i, member[p]), i < member[p], p's hyperedge emits;
+    ``v_rowptr`` [n + 1], ``v_pos`` [nnz]: the vertex-major CSR whose columns are positions of the first;
+    ``N``: (the largest vertex in a hyperedge of two or more) + 1 -- the ``edge_index.max() + 1`` of ``gcn_norm`` over the pairs;
+    ``loop`` bool [n]: ``j < N``, the vertices ``gcn_norm`` gives a self-loop;
+    ``deg`` [n]: ``loop[j] + sum of rank over j's positions`` -- the integer in-degree (with multiplicities) ``gcn_norm`` sums.
+
+    ``n`` (default: largest vertex id + 1) is the number of vertex rows.  Raises ``ValueError`` when no hyperedge has two members
+    (the expansion is empty, which ``gcn_norm`` refuses)."""
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.shape[1] == 0:
+        raise ValueError(f"gcn_norm: expected a non-empty [2, E] edge list, got an expansion of {tuple(edge_index.shape)} incidences "
+                         "without a pair")
+    if int(edge_index[0].min()) < 0:
+        raise ValueError("gcn_norm: negative vertex id")
+    e, v = _dedup_by_hyperedge(edge_index)
+    dev = v.device
+    n_e = int(e[-1]) + 1
+    n = int(v.max()) + 1 if n is None else int(n)
+    if int(v.max()) >= n:
+        raise ValueError(f"clique_implicit_structure: vertex ids reach {int(v.max())} but there are {n} vertex rows")
+    size = torch.bincount(e, minlength=n_e)
+    e_rowptr = torch.zeros(n_e + 1, dtype=torch.int64, device=dev)
+    e_rowptr[1:] = torch.cumsum(size, 0)
+    paired = size[e] >= 2
+    if not bool(paired.any()):
+        raise ValueError("gcn_norm: expected a non-empty [2, E] edge list, got (2, 0): no hyperedge has two members")
+    rank = torch.arange(v.numel(), device=dev) - e_rowptr[e]
+    N = int(v[paired].max()) + 1
+    loop = torch.arange(n, device=dev) < N
+    deg = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, v, rank) + loop.to(torch.int64)
+    v_pos = torch.argsort(v, stable=True)
+    v_rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    v_rowptr[1:] = torch.cumsum(torch.bincount(v, minlength=n), 0)
+    return dict(e_rowptr=e_rowptr, member=v, rank=rank, v_rowptr=v_rowptr, v_pos=v_pos, N=N, loop=loop, deg=deg, n=n, n_e=n_e)
+
+
+def ConstructV2V_implicit(data):
+    """CEGCN's preprocessing WITHOUT the clique expansion: where ``ConstructV2V`` + ``norm_contruction(TYPE=
+    'V2V')`` write one weighted edge per vertex pair, this keeps the V->E list -- ``data.edge_index`` = the distinct (vertex, hyperedge)
+    pairs (duplicates count once, as in ``ConstructV2V``; hyperedge ids as given), sorted by vertex -- and the GCN hop is computed from
+    prefix sums over it (``baselines.ImplicitCEGraph``, ``functional.clique_propagate``).  Sets ``data.norm = None``,
+    ``data.clique_expansion = True`` and ``data.clique_implicit = True``.  Pure torch, on the device the ids live on.  Raises the
+    ``ValueError`` of ``gcn_norm`` when no hyperedge has two members."""
+    ei = data.edge_index
+    if ei.dim() != 2 or ei.shape[0] != 2 or ei.shape[1] == 0:
+        raise ValueError(f"gcn_norm: expected a non-empty [2, E] edge list, got an expansion of {tuple(ei.shape)} incidences without a pair")
+    e_min = ei[1].min()
+    e, v = _dedup_by_hyperedge(ei)
+    if int(torch.bincount(e).max()) < 2:
+        raise ValueError("gcn_norm: expected a non-empty [2, E] edge list, got (2, 0): no hyperedge has two members")
+    data.edge_index = _sort_by_vertex(torch.stack([v, e + e_min])).contiguous()
+    data.norm = None
+    data.clique_expansion = True
+    data.clique_implicit = True
+    return data
+
+
 def gcn_norm(edge_index, edge_weight=None, add_self_loops=True):
     """torch_geometric 1.6.3 ``gcn_norm(edge_index, edge_weight, add_self_loops=True)`` as ``norm_contruction(TYPE='V2V')`` calls it:
     ``N = edge_index.max() + 1`` (not the vertex count: ids >= N get no loop), one self-loop of weight 1 per id < N,

@@ -45,9 +45,9 @@ import torch.nn.functional as F
 from . import dense
 from ._lib import AllSetHipError
 from .models import SetGNN
-from .preprocessing import (EXCLUDE_SELF_NORMTYPES, Add_Self_Loops, ConstructH_pairs, ConstructV2V, ExtractV2E, exclude_self,
-                            expand_edge_index, generate_norm_HCHA, generate_norm_HNHN, generate_norm_UniGNN, norm_contruction,
-                            rebase_hyperedge_ids)
+from .preprocessing import (EXCLUDE_SELF_NORMTYPES, Add_Self_Loops, ConstructH_pairs, ConstructV2V, ConstructV2V_implicit, ExtractV2E,
+                            exclude_self, expand_edge_index, generate_norm_HCHA, generate_norm_HNHN, generate_norm_UniGNN,
+                            norm_contruction, rebase_hyperedge_ids)
 
 ALLSET_METHODS = ('AllSetTransformer', 'AllDeepSets')
 BASELINE_METHODS = ('HGNN', 'HCHA', 'HNHN')
@@ -396,6 +396,9 @@ def build_model(args, data):
                      dropout=args.dropout, Normalization=args.normalization)
     if args.method == 'CEGAT':
         ei = getattr(data, 'edge_index', None) if data is not None else None
+        if getattr(data, 'clique_implicit', False):
+            raise ValueError("method 'CEGAT' is not built on implicit clique-expansion data (ConstructV2V_implicit): its attention logit "
+                             "does not factorise over a hyperedge; preprocess with ConstructV2V -> norm_contruction(TYPE='V2V')")
         if not getattr(data, 'clique_expansion', False) or not torch.is_tensor(ei) or ei.dim() != 2 or ei.shape[0] != 2 \
                 or ei.dtype.is_floating_point:
             raise ValueError("method 'CEGAT' attends over the clique expansion's [2, E] integer edge_index: pass data through "
@@ -500,6 +503,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--exclude_self_loo_attention', action='store_true',
                    help='with --exclude_self --method AllSetTransformer: keep the edge list unexpanded and pool with the leave-one-out '
                         'softmax (DESIGN.md section 20) where it is built; without this flag the method expands, as before')
+    p.add_argument('--CE_implicit', action='store_true',
+                   help='with --method CEGCN: do not materialise the clique expansion; the GCN hop runs as prefix sums over the '
+                        'hyperedges (DESIGN.md section 21).  Not built for CEGAT')
     p.add_argument('--PMA', action='store_true')
     p.add_argument('--heads', default=1, type=int)
     p.add_argument('--output_heads', default=1, type=int)
@@ -580,6 +586,8 @@ def preprocess(args, data: HypergraphData) -> HypergraphData:
     clique-expansion branch of CEGCN / CEGAT (:354-357: no self-loop hyperedges there, whatever ``--add_self_loop`` says); and the
     UniGCNII branch (:390-412) with the dense incidence matrix replaced by its sorted, de-duplicated pairs; and the HyperGCN branch
     (:359-360): the V->E half alone, kept as zero-based (vertex, hyperedge) pairs in ``data.HyperGCN_pairs``."""
+    if args.method == 'CEGCN' and getattr(args, 'CE_implicit', False):
+        return ConstructV2V_implicit(ExtractV2E(data))      # sets clique_expansion / clique_implicit; no pair is written
     if args.method in CE_METHODS:
         data = ExtractV2E(data)
         data = ConstructV2V(data)
@@ -776,8 +784,18 @@ def _run_loop(args, model, data, splits, device, logger, runtimes, num_params):
     return dict(best_val=best_val, best_test=best_test, num_params=num_params, avg_time=avg_time, csv=filename)
 
 
+def parse_args(argv=None):
+    """``build_parser().parse_args`` plus the combinations the parser refuses."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.CE_implicit and args.method == 'CEGAT':
+        parser.error("--CE_implicit is not built for --method CEGAT: its attention logit leaky_relu(a_l x_i + a_r x_j) does not factorise "
+                     "over a hyperedge, so CEGAT needs the explicit clique expansion (use --method CEGCN, or drop the flag)")
+    return args
+
+
 def main(argv=None):
-    run(build_parser().parse_args(argv))
+    run(parse_args(argv))
     print('All done! Exit python code')
 
 

@@ -1118,6 +1118,33 @@ int allset_loo_softmax_bwd(const int32_t* rowptr, const int32_t* col, const floa
                            float* gV, int64_t ldgv, float* galpha, float* scratch, const int32_t* long_seg, int64_t n_long,
                            int64_t n_seg, int64_t n_src, int64_t nnz, int64_t d, int64_t heads, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CEGCN's GCN hop without the clique expansion (csrc/scan.hip): with the members of a hyperedge in ascending vertex order, the sum over
+ * the expansion's pairs (i, j), i < j, into j is an exclusive prefix sum inside each hyperedge, summed over the hyperedges of j.  Added
+ * under ABI 15, additions only; detect with allset_scan_rows_supported(d) (1 for d % 4 == 0, 0 < d <= 512).  fp32, row-major, int32
+ * CSR.  No atomics, no allocation, no sync.
+ *
+ * allset_scan_rows: for every position p of every segment of the CSR (rowptr int32[n_seg + 1], rowptr[n_seg] == nnz)
+ *   out[p, :] = sum_{q in p's segment, q < p (reverse = 0) | q > p (reverse = 1)} s_src[idx(q)] * src[idx(q), :]
+ * idx(q) = col[q], or q itself when col is NULL (n_src >= nnz).  s_src f32[n_src] may be NULL (ones).  out f32[nnz, ldo]: the first
+ * (reverse: last) position of a segment and every position of a segment of one are written as zeros; an empty segment writes nothing.
+ * src and out 16-byte aligned, lds and ldo multiples of 4, out distinct from src.  Every output is the sum of the terms it names, never
+ * "segment total minus the rest".  long_seg / n_long: as for allset_loo_rows (the same threshold, the same list).
+ *
+ * allset_scan_collect: y[j, :] = drop_p(act(s[j] * (sum_{p in row j} t[col[p], :] + r_self[j] * x[j, :]) + bias)) over the CSR (rowptr
+ * int32[n_t + 1], col int32 in [0, n_pos)).  t f32[n_pos, ldt]; x f32[n_t, ldx] (read only where r_self[j] != 0); r_self, s f32[n_t] and
+ * bias f32[width] may be NULL (no self term / ones / zeros).  act / p / seed / seed_base: as for allset_hconv_fwd, the mask index of
+ * (j, c) being j * width + c.  d - 4 < width <= d: columns from `width` on are written as zeros (a caller with a width that is no
+ * multiple of 4 pads t and x with zero columns).  All rows 16-byte aligned, leading dimensions multiples of 4; y aliases neither t nor x.
+ * ------------------------------------------------------------------------------------------- */
+int allset_scan_rows_supported(int64_t d);
+int allset_scan_rows(const int32_t* rowptr, const int32_t* col, const float* src, int64_t lds, const float* s_src, float* out,
+                     int64_t ldo, const int32_t* long_seg, int64_t n_long, int reverse, int64_t n_seg, int64_t n_src, int64_t nnz,
+                     int64_t d, void* stream);
+int allset_scan_collect(const int32_t* rowptr, const int32_t* col, const float* t, int64_t ldt, const float* r_self, const float* x,
+                        int64_t ldx, const float* s, const float* bias, int act, float p, uint64_t seed, const uint64_t* seed_base,
+                        float* y, int64_t ldy, int64_t n_t, int64_t n_pos, int64_t d, int64_t width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
