@@ -549,17 +549,17 @@ class _ScaledPropagate(torch.autograd.Function):
     an epilogue) and the same propagate kernel over the opposite CSR with ``r`` and ``s`` swapped.  ``r`` / ``s`` are constants."""
 
     @staticmethod
-    def forward(ctx, x, bias, inc, to_dst, r, s, act, p):
+    def forward(ctx, x, bias, inc, to_dst, r, s, act, p, variant):
         from . import dense
         fwd, bwd = (inc.by_dst, inc.by_src) if to_dst else (inc.by_src, inc.by_dst)
         n_t, n_s = (inc.n_dst, inc.n_src) if to_dst else (inc.n_src, inc.n_dst)
         if x.shape[0] != n_s:
             raise _lib.AllSetHipError(f"scaled_propagate: x has {x.shape[0]} rows, the incidence gathers from {n_s}")
         seed, base = dense._seed_for(p)
-        y = ops.hconv_propagate(fwd, x, n_t, r, s, bias, act, p, seed, base)
+        y = ops.hconv_propagate(fwd, x, n_t, r, s, bias, act, p, seed, base, variant)
         epi = act is not None or p > 0.0 or bias is not None
         ctx.save_for_backward(y if epi else None)
-        ctx.cfg = (bwd, n_s, r, s, act, p, seed, base, epi)
+        ctx.cfg = (bwd, n_s, r, s, act, p, seed, base, epi, variant)
         ctx.bias_param = bias
         return y
 
@@ -567,11 +567,11 @@ class _ScaledPropagate(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
-        bwd, n_s, r, s, act, p, seed, base, epi = ctx.cfg
+        bwd, n_s, r, s, act, p, seed, base, epi, variant = ctx.cfg
         need_b = ctx.bias_param is not None and ctx.needs_input_grad[1]
         g, gb = _epilogue_backward(gy, y, act, p, seed, base, epi, ctx.bias_param, need_b)
-        gx = ops.hconv_propagate(bwd, g, n_s, r=s, s=r) if ctx.needs_input_grad[0] else None
-        return gx, gb, None, None, None, None, None, None
+        gx = ops.hconv_propagate(bwd, g, n_s, r=s, s=r, variant=variant) if ctx.needs_input_grad[0] else None
+        return gx, gb, None, None, None, None, None, None, None
 
 
 class _WeightedPropagate(torch.autograd.Function):
@@ -580,15 +580,15 @@ class _WeightedPropagate(torch.autograd.Function):
     in that CSR's order, ``w_src``.  The weights are constants."""
 
     @staticmethod
-    def forward(ctx, x, bias, inc, w_dst, w_src, act, p):
+    def forward(ctx, x, bias, inc, w_dst, w_src, act, p, variant):
         from . import dense
         if x.shape[0] != inc.n_src:
             raise _lib.AllSetHipError(f"weighted_propagate: x has {x.shape[0]} rows, the graph gathers from {inc.n_src}")
         seed, base = dense._seed_for(p)
-        y = ops.hconv_propagate_w(inc.by_dst, x, inc.n_dst, w_dst, bias, act, p, seed, base)
+        y = ops.hconv_propagate_w(inc.by_dst, x, inc.n_dst, w_dst, bias, act, p, seed, base, variant)
         epi = act is not None or p > 0.0 or bias is not None
         ctx.save_for_backward(y if epi else None)
-        ctx.cfg = (inc, w_src, act, p, seed, base, epi)
+        ctx.cfg = (inc, w_src, act, p, seed, base, epi, variant)
         ctx.bias_param = bias
         return y
 
@@ -596,24 +596,24 @@ class _WeightedPropagate(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
-        inc, w_src, act, p, seed, base, epi = ctx.cfg
+        inc, w_src, act, p, seed, base, epi, variant = ctx.cfg
         need_b = ctx.bias_param is not None and ctx.needs_input_grad[1]
         g, gb = _epilogue_backward(gy, y, act, p, seed, base, epi, ctx.bias_param, need_b)
-        gx = ops.hconv_propagate_w(inc.by_src, g, inc.n_src, w_src) if ctx.needs_input_grad[0] else None
-        return gx, gb, None, None, None, None, None
+        gx = ops.hconv_propagate_w(inc.by_src, g, inc.n_src, w_src, variant=variant) if ctx.needs_input_grad[0] else None
+        return gx, gb, None, None, None, None, None, None
 
 
 def weighted_propagate(x: Tensor, inc: Incidence, w_dst: Optional[Tensor], w_src: Optional[Tensor], bias: Optional[Tensor] = None,
-                       act: Optional[str] = None, p: float = 0.0) -> Tensor:
+                       act: Optional[str] = None, p: float = 0.0, variant: Optional[int] = None) -> Tensor:
     """One GCN hop (PyG ``GCNConv.propagate`` with ``edge_weight``): ``y[t] = drop_p(act(sum_{edges s -> t} w_e * x[s] + bias))``
     over ``inc`` (sources -> targets; ``inc.n_dst`` output rows).  ``w_dst`` / ``w_src``: the edge weights routed into
     ``inc.by_dst`` / ``inc.by_src`` order (both None = ones).  ``act`` None / 'relu' / 'elu'; ``p`` the dropout probability.
-    Differentiable in ``x`` and ``bias``."""
+    Differentiable in ``x`` and ``bias``.  ``variant``: kernel variant override of the forward and the backward launch (tests)."""
     if act not in ops.HCONV_ACTS:
         raise ValueError(f"weighted_propagate: act must be None, 'relu' or 'elu', got {act!r}")
     if (w_dst is None) != (w_src is None):
         raise ValueError("weighted_propagate: give the weights in both CSR orders, or neither")
-    return _WeightedPropagate.apply(x, bias, inc, w_dst, w_src, act, float(p))
+    return _WeightedPropagate.apply(x, bias, inc, w_dst, w_src, act, float(p), variant)
 
 
 class _CliquePropagate(torch.autograd.Function):
@@ -682,17 +682,18 @@ def clique_propagate(x: Tensor, graph, bias: Optional[Tensor] = None, act: Optio
 
 
 def scaled_propagate(x: Tensor, inc: Incidence, direction: str, r: Optional[Tensor] = None, s: Optional[Tensor] = None,
-                     bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0) -> Tensor:
+                     bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0, variant: Optional[int] = None) -> Tensor:
     """One hop of a hypergraph convolution over ``inc`` (sources = vertices, targets = hyperedges):
     ``direction`` 'v2e': ``y[e] = drop_p(act(s[e] * sum_{v in e} r[v] * x[v] + bias))``;
     'e2v': ``y[v] = drop_p(act(s[v] * sum_{e ni v} r[e] * x[e] + bias))``.
     ``r`` (per gathered row), ``s`` (per output row) and ``bias`` may be None; ``act`` None / 'relu' / 'elu'; ``p`` the dropout
-    probability (0 outside training).  Differentiable in ``x`` and ``bias``."""
+    probability (0 outside training).  Differentiable in ``x`` and ``bias``.  ``variant``: kernel variant override of the forward
+    and the backward launch (tests)."""
     if direction not in ("v2e", "e2v"):
         raise ValueError(f"scaled_propagate: direction must be 'v2e' or 'e2v', got {direction!r}")
     if act not in ops.HCONV_ACTS:
         raise ValueError(f"scaled_propagate: act must be None, 'relu' or 'elu', got {act!r}")
-    return _ScaledPropagate.apply(x, bias, inc, direction == "v2e", r, s, act, float(p))
+    return _ScaledPropagate.apply(x, bias, inc, direction == "v2e", r, s, act, float(p), variant)
 
 
 # ---- GAT attention hop of the clique-expansion baseline CEGAT (csrc/gat.hip) ----------------------------------------------------

@@ -502,11 +502,23 @@ HCONV_ACTS = {None: _lib.ACT_NONE, "none": _lib.ACT_NONE, "relu": _lib.ACT_RELU,
 RELU_ACTS = {k: v for k, v in HCONV_ACTS.items() if k != "elu"}
 
 
+def _hconv_variant(csr: CSR, n_t: int, flat_ok: bool, variant: Optional[int]) -> int:
+    """None: the CSR's own choice (the short-row kernel only where it is built).  1 / 2 go to the C entry as given, which refuses
+    a 2 the short-row kernel cannot take."""
+    if variant is None:
+        return csr.variant("segreduce", n_t) if flat_ok else 1
+    if variant not in (1, 2):
+        raise _lib.AllSetHipError(f"hconv_propagate: variant must be None, 1 or 2, got {variant!r}")
+    return int(variant)
+
+
 def hconv_propagate(csr: CSR, x: Tensor, n_t: int, r: Optional[Tensor] = None, s: Optional[Tensor] = None,
                     bias: Optional[Tensor] = None, act: Optional[str] = None, p: float = 0.0, seed: int = 0,
-                    seed_base: Optional[Tensor] = None) -> Tensor:
+                    seed_base: Optional[Tensor] = None, variant: Optional[int] = None) -> Tensor:
     """``y[t] = drop_p(act(s[t] * sum_{j in row t} r[col_j] * x[col_j] + bias))`` over ``csr`` (rows = outputs, the first ``n_t``
-    rows of it).  ``r`` f32[n_s], ``s`` f32[n_t], ``bias`` f32[d]: each optional.  fp32 only."""
+    rows of it).  ``r`` f32[n_s], ``s`` f32[n_t], ``bias`` f32[d]: each optional.  fp32 only.  ``variant``: kernel variant override
+    (tests): 1 one wavefront per row, 2 the short-row kernel (16-byte rows of width <= 256 only, anything else raises); None = the
+    CSR's own choice."""
     dev = require_device(csr.rowptr, x, r, s, bias)
     _f32(x, "hconv_propagate")
     for t, what in ((r, "r"), (s, "s"), (bias, "bias")):
@@ -528,7 +540,7 @@ def hconv_propagate(csr: CSR, x: Tensor, n_t: int, r: Optional[Tensor] = None, s
     y = torch.empty((n_t, d), dtype=torch.float32, device=dev)
     nnz = csr.col.numel()
     flat_ok = d % 4 == 0 and d <= 256 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
-    variant = csr.variant("segreduce", n_t) if flat_ok else 1
+    variant = _hconv_variant(csr, n_t, flat_ok, variant)
     order = csr.row_order if (variant == 1 and csr.row_order is not None and csr.row_order.numel() == n_t) else None
     algo = nnz * (4 * d + 4 + (4 if r is not None else 0)) + (n_t + 1) * 4 + n_t * 4 * d
     with on_device(dev), _timed("hconv_fwd", dev, algo):
@@ -539,9 +551,10 @@ def hconv_propagate(csr: CSR, x: Tensor, n_t: int, r: Optional[Tensor] = None, s
 
 
 def hconv_propagate_w(csr: CSR, x: Tensor, n_t: int, w: Optional[Tensor] = None, bias: Optional[Tensor] = None,
-                      act: Optional[str] = None, p: float = 0.0, seed: int = 0, seed_base: Optional[Tensor] = None) -> Tensor:
+                      act: Optional[str] = None, p: float = 0.0, seed: int = 0, seed_base: Optional[Tensor] = None,
+                      variant: Optional[int] = None) -> Tensor:
     """``y[t] = drop_p(act(sum_{j in row t} w[j] * x[col_j] + bias))`` over ``csr`` with ``w`` f32[nnz] per incidence in ``csr``'s
-    own order (None = ones).  fp32 only."""
+    own order (None = ones).  fp32 only.  ``variant``: as :func:`hconv_propagate`'s."""
     dev = require_device(csr.rowptr, x, w, bias)
     _f32(x, "hconv_propagate_w")
     for t, what in ((w, "w"), (bias, "bias")):
@@ -560,7 +573,7 @@ def hconv_propagate_w(csr: CSR, x: Tensor, n_t: int, w: Optional[Tensor] = None,
         raise _lib.AllSetHipError(f"hconv_propagate_w: CSR of {csr.n_rows} x {csr.n_cols} against {n_t} outputs / {n_s} gathered rows")
     y = torch.empty((n_t, d), dtype=torch.float32, device=dev)
     flat_ok = d % 4 == 0 and d <= 256 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
-    variant = csr.variant("segreduce", n_t) if flat_ok else 1
+    variant = _hconv_variant(csr, n_t, flat_ok, variant)
     order = csr.row_order if (variant == 1 and csr.row_order is not None and csr.row_order.numel() == n_t) else None
     algo = nnz * (4 * d + 4 + (4 if w is not None else 0)) + (n_t + 1) * 4 + n_t * 4 * d
     with on_device(dev), _timed("hconv_fwd_w", dev, algo):
