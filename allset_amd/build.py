@@ -19,7 +19,7 @@ BUILD_DIR = os.path.join(PKG_DIR, "csrc", "build")
 LIB_PATH = os.path.join(PKG_DIR, "liballset_hip.so")
 ARCH = "gfx950"
 SOURCES = ["abi.hip", "csr_build.hip", "segreduce.hip", "pma.hip", "dense.hip", "fused_mlp.hip", "fused_fwd2.hip", "fused_bwd.hip", "fused_bwd4.hip", "fused_bwd6.hip", "fused_bf16.hip", "batchnorm.hip", "input_linear.hip", "sparse_input.hip", "narrow_linear.hip", "wide_mlp.hip", "wgrad_f16.hip", "loss.hip", "optim.hip", "hconv.hip", "clique.hip", "gat.hip", "unigcn.hip", "hypergcn.hip", "unignn.hip", "han.hip", "han_sample.hip", "hattn.hip", "metapath.hip", "loo.hip", "loo_softmax.hip", "scan.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mfma.h"), os.path.join(CSRC, "row_epilogue.h"), os.path.join(CSRC, "seg_rows.h"), os.path.join(INCLUDE, "allset_hip.h"), os.path.join(INCLUDE, "allset_hip_ext.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mfma.h"), os.path.join(CSRC, "row_epilogue.h"), os.path.join(CSRC, "seg_rows.h"), os.path.join(CSRC, "flat_rows.h"), os.path.join(INCLUDE, "allset_hip.h"), os.path.join(INCLUDE, "allset_hip_ext.h")]
 CXXFLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC",
             "-Wall", "-Wno-unused-function",
             # No SLP vectorisation: packed-f32 VALU (v_pk_fma_f32 & co.) beside MFMAs is slower on gfx950

@@ -6,19 +6,19 @@
 // transposed CSR with r and s swapped and no epilogue, gx[v] = r[v] * sum_t s[t] * g[t].  The only other kernel is the
 // epilogue's backward (allset_hconv_bwd_epi below): g = gy * keep / (1 - p) * act'(y), with act' recovered from y alone.
 //
-// Mapping: segreduce.hip's (that file and its instantiations are left as they are; the skeleton is repeated here with the
-// per-source scale and the epilogue added):
+// Mapping: segreduce.hip's, with the per-source scale and the epilogue added:
 //   * one wavefront per CSR row, LPR lanes x 16 B per feature row, NS = 64 / LPR source rows gathered per load;
 //   * the up-to-64 column ids of the row arrive in ONE coalesced load (lane j holds id j, and r[id j] when r is given) and
 //     are broadcast with ds_bpermute, kUnroll = 8 gathers in flight per slot;
 //   * XCD-contiguous workgroup order, and the CSR's long-rows-first order (row_order) when the caller has one;
-//   * a short-row variant (several consecutive rows per lane group, one stream of incidences) below a mean degree of 6.
+//   * a short-row variant (several consecutive rows per lane group, one stream of incidences: flat_rows.h) below a mean degree of 6.
 // Algorithmic bytes per launch: nnz * (4d + 4) + (n_t + 1) * 4 + n_t * 4d, plus 4 * nnz for the r gathers.
 //
 // allset_hconv_fwd_w (CEGCN's GCNConv hop over the clique expansion) is the same launch with a per-INCIDENCE weight w[j] in place
 // of the per-source r[col_j]: w is read in CSR order next to the column ids (one coalesced load per 64 incidences), so the
 // backward over the transposed CSR takes w permuted into that CSR's order, once per graph.
 #include "common.h"
+#include "flat_rows.h"
 #include "row_epilogue.h"
 
 namespace allset {
@@ -26,7 +26,6 @@ namespace hconv {
 
 enum { kScNone = 0, kScR = 1, kScW = 2 };   // per-incidence scale: none, r[col_j] (per gathered row), w[j] (per CSR position)
 constexpr int kUnroll = 8;
-constexpr int kFlatRows = 7;          // rows per lane group in the short-row kernel (kFlatRows + 1 rowptr entries fit in 8 lanes)
 
 struct Epi {
   const float* s;         // per output row, or NULL
@@ -122,8 +121,9 @@ __global__ __launch_bounds__(kBlock) void hconv_fwd_kernel(
   }
 }
 
-// short-row variant: each LPR-lane group owns kFlatRows consecutive rows and walks their incidences as one stream
-// (segreduce_flat_kernel's scheme); single column chunk (d <= LPR * 4), 16-byte rows
+// short-row variant (the scheme of flat_rows.h); single column chunk (d <= LPR * 4), 16-byte rows.  The walk is written out here,
+// not taken from flat_walk(): over the header this kernel measured 0.5 % slower with a per-incidence scale (hipcc 7.2 orders the
+// loop bodies differently; profiles/flat_walk_refactor.md), so it keeps its own text.
 template <int LPR, int SC>
 __global__ __launch_bounds__(kBlock) void hconv_flat_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ r,
@@ -253,10 +253,7 @@ static void launch_fwd(int sc, unsigned grid, hipStream_t st, const int32_t* row
 template <int LPR>
 static void launch_flat(int sc, hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* r, const float* x,
                         int64_t ldx, float* y, int64_t ldy, int n_t, int d, const Epi& e, const uint64_t* seed_base) {
-  constexpr int NS = kWave / LPR;
-  const int64_t groups = (static_cast<int64_t>(n_t) + kFlatRows - 1) / kFlatRows;
-  const int64_t waves = (groups + NS - 1) / NS;
-  const unsigned grid = static_cast<unsigned>((waves + kWavesPerBlock - 1) / kWavesPerBlock);
+  const unsigned grid = flat_grid<LPR>(n_t);
   if (sc == kScR)      hconv_flat_kernel<LPR, kScR><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, e, seed_base);
   else if (sc == kScW) hconv_flat_kernel<LPR, kScW><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, e, seed_base);
   else                 hconv_flat_kernel<LPR, kScNone><<<grid, kBlock, 0, st>>>(rowptr, col, r, x, ldx, y, ldy, n_t, d, e, seed_base);
@@ -297,24 +294,11 @@ static int hconv_fwd_impl(int sc, int variant, int64_t nnz, const int32_t* row_o
   }
   const int has_r = r != nullptr ? sc : kScNone;
   if (use_flat) {
-    switch (pick_lpr(d)) {
-      case 8:  launch_flat<8>(has_r, st, rowptr, col, r, x, ldx, y, ldy, nt, di, ep, seed_base); break;
-      case 16: launch_flat<16>(has_r, st, rowptr, col, r, x, ldx, y, ldy, nt, di, ep, seed_base); break;
-      case 32: launch_flat<32>(has_r, st, rowptr, col, r, x, ldx, y, ldy, nt, di, ep, seed_base); break;
-      default: launch_flat<64>(has_r, st, rowptr, col, r, x, ldx, y, ldy, nt, di, ep, seed_base); break;
-    }
+    with_lpr(pick_lpr(d), [&](auto lpr) { launch_flat<lpr()>(has_r, st, rowptr, col, r, x, ldx, y, ldy, nt, di, ep, seed_base); });
   } else {
-    const unsigned grid = row_grid(n_t);
-    if (vec4) {
-      switch (pick_lpr(d)) {
-        case 8:  launch_fwd<4, 8>(has_r, grid, st, rowptr, col, r, x, ldx, y, ldy, nt, di, row_order, ep, seed_base); break;
-        case 16: launch_fwd<4, 16>(has_r, grid, st, rowptr, col, r, x, ldx, y, ldy, nt, di, row_order, ep, seed_base); break;
-        case 32: launch_fwd<4, 32>(has_r, grid, st, rowptr, col, r, x, ldx, y, ldy, nt, di, row_order, ep, seed_base); break;
-        default: launch_fwd<4, 64>(has_r, grid, st, rowptr, col, r, x, ldx, y, ldy, nt, di, row_order, ep, seed_base); break;
-      }
-    } else {
-      launch_fwd<1, 64>(has_r, grid, st, rowptr, col, r, x, ldx, y, ldy, nt, di, row_order, ep, seed_base);
-    }
+    with_vec_lpr<4>(vec4, d, [&](auto vec, auto lpr) {
+      launch_fwd<vec(), lpr()>(has_r, row_grid(n_t), st, rowptr, col, r, x, ldx, y, ldy, nt, di, row_order, ep, seed_base);
+    });
   }
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;

@@ -26,13 +26,13 @@
 // of the last layer); anything else: ALLSET_ERR_UNSUPPORTED and the caller composes the hop from allset_hconv_fwd.
 // Algorithmic bytes: v2e nnz * (4d + 8) + (n_e + 1) * 4 + 12 n_e + 2 n_e * 4d;  e2v nnz * (4d + 4) + (n_v + 1) * 4 + 8 n_v + 2 n_v * 4d.
 #include "common.h"
+#include "flat_rows.h"
 #include "row_epilogue.h"
 
 namespace allset {
 namespace hypergcn {
 
 constexpr int kUnroll = 8;
-constexpr int kFlatRows = 7;
 constexpr int kMaxWidth = 256;
 constexpr int kMaxScalarWidth = 64;
 
@@ -337,74 +337,49 @@ __global__ __launch_bounds__(kBlock) void e2v_kernel(const int32_t* __restrict__
   if (slot == 0 && active) finish_row<VEC>(tl, row, c0, d, acc, y, ldy);
 }
 
-// short-row variant: each LPR-lane group owns kFlatRows consecutive rows and walks their incidences as one stream
-// (hconv_flat_kernel's scheme); 16-byte rows, d <= LPR * 4
+// short-row variant (flat_rows.h); 16-byte rows, d <= LPR * 4
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void e2v_flat_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colx,
                                                           const float* __restrict__ pq, int64_t ldpq, int n_pq, Tail tl,
                                                           const uint64_t* __restrict__ seed_base, float* __restrict__ y, int64_t ldy,
                                                           int n_v, int d) {
   constexpr int VEC = 4;
-  constexpr int NS = kWave / LPR;
-  const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
-  const int lane = lane_id();
-  const int slot = lane / LPR, li = lane % LPR;
-  const int lane0 = slot * LPR;
-  const int64_t slot_global = (static_cast<int64_t>(blk) * kWavesPerBlock + (threadIdx.x >> 6)) * NS + slot;
-  const int64_t r_begin64 = slot_global * kFlatRows;
-  if (r_begin64 - static_cast<int64_t>(slot) * kFlatRows >= n_v) return;      // whole wave beyond the last row
+  FlatSlot<LPR> s;
+  if (s.wave_beyond(n_v)) return;
   tl.epi.seed = resolve_seed(seed_base, tl.epi.seed);
-  const int r_begin = static_cast<int>(min(r_begin64, static_cast<int64_t>(n_v)));
-  const int r_end = min(r_begin + kFlatRows, n_v);
-  const int c0 = li * VEC;
+  s.open(rowptr, n_v);
+  const int c0 = s.li * VEC;
   const bool active = c0 < d;
-  const int rp = (li <= r_end - r_begin) ? rowptr[r_begin + li] : 0;
-  const int q0 = __shfl(rp, lane0);
-  const int q_end = __shfl(rp, lane0 + (r_end - r_begin));
-
-  int cur_row = r_begin;
-  int cur_end = (r_begin < r_end) ? __shfl(rp, lane0 + 1) : q0;
   float acc[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+  int my_col = -1;
+  Raw<float, VEC> raw[kUnroll];
 
-  auto flush = [&]() {
-    if (active) finish_row<VEC>(tl, cur_row, c0, d, acc, y, ldy);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-    ++cur_row;
-    cur_end = __shfl(rp, lane0 + min(cur_row - r_begin + 1, LPR - 1));
-  };
-
-  for (int base = q0; base < q_end; base += LPR) {
-    const int n = min(LPR, q_end - base);
-    int my_col = -1;
-    if (li < n) {
-      my_col = colx[base + li];
-      if (my_col >= n_pq) my_col = -1;
-    }
-    for (int j = 0; j < n; j += kUnroll) {
-      Raw<float, VEC> raw[kUnroll];
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int jj = j + u;
-        const int src = __shfl(my_col, lane0 + (jj & (LPR - 1)));
-        if (jj < n && active && src >= 0) raw[u] = load_raw<float, VEC>(pq + static_cast<int64_t>(src) * ldpq + c0);
-        else raw[u] = zero_raw<float, VEC>();
-      }
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int pos = base + j + u;
-        if (j + u < n) {
-          while (pos >= cur_end) flush();                          // also steps over empty rows
-          const FVec<VEC> v = unpack<float, VEC>(raw[u]);
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) acc[k] += v.v[k];
+  flat_walk<kUnroll>(
+      s, active,
+      [&](int base, int n) {
+        my_col = -1;
+        if (s.li < n) {
+          my_col = colx[base + s.li];
+          if (my_col >= n_pq) my_col = -1;
         }
-      }
-    }
-  }
-  while (cur_row < r_end) flush();                                 // last row and trailing empty rows
+      },
+      [&](int u, int jj, bool ok) {
+        const int src = s.bcast(my_col, jj);
+        if (ok && src >= 0) raw[u] = load_raw<float, VEC>(pq + static_cast<int64_t>(src) * ldpq + c0);
+        else raw[u] = zero_raw<float, VEC>();
+      },
+      [&](int u) {
+        const FVec<VEC> v = unpack<float, VEC>(raw[u]);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[k] += v.v[k];
+      },
+      [&] {
+        if (active) finish_row<VEC>(tl, s.cur_row, c0, d, acc, y, ldy);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+      });
 }
 
 static inline int pick_group(int64_t nnz, int64_t rows) {   // lanes per CSR row of the structure kernels
@@ -423,16 +398,6 @@ static inline int width_class(int64_t d, bool rows16) {
   if (d % 4 == 0 && d <= kMaxWidth && rows16) return 1;
   if (d <= kMaxScalarWidth) return 0;
   return -1;
-}
-
-template <int LPR>
-static void launch_e2v_flat(hipStream_t st, const int32_t* rowptr, const int32_t* colx, const float* pq, int64_t ldpq, int n_pq,
-                            const Tail& tl, const uint64_t* seed_base, float* y, int64_t ldy, int n_v, int d) {
-  constexpr int NS = kWave / LPR;
-  const int64_t groups = (static_cast<int64_t>(n_v) + kFlatRows - 1) / kFlatRows;
-  const int64_t waves = (groups + NS - 1) / NS;
-  const unsigned grid = static_cast<unsigned>((waves + kWavesPerBlock - 1) / kWavesPerBlock);
-  e2v_flat_kernel<LPR><<<grid, kBlock, 0, st>>>(rowptr, colx, pq, ldpq, n_pq, tl, seed_base, y, ldy, n_v, d);
 }
 
 }  // namespace hypergcn
@@ -531,16 +496,9 @@ extern "C" int allset_hypergcn_v2e(int mediators, int64_t nnz, const int32_t* ro
   }
   ALLSET_REQUIRE(rowptr && (nnz == 0 || col), "hypergcn_v2e: null rowptr/col");
   const unsigned grid = row_grid(n_e);
-  if (wc == 1) {
-    switch (pick_lpr(d)) {
-      case 8:  v2e_kernel<4, 8><<<grid, kBlock, 0, st>>>(rowptr, col, S, I, w, dinv, x, ldx, pq, ldpq, ne, di, row_order); break;
-      case 16: v2e_kernel<4, 16><<<grid, kBlock, 0, st>>>(rowptr, col, S, I, w, dinv, x, ldx, pq, ldpq, ne, di, row_order); break;
-      case 32: v2e_kernel<4, 32><<<grid, kBlock, 0, st>>>(rowptr, col, S, I, w, dinv, x, ldx, pq, ldpq, ne, di, row_order); break;
-      default: v2e_kernel<4, 64><<<grid, kBlock, 0, st>>>(rowptr, col, S, I, w, dinv, x, ldx, pq, ldpq, ne, di, row_order); break;
-    }
-  } else {
-    v2e_kernel<1, 64><<<grid, kBlock, 0, st>>>(rowptr, col, S, I, w, dinv, x, ldx, pq, ldpq, ne, di, row_order);
-  }
+  with_vec_lpr<4>(wc == 1, d, [&](auto vec, auto lpr) {
+    v2e_kernel<vec(), lpr()><<<grid, kBlock, 0, st>>>(rowptr, col, S, I, w, dinv, x, ldx, pq, ldpq, ne, di, row_order);
+  });
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }
@@ -576,24 +534,13 @@ extern "C" int allset_hypergcn_e2v(int variant, int64_t nnz, const int32_t* row_
   const bool use_flat = wc == 1 && (variant == 2 || (variant == 0 && n_v > kFlatMinRows &&
                                                      static_cast<double>(nnz) < kFlatMaxMeanDegree * static_cast<double>(n_v)));
   if (use_flat) {
-    switch (pick_lpr(d)) {
-      case 8:  launch_e2v_flat<8>(st, rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di); break;
-      case 16: launch_e2v_flat<16>(st, rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di); break;
-      case 32: launch_e2v_flat<32>(st, rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di); break;
-      default: launch_e2v_flat<64>(st, rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di); break;
-    }
+    with_lpr(pick_lpr(d), [&](auto lpr) {
+      e2v_flat_kernel<lpr()><<<flat_grid<lpr()>(n_v), kBlock, 0, st>>>(rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di);
+    });
   } else {
-    const unsigned grid = row_grid(n_v);
-    if (wc == 1) {
-      switch (pick_lpr(d)) {
-        case 8:  e2v_kernel<4, 8><<<grid, kBlock, 0, st>>>(rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di, row_order); break;
-        case 16: e2v_kernel<4, 16><<<grid, kBlock, 0, st>>>(rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di, row_order); break;
-        case 32: e2v_kernel<4, 32><<<grid, kBlock, 0, st>>>(rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di, row_order); break;
-        default: e2v_kernel<4, 64><<<grid, kBlock, 0, st>>>(rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di, row_order); break;
-      }
-    } else {
-      e2v_kernel<1, 64><<<grid, kBlock, 0, st>>>(rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di, row_order);
-    }
+    with_vec_lpr<4>(wc == 1, d, [&](auto vec, auto lpr) {
+      e2v_kernel<vec(), lpr()><<<row_grid(n_v), kBlock, 0, st>>>(rowptr, colx, pq, ldpq, npq, tl, seed_base, y, ldy, nv, di, row_order);
+    });
   }
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;

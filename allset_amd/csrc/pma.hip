@@ -19,6 +19,7 @@
 #include <float.h>
 
 #include "common.h"
+#include "flat_rows.h"
 
 namespace allset {
 
@@ -115,12 +116,9 @@ __global__ __launch_bounds__(kBlock) void pma_fwd_kernel(
 }
 
 
-// ---- short-row variant of pma_fwd (see segreduce_flat_kernel): each LPR-lane slot owns kPmaFlatRows consecutive
-// target rows and walks their incidences as one stream, restarting its online-softmax state at every row end.
+// ---- short-row variant of pma_fwd (flat_rows.h): the slot restarts its online-softmax state at every row end.
 // Needed where rows are short by construction: E->V under hyperedge sharding (each rank holds ~deg/P incidences of a
 // vertex) and graphs with self-loop hyperedges.  Whole row in one column chunk (d <= LPR*VEC).
-constexpr int kPmaFlatRows = 7;
-
 template <typename T, int VEC, int LPR>
 __global__ __launch_bounds__(kBlock) void pma_fwd_flat_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ alpha, int64_t lda,
@@ -128,87 +126,60 @@ __global__ __launch_bounds__(kBlock) void pma_fwd_flat_kernel(
     float* __restrict__ m_out, float* __restrict__ l_out, int n_t, int H, int C, const int32_t* __restrict__ row_ids) {
   // row_ids (optional): the CSR handed in is a COMPACTED one -- row i of it is row row_ids[i] of the outputs (the short rows of a
   // skewed incidence; the long ones go to the one-wave-per-row kernel with their own list: ops.CSR.split)
-  constexpr int NS = kWave / LPR;
-  const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
-  const int lane = lane_id();
-  const int slot = lane / LPR, li = lane % LPR;
-  const int lane0 = slot * LPR;
-  const int64_t slot_global = (static_cast<int64_t>(blk) * kWavesPerBlock + (threadIdx.x >> 6)) * NS + slot;
-  const int64_t r_begin64 = slot_global * kPmaFlatRows;
-  if (r_begin64 - static_cast<int64_t>(slot) * kPmaFlatRows >= n_t) return;
-  const int r_begin = static_cast<int>(min(r_begin64, static_cast<int64_t>(n_t)));
-  const int r_end = min(r_begin + kPmaFlatRows, n_t);
+  FlatSlot<LPR> s;
+  if (s.wave_beyond(n_t)) return;
+  s.open(rowptr, n_t);
   const int d = H * C;
-  const int c0 = li * VEC;
+  const int c0 = s.li * VEC;
   const bool active = c0 < d;
   const int h = active ? c0 / C : 0;
   const bool head_leader = active && (c0 % C == 0);
-  const int rp = (li <= r_end - r_begin) ? rowptr[r_begin + li] : 0;
-  const int rid = (li < r_end - r_begin) ? (row_ids ? row_ids[r_begin + li] : r_begin + li) : 0;      // output row of slot row li
-  const int q0 = __shfl(rp, lane0);
-  const int q_end = __shfl(rp, lane0 + (r_end - r_begin));
-
-  int cur_row = r_begin;
-  int cur_end = (r_begin < r_end) ? __shfl(rp, lane0 + 1) : q0;
+  const int rid = (s.li < s.r_end - s.r_begin) ? (row_ids ? row_ids[s.r_begin + s.li] : s.r_begin + s.li) : 0;      // output row of slot row li
   float m = -FLT_MAX, l = 0.f;
   float acc[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+  int my_col = 0;
+  Raw<T, VEC> raw[kPmaUnroll];
+  float a[kPmaUnroll];
 
-  auto flush = [&]() {
-    const int orow = __shfl(rid, lane0 + min(cur_row - r_begin, LPR - 1));
-    if (active) {
-      const float inv = l > 0.f ? 1.f / (l + kSoftmaxEps) : 0.f;
-      FVec<VEC> r;
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) { r.v[k] = acc[k] * inv; acc[k] = 0.f; }
-      store_vec<T, VEC>(out + static_cast<int64_t>(orow) * ldo + c0, r);
-      if (head_leader) {
-        m_out[static_cast<int64_t>(orow) * H + h] = l > 0.f ? m : 0.f;
-        l_out[static_cast<int64_t>(orow) * H + h] = l;
-      }
-    }
-    m = -FLT_MAX; l = 0.f;
-    ++cur_row;
-    cur_end = __shfl(rp, lane0 + min(cur_row - r_begin + 1, LPR - 1));
-  };
-
-  for (int base = q0; base < q_end; base += LPR) {
-    const int n = min(LPR, q_end - base);
-    const int my_col = (li < n) ? col[base + li] : 0;
-    for (int j = 0; j < n; j += kPmaUnroll) {
-      Raw<T, VEC> raw[kPmaUnroll];
-      float a[kPmaUnroll];
-#pragma unroll
-      for (int u = 0; u < kPmaUnroll; ++u) {
-        const int jj = j + u;
-        const int src = __shfl(my_col, lane0 + (jj & (LPR - 1)));
+  flat_walk<kPmaUnroll>(
+      s, active, [&](int base, int n) { my_col = (s.li < n) ? col[base + s.li] : 0; },
+      [&](int u, int jj, bool ok) {
+        const int src = s.bcast(my_col, jj);
         a[u] = 0.f;
         raw[u] = zero_raw<T, VEC>();
-        if (jj < n && active) {
+        if (ok) {
           a[u] = alpha[static_cast<int64_t>(src) * lda + h];
           raw[u] = load_raw<T, VEC>(V + static_cast<int64_t>(src) * ldv + c0);
         }
-      }
+      },
+      [&](int u) {
+        const FVec<VEC> vu = unpack<T, VEC>(raw[u]);
+        const float av = leaky_relu(a[u], slope);
+        const float m_new = fmaxf(m, av);
+        const float sc = __expf(m - m_new);
+        const float pe = __expf(av - m_new);
+        l = fmaf(l, sc, pe);
 #pragma unroll
-      for (int u = 0; u < kPmaUnroll; ++u) {
-        const int pos = base + j + u;
-        if (j + u < n) {
-          while (pos >= cur_end) flush();
-          const FVec<VEC> vu = unpack<T, VEC>(raw[u]);
-          const float av = leaky_relu(a[u], slope);
-          const float m_new = fmaxf(m, av);
-          const float sc = __expf(m - m_new);
-          const float pe = __expf(av - m_new);
-          l = fmaf(l, sc, pe);
+        for (int k = 0; k < VEC; ++k) acc[k] = fmaf(acc[k], sc, pe * vu.v[k]);
+        m = m_new;
+      },
+      [&] {
+        const int orow = s.bcast(rid, min(s.cur_row - s.r_begin, LPR - 1));
+        if (active) {
+          const float inv = l > 0.f ? 1.f / (l + kSoftmaxEps) : 0.f;
+          FVec<VEC> r;
 #pragma unroll
-          for (int k = 0; k < VEC; ++k) acc[k] = fmaf(acc[k], sc, pe * vu.v[k]);
-          m = m_new;
+          for (int k = 0; k < VEC; ++k) { r.v[k] = acc[k] * inv; acc[k] = 0.f; }
+          store_vec<T, VEC>(out + static_cast<int64_t>(orow) * ldo + c0, r);
+          if (head_leader) {
+            m_out[static_cast<int64_t>(orow) * H + h] = l > 0.f ? m : 0.f;
+            l_out[static_cast<int64_t>(orow) * H + h] = l;
+          }
         }
-      }
-    }
-  }
-  while (cur_row < r_end) flush();
+        m = -FLT_MAX; l = 0.f;
+      });
 }
 
 // p[j,h] in CSR order, for return_attention_weights
@@ -418,9 +389,9 @@ __global__ __launch_bounds__(kBlock) void pma_bwd_src_kernel(
 }
 
 
-// ---- short-row variant of pma_bwd_src: each slot owns kPmaFlatRows consecutive SOURCE rows (transposed CSR) and walks
-// their incidences as one stream.  The rows' own logits and V rows are requested up front (static shift registers keep
-// the indexing compile-time), so a row end costs VEC FMAs, one head-group reduction and two stores.
+// ---- short-row variant of pma_bwd_src (flat_rows.h) over SOURCE rows (transposed CSR).  The rows' own logits and V rows are
+// requested up front (static shift registers keep the indexing compile-time), so a row end costs VEC FMAs, one head-group
+// reduction and two stores.
 template <typename T, int VEC, int LPR>
 __global__ __launch_bounds__(kBlock) void pma_bwd_src_flat_kernel(
     const int32_t* __restrict__ rowptrT, const int32_t* __restrict__ colT, const float* __restrict__ alpha,
@@ -428,17 +399,11 @@ __global__ __launch_bounds__(kBlock) void pma_bwd_src_flat_kernel(
     const float* __restrict__ stats, int64_t lds, float slope, T* __restrict__ gV, int64_t ldgv,
     float* __restrict__ galpha, int n_s, int H, int C, const int32_t* __restrict__ row_ids) {
   // row_ids (optional): compacted transposed CSR -- its row i is source row row_ids[i] (see pma_fwd_flat_kernel)
-  constexpr int NS = kWave / LPR;
-  constexpr int R = kPmaFlatRows;
-  const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
-  const int lane = lane_id();
-  const int slot = lane / LPR, li = lane % LPR;
-  const int lane0 = slot * LPR;
-  const int64_t slot_global = (static_cast<int64_t>(blk) * kWavesPerBlock + (threadIdx.x >> 6)) * NS + slot;
-  const int64_t r_begin64 = slot_global * R;
-  if (r_begin64 - static_cast<int64_t>(slot) * R >= n_s) return;
-  const int r_begin = static_cast<int>(min(r_begin64, static_cast<int64_t>(n_s)));
-  const int r_end = min(r_begin + R, n_s);
+  constexpr int R = kFlatRows;
+  FlatSlot<LPR> s;
+  if (s.wave_beyond(n_s)) return;
+  s.open(rowptrT, n_s);
+  const int li = s.li;
   const int d = H * C, G = C / VEC;
   const int c0 = li * VEC;
   const bool active = c0 < d;
@@ -446,10 +411,7 @@ __global__ __launch_bounds__(kBlock) void pma_bwd_src_flat_kernel(
   const int q = active ? (c0 % C) / VEC : 0;
   const int n_act = min(LPR, d / VEC);
   const int grp_end = min(li - q + G, n_act);
-  const int rp = (li <= r_end - r_begin) ? rowptrT[r_begin + li] : 0;
-  const int rid = (li < r_end - r_begin) ? (row_ids ? row_ids[r_begin + li] : r_begin + li) : 0;      // source row of slot row li
-  const int q0 = __shfl(rp, lane0);
-  const int q_end = __shfl(rp, lane0 + (r_end - r_begin));
+  const int rid = (li < s.r_end - s.r_begin) ? (row_ids ? row_ids[s.r_begin + li] : s.r_begin + li) : 0;      // source row of slot row li
   // own-row data of the slot's rows, requested now, consumed at the row ends
   float a_raw[R];
   Raw<T, VEC> v_raw[R];
@@ -457,88 +419,65 @@ __global__ __launch_bounds__(kBlock) void pma_bwd_src_flat_kernel(
   for (int i = 0; i < R; ++i) {
     a_raw[i] = 0.f;
     v_raw[i] = zero_raw<T, VEC>();
-    const int srow = __shfl(rid, lane0 + i);
-    if (active && r_begin + i < r_end) {
+    const int srow = s.bcast(rid, i);
+    if (active && s.r_begin + i < s.r_end) {
       a_raw[i] = alpha[static_cast<int64_t>(srow) * H + h];
       v_raw[i] = load_raw<T, VEC>(V + static_cast<int64_t>(srow) * ldv + c0);
     }
   }
-  int cur_row = r_begin;
-  int cur_end = (r_begin < r_end) ? __shfl(rp, lane0 + 1) : q0;
   float a_s = leaky_relu(a_raw[0], slope);
   float gv[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) gv[k] = 0.f;
   float D = 0.f;
+  int my_col = 0;
+  Raw<T, VEC> g[kPmaUnroll];
+  float2 st[kPmaUnroll];
 
-  auto flush = [&]() {
-    const FVec<VEC> vown = unpack<T, VEC>(v_raw[0]);
-    const int orow = __shfl(rid, lane0 + min(cur_row - r_begin, LPR - 1));
-    float S = 0.f;
-    if (active) {
-      FVec<VEC> r;
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) { r.v[k] = gv[k]; S = fmaf(vown.v[k], gv[k], S); gv[k] = 0.f; }
-      store_vec<T, VEC>(gV + static_cast<int64_t>(orow) * ldgv + c0, r);
-    }
-    S = head_group_reduce<LPR>(S, li, grp_end);
-    if (active && q == 0)
-      galpha[static_cast<int64_t>(orow) * H + h] = (a_raw[0] > 0.f ? 1.f : slope) * (S - D);
-    D = 0.f;
-#pragma unroll
-    for (int i = 0; i + 1 < R; ++i) { a_raw[i] = a_raw[i + 1]; v_raw[i] = v_raw[i + 1]; }
-    a_s = leaky_relu(a_raw[0], slope);
-    ++cur_row;
-    cur_end = __shfl(rp, lane0 + min(cur_row - r_begin + 1, LPR - 1));
-  };
-
-  for (int base = q0; base < q_end; base += LPR) {
-    const int n = min(LPR, q_end - base);
-    const int my_col = (li < n) ? colT[base + li] : 0;
-    for (int j = 0; j < n; j += kPmaUnroll) {
-      Raw<T, VEC> g[kPmaUnroll];
-      float2 st[kPmaUnroll];
-#pragma unroll
-      for (int u = 0; u < kPmaUnroll; ++u) {
-        const int jj = j + u;
-        const int t = __shfl(my_col, lane0 + (jj & (LPR - 1)));
+  flat_walk<kPmaUnroll>(
+      s, active, [&](int base, int n) { my_col = (li < n) ? colT[base + li] : 0; },
+      [&](int u, int jj, bool ok) {
+        const int t = s.bcast(my_col, jj);
         g[u] = zero_raw<T, VEC>();
         st[u] = make_float2(0.f, 0.f);
-        if (jj < n && active) {
+        if (ok) {
           g[u] = load_raw<T, VEC>(gout + static_cast<int64_t>(t) * ldg + c0);
           st[u] = *reinterpret_cast<const float2*>(stats + static_cast<int64_t>(t) * lds + h * 2);
         }
-      }
+      },
+      [&](int u) {
+        const float p = __expf(a_s - st[u].x);
+        const FVec<VEC> gu = unpack<T, VEC>(g[u]);
 #pragma unroll
-      for (int u = 0; u < kPmaUnroll; ++u) {
-        const int pos = base + j + u;
-        if (j + u < n) {
-          while (pos >= cur_end) flush();
-          const float p = __expf(a_s - st[u].x);
-          const FVec<VEC> gu = unpack<T, VEC>(g[u]);
+        for (int k = 0; k < VEC; ++k) gv[k] = fmaf(p, gu.v[k], gv[k]);
+        D = fmaf(p, st[u].y, D);
+      },
+      [&] {
+        const FVec<VEC> vown = unpack<T, VEC>(v_raw[0]);
+        const int orow = s.bcast(rid, min(s.cur_row - s.r_begin, LPR - 1));
+        float S = 0.f;
+        if (active) {
+          FVec<VEC> r;
 #pragma unroll
-          for (int k = 0; k < VEC; ++k) gv[k] = fmaf(p, gu.v[k], gv[k]);
-          D = fmaf(p, st[u].y, D);
+          for (int k = 0; k < VEC; ++k) { r.v[k] = gv[k]; S = fmaf(vown.v[k], gv[k], S); gv[k] = 0.f; }
+          store_vec<T, VEC>(gV + static_cast<int64_t>(orow) * ldgv + c0, r);
         }
-      }
-    }
-  }
-  while (cur_row < r_end) flush();
+        S = head_group_reduce<LPR>(S, li, grp_end);
+        if (active && q == 0)
+          galpha[static_cast<int64_t>(orow) * H + h] = (a_raw[0] > 0.f ? 1.f : slope) * (S - D);
+        D = 0.f;
+#pragma unroll
+        for (int i = 0; i + 1 < R; ++i) { a_raw[i] = a_raw[i + 1]; v_raw[i] = v_raw[i + 1]; }
+        a_s = leaky_relu(a_raw[0], slope);
+      });
 }
 
-#define ALLSET_PMA_DISPATCH_T(KERNEL, T, WIDE, GRID, ST, ...)                                \
-  do {                                                                                       \
-    if (wide_ok) {                                                                           \
-      switch (pick_lpr(d, WIDE)) {                                                           \
-        case 8:  KERNEL<T, WIDE, 8><<<GRID, kBlock, 0, ST>>>(__VA_ARGS__); break;            \
-        case 16: KERNEL<T, WIDE, 16><<<GRID, kBlock, 0, ST>>>(__VA_ARGS__); break;           \
-        case 32: KERNEL<T, WIDE, 32><<<GRID, kBlock, 0, ST>>>(__VA_ARGS__); break;           \
-        default: KERNEL<T, WIDE, 64><<<GRID, kBlock, 0, ST>>>(__VA_ARGS__); break;           \
-      }                                                                                      \
-    } else {                                                                                 \
-      KERNEL<T, 1, 64><<<GRID, kBlock, 0, ST>>>(__VA_ARGS__);                                \
-    }                                                                                        \
-  } while (0)
+// the storage type and the elements of its 16-byte packet as compile-time values: f(T{}, IntC<WIDE>{})
+template <class F>
+static void with_storage(int dtype, F&& f) {
+  if (dtype == ALLSET_F32) f(float{}, IntC<4>{});
+  else f(bf16_t{}, IntC<8>{});
+}
 
 static int check_pma_dims(const char* who, int64_t n_a, int64_t n_b, int64_t H, int64_t C) {
   ALLSET_REQUIRE(n_a >= 0 && n_b >= 0, "%s: negative size", who);
@@ -657,30 +596,25 @@ static int pma_fwd_impl(int dtype, int variant, int64_t nnz_hint, const int32_t*
     return ALLSET_ERR_UNSUPPORTED;
   }
   if (flat_ok && (variant == 2 || (variant == 0 && nnz_hint >= 0 && static_cast<double>(nnz_hint) < 6.0 * static_cast<double>(n_t)))) {
-    const int lpr = pick_lpr(d, wide);
-    const int64_t rows_per_block = static_cast<int64_t>(kWavesPerBlock) * (kWave / lpr) * kPmaFlatRows;
-    const unsigned fgrid = static_cast<unsigned>((n_t + rows_per_block - 1) / rows_per_block);
-#define ALLSET_PMA_FLAT(T, WIDE, LPRV)                                                                              \
-  pma_fwd_flat_kernel<T, WIDE, LPRV><<<fgrid, kBlock, 0, st>>>(rowptr, col, alpha, lda, static_cast<const T*>(V), ldv, slope, \
-                                                               static_cast<T*>(out), ldo, m, l, static_cast<int>(n_t),   \
-                                                               static_cast<int>(H), static_cast<int>(C), variant == 2 ? row_order : nullptr)
-    if (dtype == ALLSET_F32) {
-      switch (lpr) { case 8: ALLSET_PMA_FLAT(float, 4, 8); break; case 16: ALLSET_PMA_FLAT(float, 4, 16); break;
-                     case 32: ALLSET_PMA_FLAT(float, 4, 32); break; default: ALLSET_PMA_FLAT(float, 4, 64); break; }
-    } else {
-      switch (lpr) { case 8: ALLSET_PMA_FLAT(bf16_t, 8, 8); break; case 16: ALLSET_PMA_FLAT(bf16_t, 8, 16); break;
-                     case 32: ALLSET_PMA_FLAT(bf16_t, 8, 32); break; default: ALLSET_PMA_FLAT(bf16_t, 8, 64); break; }
-    }
-#undef ALLSET_PMA_FLAT
+    with_storage(dtype, [&](auto tag, auto wd) {
+      using T = decltype(tag);
+      with_lpr(pick_lpr(d, wd()), [&](auto lpr) {
+        pma_fwd_flat_kernel<T, wd(), lpr()><<<flat_grid<lpr()>(n_t), kBlock, 0, st>>>(
+            rowptr, col, alpha, lda, static_cast<const T*>(V), ldv, slope, static_cast<T*>(out), ldo, m, l, static_cast<int>(n_t),
+            static_cast<int>(H), static_cast<int>(C), variant == 2 ? row_order : nullptr);
+      });
+    });
     ALLSET_LAUNCH_CHECK();
     return ALLSET_OK;
   }
-  if (dtype == ALLSET_F32)
-    ALLSET_PMA_DISPATCH_T(pma_fwd_kernel, float, 4, row_grid(n_t), st, rowptr, col, alpha, lda, static_cast<const float*>(V), ldv, slope,
-                          static_cast<float*>(out), ldo, m, l, static_cast<int>(n_t), static_cast<int>(H), static_cast<int>(C), row_order);
-  else
-    ALLSET_PMA_DISPATCH_T(pma_fwd_kernel, bf16_t, 8, row_grid(n_t), st, rowptr, col, alpha, lda, static_cast<const bf16_t*>(V), ldv, slope,
-                          static_cast<bf16_t*>(out), ldo, m, l, static_cast<int>(n_t), static_cast<int>(H), static_cast<int>(C), row_order);
+  with_storage(dtype, [&](auto tag, auto wd) {
+    using T = decltype(tag);
+    with_vec_lpr<wd()>(wide_ok, d, [&](auto vec, auto lpr) {
+      pma_fwd_kernel<T, vec(), lpr()><<<row_grid(n_t), kBlock, 0, st>>>(
+          rowptr, col, alpha, lda, static_cast<const T*>(V), ldv, slope, static_cast<T*>(out), ldo, m, l, static_cast<int>(n_t),
+          static_cast<int>(H), static_cast<int>(C), row_order);
+    });
+  });
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }
@@ -728,33 +662,27 @@ static int pma_bwd_stats_impl(int dtype, const void* out, int64_t ldo, const voi
   const bool wide_ok = (C % wide == 0) && (ldo % wide == 0) && (ldg % wide == 0) && aligned16(out) && aligned16(gout);
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (wide_ok && d <= 64 * wide) {        // the whole row in one chunk: slot-per-row kernel, no LDS
-    const int lpr = pick_lpr(d, wide);
-    const int64_t rows_per_block = static_cast<int64_t>(kWavesPerBlock) * (kWave / lpr) * kStatsRows;
-    const unsigned fgrid = static_cast<unsigned>((n_t + rows_per_block - 1) / rows_per_block);
-#define ALLSET_PMA_STATS(T, WIDE, LPRV)                                                                               \
-  pma_bwd_stats_flat_kernel<T, WIDE, LPRV><<<fgrid, kBlock, 0, st>>>(static_cast<const T*>(out), ldo,                   \
-                                                                     static_cast<const T*>(gout), ldg, m, l, stats, lds, \
-                                                                     static_cast<int>(n_t), static_cast<int>(H),        \
-                                                                     static_cast<int>(C))
-    if (dtype == ALLSET_F32) {
-      switch (lpr) { case 8: ALLSET_PMA_STATS(float, 4, 8); break; case 16: ALLSET_PMA_STATS(float, 4, 16); break;
-                     case 32: ALLSET_PMA_STATS(float, 4, 32); break; default: ALLSET_PMA_STATS(float, 4, 64); break; }
-    } else {
-      switch (lpr) { case 8: ALLSET_PMA_STATS(bf16_t, 8, 8); break; case 16: ALLSET_PMA_STATS(bf16_t, 8, 16); break;
-                     case 32: ALLSET_PMA_STATS(bf16_t, 8, 32); break; default: ALLSET_PMA_STATS(bf16_t, 8, 64); break; }
-    }
-#undef ALLSET_PMA_STATS
+    with_storage(dtype, [&](auto tag, auto wd) {
+      using T = decltype(tag);
+      with_lpr(pick_lpr(d, wd()), [&](auto lpr) {
+        const int64_t rows_per_block = static_cast<int64_t>(kWavesPerBlock) * (kWave / lpr()) * kStatsRows;
+        const unsigned fgrid = static_cast<unsigned>((n_t + rows_per_block - 1) / rows_per_block);
+        pma_bwd_stats_flat_kernel<T, wd(), lpr()><<<fgrid, kBlock, 0, st>>>(
+            static_cast<const T*>(out), ldo, static_cast<const T*>(gout), ldg, m, l, stats, lds, static_cast<int>(n_t),
+            static_cast<int>(H), static_cast<int>(C));
+      });
+    });
     ALLSET_LAUNCH_CHECK();
     return ALLSET_OK;
   }
-  if (dtype == ALLSET_F32)
-    ALLSET_PMA_DISPATCH_T(pma_bwd_stats_kernel, float, 4, row_grid(n_t), st, static_cast<const float*>(out), ldo,
-                          static_cast<const float*>(gout), ldg, m, l, stats, lds, static_cast<int>(n_t), static_cast<int>(H),
-                          static_cast<int>(C));
-  else
-    ALLSET_PMA_DISPATCH_T(pma_bwd_stats_kernel, bf16_t, 8, row_grid(n_t), st, static_cast<const bf16_t*>(out), ldo,
-                          static_cast<const bf16_t*>(gout), ldg, m, l, stats, lds, static_cast<int>(n_t), static_cast<int>(H),
-                          static_cast<int>(C));
+  with_storage(dtype, [&](auto tag, auto wd) {
+    using T = decltype(tag);
+    with_vec_lpr<wd()>(wide_ok, d, [&](auto vec, auto lpr) {
+      pma_bwd_stats_kernel<T, vec(), lpr()><<<row_grid(n_t), kBlock, 0, st>>>(
+          static_cast<const T*>(out), ldo, static_cast<const T*>(gout), ldg, m, l, stats, lds, static_cast<int>(n_t),
+          static_cast<int>(H), static_cast<int>(C));
+    });
+  });
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }
@@ -813,33 +741,26 @@ static int pma_bwd_src_impl(int dtype, int variant, int64_t nnz_hint, const int3
     return ALLSET_ERR_UNSUPPORTED;
   }
   if (flat_ok && (variant == 2 || (variant == 0 && nnz_hint >= 0 && static_cast<double>(nnz_hint) < 6.0 * static_cast<double>(n_s)))) {
-    const int lpr = pick_lpr(d, wide);
-    const int64_t rows_per_block = static_cast<int64_t>(kWavesPerBlock) * (kWave / lpr) * kPmaFlatRows;
-    const unsigned fgrid = static_cast<unsigned>((n_s + rows_per_block - 1) / rows_per_block);
-#define ALLSET_PMA_FLATB(T, WIDE, LPRV)                                                                                  \
-  pma_bwd_src_flat_kernel<T, WIDE, LPRV><<<fgrid, kBlock, 0, st>>>(rowptrT, colT, alpha, static_cast<const T*>(V), ldv,   \
-                                                                   static_cast<const T*>(gout), ldg, stats, lds, slope,    \
-                                                                   static_cast<T*>(gV), ldgv, galpha, static_cast<int>(n_s), \
-                                                                   static_cast<int>(H), static_cast<int>(C), variant == 2 ? row_order : nullptr)
-    if (dtype == ALLSET_F32) {
-      switch (lpr) { case 8: ALLSET_PMA_FLATB(float, 4, 8); break; case 16: ALLSET_PMA_FLATB(float, 4, 16); break;
-                     case 32: ALLSET_PMA_FLATB(float, 4, 32); break; default: ALLSET_PMA_FLATB(float, 4, 64); break; }
-    } else {
-      switch (lpr) { case 8: ALLSET_PMA_FLATB(bf16_t, 8, 8); break; case 16: ALLSET_PMA_FLATB(bf16_t, 8, 16); break;
-                     case 32: ALLSET_PMA_FLATB(bf16_t, 8, 32); break; default: ALLSET_PMA_FLATB(bf16_t, 8, 64); break; }
-    }
-#undef ALLSET_PMA_FLATB
+    with_storage(dtype, [&](auto tag, auto wd) {
+      using T = decltype(tag);
+      with_lpr(pick_lpr(d, wd()), [&](auto lpr) {
+        pma_bwd_src_flat_kernel<T, wd(), lpr()><<<flat_grid<lpr()>(n_s), kBlock, 0, st>>>(
+            rowptrT, colT, alpha, static_cast<const T*>(V), ldv, static_cast<const T*>(gout), ldg, stats, lds, slope,
+            static_cast<T*>(gV), ldgv, galpha, static_cast<int>(n_s), static_cast<int>(H), static_cast<int>(C),
+            variant == 2 ? row_order : nullptr);
+      });
+    });
     ALLSET_LAUNCH_CHECK();
     return ALLSET_OK;
   }
-  if (dtype == ALLSET_F32)
-    ALLSET_PMA_DISPATCH_T(pma_bwd_src_kernel, float, 4, row_grid(n_s), st, rowptrT, colT, alpha, static_cast<const float*>(V), ldv,
-                          static_cast<const float*>(gout), ldg, stats, lds, slope, static_cast<float*>(gV), ldgv, galpha,
-                          static_cast<int>(n_s), static_cast<int>(H), static_cast<int>(C), row_order);
-  else
-    ALLSET_PMA_DISPATCH_T(pma_bwd_src_kernel, bf16_t, 8, row_grid(n_s), st, rowptrT, colT, alpha, static_cast<const bf16_t*>(V), ldv,
-                          static_cast<const bf16_t*>(gout), ldg, stats, lds, slope, static_cast<bf16_t*>(gV), ldgv, galpha,
-                          static_cast<int>(n_s), static_cast<int>(H), static_cast<int>(C), row_order);
+  with_storage(dtype, [&](auto tag, auto wd) {
+    using T = decltype(tag);
+    with_vec_lpr<wd()>(wide_ok, d, [&](auto vec, auto lpr) {
+      pma_bwd_src_kernel<T, vec(), lpr()><<<row_grid(n_s), kBlock, 0, st>>>(
+          rowptrT, colT, alpha, static_cast<const T*>(V), ldv, static_cast<const T*>(gout), ldg, stats, lds, slope,
+          static_cast<T*>(gV), ldgv, galpha, static_cast<int>(n_s), static_cast<int>(H), static_cast<int>(C), row_order);
+    });
+  });
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }

@@ -15,6 +15,7 @@
 // HBM-bound by construction: algorithmic bytes per launch are nnz*(4*d + 4) + (n_t+1)*4 + n_t*4*d
 // (SURVEY.md section 8(d3)); VALU work is one FMA per gathered element.
 #include "common.h"
+#include "flat_rows.h"
 #include "mfma.h"     // dpp_row
 
 namespace allset {
@@ -129,88 +130,56 @@ __global__ __launch_bounds__(kBlock) void segreduce_kernel(
 }
 
 
-// ---- short-row variant (sum / mean, single column chunk): several consecutive CSR rows per LPR-lane group ----------
-// One wave per row spends a wave launch and three dependent round trips (rowptr -> col -> gather) on every row; at
-// degree <= 4 that overhead, not bandwidth, sets the time (profiles: 4M rows take ~1.6 ms whether they hold 1 or 4
-// incidences).  Here each LPR-lane group ("slot") owns kFlatRows consecutive rows and walks their incidences as ONE
-// stream: the rows' rowptr entries arrive in one load (lane i holds rowptr[r0+i]), the column ids of consecutive rows
-// are contiguous in the CSR and arrive LPR at a time, the gathers of a batch are in flight together regardless of row
-// boundaries, and a row is flushed (one coalesced store) whenever the stream crosses its end.  Slots never combine.
-constexpr int kFlatRows = 7;       // rows per slot; kFlatRows + 1 rowptr entries must fit in the smallest slot (8 lanes)
-
+// ---- short-row variant (flat_rows.h): sum / mean, single column chunk ------------------------------------------------
 template <typename T, int VEC, int LPR, bool WEIGHTED>
 __global__ __launch_bounds__(kBlock) void segreduce_flat_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ w,
     const T* __restrict__ x, int64_t ldx, T* __restrict__ out, int64_t ldo, int n_t, int d, int mean) {
-  constexpr int NS = kWave / LPR;
-  const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
-  const int lane = lane_id();
-  const int slot = lane / LPR, li = lane % LPR;
-  const int lane0 = slot * LPR;                                   // first lane of this slot
-  const int64_t slot_global = (static_cast<int64_t>(blk) * kWavesPerBlock + (threadIdx.x >> 6)) * NS + slot;
-  const int64_t r_begin64 = slot_global * kFlatRows;
-  if (r_begin64 - static_cast<int64_t>(slot) * kFlatRows >= n_t) return;      // whole wave beyond the last row
-  const int r_begin = static_cast<int>(min(r_begin64, static_cast<int64_t>(n_t)));
-  const int r_end = min(r_begin + kFlatRows, n_t);
-  const int c0 = li * VEC;
+  FlatSlot<LPR> s;
+  if (s.wave_beyond(n_t)) return;
+  s.open(rowptr, n_t);
+  const int c0 = s.li * VEC;
   const bool active = c0 < d;
-  // lane i of the slot holds rowptr[r_begin + i], i = 0 .. r_end - r_begin
-  const int rp = (li <= r_end - r_begin) ? rowptr[r_begin + li] : 0;
-  const int q0 = __shfl(rp, lane0);
-  const int q_end = __shfl(rp, lane0 + (r_end - r_begin));
-
-  int cur_row = r_begin;
-  int cur_start = q0;
-  int cur_end = (r_begin < r_end) ? __shfl(rp, lane0 + 1) : q0;
+  int cur_start = s.q0;              // of the current row: the mean's count is cur_end - cur_start
   float acc[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+  int my_col = 0;
+  float my_w = 0.f;
+  Raw<T, VEC> raw[kUnroll];
+  float ww[kUnroll];
 
-  auto flush = [&]() {       // store the finished row and step to the next one (slot-uniform control flow)
-    if (active) {
-      const float scale = mean ? 1.f / static_cast<float>(max(cur_end - cur_start, 1)) : 1.f;
-      FVec<VEC> r;
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) { r.v[k] = acc[k] * scale; acc[k] = 0.f; }
-      store_vec<T, VEC>(out + static_cast<int64_t>(cur_row) * ldo + c0, r);
-    }
-    ++cur_row;
-    cur_start = cur_end;
-    cur_end = __shfl(rp, lane0 + min(cur_row - r_begin + 1, LPR - 1));
-  };
-
-  for (int base = q0; base < q_end; base += LPR) {
-    const int n = min(LPR, q_end - base);
-    int my_col = 0;
-    float my_w = 0.f;
-    if (li < n) {
-      my_col = col[base + li];
-      if constexpr (WEIGHTED) my_w = w[base + li];
-    }
-    for (int j = 0; j < n; j += kUnroll) {
-      Raw<T, VEC> raw[kUnroll];
-      float ww[kUnroll];
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int jj = j + u;
-        const int src = __shfl(my_col, lane0 + (jj & (LPR - 1)));
-        if constexpr (WEIGHTED) ww[u] = __shfl(my_w, lane0 + (jj & (LPR - 1))); else ww[u] = 1.f;
-        if (jj < n && active) raw[u] = load_raw<T, VEC>(x + static_cast<int64_t>(src) * ldx + c0);
-        else raw[u] = zero_raw<T, VEC>();
-      }
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int pos = base + j + u;
-        if (j + u < n) {
-          while (pos >= cur_end) flush();                          // also steps over empty rows
-          const FVec<VEC> v = unpack<T, VEC>(raw[u]);
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) acc[k] = fmaf(ww[u], v.v[k], acc[k]);
+  flat_walk<kUnroll>(
+      s, active,
+      [&](int base, int n) {
+        my_col = 0;
+        my_w = 0.f;
+        if (s.li < n) {
+          my_col = col[base + s.li];
+          if constexpr (WEIGHTED) my_w = w[base + s.li];
         }
-      }
-    }
-  }
-  while (cur_row < r_end) flush();                                 // last row and trailing empty rows
+      },
+      [&](int u, int jj, bool ok) {
+        const int src = s.bcast(my_col, jj);
+        if constexpr (WEIGHTED) ww[u] = s.bcast(my_w, jj); else ww[u] = 1.f;
+        if (ok) raw[u] = load_raw<T, VEC>(x + static_cast<int64_t>(src) * ldx + c0);
+        else raw[u] = zero_raw<T, VEC>();
+      },
+      [&](int u) {
+        const FVec<VEC> v = unpack<T, VEC>(raw[u]);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[k] = fmaf(ww[u], v.v[k], acc[k]);
+      },
+      [&] {
+        if (active) {
+          const float scale = mean ? 1.f / static_cast<float>(max(s.cur_end - cur_start, 1)) : 1.f;
+          FVec<VEC> r;
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) { r.v[k] = acc[k] * scale; acc[k] = 0.f; }
+          store_vec<T, VEC>(out + static_cast<int64_t>(s.cur_row) * ldo + c0, r);
+        }
+        cur_start = s.cur_end;
+      });
 }
 
 // gx[s,c] = sum_{j in T-row s} [argext[colT[j],c] == posT[j]] * wT[j] * gout[colT[j],c]
@@ -257,7 +226,7 @@ __global__ __launch_bounds__(kBlock) void segmax_bwd_kernel(
           const int ps = __shfl(my_pos, jj & (kWave - 1));
           pos[u] = ok ? ps : -2;                                      // -2 never equals an arg entry (>= -1)
           ww[u] = __shfl(my_w, jj & (kWave - 1));
-          if (ok) {
+          if (jj < n && active) {
             g[u] = load_vec<float, VEC>(gout + static_cast<int64_t>(t) * ldg + c0);
             load_vec_i32<VEC>(argext + static_cast<int64_t>(t) * d + c0, a[u]);
           } else {
@@ -402,26 +371,15 @@ static void launch_segreduce(int mode_ext, bool weighted, unsigned grid, hipStre
   }
 }
 
-template <typename T, int VEC, int LPR>
-static void launch_flat(bool weighted, hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* w,
-                        const T* x, int64_t ldx, T* out, int64_t ldo, int n_t, int d, int mean) {
-  constexpr int NS = kWave / LPR;
-  const int64_t rows_per_block = static_cast<int64_t>(kWavesPerBlock) * NS * kFlatRows;
-  const unsigned grid = static_cast<unsigned>((n_t + rows_per_block - 1) / rows_per_block);
-  if (weighted) segreduce_flat_kernel<T, VEC, LPR, true><<<grid, kBlock, 0, st>>>(rowptr, col, w, x, ldx, out, ldo, n_t, d, mean);
-  else          segreduce_flat_kernel<T, VEC, LPR, false><<<grid, kBlock, 0, st>>>(rowptr, col, w, x, ldx, out, ldo, n_t, d, mean);
-}
-
 // short-row path: sum/mean, 16-byte packets, the whole row in one column chunk
 template <typename T, int WIDE>
 static void dispatch_flat(bool weighted, hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* w,
                           const T* x, int64_t ldx, T* out, int64_t ldo, int n_t, int d, int mean) {
-  switch (pick_lpr(d, WIDE)) {
-    case 8:  launch_flat<T, WIDE, 8>(weighted, st, rowptr, col, w, x, ldx, out, ldo, n_t, d, mean); break;
-    case 16: launch_flat<T, WIDE, 16>(weighted, st, rowptr, col, w, x, ldx, out, ldo, n_t, d, mean); break;
-    case 32: launch_flat<T, WIDE, 32>(weighted, st, rowptr, col, w, x, ldx, out, ldo, n_t, d, mean); break;
-    default: launch_flat<T, WIDE, 64>(weighted, st, rowptr, col, w, x, ldx, out, ldo, n_t, d, mean); break;
-  }
+  with_lpr(pick_lpr(d, WIDE), [&](auto lpr) {
+    const unsigned grid = flat_grid<lpr()>(n_t);
+    if (weighted) segreduce_flat_kernel<T, WIDE, lpr(), true><<<grid, kBlock, 0, st>>>(rowptr, col, w, x, ldx, out, ldo, n_t, d, mean);
+    else          segreduce_flat_kernel<T, WIDE, lpr(), false><<<grid, kBlock, 0, st>>>(rowptr, col, w, x, ldx, out, ldo, n_t, d, mean);
+  });
 }
 
 template <typename T, int WIDE>
@@ -429,16 +387,9 @@ static void dispatch_segreduce(bool wide_ok, int mode_ext, bool weighted, unsign
                                const int32_t* rowptr, const int32_t* col, const float* w, const T* x, int64_t ldx,
                                T* out, int64_t ldo, int32_t* argext, int n_t, int d, int mean, float sign,
                                const int32_t* row_order) {
-  if (wide_ok) {
-    switch (pick_lpr(d, WIDE, ALLSET_SEG_MAX_LPR)) {
-      case 8:  launch_segreduce<T, WIDE, 8>(mode_ext, weighted, grid, st, rowptr, col, w, x, ldx, out, ldo, argext, n_t, d, mean, sign, row_order); break;
-      case 16: launch_segreduce<T, WIDE, 16>(mode_ext, weighted, grid, st, rowptr, col, w, x, ldx, out, ldo, argext, n_t, d, mean, sign, row_order); break;
-      case 32: launch_segreduce<T, WIDE, 32>(mode_ext, weighted, grid, st, rowptr, col, w, x, ldx, out, ldo, argext, n_t, d, mean, sign, row_order); break;
-      default: launch_segreduce<T, WIDE, 64>(mode_ext, weighted, grid, st, rowptr, col, w, x, ldx, out, ldo, argext, n_t, d, mean, sign, row_order); break;
-    }
-  } else {
-    launch_segreduce<T, 1, 64>(mode_ext, weighted, grid, st, rowptr, col, w, x, ldx, out, ldo, argext, n_t, d, mean, sign, row_order);
-  }
+  with_vec_lpr<WIDE>(wide_ok, d, ALLSET_SEG_MAX_LPR, [&](auto vec, auto lpr) {
+    launch_segreduce<T, vec(), lpr()>(mode_ext, weighted, grid, st, rowptr, col, w, x, ldx, out, ldo, argext, n_t, d, mean, sign, row_order);
+  });
 }
 
 template <int VEC, int LPR>
@@ -539,16 +490,9 @@ extern "C" int allset_segmax_bwd(const int32_t* rowptrT, const int32_t* colT, co
   const bool vec4 = (d % 4 == 0) && (ldg % 4 == 0) && (ldx % 4 == 0) && aligned16(gout) && aligned16(gx);
   const unsigned grid = row_grid(n_s);
   const int ns = static_cast<int>(n_s), di = static_cast<int>(d);
-  if (vec4) {
-    switch (pick_lpr(d)) {
-      case 8:  launch_segmax_bwd<4, 8>(wT != nullptr, grid, st, rowptrT, colT, posT, wT, argext, gout, ldg, gx, ldx, ns, di); break;
-      case 16: launch_segmax_bwd<4, 16>(wT != nullptr, grid, st, rowptrT, colT, posT, wT, argext, gout, ldg, gx, ldx, ns, di); break;
-      case 32: launch_segmax_bwd<4, 32>(wT != nullptr, grid, st, rowptrT, colT, posT, wT, argext, gout, ldg, gx, ldx, ns, di); break;
-      default: launch_segmax_bwd<4, 64>(wT != nullptr, grid, st, rowptrT, colT, posT, wT, argext, gout, ldg, gx, ldx, ns, di); break;
-    }
-  } else {
-    launch_segmax_bwd<1, 64>(wT != nullptr, grid, st, rowptrT, colT, posT, wT, argext, gout, ldg, gx, ldx, ns, di);
-  }
+  with_vec_lpr<4>(vec4, d, [&](auto vec, auto lpr) {
+    launch_segmax_bwd<vec(), lpr()>(wT != nullptr, grid, st, rowptrT, colT, posT, wT, argext, gout, ldg, gx, ldx, ns, di);
+  });
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }
@@ -572,24 +516,16 @@ extern "C" int allset_sddmm_rowdot(int reduce, const int32_t* rowptr, const int3
   // 16-byte path: one column block (d <= 256), aligned rows; anything else takes the scalar kernel
   const bool vec4 = (d % 4 == 0) && d <= 256 && (ldx % 4 == 0) && (ldg % 4 == 0) && aligned16(x) && aligned16(gout) &&
                     (!ext || aligned16(argext));
-#define ALLSET_SDDMM(LPR_)                                                                                                   \
-  do {                                                                                                                       \
-    if (ext) sddmm_rowdot_vec_kernel<LPR_, kModeExt><<<grid, kBlock, 0, st>>>(rowptr, col, x, ldx, gout, ldg, argext, gw, nt, di, mean); \
-    else     sddmm_rowdot_vec_kernel<LPR_, kModeSum><<<grid, kBlock, 0, st>>>(rowptr, col, x, ldx, gout, ldg, nullptr, gw, nt, di, mean); \
-  } while (0)
   if (vec4) {
-    switch (pick_lpr(d)) {
-      case 8:  ALLSET_SDDMM(8); break;
-      case 16: ALLSET_SDDMM(16); break;
-      case 32: ALLSET_SDDMM(32); break;
-      default: ALLSET_SDDMM(64); break;
-    }
+    with_lpr(pick_lpr(d), [&](auto lpr) {
+      if (ext) sddmm_rowdot_vec_kernel<lpr(), kModeExt><<<grid, kBlock, 0, st>>>(rowptr, col, x, ldx, gout, ldg, argext, gw, nt, di, mean);
+      else     sddmm_rowdot_vec_kernel<lpr(), kModeSum><<<grid, kBlock, 0, st>>>(rowptr, col, x, ldx, gout, ldg, nullptr, gw, nt, di, mean);
+    });
   } else if (ext) {
     sddmm_rowdot_kernel<kModeExt><<<grid, kBlock, 0, st>>>(rowptr, col, x, ldx, gout, ldg, argext, gw, nt, di, mean);
   } else {
     sddmm_rowdot_kernel<kModeSum><<<grid, kBlock, 0, st>>>(rowptr, col, x, ldx, gout, ldg, nullptr, gw, nt, di, mean);
   }
-#undef ALLSET_SDDMM
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }

@@ -7,8 +7,7 @@
 // a = 0 and Xi = alpha * x0.  The backward needs no kernel of its own: with r'[v] = (1 - alpha) * degV[v] * t[v],
 // gXe = allset_hconv_fwd over the transposed CSR with r = r', and gx0 = alpha * gXi.
 //
-// Mapping: hconv.hip's (that file and its instantiations are left as they are; the skeleton is repeated here without the
-// per-incidence scale and with the row tail in place of the epilogue):
+// Mapping: hconv.hip's, without the per-incidence scale and with the row tail in place of the epilogue:
 //   * one wavefront OWNS a whole output row: LPR lanes x 16 B per feature row, NS = 64 / LPR hyperedge rows gathered per load; widths
 //     above 256 take two 16-byte packets per lane (NCH = 2, LPR = 64), so d <= 512 stays in registers and the row norm is a
 //     cross-lane reduction -- no second pass over the row, no atomics;
@@ -22,12 +21,12 @@
 // Algorithmic bytes per launch: those of allset_hconv_fwd without r, nnz * (4d + 4) + (n_t + 1) * 4 + n_t * 4d, plus one read of
 // x0, n_t * 4d (and n_t * 4 each for degV and t_out).
 #include "common.h"
+#include "flat_rows.h"
 
 namespace allset {
 namespace unigcn {
 
 constexpr int kMaxWidth = 512;
-constexpr int kFlatRows = 7;          // rows per lane group in the short-row kernel (kFlatRows + 1 rowptr entries fit in 8 lanes)
 constexpr int kFlatUnroll = 8;
 
 struct Tail {
@@ -133,68 +132,40 @@ __global__ __launch_bounds__(kBlock) void unigcn_hop_kernel(
   finish_row<LPR, NCH>(tl, row, li, d, acc, xi, ldxi, slot == 0);
 }
 
-// short-row variant: each LPR-lane group owns kFlatRows consecutive rows and walks their incidences as one stream
-// (hconv_flat_kernel's scheme); single column chunk (d <= LPR * 4).  Everything that steers the walk is uniform within a lane
-// group, so the group's lanes reach every flush together and the norm's butterfly stays inside the group.
+// short-row variant (flat_rows.h); single column chunk (d <= LPR * 4).  Every lane of the slot calls finish_row: the norm's
+// butterfly stays inside the slot.
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void unigcn_flat_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ xe, int64_t ldxe, Tail tl,
     float* __restrict__ xi, int64_t ldxi, int n_t, int d) {
-  constexpr int NS = kWave / LPR;
-  const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
-  const int lane = lane_id();
-  const int slot = lane / LPR, li = lane % LPR;
-  const int lane0 = slot * LPR;
-  const int64_t slot_global = (static_cast<int64_t>(blk) * kWavesPerBlock + (threadIdx.x >> 6)) * NS + slot;
-  const int64_t r_begin64 = slot_global * kFlatRows;
-  if (r_begin64 - static_cast<int64_t>(slot) * kFlatRows >= n_t) return;      // whole wave beyond the last row
-  const int r_begin = static_cast<int>(min(r_begin64, static_cast<int64_t>(n_t)));
-  const int r_end = min(r_begin + kFlatRows, n_t);
-  const int c0 = li * 4;
+  FlatSlot<LPR> s;
+  if (s.wave_beyond(n_t)) return;
+  s.open(rowptr, n_t);
+  const int c0 = s.li * 4;
   const bool active = c0 < d;
-  const int rp = (li <= r_end - r_begin) ? rowptr[r_begin + li] : 0;
-  const int q0 = __shfl(rp, lane0);
-  const int q_end = __shfl(rp, lane0 + (r_end - r_begin));
-
-  int cur_row = r_begin;
-  int cur_end = (r_begin < r_end) ? __shfl(rp, lane0 + 1) : q0;
   float acc[1][4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) acc[0][k] = 0.f;
+  int my_col = 0;
+  Raw<float, 4> raw[kFlatUnroll];
 
-  auto flush = [&]() {
-    finish_row<LPR, 1>(tl, cur_row, li, d, acc, xi, ldxi, true);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[0][k] = 0.f;
-    ++cur_row;
-    cur_end = __shfl(rp, lane0 + min(cur_row - r_begin + 1, LPR - 1));
-  };
-
-  for (int base = q0; base < q_end; base += LPR) {
-    const int n = min(LPR, q_end - base);
-    const int my_col = li < n ? col[base + li] : 0;
-    for (int j = 0; j < n; j += kFlatUnroll) {
-      Raw<float, 4> raw[kFlatUnroll];
-#pragma unroll
-      for (int u = 0; u < kFlatUnroll; ++u) {
-        const int jj = j + u;
-        const int src = __shfl(my_col, lane0 + (jj & (LPR - 1)));
-        if (jj < n && active) raw[u] = load_raw<float, 4>(xe + static_cast<int64_t>(src) * ldxe + c0);
+  flat_walk<kFlatUnroll>(
+      s, active, [&](int base, int n) { my_col = s.li < n ? col[base + s.li] : 0; },
+      [&](int u, int jj, bool ok) {
+        const int src = s.bcast(my_col, jj);
+        if (ok) raw[u] = load_raw<float, 4>(xe + static_cast<int64_t>(src) * ldxe + c0);
         else raw[u] = zero_raw<float, 4>();
-      }
+      },
+      [&](int u) {
+        const FVec<4> v = unpack<float, 4>(raw[u]);
 #pragma unroll
-      for (int u = 0; u < kFlatUnroll; ++u) {
-        const int pos = base + j + u;
-        if (j + u < n) {
-          while (pos >= cur_end) flush();                          // also steps over empty rows
-          const FVec<4> v = unpack<float, 4>(raw[u]);
+        for (int k = 0; k < 4; ++k) acc[0][k] += v.v[k];
+      },
+      [&] {
+        finish_row<LPR, 1>(tl, s.cur_row, s.li, d, acc, xi, ldxi, true);
 #pragma unroll
-          for (int k = 0; k < 4; ++k) acc[0][k] += v.v[k];
-        }
-      }
-    }
-  }
-  while (cur_row < r_end) flush();                                 // last row and trailing empty rows
+        for (int k = 0; k < 4; ++k) acc[0][k] = 0.f;
+      });
 }
 
 template <int LPR, int NCH>
@@ -202,16 +173,6 @@ static void launch_rows(hipStream_t st, const int32_t* rowptr, const int32_t* co
                         float* xi, int64_t ldxi, int n_t, int d, const int32_t* row_order) {
   const unsigned grid = static_cast<unsigned>((static_cast<int64_t>(n_t) + kWavesPerBlock - 1) / kWavesPerBlock);
   unigcn_hop_kernel<LPR, NCH><<<grid, kBlock, 0, st>>>(rowptr, col, xe, ldxe, tl, xi, ldxi, n_t, d, row_order);
-}
-
-template <int LPR>
-static void launch_flat(hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* xe, int64_t ldxe, const Tail& tl,
-                        float* xi, int64_t ldxi, int n_t, int d) {
-  constexpr int NS = kWave / LPR;
-  const int64_t groups = (static_cast<int64_t>(n_t) + kFlatRows - 1) / kFlatRows;
-  const int64_t waves = (groups + NS - 1) / NS;
-  const unsigned grid = static_cast<unsigned>((waves + kWavesPerBlock - 1) / kWavesPerBlock);
-  unigcn_flat_kernel<LPR><<<grid, kBlock, 0, st>>>(rowptr, col, xe, ldxe, tl, xi, ldxi, n_t, d);
 }
 
 }  // namespace unigcn
@@ -254,21 +215,13 @@ extern "C" int allset_unigcn_hop_fwd(int variant, int64_t nnz, const int32_t* ro
   const bool use_flat = d <= 256 && (variant == 2 || (variant == 0 && n_t > kFlatMinRows &&
                                                       static_cast<double>(nnz) < kFlatMaxMeanDegree * static_cast<double>(n_t)));
   if (use_flat) {
-    switch (pick_lpr(d)) {
-      case 8:  launch_flat<8>(st, rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di); break;
-      case 16: launch_flat<16>(st, rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di); break;
-      case 32: launch_flat<32>(st, rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di); break;
-      default: launch_flat<64>(st, rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di); break;
-    }
+    with_lpr(pick_lpr(d), [&](auto lpr) {
+      unigcn_flat_kernel<lpr()><<<flat_grid<lpr()>(n_t), kBlock, 0, st>>>(rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di);
+    });
   } else if (d > 256) {
     launch_rows<64, 2>(st, rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di, row_order);
   } else {
-    switch (pick_lpr(d)) {
-      case 8:  launch_rows<8, 1>(st, rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di, row_order); break;
-      case 16: launch_rows<16, 1>(st, rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di, row_order); break;
-      case 32: launch_rows<32, 1>(st, rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di, row_order); break;
-      default: launch_rows<64, 1>(st, rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di, row_order); break;
-    }
+    with_lpr(pick_lpr(d), [&](auto lpr) { launch_rows<lpr(), 1>(st, rowptr, col, xe, ldxe, tl, xi, ldxi, nt, di, row_order); });
   }
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;

@@ -18,8 +18,7 @@
 //   ae[e, h] = <xe[e, h, :], att[h, :]>                     h < H, C columns per head, taken from the row while in registers
 // which saves the logit pass's read of [M, d].
 //
-// Mapping: unigcn.hip's (that file, hconv.hip, pma.hip and gat.hip are left as they are; the gather skeleton is repeated here
-// once, with the row's finish as a template parameter):
+// Mapping: unigcn.hip's, with the row's finish as a template parameter:
 //   * one wavefront OWNS a whole output row: LPR lanes x 16 B per feature row, NS = 64 / LPR rows gathered per load; widths above
 //     256 take two 16-byte packets per lane (NCH = 2, LPR = 64), so d <= 512 stays in registers and the row norm / the per-head
 //     dot products are cross-lane reductions -- no second pass over the row, no atomics;
@@ -34,13 +33,13 @@
 // Algorithmic bytes per launch, K1: nnz * (4d + 4) + (n_t + 1) * 4 + n_t * 4d, plus n_t * 4d for xs and n_t * 4 each for s and
 // t_out; K2: nnz * (4d + 4) + (n_t + 1) * 4 + n_t * (4d + 4H + 4) + 4d.
 #include "common.h"
+#include "flat_rows.h"
 #include "row_epilogue.h"
 
 namespace allset {
 namespace unignn {
 
 constexpr int kMaxWidth = 512;
-constexpr int kFlatRows = 7;          // rows per lane group in the short-row kernel (kFlatRows + 1 rowptr entries fit in 8 lanes)
 constexpr int kFlatUnroll = 8;
 
 // K1's row tail.  The LPR lanes that together hold row `row` call finish(): lane li has columns (ch * LPR + li) * 4 .. + 3 of the
@@ -224,69 +223,41 @@ __global__ __launch_bounds__(kBlock) void unignn_rows_kernel(
   fin.template finish<LPR, NCH>(row, li, d, acc, slot == 0);
 }
 
-// short-row variant: each LPR-lane group owns kFlatRows consecutive rows and walks their incidences as one stream
-// (hconv_flat_kernel's scheme); single column chunk (d <= LPR * 4).  Everything that steers the walk is uniform within a lane
-// group, so the group's lanes reach every flush together and the finish's reductions stay inside the group.
+// short-row variant (flat_rows.h); single column chunk (d <= LPR * 4).  Every lane of the slot calls the finish: its reductions
+// stay inside the slot.
 template <int LPR, class Finish>
 __global__ __launch_bounds__(kBlock) void unignn_flat_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ x, int64_t ldx, Finish fin,
     int n_t, int d, const uint64_t* __restrict__ seed_base) {
-  constexpr int NS = kWave / LPR;
-  const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
-  const int lane = lane_id();
-  const int slot = lane / LPR, li = lane % LPR;
-  const int lane0 = slot * LPR;
-  const int64_t slot_global = (static_cast<int64_t>(blk) * kWavesPerBlock + (threadIdx.x >> 6)) * NS + slot;
-  const int64_t r_begin64 = slot_global * kFlatRows;
-  if (r_begin64 - static_cast<int64_t>(slot) * kFlatRows >= n_t) return;      // whole wave beyond the last row
+  FlatSlot<LPR> s;
+  if (s.wave_beyond(n_t)) return;
   fin.prepare(seed_base);
-  const int r_begin = static_cast<int>(min(r_begin64, static_cast<int64_t>(n_t)));
-  const int r_end = min(r_begin + kFlatRows, n_t);
-  const int c0 = li * 4;
+  s.open(rowptr, n_t);
+  const int c0 = s.li * 4;
   const bool active = c0 < d;
-  const int rp = (li <= r_end - r_begin) ? rowptr[r_begin + li] : 0;
-  const int q0 = __shfl(rp, lane0);
-  const int q_end = __shfl(rp, lane0 + (r_end - r_begin));
-
-  int cur_row = r_begin;
-  int cur_end = (r_begin < r_end) ? __shfl(rp, lane0 + 1) : q0;
   float acc[1][4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) acc[0][k] = 0.f;
+  int my_col = 0;
+  Raw<float, 4> raw[kFlatUnroll];
 
-  auto flush = [&]() {
-    fin.template finish<LPR, 1>(cur_row, li, d, acc, true);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[0][k] = 0.f;
-    ++cur_row;
-    cur_end = __shfl(rp, lane0 + min(cur_row - r_begin + 1, LPR - 1));
-  };
-
-  for (int base = q0; base < q_end; base += LPR) {
-    const int n = min(LPR, q_end - base);
-    const int my_col = li < n ? col[base + li] : 0;
-    for (int j = 0; j < n; j += kFlatUnroll) {
-      Raw<float, 4> raw[kFlatUnroll];
-#pragma unroll
-      for (int u = 0; u < kFlatUnroll; ++u) {
-        const int jj = j + u;
-        const int src = __shfl(my_col, lane0 + (jj & (LPR - 1)));
-        if (jj < n && active) raw[u] = load_raw<float, 4>(x + static_cast<int64_t>(src) * ldx + c0);
+  flat_walk<kFlatUnroll>(
+      s, active, [&](int base, int n) { my_col = s.li < n ? col[base + s.li] : 0; },
+      [&](int u, int jj, bool ok) {
+        const int src = s.bcast(my_col, jj);
+        if (ok) raw[u] = load_raw<float, 4>(x + static_cast<int64_t>(src) * ldx + c0);
         else raw[u] = zero_raw<float, 4>();
-      }
+      },
+      [&](int u) {
+        const FVec<4> v = unpack<float, 4>(raw[u]);
 #pragma unroll
-      for (int u = 0; u < kFlatUnroll; ++u) {
-        const int pos = base + j + u;
-        if (j + u < n) {
-          while (pos >= cur_end) flush();                          // also steps over empty rows
-          const FVec<4> v = unpack<float, 4>(raw[u]);
+        for (int k = 0; k < 4; ++k) acc[0][k] += v.v[k];
+      },
+      [&] {
+        fin.template finish<LPR, 1>(s.cur_row, s.li, d, acc, true);
 #pragma unroll
-          for (int k = 0; k < 4; ++k) acc[0][k] += v.v[k];
-        }
-      }
-    }
-  }
-  while (cur_row < r_end) flush();                                 // last row and trailing empty rows
+        for (int k = 0; k < 4; ++k) acc[0][k] = 0.f;
+      });
 }
 
 template <int LPR, int NCH, class Finish>
@@ -296,16 +267,6 @@ static void launch_rows(hipStream_t st, const int32_t* rowptr, const int32_t* co
   unignn_rows_kernel<LPR, NCH, Finish><<<grid, kBlock, 0, st>>>(rowptr, col, x, ldx, fin, n_t, d, row_order, seed_base);
 }
 
-template <int LPR, class Finish>
-static void launch_flat(hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* x, int64_t ldx, const Finish& fin,
-                        int n_t, int d, const uint64_t* seed_base) {
-  constexpr int NS = kWave / LPR;
-  const int64_t groups = (static_cast<int64_t>(n_t) + kFlatRows - 1) / kFlatRows;
-  const int64_t waves = (groups + NS - 1) / NS;
-  const unsigned grid = static_cast<unsigned>((waves + kWavesPerBlock - 1) / kWavesPerBlock);
-  unignn_flat_kernel<LPR, Finish><<<grid, kBlock, 0, st>>>(rowptr, col, x, ldx, fin, n_t, d, seed_base);
-}
-
 // variant 0 auto / 1 one wavefront per row / 2 short rows (the caller has checked that 2 comes with d <= 256)
 template <class Finish>
 static void dispatch(int variant, int64_t nnz, hipStream_t st, const int32_t* rowptr, const int32_t* col, const float* x, int64_t ldx,
@@ -313,21 +274,13 @@ static void dispatch(int variant, int64_t nnz, hipStream_t st, const int32_t* ro
   const bool use_flat = d <= 256 && (variant == 2 || (variant == 0 && n_t > kFlatMinRows &&
                                                       static_cast<double>(nnz) < kFlatMaxMeanDegree * static_cast<double>(n_t)));
   if (use_flat) {
-    switch (pick_lpr(d)) {
-      case 8:  launch_flat<8>(st, rowptr, col, x, ldx, fin, n_t, d, seed_base); break;
-      case 16: launch_flat<16>(st, rowptr, col, x, ldx, fin, n_t, d, seed_base); break;
-      case 32: launch_flat<32>(st, rowptr, col, x, ldx, fin, n_t, d, seed_base); break;
-      default: launch_flat<64>(st, rowptr, col, x, ldx, fin, n_t, d, seed_base); break;
-    }
+    with_lpr(pick_lpr(d), [&](auto lpr) {
+      unignn_flat_kernel<lpr(), Finish><<<flat_grid<lpr()>(n_t), kBlock, 0, st>>>(rowptr, col, x, ldx, fin, n_t, d, seed_base);
+    });
   } else if (d > 256) {
     launch_rows<64, 2>(st, rowptr, col, x, ldx, fin, n_t, d, row_order, seed_base);
   } else {
-    switch (pick_lpr(d)) {
-      case 8:  launch_rows<8, 1>(st, rowptr, col, x, ldx, fin, n_t, d, row_order, seed_base); break;
-      case 16: launch_rows<16, 1>(st, rowptr, col, x, ldx, fin, n_t, d, row_order, seed_base); break;
-      case 32: launch_rows<32, 1>(st, rowptr, col, x, ldx, fin, n_t, d, row_order, seed_base); break;
-      default: launch_rows<64, 1>(st, rowptr, col, x, ldx, fin, n_t, d, row_order, seed_base); break;
-    }
+    with_lpr(pick_lpr(d), [&](auto lpr) { launch_rows<lpr(), 1>(st, rowptr, col, x, ldx, fin, n_t, d, row_order, seed_base); });
   }
 }
 

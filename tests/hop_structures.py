@@ -873,3 +873,82 @@ def units(got, ref):
     got = got.detach().cpu().double()
     assert got.shape == ref.shape, f"shape {tuple(got.shape)} against {tuple(ref.shape)}"
     return float(((got - ref).abs() / (1e-4 + 1e-4 * ref.abs())).max()) if ref.numel() else 0.0
+
+
+# ---- the short-row kernels of csrc/segreduce.hip and csrc/pma.hip (ops.segreduce / pma_fwd / pma_bwd_src with variant=2) ---------------
+# tests/test_gpu_flat_walk.py: every structure at every width the kernels build (one column chunk, d <= 256), against the float64
+# operator seam of oracle/allset_oracle.py that tests/test_gpu_ops.py holds these kernels to.
+FLAT_WIDTHS = tuple(d for d in VEC_WIDTHS if d <= 256)
+FLAT_PMA_HC = OrderedDict((d, hc) for d, hc in GAT_VEC_HC.items() if d <= 256)
+FLAT_SPLIT_STRUCT = "lengths"                     # long and short rows in one CSR: ops.size_split at CSR_LONG_T cuts off the T + 1 row
+
+
+def flat_segreduce_inputs(name, d):
+    n_src, n_dst, ei = structures()[name]
+    rng = np.random.default_rng(hash_id(_cid("flat-seg", name, d)))
+    return dict(n_src=n_src, n_dst=n_dst, ei=torch.from_numpy(ei), x=randn(rng, n_src, d), w=positive(rng, ei.shape[1]))
+
+
+def flat_segreduce_reference(inp, x, aggr, weighted):
+    """``oracle.deepsets_aggregate`` in float64, padded to ``n_dst`` rows (the scatter stops at the last row that received anything;
+    without any incidence every row is 0)."""
+    from oracle import allset_oracle
+    nnz = inp["ei"].shape[1]
+    if nnz == 0:
+        return torch.zeros(inp["n_dst"], x.shape[1], dtype=D64)
+    out = allset_oracle.deepsets_aggregate(x, inp["ei"], inp["w"] if weighted else torch.ones(nnz, dtype=D64), aggr)
+    return torch.cat([out, out.new_zeros(inp["n_dst"] - out.shape[0], x.shape[1])])
+
+
+def flat_pma_inputs(name, H, C, transposed):
+    """``transposed``: the structure's target rows become the SOURCES (the rows of the backward's transposed CSR)."""
+    n_src, n_dst, ei = structures()[name]
+    if transposed:
+        n_src, n_dst, ei = n_dst, n_src, ei[::-1].copy()
+    rng = np.random.default_rng(hash_id(_cid("flat-pma", name, H, C, transposed)))
+    return dict(n_src=n_src, n_dst=n_dst, ei=torch.from_numpy(ei), H=H, C=C, V=randn(rng, n_src, H * C),
+                alpha=logit_terms(rng, n_src, H, True), G=randn(rng, n_dst, H * C))
+
+
+def flat_pma_reference(inp):
+    """``(out, m, l, gV, galpha)``: ``oracle.pma_aggregate`` in float64 and its autograd under ``(out * G).sum()``; m and l are the two
+    intermediates of ``oracle.segment_softmax`` (the segment max, 0 for a row that receives nothing, and the segment sum of
+    exp(a - max)).  Without any incidence every output is 0 (the scatter's rule)."""
+    from oracle import allset_oracle
+    n_s, n_t, H, C, ei = inp["n_src"], inp["n_dst"], inp["H"], inp["C"], inp["ei"]
+    if ei.shape[1] == 0:
+        return (torch.zeros(n_t, H * C, dtype=D64), torch.zeros(n_t, H, dtype=D64), torch.zeros(n_t, H, dtype=D64),
+                torch.zeros(n_s, H * C, dtype=D64), torch.zeros(n_s, H, dtype=D64))
+    V, alpha = inp["V"].clone().requires_grad_(True), inp["alpha"].clone().requires_grad_(True)
+    out, _ = allset_oracle.pma_aggregate(V.view(n_s, H, C), alpha, ei, 0.2)
+    out = torch.cat([out, out.new_zeros(n_t - out.shape[0], H, C)]).reshape(n_t, H * C)
+    gV, ga = torch.autograd.grad(out, (V, alpha), inp["G"])
+    a = torch.nn.functional.leaky_relu(inp["alpha"].index_select(0, ei[0]), 0.2)
+    m = allset_oracle.scatter(a, ei[1], n_t, "max")
+    l = allset_oracle.scatter((a - m.index_select(0, ei[1])).exp(), ei[1], n_t, "sum")
+    return out.detach(), m, l, gV, ga
+
+
+# The one structure whose logit gradient cannot be held to the family rule's scale -- the backward's ``one_col`` (HAN_GEL_SLACK above):
+# with the structure's rows as SOURCE rows, ``one_row`` has every incidence leaving ONE source, and every target's softmax runs over
+# copies of that source alone, so ``galpha[s, h] = lrelu'(alpha_s) * sum_j p_j (<V_s, g_tj> - delta_tj)`` sums 1500 terms of magnitude
+# O(1) that cancel to exactly 0 whatever the inputs -- max |want| is no scale at all.  pma_bwd_src_{,flat_}kernel form it as the
+# difference of two accumulated fp32 sums (S - D, no per-incidence dot product), so what is left is those sums' rounding error.  Its
+# allowance is the probabilistic bound of an m-term sum in precision u, ``sqrt(m) * u * sum |terms|`` (Higham & Mary 2019, lambda = 1;
+# the worst-case ``m * u`` form that HAN_GEL_SLACK uses would be ~0.5 here and check nothing), with u = 2^-24, m = (incidences of the
+# source) + C and sum |terms| = lrelu' * sum_j p_j (sum_c |V_s g_tj| + |delta_tj|), all from the float64 reference: 1e-3 .. 4e-2 at the
+# hub source over the nine widths, where ONE dropped or doubled incidence moves galpha by p_j |delta_tj| ~ 0.05 .. 1 (host file).  Observed on the
+# MI355X (parent's library and this one alike): |diff| 1.5e-4 against want 0 at d = 32.
+FLAT_GALPHA_SLACK = ("one_row",)
+
+
+def flat_pma_galpha_slack(inp):
+    """float64 [n_src, H]: ``sqrt(m) * 2^-24 * sum |terms|`` of ``galpha`` (see FLAT_GALPHA_SLACK)."""
+    from oracle import allset_oracle
+    n_s, n_t, H, C, (src, dst) = inp["n_src"], inp["n_dst"], inp["H"], inp["C"], inp["ei"]
+    V, G = inp["V"].view(n_s, H, C), inp["G"].view(n_t, H, C)
+    p = allset_oracle.segment_softmax(torch.nn.functional.leaky_relu(inp["alpha"][src], 0.2), dst, n_t)
+    delta = (allset_oracle.scatter(V[src] * p.unsqueeze(-1), dst, n_t, "sum") * G).sum(-1)
+    terms = p * torch.where(inp["alpha"][src] > 0, 1.0, 0.2) * ((V[src].abs() * G[dst].abs()).sum(-1) + delta[dst].abs())
+    m = torch.bincount(src, minlength=n_s).double() + C
+    return m.sqrt().unsqueeze(1) * 2.0 ** -24 * allset_oracle.scatter(terms, src, n_s, "sum")

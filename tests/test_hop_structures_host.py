@@ -342,3 +342,63 @@ def test_hconv_variant_hook_keeps_the_csrs_choice_and_passes_an_override_on():
         assert ops._hconv_variant(csr, n, True, 1) == 1 and ops._hconv_variant(csr, n, False, 2) == 2   # as given: the C entry refuses
     with pytest.raises(AllSetHipError, match="variant must be None, 1 or 2"):
         ops._hconv_variant(small, 50, True, 0)
+
+
+# ---- the short-row kernels of segreduce.hip / pma.hip (tests/test_gpu_flat_walk.py) -------------------------------------------------
+def test_flat_walk_widths_take_every_lane_group_and_the_split_structure_has_both_kinds_of_rows():
+    from allset_amd import ops
+    assert hs.FLAT_WIDTHS == (4, 12, 32, 36, 64, 68, 128, 132, 256) and tuple(hs.FLAT_PMA_HC) == hs.FLAT_WIDTHS
+    assert {hs.pick_lpr(d, 4) for d in hs.FLAT_WIDTHS} == {8, 16, 32, 64}
+    assert {hs.pick_lpr(d, 8) for d in hs.FLAT_WIDTHS if d % 8 == 0} == {8, 16, 32}      # bf16: 8 elements per 16-byte packet
+    assert all(H * C == d and C % 4 == 0 for d, (H, C) in hs.FLAT_PMA_HC.items())
+    n_src, n_dst, ei = hs.structures()[hs.FLAT_SPLIT_STRUCT]
+    deg = torch.from_numpy(_deg(ei, n_dst, 1))
+    rowptr = torch.zeros(n_dst + 1, dtype=torch.int32)
+    rowptr[1:] = torch.cumsum(deg, 0)
+    col = torch.zeros(int(deg.sum()), dtype=torch.int32)
+    sp = ops.size_split(rowptr, col, n_dst, int(deg.max()), threshold=hs.CSR_LONG_T)
+    assert sp is not None and sp.long_ids.tolist() == [int(deg.argmax())] and sp.short_ids.numel() == n_dst - 1
+    short_deg = (sp.rowptr_short[1:] - sp.rowptr_short[:-1]).tolist()
+    assert max(short_deg) == hs.CSR_LONG_T and 0 in short_deg and sp.short_ids.tolist() != list(range(n_dst - 1))   # ids are not the identity
+
+
+@pytest.mark.parametrize("name", list(hs.structures()))
+def test_flat_walk_references_are_finite_and_clear_of_the_leaky_relu_kink(name):
+    d = hs.FLAT_WIDTHS[list(hs.structures()).index(name) % len(hs.FLAT_WIDTHS)]
+    inp = hs.flat_segreduce_inputs(name, d)
+    for aggr, weighted in (("add", False), ("mean", False), ("add", True)):
+        ref = hs.flat_segreduce_reference(inp, inp["x"], aggr, weighted)
+        assert ref.shape == (inp["n_dst"], d) and bool(torch.isfinite(ref).all())
+    H, C = hs.FLAT_PMA_HC[d]
+    for transposed in (False, True):
+        pin = hs.flat_pma_inputs(name, H, C, transposed)
+        assert float(pin["alpha"].abs().min()) >= hs.LOGIT_MARGIN
+        out, m, l, gV, ga = hs.flat_pma_reference(pin)
+        assert out.shape == (pin["n_dst"], d) and m.shape == l.shape == (pin["n_dst"], H)
+        assert gV.shape == (pin["n_src"], d) and ga.shape == (pin["n_src"], H)
+        assert all(bool(torch.isfinite(t).all()) for t in (out, m, l, gV, ga))
+        got = torch.from_numpy(_deg(pin["ei"].numpy(), pin["n_dst"], 1)) > 0
+        assert torch.equal(l.min(dim=1).values >= 1.0, got) and torch.equal(l.max(dim=1).values > 0, got)   # l >= 1 where a row has members
+
+
+def test_flat_walk_galpha_slack_stays_far_below_one_incidence_at_every_width():
+    """The allowance of hop_structures.FLAT_GALPHA_SLACK: non-zero at the hub source alone, between the family rule's 1e-4 and 5e-2
+    at every width, and at least 4 times smaller than what the smallest single incidence contributes to D (so a dropped or doubled
+    incidence cannot hide in it)."""
+    from oracle import allset_oracle
+    for name in hs.FLAT_GALPHA_SLACK:
+        for d, (H, C) in hs.FLAT_PMA_HC.items():
+            pin = hs.flat_pma_inputs(name, H, C, True)
+            ga = hs.flat_pma_reference(pin)[4]
+            slack = hs.flat_pma_galpha_slack(pin)
+            src, dst = pin["ei"]
+            hub = int(src[0])
+            assert len(set(src.tolist())) == 1 and float(ga.abs().max()) < 1e-12
+            assert 1e-4 < float(slack[hub].min()) and float(slack[hub].max()) < 5e-2, (d, slack[hub])
+            assert float(slack.sum() - slack[hub].sum()) == 0.0
+            p = allset_oracle.segment_softmax(torch.nn.functional.leaky_relu(pin["alpha"][src], 0.2), dst, pin["n_dst"])
+            out = hs.flat_pma_reference(pin)[0].view(pin["n_dst"], H, C)
+            delta = (out * pin["G"].view(pin["n_dst"], H, C)).sum(-1)
+            one = (p * delta[dst].abs() * torch.where(pin["alpha"][src] > 0, 1.0, 0.2))
+            print(d, "slack", slack[hub].tolist(), "median single-incidence term", one.median(dim=0).values.tolist())
+            assert bool((4 * slack[hub] < one.median(dim=0).values).all()), d
