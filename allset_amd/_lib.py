@@ -269,6 +269,7 @@ SIGNATURES = {
     # only; detect with allset_han_sampling_supported)
     "allset_han_sampling_supported": [],
     "allset_han_walk": [c_int, _P, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, c_int64, c_uint64, c_uint64, _P, _P],
+    "allset_han_walk_typed": [c_int, c_int64, _P, _P, _P, _P, c_int64, c_int64, c_uint64, c_uint64, _P, _P],
     "allset_han_block_rows": [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P],
     "allset_han_block_compact": [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P],
     "allset_han_block_hop_fwd": [c_int64, _P, _P, _P, _P, _P, c_int64, c_float, _P, c_float, c_uint64, _P, _P, c_int64, _P, c_int64, _P,

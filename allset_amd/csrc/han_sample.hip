@@ -19,6 +19,18 @@
 // The uniform pick is multiply-shift, index = (u32 * degree) >> 32: every index is taken by floor(2^32 / degree) or one more of the
 // 2^32 values, so its probability is within degree / 2^32 (relative) of 1 / degree -- 2.4e-7 for a row of 1000.
 //
+// ---- the typed walk ----------------------------------------------------------------------------------------------------------
+// A typed graph's metapath is a chain of L <= kMaxHops relation CSRs (rows = source ids of the hop's source type, int32 columns =
+// ids of its destination type, duplicate edges kept: a duplicated edge is twice as likely, DGL's multigraph walk).  Same mapping:
+// one lane per (seed, walk), 2 L dependent loads.  The relation table (rowptr, col, n_rows per hop) is wave-uniform and travels by
+// value as a kernel argument; the hop loop is unrolled over kMaxHops so that every table access has a constant offset (scalar
+// loads, no scratch).  An id is range-checked against the hop's n_rows BEFORE it indexes that hop's rowptr: a seed outside
+// [0, n_rows[0]), an empty row, or an intermediate id outside the next hop's rows ends the walk with -1 and reads nothing further.
+// Random numbers: hop h of a walk draws walk_hash(key ^ (h >> 1) * odd constant, seed node, walk, h & 1).  For h < 2 that IS the
+// two-hop walk's draw, so L = 2 over the same CSRs is bit-identical to allset_han_walk with id_base 0; hops 2 j and 2 j + 1 differ in
+// the counter and hop pairs j != j' in the key, so the hops of one walk draw independently even where a metapath repeats a
+// relation.  The key is still the seed NODE, never its position in the batch nor the node the walk currently stands on.
+//
 // ---- block rows --------------------------------------------------------------------------------------------------------------
 // One wave per seed, one lane per walk (k <= 64): drop -1 and the seed itself, keep the first lane of every distinct endpoint, rank
 // the survivors by global id (two 64-step shuffle passes, no LDS), write them ascending into row b of a B x (k + 1) slab, then the
@@ -75,6 +87,39 @@ __global__ __launch_bounds__(kBlock) void walk_kernel(
     }
   }
   out[tid] = r;
+}
+
+constexpr int kMaxHops = 8;
+constexpr uint64_t kHopPairKey = 0xA0761D6478BD642FULL;
+
+struct HopTable {
+  const int32_t* rowptr[kMaxHops];
+  const int32_t* col[kMaxHops];  // null only for a relation without edges: nothing is read through it
+  int n_rows[kMaxHops];
+};
+
+__global__ __launch_bounds__(kBlock) void walk_typed_kernel(const HopTable t, int L, const int32_t* __restrict__ seeds, int B, int k,
+                                                            uint64_t key, int32_t* __restrict__ out) {
+  const int64_t tid = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (tid >= static_cast<int64_t>(B) * k) return;
+  const int b = static_cast<int>(tid / k), w = static_cast<int>(tid % k);
+  const int s = seeds[b];
+  int cur = s;
+#pragma unroll
+  for (int h = 0; h < kMaxHops; ++h) {
+    if (h < L) {
+      int nxt = -1;
+      if (cur >= 0 && cur < t.n_rows[h]) {
+        const int r0 = t.rowptr[h][cur], r1 = t.rowptr[h][cur + 1];
+        if (r1 > r0 && t.col[h] != nullptr) {
+          const uint32_t u = walk_hash(key ^ (static_cast<uint64_t>(h >> 1) * kHopPairKey), static_cast<uint32_t>(s), w, h & 1);
+          nxt = t.col[h][r0 + uniform_pick(u, r1 - r0)];
+        }
+      }
+      cur = nxt;
+    }
+  }
+  out[tid] = cur;
 }
 
 // first index in sorted a[0, n) whose value is >= v
@@ -196,6 +241,35 @@ extern "C" int allset_han_walk(int metapath, const int32_t* rowptr_a, const int3
   walk_kernel<<<lane_grid(B * k), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
       rowptr_a, col_a, rowptr_b, col_b, static_cast<int>(n_a), static_cast<int>(n_b), static_cast<int>(id_base), seeds,
       static_cast<int>(B), static_cast<int>(k), key, endpoints);
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
+}
+
+extern "C" int allset_han_walk_typed(int metapath, int64_t L, const int32_t* const* rowptrs, const int32_t* const* cols,
+                                     const int64_t* n_rows, const int32_t* seeds, int64_t B, int64_t k, uint64_t seed,
+                                     uint64_t counter, int32_t* endpoints, void* stream) {
+  clear_error();
+  ALLSET_REQUIRE(metapath >= 0 && metapath < 256, "han_walk_typed: metapath index must be in [0, 256)");
+  ALLSET_REQUIRE(L >= 1 && L <= kMaxHops, "han_walk_typed: a metapath has 1 to %d hops (HAN_MAX_HOPS), got %lld", kMaxHops,
+                 static_cast<long long>(L));
+  int rc = check_batch("han_walk_typed", B, k);
+  if (rc != ALLSET_OK) return rc;
+  ALLSET_REQUIRE(rowptrs && cols && n_rows, "han_walk_typed: null relation table");
+  HopTable t = {};
+  for (int h = 0; h < L; ++h) {
+    ALLSET_REQUIRE(n_rows[h] >= 0 && n_rows[h] < INT32_MAX, "han_walk_typed: sizes must fit int32 (hop %d)", h);
+    t.n_rows[h] = static_cast<int>(n_rows[h]);
+  }
+  if (B == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(seeds && endpoints, "han_walk_typed: null seeds/endpoints");
+  for (int h = 0; h < L; ++h) {
+    ALLSET_REQUIRE(rowptrs[h], "han_walk_typed: null rowptr (hop %d)", h);
+    t.rowptr[h] = rowptrs[h];
+    t.col[h] = cols[h];
+  }
+  const uint64_t key = (counter * 0x9E3779B97F4A7C15ULL + seed) ^ (static_cast<uint64_t>(metapath + 1) * 0xD1B54A32D192ED03ULL);
+  walk_typed_kernel<<<lane_grid(B * k), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
+      t, static_cast<int>(L), seeds, static_cast<int>(B), static_cast<int>(k), key, endpoints);
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }

@@ -14,6 +14,11 @@ Orderings chosen here (DGL's are hash-table orders): a target's neighbours ascen
 source nodes = the seeds in the given order, then the other distinct nodes ascending.  Random numbers are counter-based, keyed on
 ``(seed, step counter, metapath, global seed node, walk, hop)``: a node's neighbours do not depend on the batch it is in.
 
+A typed graph (the reference's ``ACMRaw`` branch, metapaths of edge types such as ``[['pa', 'ap'], ['pf', 'fp']]``) is sampled through
+:class:`TypedMetapathWalker` over a ``han_hetero.HeteroGraph``: the walk follows the metapath's chain of relation CSRs (any length up
+to ``ops.HAN_MAX_HOPS``, duplicate edges kept) in the ids of the node type every metapath starts from and ends on; everything after
+the walk is the same code.  ``--hetero`` runs it.
+
 Reference quirks kept: ``evaluate`` samples ``2 k`` walks and returns the LAST batch's loss (which ``EarlyStopping`` then consumes);
 ``HAN.forward`` hands the same blocks to every layer, so only ``len(num_heads) == 1`` can work -- more raises ``ValueError``.
 """
@@ -29,9 +34,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, dense, ops
+from . import _lib, dense, han_hetero, ops
 from .functional import han_block_propagate, semantic_attention
 from .han import EarlyStopping, SemanticAttention, _first, node_features, rand_train_test_idx, score
+from .han_hetero import META_PATHS, CanonicalEType, HeteroGraph, _check_metapath
 from .incidence import Incidence
 
 Tensor = torch.Tensor
@@ -82,7 +88,60 @@ class MetapathWalker:
         return (self.v2e, self.e2v, 0) if mp == 0 else (self.e2v, self.v2e, self.n_v)
 
 
-def _seeds_on_device(walker: MetapathWalker, seeds, check_dups: bool) -> Tensor:
+class TypedMetapathWalker:
+    """A typed graph for the sampler: metapaths are lists of ``g``'s edge types (names or canonical triples), walked over the chain of
+    ``g.csr(etype)`` -- duplicate edges kept, so a duplicated edge is twice as likely, as in DGL's multigraph walk.  The sampler builds a
+    homogeneous neighbour graph on ONE node type (DGL's ``RandomWalkNeighborSampler``): every metapath starts from and ends on it.  That
+    type is fixed by the first metapaths the walker is used with (``ntype``, and ``n`` = its node count: the seeds' id range); a
+    walker serves one node type, a second one over the same graph shares its CSRs."""
+
+    def __init__(self, g: HeteroGraph):
+        if not isinstance(g, HeteroGraph):
+            raise TypeError(f"TypedMetapathWalker: a han_hetero.HeteroGraph is required (got {type(g).__name__})")
+        self.g = g
+        self.device = g.edges(g.canonical_etypes[0])[0].device
+        self.ntype: Optional[str] = None
+        self.n: Optional[int] = None
+
+    def resolve(self, metapath) -> List[CanonicalEType]:
+        """The metapath's relations.  Host only; ``ValueError`` for an empty metapath, an unknown edge type, a step that does not start
+        where the previous one ended, more than ``ops.HAN_MAX_HOPS`` steps, or a metapath that does not end on the type it starts
+        from (its endpoints would be taken for ids of the seeds' type)."""
+        rels = _check_metapath(self.g, metapath)
+        if len(rels) > ops.HAN_MAX_HOPS:
+            raise ValueError(f"metapath {list(metapath)!r} has {len(rels)} steps: the walk kernel is built for at most HAN_MAX_HOPS = "
+                             f"{ops.HAN_MAX_HOPS}")
+        if rels[0][0] != rels[-1][2]:
+            raise ValueError(f"metapath {list(metapath)!r} leads from {rels[0][0]!r} to {rels[-1][2]!r}: the sampled neighbours are nodes "
+                             "of the seeds' type, so a metapath must end on the type it starts from")
+        return rels
+
+    def bind(self, metapath_list) -> List[List[CanonicalEType]]:
+        """Every metapath resolved; all must start from one node type, which becomes (or must be) the walker's."""
+        chains = [self.resolve(m) for m in metapath_list]
+        heads = sorted({rels[0][0] for rels in chains})
+        if len(heads) != 1:
+            raise ValueError(f"metapaths {[list(m) for m in metapath_list]!r} start from {len(heads)} node types {heads}: the seeds of a "
+                             "batch are ids of ONE type")
+        if self.ntype is not None and self.ntype != heads[0]:
+            raise ValueError(f"this walker samples {self.ntype!r} nodes; metapaths from {heads[0]!r} need a TypedMetapathWalker of "
+                             "their own")
+        self.ntype, self.n = heads[0], self.g.number_of_nodes(heads[0])
+        return chains
+
+    def chain(self, rels: Sequence[CanonicalEType]) -> List[ops.CSR]:
+        return [self.g.csr(rel) for rel in rels]
+
+
+def _walk(walker, mp: int, rels, s32: Tensor, k: int, seed: int, counter: int) -> Tensor:
+    """int32[B, k] endpoints of metapath ``mp``: over ``rels`` (a typed walker's relation chain) or, ``rels`` None, the incidence."""
+    if rels is not None:
+        return ops.han_walk_typed(mp, walker.chain(rels), s32, k, seed, counter)
+    a, b, base = walker.orientation(mp)
+    return ops.han_walk(mp, a, b, base, s32, k, seed, counter)
+
+
+def _seeds_on_device(walker, seeds, check_dups: bool) -> Tensor:
     """int32[B] on the walker's device.  A host list / CPU tensor is range-checked (and checked for duplicates) on the host for free;
     a device tensor is taken as it is -- out-of-range ids there are nodes without out-edges to the walk."""
     if torch.is_tensor(seeds) and seeds.is_cuda:
@@ -98,15 +157,21 @@ def _seeds_on_device(walker: MetapathWalker, seeds, check_dups: bool) -> Tensor:
     return torch.from_numpy(host.astype(np.int32)).to(walker.device)
 
 
-def random_walk_endpoints(walker: MetapathWalker, metapath, seeds, num_walks: int, seed: int, counter: int) -> Tensor:
+def random_walk_endpoints(walker, metapath, seeds, num_walks: int, seed: int, counter: int, index: int = 0) -> Tensor:
     """The raw walks: int64[B, num_walks] endpoints in global ids, -1 for a walk that terminated (a seed without out-edges in this
-    metapath).  A pure function of its arguments."""
-    mp = metapath_index(metapath)
+    metapath).  A pure function of its arguments.  With a :class:`TypedMetapathWalker`, ``metapath`` is a list of edge types and
+    ``index`` its position in the sampler's metapath list (the metapath index of the random-number key)."""
+    typed = isinstance(walker, TypedMetapathWalker)
+    if typed:
+        if not 0 <= int(index) < 256:
+            raise ValueError(f"index must be in [0, 256) (got {index})")
+        mp, rels = int(index), walker.bind([metapath])[0]
+    else:
+        mp, rels = metapath_index(metapath), None
     if not 1 <= int(num_walks) <= ops.HAN_MAX_WALKS:
         raise ValueError(f"num_walks must be in [1, {ops.HAN_MAX_WALKS}] (got {num_walks})")
     s32 = _seeds_on_device(walker, seeds, check_dups=False)
-    a, b, base = walker.orientation(mp)
-    return ops.han_walk(mp, a, b, base, s32, int(num_walks), seed, counter).long()
+    return _walk(walker, mp, rels, s32, int(num_walks), seed, counter).long()
 
 
 class Block:
@@ -141,14 +206,22 @@ class Block:
 
 class HANSampler:
     """``HANSampler(g, metapath_list, num_neighbors)`` of the reference with the device-resident walker in ``g``'s place and an
-    explicit ``seed``.  Every :meth:`sample_blocks` call takes the next step counter (or the one given)."""
+    explicit ``seed``.  Every :meth:`sample_blocks` call takes the next step counter (or the one given).  With a
+    :class:`TypedMetapathWalker`, ``metapath_list`` holds lists of edge types and a metapath's index is its position in the list."""
 
-    def __init__(self, walker: MetapathWalker, metapath_list, num_neighbors: int, seed: int = 0):
+    def __init__(self, walker, metapath_list, num_neighbors: int, seed: int = 0):
         if not 1 <= int(num_neighbors) <= ops.HAN_MAX_WALKS:
             raise ValueError(f"num_neighbors must be in [1, {ops.HAN_MAX_WALKS}] (got {num_neighbors}): the walk kernel is built for "
                              f"at most {ops.HAN_MAX_WALKS} walks per seed")
         self.walker, self.num_neighbors, self.seed = walker, int(num_neighbors), int(seed)
-        self.metapaths = [metapath_index(m) for m in metapath_list]
+        if isinstance(walker, TypedMetapathWalker):
+            self.chains = walker.bind(metapath_list)
+            if not 1 <= len(self.chains) <= 256:
+                raise ValueError(f"{len(self.chains)} metapaths: the walk's key holds a metapath index in [0, 256)")
+            self.metapaths = list(range(len(self.chains)))
+        else:
+            self.metapaths = [metapath_index(m) for m in metapath_list]
+            self.chains = [None] * len(self.metapaths)
         self.counter = 0
 
     def sample_blocks(self, seeds, counter: Optional[int] = None):
@@ -164,9 +237,8 @@ class HANSampler:
         dup = (sorted_seeds[1:] == sorted_seeds[:-1]).any().to(torch.int64).view(1) if B > 1 else torch.zeros(1, dtype=torch.int64, device=dev)
         slab = B * (k + 1)
         staged, sizes = [], [dup]
-        for mp in self.metapaths:
-            a, b, base = w.orientation(mp)
-            ends = ops.han_walk(mp, a, b, base, s32, k, self.seed, counter)
+        for mp, rels in zip(self.metapaths, self.chains):
+            ends = _walk(w, mp, rels, s32, k, self.seed, counter)
             rows, extra, counts = ops.han_block_rows(ends, s32, sorted_seeds)
             rowptr = torch.zeros(B + 1, dtype=torch.int32, device=dev)
             rowptr[1:] = torch.cumsum(counts, 0)
@@ -325,6 +397,8 @@ def evaluate(model, g, metapath_list, num_neighbors, features, labels, val_nid, 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser('mini-batch HAN')
     p.add_argument('-s', '--seed', type=int, default=1, help='Random seed')
+    p.add_argument('--hetero', action='store_true', help="one typed graph and metapaths of edge types (the reference's ACMRaw branch; "
+                   "--dataset synthetic) instead of the hypergraph's VEV / EVE walks")
     p.add_argument('--batch_size', type=int, default=32)
     p.add_argument('--num_neighbors', type=int, default=20)
     p.add_argument('--lr', type=float, default=0.001)
@@ -355,7 +429,11 @@ def setup(args: dict) -> dict:
 
 
 def load_data(args: dict):
-    """``(walker, features, labels, num_classes)`` on ``args['device']``."""
+    """``(walker, features, labels, num_classes)`` on ``args['device']``; with ``--hetero`` the walker is over the typed graph of
+    ``han_hetero.load_data`` and the labelled nodes are its papers."""
+    if args.get('hetero'):
+        g, features, labels, num_classes = han_hetero.load_data(args)
+        return TypedMetapathWalker(g), features, labels, num_classes
     from . import train
     from .preprocessing import ExtractV2E
     targs = SimpleNamespace(dname=args['dataset'], raw_data_dir=args.get('raw_data_dir'), processed_data=args.get('processed_data'),
@@ -368,7 +446,7 @@ def load_data(args: dict):
 
 def main(args: dict) -> dict:
     walker, features, labels, num_classes = load_data(args)
-    metapath_list = DEFAULT_METAPATHS
+    metapath_list = META_PATHS if args.get('hetero') else DEFAULT_METAPATHS
     k, bs = args['num_neighbors'], args['batch_size']
     if 2 * k > ops.HAN_MAX_WALKS:
         raise ValueError(f"--num_neighbors {k}: evaluation samples twice as many walks and the kernel is built for {ops.HAN_MAX_WALKS}")

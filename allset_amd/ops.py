@@ -5,8 +5,8 @@ tensors; outputs are allocated with torch (plumbing) and filled by the HIP kerne
 from __future__ import annotations
 
 from collections import defaultdict
-from ctypes import byref, c_int64 as c_int64_t, c_size_t
-from typing import Dict, List, NamedTuple, Optional, Tuple
+from ctypes import byref, c_int64 as c_int64_t, c_size_t, c_void_p
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -1534,6 +1534,7 @@ def han_sem_bwd(z: Tensor, W1: Tensor, b1: Tensor, q: Tensor, wbeta: Tensor, gou
 
 # ---- mini-batch HAN: the metapath random walk, the block construction and the bipartite hop (csrc/han_sample.hip) ----------------------
 HAN_MAX_WALKS = 64
+HAN_MAX_HOPS = 8
 
 
 def _i32(t: Tensor, what: str) -> Tensor:
@@ -1557,6 +1558,38 @@ def han_walk(metapath: int, csr_a: CSR, csr_b: CSR, id_base: int, seeds: Tensor,
                                           csr_a.n_rows, csr_b.n_rows, int(id_base), ptr(seeds), B, k,
                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF, ptr(out), stream_of(dev)),
               "allset_han_walk")
+    return out
+
+
+def han_walk_typed(metapath_index: int, csrs: Sequence[CSR], seeds: Tensor, k: int, seed: int, counter: int) -> Tensor:
+    """``k`` walks per seed along the chain ``csrs`` of relation CSRs (rows = source ids, as ``HeteroGraph.csr`` builds them;
+    duplicate edges kept): endpoints int32[B, k] in the ids of the last relation's destination type, -1 where the walk terminates.
+    ``seeds`` int32[B] ids of the first relation's source type.  For two hops, bit-identical to :func:`han_walk` with ``id_base`` 0."""
+    csrs = list(csrs)
+    L = len(csrs)
+    if not 1 <= L <= HAN_MAX_HOPS:
+        raise _lib.AllSetHipError(f"han_walk_typed: a metapath of {L} hops; the walk kernel is built for 1 to HAN_MAX_HOPS = "
+                                  f"{HAN_MAX_HOPS}")
+    dev = require_device(*[t for c in csrs for t in (c.rowptr, c.col)], seeds)
+    seeds = _i32(seeds, "han_walk_typed seeds")
+    for i, c in enumerate(csrs):
+        _i32(c.rowptr, f"han_walk_typed rowptr of hop {i}"), _i32(c.col, f"han_walk_typed col of hop {i}")
+        if not (c.rowptr.is_contiguous() and c.col.is_contiguous()) or c.rowptr.numel() != c.n_rows + 1:
+            raise _lib.AllSetHipError(f"han_walk_typed: hop {i}: rowptr of {c.rowptr.numel()} entries for {c.n_rows} rows, or a "
+                                      "non-contiguous CSR")
+        if i + 1 < L and c.n_cols != csrs[i + 1].n_rows:
+            raise _lib.AllSetHipError(f"han_walk_typed: hop {i} leads to {c.n_cols} nodes but hop {i + 1} starts from "
+                                      f"{csrs[i + 1].n_rows}: the chain's relations do not meet")
+    B, k = seeds.numel(), int(k)
+    out = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    rowptrs = (c_void_p * L)(*[ptr(c.rowptr) for c in csrs])
+    cols = (c_void_p * L)(*[ptr(c.col) if c.col.numel() else None for c in csrs])
+    n_rows = (c_int64_t * L)(*[c.n_rows for c in csrs])
+    # per walk and hop two row pointers and one column, then the endpoint
+    with on_device(dev), _timed("han_walk_typed", dev, B * max(k, 0) * (12 * L + 4) + B * 4):
+        check(_lib.load().allset_han_walk_typed(int(metapath_index), L, rowptrs, cols, n_rows, ptr(seeds), B, k,
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF, ptr(out),
+                                                stream_of(dev)), "allset_han_walk_typed")
     return out
 
 

@@ -970,6 +970,17 @@ int allset_han_sem_bwd(const float* z, const float* W1, const float* b1, const f
  * library's counter hash keyed on (seed, counter, metapath, global id of the seed node, walk index, hop) -- NOT on the seed's
  * position in the batch: a node's walks are the same in every batch.
  *
+ * allset_han_walk_typed: the same walk over a TYPED graph's metapath, a chain of L relation CSRs, 1 <= L <= 8 (HAN_MAX_HOPS;
+ * ALLSET_ERR_INVALID_ARGUMENT outside).  rowptrs / cols / n_rows are HOST arrays of L entries: hop h's device rowptr int32[n_rows[h] + 1],
+ * its device col (ids of the hop's destination type, duplicate edges kept: a duplicated edge is twice as likely; may be null for a
+ * relation without edges) and its row count.  seeds int32[B] are ids of the first hop's source type; endpoints int32[B, k] are ids
+ * of the last hop's destination type, -1 where the walk terminated: a seed outside [0, n_rows[0]), an empty row at any hop, or an
+ * intermediate id outside the next hop's rows -- every id is range-checked before it is used as a row, nothing further is read.
+ * Hop h draws with the key of allset_han_walk xor (h >> 1) * 0xA0761D6478BD642F and hop index h & 1: a pure function of (seed,
+ * counter, metapath, seed node, walk, hop), independent between the hops of a walk, and for L = 2 bit-identical to
+ * allset_han_walk(..., id_base = 0, ...) over the same two CSRs.  The table travels as a kernel argument: no allocation, no
+ * synchronisation, capturable.
+ *
  * allset_han_block_rows: per seed, the distinct endpoints other than -1 and the seed itself, ascending by global id, then the seed
  * (its one self-loop), then -1 padding, in row b of rows int32[B, k + 1]; counts int32[B] (self-loop included).  seeds_sorted
  * int32[B] = the seeds ascending.  extra int32[B, k + 1]: the same entries with members of the seed set and the padding replaced
@@ -988,6 +999,9 @@ int allset_han_sampling_supported(void);
 int allset_han_walk(int metapath, const int32_t* rowptr_a, const int32_t* col_a, const int32_t* rowptr_b, const int32_t* col_b,
                     int64_t n_a, int64_t n_b, int64_t id_base, const int32_t* seeds, int64_t B, int64_t k, uint64_t seed,
                     uint64_t counter, int32_t* endpoints, void* stream);
+int allset_han_walk_typed(int metapath, int64_t L, const int32_t* const* rowptrs, const int32_t* const* cols, const int64_t* n_rows,
+                          const int32_t* seeds, int64_t B, int64_t k, uint64_t seed, uint64_t counter, int32_t* endpoints,
+                          void* stream);
 int allset_han_block_rows(const int32_t* endpoints, const int32_t* seeds, const int32_t* seeds_sorted, int64_t B, int64_t k,
                           int32_t* rows, int32_t* extra, int32_t* counts, void* stream);
 int allset_han_block_compact(const int32_t* rows, const int32_t* counts, const int32_t* rowptr, const int32_t* seeds_sorted,
