@@ -270,7 +270,13 @@ SIGNATURES = {
     "allset_han_sampling_supported": [],
     "allset_han_walk": [c_int, _P, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, c_int64, c_uint64, c_uint64, _P, _P],
     "allset_han_walk_typed": [c_int, c_int64, _P, _P, _P, _P, c_int64, c_int64, c_uint64, c_uint64, _P, _P],
+    "allset_han_walk_dc": [c_int, _P, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, c_int64, c_uint64, _P, c_uint64, _P, _P],
+    "allset_han_walk_typed_dc": [c_int, c_int64, _P, _P, _P, _P, c_int64, c_int64, c_uint64, _P, c_uint64, _P, _P],
     "allset_han_block_rows": [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P],
+    "allset_han_block_fixed_max_slab": [_P],
+    "allset_han_block_relabel": [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P],
+    "allset_han_block_compact_fixed": [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P],
+    "allset_han_block_transpose": [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P],
     "allset_han_block_compact": [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P],
     "allset_han_block_hop_fwd": [c_int64, _P, _P, _P, _P, _P, c_int64, c_float, _P, c_float, c_uint64, _P, _P, c_int64, _P, c_int64, _P,
                                  _P, c_int64, c_int64, c_int64, c_int64, _P],

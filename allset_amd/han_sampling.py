@@ -19,6 +19,10 @@ A typed graph (the reference's ``ACMRaw`` branch, metapaths of edge types such a
 to ``ops.HAN_MAX_HOPS``, duplicate edges kept) in the ids of the node type every metapath starts from and ends on; everything after
 the walk is the same code.  ``--hetero`` runs it.
 
+``HANSampler.sample_blocks_fixed`` builds the same blocks at a capacity that depends on ``(B, k)`` alone and never reads a size back
+(:class:`FixedBlock`); :class:`GraphedSampledStep` replays one whole training step -- sampler included -- as one hipGraph
+(``--fixed_blocks`` / ``--graph_step``).
+
 Reference quirks kept: ``evaluate`` samples ``2 k`` walks and returns the LAST batch's loss (which ``EarlyStopping`` then consumes);
 ``HAN.forward`` hands the same blocks to every layer, so only ``len(num_heads) == 1`` can work -- more raises ``ValueError``.
 """
@@ -133,12 +137,13 @@ class TypedMetapathWalker:
         return [self.g.csr(rel) for rel in rels]
 
 
-def _walk(walker, mp: int, rels, s32: Tensor, k: int, seed: int, counter: int) -> Tensor:
-    """int32[B, k] endpoints of metapath ``mp``: over ``rels`` (a typed walker's relation chain) or, ``rels`` None, the incidence."""
+def _walk(walker, mp: int, rels, s32: Tensor, k: int, seed: int, counter, counter_add: int = 0) -> Tensor:
+    """int32[B, k] endpoints of metapath ``mp``: over ``rels`` (a typed walker's relation chain) or, ``rels`` None, the incidence.
+    ``counter``: an int, or a 1-element device tensor (plus ``counter_add``) the walk kernel reads."""
     if rels is not None:
-        return ops.han_walk_typed(mp, walker.chain(rels), s32, k, seed, counter)
+        return ops.han_walk_typed(mp, walker.chain(rels), s32, k, seed, counter, counter_add)
     a, b, base = walker.orientation(mp)
-    return ops.han_walk(mp, a, b, base, s32, k, seed, counter)
+    return ops.han_walk(mp, a, b, base, s32, k, seed, counter, counter_add)
 
 
 def _seeds_on_device(walker, seeds, check_dups: bool) -> Tensor:
@@ -204,6 +209,59 @@ class Block:
         return self.src_ids
 
 
+class FixedBlock(Block):
+    """A :class:`Block` whose Python-side shape depends on ``(B, k)`` alone, built without a host read-back
+    (:meth:`HANSampler.sample_blocks_fixed`): ``n_dst = B`` and ``n_src = nnz = B * (k + 1)``, the capacity that cannot overflow (at
+    most ``B * k`` distinct non-seed nodes, at most ``k + 1`` slots per target).  The real sizes stay on the device in ``sizes``,
+    int32[2] = ``{nnz_real, n_extra}`` (``n_src_real = B + n_extra``); :meth:`exact` reads them back and returns the ordinary block --
+    for tests and debugging, never for the training path.
+
+    Padding contract (what the hop kernels and a feature gather rely on):
+
+    * ``rowptr[B] == nnz_real``: no target row contains a slot ``>= nnz_real``;
+    * ``rowptrT[j] == nnz_real`` for every ``j >= n_src_real``: padded source rows are EMPTY rows of the source-major CSR (the hop's
+      backward writes exact zeros for them);
+    * every entry of ``col``, ``colT``, ``slotT``, ``dst`` and ``src_ids`` is in range over the full capacity: padding is 0, and the
+      first seed's id in ``src_ids``, so ``features[src_ids]`` is a valid gather;
+    * the real part is :meth:`HANSampler.sample_blocks`'s block entry for entry: ``rowptr``, ``col[:nnz]``, ``dst[:nnz]``,
+      ``src_ids[:n_src]``, ``rowptrT[:n_src + 1]``, ``colT[:nnz]``, ``slotT[:nnz]``; ``perm`` is the identity.
+
+    ``src`` / ``dst`` (the int64 edge list) and ``perm`` are made on first use: the model reads neither."""
+
+    def __init__(self, B: int, k: int, src_ids: Tensor, rowptr: Tensor, col: Tensor, dst32: Tensor, rowptrT: Tensor, colT: Tensor,
+                 slotT: Tensor, sizes: Tensor):
+        cap = FixedBlock.capacity(B, k)
+        self.n_dst, self.n_src, self.nnz, self.k = int(B), cap, cap, int(k)
+        self.src_ids, self.rowptr, self.col, self.dst32 = src_ids, rowptr, col, dst32
+        self.rowptrT, self.colT, self.slotT, self.sizes = rowptrT, colT, slotT, sizes
+
+    @staticmethod
+    def capacity(B: int, k: int) -> int:
+        """``B * (k + 1)``: source rows and slots of a fixed block of ``B`` targets with ``k`` walks each."""
+        return int(B) * (int(k) + 1)
+
+    @property
+    def src(self) -> Tensor:
+        return self.col.long()
+
+    @property
+    def dst(self) -> Tensor:
+        return self.dst32.long()
+
+    @property
+    def perm(self) -> Tensor:
+        return torch.arange(self.nnz, dtype=torch.int32, device=self.col.device)
+
+    def exact(self) -> Block:
+        """The ordinary :class:`Block` of the real part.  ONE host read-back: tests and debugging only."""
+        nnz, n_extra = (int(v) for v in self.sizes.tolist())
+        n_src = self.n_dst + n_extra
+        col, dst = self.col[:nnz], self.dst32[:nnz]
+        return Block(self.n_dst, n_src, self.src_ids[:n_src], col.long(), dst.long(), self.rowptr, col,
+                     torch.arange(nnz, dtype=torch.int32, device=col.device), self.rowptrT[:n_src + 1], self.colT[:nnz],
+                     self.slotT[:nnz])
+
+
 class HANSampler:
     """``HANSampler(g, metapath_list, num_neighbors)`` of the reference with the device-resident walker in ``g``'s place and an
     explicit ``seed``.  Every :meth:`sample_blocks` call takes the next step counter (or the one given).  With a
@@ -223,6 +281,48 @@ class HANSampler:
             self.metapaths = [metapath_index(m) for m in metapath_list]
             self.chains = [None] * len(self.metapaths)
         self.counter = 0
+        self.status: Optional[Tensor] = None       # sticky device word of the fixed path (1: a batch held duplicate seeds)
+
+    def sample_blocks_fixed(self, seeds, counter=None, counter_add: int = 0):
+        """``(seeds, [FixedBlock per metapath])``: :meth:`sample_blocks`'s blocks at the capacity ``B * (k + 1)`` (see
+        :class:`FixedBlock`), with NO host read-back and shapes that depend on ``(B, k)`` alone, so the call can be captured in a
+        hipGraph.  ``counter``: None (the sampler's next step counter), an int, or a 1-element uint64 / int64 device tensor the walk
+        kernels read (effective counter ``counter + counter_add``).  Duplicate seeds: a host list / CPU tensor is checked here; for
+        a device tensor the flag goes into the sampler's sticky device status word and :meth:`check` raises.  ``ValueError`` for an
+        empty batch; the library's "exceeds the built maximum" error beyond ``ops.han_fixed_max_slab()`` slots."""
+        w, k = self.walker, self.num_neighbors
+        B = int(seeds.numel()) if torch.is_tensor(seeds) else int(np.asarray(seeds).size)
+        if B == 0:
+            raise ValueError("sample_blocks_fixed: an empty batch (B == 0) has no fixed-capacity block")
+        ops.han_fixed_check(B, k)
+        if torch.is_tensor(counter) and not counter.is_cuda:
+            raise ValueError("sample_blocks_fixed: a counter tensor must live on the device; pass an int for a host counter")
+        s32 = _seeds_on_device(w, seeds, check_dups=True)
+        if counter is None:
+            counter = self.counter
+            self.counter += 1
+        if self.status is None:
+            self.status = torch.zeros(1, dtype=torch.int32, device=w.device)
+        sorted_seeds, order = torch.sort(s32)
+        blocks = []
+        for mp, rels in zip(self.metapaths, self.chains):
+            ends = _walk(w, mp, rels, s32, k, self.seed, counter, counter_add)
+            rows, extra, counts = ops.han_block_rows(ends, s32, sorted_seeds)
+            flat = torch.sort(extra.view(-1)).values
+            rowptr, uniq, sizes = ops.han_block_relabel(counts, flat, sorted_seeds, k, self.status)
+            col, dst, key, src_ids = ops.han_block_compact_fixed(rows, counts, rowptr, s32, sorted_seeds, order, uniq, sizes)
+            # source-major orientation: a stable sort of the slots by their key (the local source id; the capacity for padding)
+            keys_sorted, perm = torch.sort(key, stable=True)
+            rowptrT, colT, slotT = ops.han_block_transpose(keys_sorted, perm, dst, B, k)
+            blocks.append(FixedBlock(B, k, src_ids, rowptr, col, dst, rowptrT, colT, slotT, sizes))
+        return seeds, blocks
+
+    def check(self) -> None:
+        """Reads the fixed path's sticky status word (ONE read-back) and raises the ``ValueError`` of :meth:`sample_blocks` if any
+        batch of device seeds since the last call held duplicates; the word is cleared."""
+        if self.status is not None and int(self.status.item()):
+            self.status.zero_()
+            raise ValueError("duplicate seeds: a block's target nodes are distinct (dgl.to_block raises too)")
 
     def sample_blocks(self, seeds, counter: Optional[int] = None):
         """``(seeds, [Block per metapath])``.  One host read-back per call (every block's edge and node counts, together)."""
@@ -367,6 +467,99 @@ class HAN(nn.Module):
 
 
 # --------------------------------------------------------------------------------------------------
+# the whole step as one hipGraph
+# --------------------------------------------------------------------------------------------------
+
+class GraphedSampledStep:
+    """One mini-batch training step -- the device walk counter += 1, ``sample_blocks_fixed`` from a static int32 seed buffer, the
+    feature gather, forward, loss against a static label buffer, backward, optimizer -- captured as ONE graph on one stream
+    (``graphs.GraphedTrainStep``'s protocol: warm-up on the capture stream, ``dense.device_seed_counter`` for the dropout masks,
+    ``dense.deferred_param_grads``, a capturable optimizer, ``restore=True`` puts parameters and optimizer state back so that the
+    first replay is step 1).  ``loss = step(ids)`` copies ``ids`` and ``labels[ids]`` into the static buffers, replays and returns
+    the static loss tensor.  The batch size is fixed here; a shorter last batch goes through the eager path.  Replay ``i`` walks
+    with the step counter the sampler's next eager call would have used, and the sampler's counter advances with it."""
+
+    def __init__(self, model: nn.Module, sampler: HANSampler, features: Tensor, labels: Tensor, loss_fn, optimizer, batch_size: int,
+                 warmup: int = 3, train_mode: bool = True, restore: bool = True):
+        from .graphs import _side_stream_warmup
+        from .optim import FusedAdam
+        for grp in optimizer.param_groups:
+            if not grp.get("capturable", False):
+                raise _lib.AllSetHipError("GraphedSampledStep needs a capturable optimizer (optim.FusedAdam, or "
+                                          "torch.optim.Adam(..., capturable=True))")
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError("GraphedSampledStep: batch_size must be >= 1")
+        ops.han_fixed_check(B, sampler.num_neighbors)
+        _lib.require_device(features, labels)
+        if B > sampler.walker.n:
+            raise ValueError(f"GraphedSampledStep: batch_size {B} exceeds the {sampler.walker.n} nodes seeds are drawn from")
+        dev = features.device
+        self.model, self.sampler, self.optimizer, self.labels, self.batch_size = model, sampler, optimizer, labels, B
+        self.ids = torch.arange(B, dtype=torch.int32, device=dev)                 # warm-up seeds: distinct and in range
+        self.batch_labels = labels[:B].clone()
+        self.walk_counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)             # the dropout masks' device seed counter
+        # (derived from the sampler's seed, not drawn: building the step leaves torch's generators where the eager driver has them)
+        self.counter.fill_(((sampler.seed + 1) * 0x9E3779B97F4A7C15) & 0x3FFFFFFFFFFFFFFF)
+        model.train(train_mode)
+        one = self._one = torch.ones((), dtype=torch.float32, device=dev)
+        fused = isinstance(optimizer, FusedAdam)
+
+        def one_step():
+            optimizer.zero_grad(set_to_none=True)
+            self.walk_counter.add_(1)
+            _, blocks = sampler.sample_blocks_fixed(self.ids, counter=self.walk_counter)
+            loss = loss_fn(model(blocks, load_subtensors(blocks, features)), self.batch_labels)
+            with dense.deferred_param_grads(bump_i64=self.counter, bump_f32=optimizer.step_counters if fused else None):
+                loss.backward(one if (loss.dim() == 0 and loss.dtype == one.dtype) else None)
+            if fused:
+                optimizer.step(counters_advanced=True)
+            else:
+                optimizer.step()
+            return loss
+
+        params = [p for grp in optimizer.param_groups for p in grp["params"]]
+        if restore:
+            with torch.no_grad():
+                p_snap = [p.detach().clone() for p in params]
+                s_snap = {p: {k: v.clone() for k, v in optimizer.state.get(p, {}).items() if torch.is_tensor(v)} for p in params}
+                b_snap = [(b, b.detach().clone()) for b in model.buffers()]
+        with torch.cuda.device(dev), dense.device_seed_counter(self.counter):
+            st = _side_stream_warmup(one_step, max(1, warmup))
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=st):
+                self.loss = one_step()
+        if restore:
+            with torch.no_grad():
+                for p, snap in zip(params, p_snap):
+                    p.copy_(snap)
+                    for k, v in optimizer.state.get(p, {}).items():
+                        if torch.is_tensor(v):
+                            v.copy_(s_snap[p][k]) if k in s_snap[p] else v.zero_()
+                for b, snap in b_snap:
+                    b.copy_(snap)
+        self._walk_mirror: Optional[int] = None                                   # the device walk counter's value, as the host knows it
+
+    def step(self, ids: Tensor) -> Tensor:
+        if ids.numel() != self.batch_size:
+            raise ValueError(f"GraphedSampledStep: {ids.numel()} seeds for a step captured at batch size {self.batch_size}; run a "
+                             "shorter batch through the eager path")
+        _lib.require_device(ids)
+        self.ids.copy_(ids.view(-1))
+        torch.index_select(self.labels, 0, ids.view(-1).long(), out=self.batch_labels)
+        want = self.sampler.counter - 1                                          # the graph adds one before it walks
+        if self._walk_mirror != want:
+            self.walk_counter.fill_(want)
+        self.graph.replay()
+        self._walk_mirror = want + 1
+        self.sampler.counter += 1
+        return self.loss
+
+    __call__ = step
+
+
+# --------------------------------------------------------------------------------------------------
 # driver (reference DGL_HAN/train_sampling.py)
 # --------------------------------------------------------------------------------------------------
 
@@ -417,11 +610,16 @@ def build_parser() -> argparse.ArgumentParser:
     # additions of this driver: where train.py's loaders find a named dataset
     p.add_argument('--raw_data_dir', default=None)
     p.add_argument('--processed_data', default=None)
+    p.add_argument('--fixed_blocks', action='store_true', help='train over fixed-capacity blocks built without a host read-back '
+                   '(HANSampler.sample_blocks_fixed) and optim.FusedAdam')
+    p.add_argument('--graph_step', action='store_true', help='implies --fixed_blocks: full batches replay one captured hipGraph '
+                   '(GraphedSampledStep); the last, shorter batch of an epoch and evaluation run eagerly')
     return p
 
 
 def setup(args: dict) -> dict:
     args['num_heads'] = [8]
+    args['fixed_blocks'] = bool(args.get('fixed_blocks') or args.get('graph_step'))       # --graph_step implies --fixed_blocks
     np.random.seed(args['seed'])
     torch.manual_seed(args['seed'])
     args['device'] = f"cuda:{args['cuda']}"
@@ -461,7 +659,15 @@ def main(args: dict) -> dict:
                     num_heads=args['num_heads'], dropout=args['dropout']).to(args['device'])
         stopper = EarlyStopping(patience=args['patience'])
         loss_fn = torch.nn.CrossEntropyLoss()
-        optimizer = torch.optim.Adam(model.parameters(), lr=args['lr'], weight_decay=args['weight_decay'])
+        fixed = bool(args.get('fixed_blocks') or args.get('graph_step'))
+        graphed = None
+        if fixed:
+            from .optim import FusedAdam
+            optimizer = FusedAdam(model.parameters(), lr=args['lr'], weight_decay=args['weight_decay'])
+            if args.get('graph_step') and train_nid.numel() >= bs:
+                graphed = GraphedSampledStep(model, sampler, features, labels, loss_fn, optimizer, bs)
+        else:
+            optimizer = torch.optim.Adam(model.parameters(), lr=args['lr'], weight_decay=args['weight_decay'])
         start = time.time()
         epoch_losses = []
         eval_counter = 1 << 40                                         # evaluation draws from its own range of step counters
@@ -470,7 +676,10 @@ def main(args: dict) -> dict:
             perm = torch.randperm(train_nid.numel(), generator=shuffle).to(train_nid.device)       # DataLoader(shuffle=True)
             losses = []
             for ids in _batches(train_nid[perm], bs):
-                seeds, blocks = sampler.sample_blocks(ids)
+                if graphed is not None and ids.numel() == bs:
+                    losses.append(graphed.step(ids).detach().clone())
+                    continue
+                seeds, blocks = sampler.sample_blocks_fixed(ids) if fixed else sampler.sample_blocks(ids)
                 logits = model(blocks, load_subtensors(blocks, features))
                 loss = loss_fn(logits, labels[ids])
                 optimizer.zero_grad()
@@ -478,6 +687,8 @@ def main(args: dict) -> dict:
                 optimizer.step()
                 losses.append(loss.detach())
             epoch_losses.append(float(torch.stack(losses).mean()))
+            if fixed:
+                sampler.check()                                            # the epoch's one read of the duplicate-seed status word
             val_loss, val_acc, _, _ = evaluate(model, walker, metapath_list, k, features, labels, val_nid, loss_fn, bs, sample_seed,
                                                eval_counter)
             eval_counter += 1 << 20

@@ -1543,16 +1543,41 @@ def _i32(t: Tensor, what: str) -> Tensor:
     return t.contiguous()
 
 
-def han_walk(metapath: int, csr_a: CSR, csr_b: CSR, id_base: int, seeds: Tensor, k: int, seed: int, counter: int) -> Tensor:
+def _han_counter(who: str, counter, counter_add: int):
+    """``(device tensor or None, 64-bit value)`` of a walk's step counter: an int travels by value (``counter_add`` added here); a
+    1-element uint64 / int64 DEVICE tensor is read by the kernel, which adds ``counter_add`` (64-bit wrap either way)."""
+    add = int(counter_add) & 0xFFFFFFFFFFFFFFFF
+    if not torch.is_tensor(counter):
+        return None, (int(counter) + add) & 0xFFFFFFFFFFFFFFFF
+    if counter.dtype not in (torch.uint64, torch.int64) or counter.numel() != 1:
+        raise _lib.AllSetHipError(f"{who}: a counter tensor is ONE uint64 / int64 element (got {counter.dtype}, {counter.numel()} "
+                                  "elements)")
+    if not counter.is_cuda:
+        raise _lib.AllSetHipError(f"{who}: a counter tensor must live on the device (got a CPU tensor); pass an int for a host counter")
+    return counter, add
+
+
+def han_walk(metapath: int, csr_a: CSR, csr_b: CSR, id_base: int, seeds: Tensor, k: int, seed: int, counter, counter_add: int = 0) -> Tensor:
     """``k`` two-hop walks per seed over CSR ``csr_a`` then ``csr_b`` (the binarised incidence in the metapath's orientation):
-    endpoints int32[B, k] in global ids, -1 where the walk terminates.  ``seeds`` int32[B] global ids."""
-    dev = require_device(csr_a.rowptr, csr_a.col, csr_b.rowptr, csr_b.col, seeds)
+    endpoints int32[B, k] in global ids, -1 where the walk terminates.  ``seeds`` int32[B] global ids.  ``counter``: an int, or a
+    1-element uint64 / int64 device tensor the kernel reads (the effective counter is ``counter + counter_add`` mod 2^64; equal
+    effective counters give bit-identical walks)."""
+    ctensor, cval = _han_counter("han_walk", counter, counter_add)
+    dev = require_device(csr_a.rowptr, csr_a.col, csr_b.rowptr, csr_b.col, seeds, ctensor)
     seeds = _i32(seeds, "han_walk seeds")
     B, k = seeds.numel(), int(k)
     if csr_a.n_cols != csr_b.n_rows or csr_b.n_cols != csr_a.n_rows:
         raise _lib.AllSetHipError(f"han_walk: CSR A {csr_a.n_rows} x {csr_a.n_cols} and CSR B {csr_b.n_rows} x {csr_b.n_cols} are not "
                                   "the two orientations of one incidence")
     out = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    if ctensor is not None:
+        with on_device(dev), _timed("han_walk", dev, B * max(k, 0) * 20 + B * 4):
+            check(_lib.load().allset_han_walk_dc(int(metapath), ptr(csr_a.rowptr), ptr(csr_a.col), ptr(csr_b.rowptr), ptr(csr_b.col),
+                                                 csr_a.n_rows, csr_b.n_rows, int(id_base), ptr(seeds), B, k,
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ctensor), cval, ptr(out), stream_of(dev)),
+                  "allset_han_walk_dc")
+        return out
+    counter = cval
     with on_device(dev), _timed("han_walk", dev, B * max(k, 0) * 20 + B * 4):
         check(_lib.load().allset_han_walk(int(metapath), ptr(csr_a.rowptr), ptr(csr_a.col), ptr(csr_b.rowptr), ptr(csr_b.col),
                                           csr_a.n_rows, csr_b.n_rows, int(id_base), ptr(seeds), B, k,
@@ -1561,16 +1586,18 @@ def han_walk(metapath: int, csr_a: CSR, csr_b: CSR, id_base: int, seeds: Tensor,
     return out
 
 
-def han_walk_typed(metapath_index: int, csrs: Sequence[CSR], seeds: Tensor, k: int, seed: int, counter: int) -> Tensor:
+def han_walk_typed(metapath_index: int, csrs: Sequence[CSR], seeds: Tensor, k: int, seed: int, counter, counter_add: int = 0) -> Tensor:
     """``k`` walks per seed along the chain ``csrs`` of relation CSRs (rows = source ids, as ``HeteroGraph.csr`` builds them;
     duplicate edges kept): endpoints int32[B, k] in the ids of the last relation's destination type, -1 where the walk terminates.
-    ``seeds`` int32[B] ids of the first relation's source type.  For two hops, bit-identical to :func:`han_walk` with ``id_base`` 0."""
+    ``seeds`` int32[B] ids of the first relation's source type.  For two hops, bit-identical to :func:`han_walk` with ``id_base`` 0.
+    ``counter`` / ``counter_add`` as there."""
+    ctensor, cval = _han_counter("han_walk_typed", counter, counter_add)
     csrs = list(csrs)
     L = len(csrs)
     if not 1 <= L <= HAN_MAX_HOPS:
         raise _lib.AllSetHipError(f"han_walk_typed: a metapath of {L} hops; the walk kernel is built for 1 to HAN_MAX_HOPS = "
                                   f"{HAN_MAX_HOPS}")
-    dev = require_device(*[t for c in csrs for t in (c.rowptr, c.col)], seeds)
+    dev = require_device(*[t for c in csrs for t in (c.rowptr, c.col)], seeds, ctensor)
     seeds = _i32(seeds, "han_walk_typed seeds")
     for i, c in enumerate(csrs):
         _i32(c.rowptr, f"han_walk_typed rowptr of hop {i}"), _i32(c.col, f"han_walk_typed col of hop {i}")
@@ -1586,6 +1613,13 @@ def han_walk_typed(metapath_index: int, csrs: Sequence[CSR], seeds: Tensor, k: i
     cols = (c_void_p * L)(*[ptr(c.col) if c.col.numel() else None for c in csrs])
     n_rows = (c_int64_t * L)(*[c.n_rows for c in csrs])
     # per walk and hop two row pointers and one column, then the endpoint
+    if ctensor is not None:
+        with on_device(dev), _timed("han_walk_typed", dev, B * max(k, 0) * (12 * L + 4) + B * 4):
+            check(_lib.load().allset_han_walk_typed_dc(int(metapath_index), L, rowptrs, cols, n_rows, ptr(seeds), B, k,
+                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ctensor), cval, ptr(out), stream_of(dev)),
+                  "allset_han_walk_typed_dc")
+        return out
+    counter = cval
     with on_device(dev), _timed("han_walk_typed", dev, B * max(k, 0) * (12 * L + 4) + B * 4):
         check(_lib.load().allset_han_walk_typed(int(metapath_index), L, rowptrs, cols, n_rows, ptr(seeds), B, k,
                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF, ptr(out),
@@ -1628,3 +1662,99 @@ def han_block_compact(rows: Tensor, counts: Tensor, rowptr: Tensor, seeds_sorted
                                                    ptr(seed_perm.contiguous()), ptr(uniq.contiguous()), int(n_extra), B, k, int(nnz), ptr(col),
                                                    ptr(dst), stream_of(dev)), "allset_han_block_compact")
     return col, dst
+
+
+_HAN_FIXED_MAX_SLAB: Optional[int] = None
+
+
+def han_fixed_max_slab() -> int:
+    """The largest slab ``B * (k + 1)`` the fixed-capacity block kernels are built for."""
+    global _HAN_FIXED_MAX_SLAB
+    if _HAN_FIXED_MAX_SLAB is None:
+        n = c_int64_t(0)
+        check(_lib.load().allset_han_block_fixed_max_slab(byref(n)), "allset_han_block_fixed_max_slab")
+        _HAN_FIXED_MAX_SLAB = n.value
+    return _HAN_FIXED_MAX_SLAB
+
+
+def han_fixed_check(B: int, k: int) -> int:
+    """The capacity ``B * (k + 1)`` of a fixed block; refuses (host only) an empty batch, ``k`` outside the walk's and a slab beyond
+    :func:`han_fixed_max_slab`."""
+    B, k = int(B), int(k)
+    if B < 1:
+        raise _lib.AllSetHipError("a fixed-capacity block needs at least one seed (B == 0)")
+    if not 1 <= k <= HAN_MAX_WALKS:
+        raise _lib.AllSetHipError(f"a fixed-capacity block: k = {k} walks per seed outside [1, {HAN_MAX_WALKS}]")
+    cap, limit = B * (k + 1), han_fixed_max_slab()
+    if cap > limit:
+        raise _lib.AllSetHipError(f"a fixed-capacity block of B * (k + 1) = {B} * {k + 1} = {cap} slots exceeds the built maximum "
+                                  f"({limit}): not built")
+    return cap
+
+
+def han_block_relabel(counts: Tensor, extra_sorted: Tensor, seeds_sorted: Tensor, k: int, status: Optional[Tensor] = None
+                      ) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(rowptr int32[B + 1], uniq int32[cap], sizes int32[2] = {nnz, n_extra})`` from the row lengths and the SORTED extra slab
+    (``cap = B * (k + 1)`` entries), one launch; ``status`` (int32[1]) is set to 1 when ``seeds_sorted`` holds a duplicate."""
+    dev = require_device(counts, extra_sorted, seeds_sorted, status)
+    for t in (counts, extra_sorted, seeds_sorted) + ((status,) if status is not None else ()):
+        _i32(t, "han_block_relabel")
+    B = counts.numel()
+    cap = han_fixed_check(B, k)
+    if extra_sorted.numel() != cap or seeds_sorted.numel() != B or (status is not None and status.numel() != 1) or not (
+            counts.is_contiguous() and extra_sorted.is_contiguous() and seeds_sorted.is_contiguous()):
+        raise _lib.AllSetHipError(f"han_block_relabel: extra slab of {extra_sorted.numel()} / {seeds_sorted.numel()} sorted seeds for "
+                                  f"B = {B}, k = {k}, or a non-contiguous tensor")
+    rowptr = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    uniq = torch.empty((cap,), dtype=torch.int32, device=dev)
+    sizes = torch.empty((2,), dtype=torch.int32, device=dev)
+    with on_device(dev), _timed("han_block_relabel", dev, (2 * B + 2 * cap) * 4):
+        check(_lib.load().allset_han_block_relabel(ptr(counts), ptr(extra_sorted), ptr(seeds_sorted), B, int(k), ptr(rowptr), ptr(uniq),
+                                                   ptr(sizes), ptr(status), stream_of(dev)), "allset_han_block_relabel")
+    return rowptr, uniq, sizes
+
+
+def han_block_compact_fixed(rows: Tensor, counts: Tensor, rowptr: Tensor, seeds: Tensor, seeds_sorted: Tensor, seed_order: Tensor,
+                            uniq: Tensor, sizes: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``(col, dst, key int32[cap], src_ids int64[cap])``: :func:`han_block_compact` with the sizes on the device and every slot
+    written (padding: ``col = dst = 0``, ``key = cap``; ``src_ids``: the seeds, the distinct other nodes, then the first seed)."""
+    dev = require_device(rows, counts, rowptr, seeds, seeds_sorted, seed_order, uniq, sizes)
+    for t in (rows, counts, rowptr, seeds, seeds_sorted, uniq, sizes):
+        _i32(t, "han_block_compact_fixed")
+    if rows.dim() != 2 or seed_order.dtype != torch.int64:
+        raise _lib.AllSetHipError(f"han_block_compact_fixed: rows {tuple(rows.shape)}, seed_order {seed_order.dtype} (int64: the sort's "
+                                  "permutation)")
+    B, k = rows.shape[0], rows.shape[1] - 1
+    cap = han_fixed_check(B, k)
+    ts = (rows, counts, rowptr, seeds, seeds_sorted, seed_order, uniq, sizes)
+    if ([t.numel() for t in ts] != [cap, B, B + 1, B, B, B, cap, 2]) or not all(t.is_contiguous() for t in ts):
+        raise _lib.AllSetHipError(f"han_block_compact_fixed: sizes {[t.numel() for t in ts]} for B = {B}, k = {k}, or a non-contiguous "
+                                  "tensor")
+    col = torch.empty((cap,), dtype=torch.int32, device=dev)
+    dst = torch.empty((cap,), dtype=torch.int32, device=dev)
+    key = torch.empty((cap,), dtype=torch.int32, device=dev)
+    src_ids = torch.empty((cap,), dtype=torch.int64, device=dev)
+    with on_device(dev), _timed("han_block_compact_fixed", dev, cap * 28):
+        check(_lib.load().allset_han_block_compact_fixed(ptr(rows), ptr(counts), ptr(rowptr), ptr(seeds), ptr(seeds_sorted),
+                                                         ptr(seed_order), ptr(uniq), ptr(sizes), B, k, ptr(col), ptr(dst), ptr(key),
+                                                         ptr(src_ids), stream_of(dev)), "allset_han_block_compact_fixed")
+    return col, dst, key, src_ids
+
+
+def han_block_transpose(keys_sorted: Tensor, perm: Tensor, dst: Tensor, B: int, k: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(rowptrT int32[cap + 1], colT, slotT int32[cap])`` of the source-major CSR from the stably sorted keys of
+    :func:`han_block_compact_fixed` and the sort's permutation (int64), one launch."""
+    dev = require_device(keys_sorted, perm, dst)
+    _i32(keys_sorted, "han_block_transpose"), _i32(dst, "han_block_transpose")
+    cap = han_fixed_check(B, k)
+    if perm.dtype != torch.int64 or [keys_sorted.numel(), perm.numel(), dst.numel()] != [cap] * 3 or not (
+            keys_sorted.is_contiguous() and perm.is_contiguous() and dst.is_contiguous()):
+        raise _lib.AllSetHipError(f"han_block_transpose: keys {keys_sorted.numel()} / perm {perm.numel()} ({perm.dtype}) / dst "
+                                  f"{dst.numel()} for a capacity of {cap}, or a non-contiguous tensor")
+    rowptrT = torch.empty((cap + 1,), dtype=torch.int32, device=dev)
+    colT = torch.empty((cap,), dtype=torch.int32, device=dev)
+    slotT = torch.empty((cap,), dtype=torch.int32, device=dev)
+    with on_device(dev), _timed("han_block_transpose", dev, cap * 28):
+        check(_lib.load().allset_han_block_transpose(ptr(keys_sorted), ptr(perm), ptr(dst), int(B), int(k), ptr(rowptrT), ptr(colT),
+                                                     ptr(slotT), stream_of(dev)), "allset_han_block_transpose")
+    return rowptrT, colT, slotT

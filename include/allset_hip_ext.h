@@ -981,6 +981,11 @@ int allset_han_sem_bwd(const float* z, const float* W1, const float* b1, const f
  * allset_han_walk(..., id_base = 0, ...) over the same two CSRs.  The table travels as a kernel argument: no allocation, no
  * synchronisation, capturable.
  *
+ * allset_han_walk_dc / allset_han_walk_typed_dc: the two walks with the step counter in DEVICE memory: `counter` points to one
+ * uint64 the kernel reads when it runs, and the effective counter is *counter + counter_add (wrapping in 64 bits).  The key is formed
+ * in the kernel; for equal effective counters the endpoints are bit-identical to the by-value entries'.  A captured graph whose
+ * counter another node advances draws new walks at every replay.
+ *
  * allset_han_block_rows: per seed, the distinct endpoints other than -1 and the seed itself, ascending by global id, then the seed
  * (its one self-loop), then -1 padding, in row b of rows int32[B, k + 1]; counts int32[B] (self-loop included).  seeds_sorted
  * int32[B] = the seeds ascending.  extra int32[B, k + 1]: the same entries with members of the seed set and the padding replaced
@@ -989,6 +994,20 @@ int allset_han_sem_bwd(const float* z, const float* W1, const float* b1, const f
  * allset_han_block_compact: rowptr int32[B + 1] = exclusive prefix sum of counts, nnz = rowptr[B]; seed_perm int32[B]: position in
  * seeds of seeds_sorted[i]; uniq int32[n_extra]: the distinct non-seed source nodes ascending.  Writes the target-major CSR's
  * col int32[nnz] (block-local source ids: seeds first in their given order, then uniq's order) and dst int32[nnz] (the target b).
+ *
+ * Fixed-capacity block, no size ever read back: every array is sized by the slab cap = B (k + 1), B >= 1, cap <=
+ * allset_han_block_fixed_max_slab() (ALLSET_ERR_UNSUPPORTED beyond); the real sizes stay in sizes int32[2] = {nnz, n_extra}.
+ * allset_han_block_relabel (ONE launch of one workgroup): counts int32[B] and extra_sorted int32[cap] (the extra slab of
+ * allset_han_block_rows, sorted ascending) -> rowptr int32[B + 1] (exclusive prefix sum of counts), uniq int32[cap] (the distinct
+ * entries other than INT32_MAX ascending, the tail INT32_MAX) and sizes; status (may be null) is set to 1 -- never cleared -- when
+ * seeds_sorted int32[B] holds two equal neighbours (duplicate seeds).
+ * allset_han_block_compact_fixed: allset_han_block_compact with nnz / n_extra taken from sizes and seed_order int64[B] (the
+ * permutation of the seeds' sort) in seed_perm's place; writes ALL cap slots of col, dst and key int32[cap] -- real slots as there
+ * with key = col, slots >= nnz as col = dst = 0 and key = cap -- and src_ids int64[cap]: the seeds, then uniq[0, n_extra), then the
+ * first seed.  allset_han_block_transpose (one launch): keys_sorted int32[cap] and perm int64[cap] (a STABLE sort of key and its
+ * permutation) -> rowptrT int32[cap + 1] (rowptrT[j] = the first position whose key is >= j: nnz for every j past the real source
+ * rows), colT = dst[perm] and slotT = perm int32[cap], both 0 for padding.  Every entry written is in range; perm is range-checked
+ * before it indexes dst.
  *
  * allset_han_block_hop_fwd / _bwd_stats / _bwd_src: allset_han_hop_fwd / _bwd_stats / _bwd_src over a bipartite block of n_src
  * source rows and n_dst <= n_src target rows: x, el, gx, gel have n_src rows; er, y, outpos, ppos, lse, gy, g, stats, ger have
@@ -1002,8 +1021,22 @@ int allset_han_walk(int metapath, const int32_t* rowptr_a, const int32_t* col_a,
 int allset_han_walk_typed(int metapath, int64_t L, const int32_t* const* rowptrs, const int32_t* const* cols, const int64_t* n_rows,
                           const int32_t* seeds, int64_t B, int64_t k, uint64_t seed, uint64_t counter, int32_t* endpoints,
                           void* stream);
+int allset_han_walk_dc(int metapath, const int32_t* rowptr_a, const int32_t* col_a, const int32_t* rowptr_b, const int32_t* col_b,
+                       int64_t n_a, int64_t n_b, int64_t id_base, const int32_t* seeds, int64_t B, int64_t k, uint64_t seed,
+                       const uint64_t* counter, uint64_t counter_add, int32_t* endpoints, void* stream);
+int allset_han_walk_typed_dc(int metapath, int64_t L, const int32_t* const* rowptrs, const int32_t* const* cols, const int64_t* n_rows,
+                             const int32_t* seeds, int64_t B, int64_t k, uint64_t seed, const uint64_t* counter, uint64_t counter_add,
+                             int32_t* endpoints, void* stream);
 int allset_han_block_rows(const int32_t* endpoints, const int32_t* seeds, const int32_t* seeds_sorted, int64_t B, int64_t k,
                           int32_t* rows, int32_t* extra, int32_t* counts, void* stream);
+int allset_han_block_fixed_max_slab(int64_t* slots);
+int allset_han_block_relabel(const int32_t* counts, const int32_t* extra_sorted, const int32_t* seeds_sorted, int64_t B, int64_t k,
+                             int32_t* rowptr, int32_t* uniq, int32_t* sizes, int32_t* status, void* stream);
+int allset_han_block_compact_fixed(const int32_t* rows, const int32_t* counts, const int32_t* rowptr, const int32_t* seeds,
+                                   const int32_t* seeds_sorted, const int64_t* seed_order, const int32_t* uniq, const int32_t* sizes,
+                                   int64_t B, int64_t k, int32_t* col, int32_t* dst, int32_t* key, int64_t* src_ids, void* stream);
+int allset_han_block_transpose(const int32_t* keys_sorted, const int64_t* perm, const int32_t* dst, int64_t B, int64_t k,
+                               int32_t* rowptrT, int32_t* colT, int32_t* slotT, void* stream);
 int allset_han_block_compact(const int32_t* rows, const int32_t* counts, const int32_t* rowptr, const int32_t* seeds_sorted,
                              const int32_t* seed_perm, const int32_t* uniq, int64_t n_extra, int64_t B, int64_t k, int64_t nnz,
                              int32_t* col, int32_t* dst, void* stream);

@@ -8,6 +8,12 @@ same device with torch's own generator, and ``tests/han_sampling_oracle.py`` is 
 median of ``--repeats`` repetitions of ``--steps`` steps with the spread (min .. max) beside it.
 
     python tools/han_sampling_profile.py [--out profiles/han_sampling.json]
+
+``--fixed`` measures the sync-free path instead, for the same four rows: the eager step as it was (the
+yardstick, re-measured in the same session), the sampler over ``sample_blocks_fixed`` (launches and time), the eager step on fixed
+blocks and the step replayed as one graph (``GraphedSampledStep``):
+
+    python tools/han_sampling_profile.py --fixed --out profiles/han_sampling_fixed.json
 """
 from __future__ import annotations
 
@@ -106,6 +112,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--num_neighbors", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fixed", action="store_true", help="the fixed-capacity / graphed columns instead of the eager breakdown")
     a = ap.parse_args()
     from allset_amd import han_sampling as hs, ops
     import han_sampling_oracle as orc
@@ -162,6 +169,42 @@ def main():
                 sample()
                 fwd_bwd()
 
+            if a.fixed:
+                from allset_amd.optim import FusedAdam
+
+                def sample_fixed():
+                    state["fixed"] = sampler.sample_blocks_fixed(ids)[1]
+
+                torch.manual_seed(0)
+                model_f = hs.HAN(2, feats.shape[1], 8, n_cls, [8], 0.6).to(DEV).train()
+                opt_f = FusedAdam(model_f.parameters(), lr=0.001, weight_decay=0.001)
+
+                def step_fixed():
+                    sample_fixed()
+                    blocks = state["fixed"]
+                    loss = loss_fn(model_f(blocks, hs.load_subtensors(blocks, feats)), labels[ids])
+                    opt_f.zero_grad()
+                    loss.backward()
+                    opt_f.step()
+
+                torch.manual_seed(0)
+                model_g = hs.HAN(2, feats.shape[1], 8, n_cls, [8], 0.6).to(DEV).train()
+                opt_g = FusedAdam(model_g.parameters(), lr=0.001, weight_decay=0.001)
+                graphed = hs.GraphedSampledStep(model_g, hs.HANSampler(walker, hs.DEFAULT_METAPATHS, k, seed=1), feats, labels, loss_fn,
+                                                opt_g, B)
+                step(), step_fixed(), graphed.step(ids)
+                r = dict(dataset=dname, batch_size=B, num_neighbors=k, capacity=hs.FixedBlock.capacity(B, k),
+                         n_src=[b.n_src for b in state["blocks"]], nnz=[b.nnz for b in state["blocks"]])
+                r["step_eager"] = timed(step, a.steps, a.repeats)                     # the yardstick: the step as it was
+                r["sampler_hip"] = timed(sample, a.steps, a.repeats)
+                r["sampler_fixed"] = timed(sample_fixed, a.steps, a.repeats)
+                r["step_fixed_eager"] = timed(step_fixed, a.steps, a.repeats)
+                r["step_graphed"] = timed(lambda: graphed.step(ids), a.steps, a.repeats)
+                r["launches"] = dict(sampler=count_launches(sample), sampler_fixed=count_launches(sample_fixed),
+                                     step=count_launches(step), step_fixed_eager=count_launches(step_fixed))
+                results.append(r)
+                print(json.dumps(r), flush=True)
+                continue
             sample()
             r = dict(dataset=dname, batch_size=B, num_neighbors=k, n_src=[b.n_src for b in state["blocks"]],
                      nnz=[b.nnz for b in state["blocks"]])
