@@ -21,6 +21,7 @@ CORE_ABI_VERSION = 1
 SUM, MEAN, MAX, MIN = 0, 1, 2, 3
 F32, BF16 = 0, 1
 REDUCE_AS_TREE = 0x100
+PACK_PITCH_DW, PACK_CAP = 64, 60                              # include/allset_hip_ext.h kPackPitchDw / kPackCap
 ARITH_AUTO, ARITH_BF16X6, ARITH_FP16X3 = 0, 1, 2          # include/allset_hip_ext.h ALLSET_ARITH_*
 ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2                       # include/allset_hip_ext.h ALLSET_HCONV_ACT_*
 REDUCE_CODES = {"add": SUM, "sum": SUM, "mean": MEAN, "max": MAX, "min": MIN}
@@ -317,6 +318,9 @@ SIGNATURES = {
     "allset_scan_rows": [_P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, _P],
     "allset_scan_collect": [_P, _P, _P, c_int64, _P, _P, c_int64, _P, _P, c_int, c_float, c_uint64, _P, _P, c_int64, c_int64, c_int64,
                             c_int64, c_int64, _P],
+    # packed nonzero rows for the forward Deep Sets gather (under ABI 15, additions only; fp32, d = 128)
+    "allset_pack_rows_f32": [_P, c_int64, _P, c_int64, c_int64, _P],
+    "allset_segreduce_packed_fwd": [c_int, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

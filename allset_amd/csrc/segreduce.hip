@@ -355,6 +355,177 @@ __global__ __launch_bounds__(kBlock) void sddmm_rowdot_vec_kernel(
   }
 }
 
+// ---- packed nonzero rows (include/allset_hip_ext.h: 128-bit occupancy mask + the occupied elements, 256 bytes per row) --------
+// The forward aggregations gather dropout(relu(.)) tables, about 3/4 zeros: a packed row is two 128-byte lines where the dense row is
+// four, and what bounds the gather is the count of line requests.
+constexpr int kPackRowsPerWave = 4;      // pack_rows_kernel: two rows per 16-byte load instruction, two of them in flight
+constexpr int kExpand = 2;               // segreduce_packed_kernel: gathered rows per slot expanded through LDS together (and skipped together)
+
+// the LDS hand-off between lanes of ONE wave (the LDS serves a wave's operations in order): keeps the compiler from moving accesses across
+__device__ __forceinline__ void lds_wave_handoff() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// 0xFFFFFFFF when bit `b` of `m` is set, else 0: one signed bit-field extract
+__device__ __forceinline__ uint32_t all_ones_if_bit(uint32_t m, int b) {
+  return static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(m), static_cast<unsigned>(b), 1u));
+}
+
+__device__ __forceinline__ int mask_count(const uint4& m) { return __popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w); }
+
+// Half a wave per row, 16 bytes per lane (columns 4 li .. 4 li + 3): the mask dwords are OR-reduced over the 8 lanes that share one, the
+// values are scattered into an LDS image of the row at 4 + (occupied columns below), and the wave's four images leave in ONE coalesced
+// 16-byte store per lane (1 KiB).
+__global__ __launch_bounds__(kBlock) void pack_rows_kernel(const float* __restrict__ x, int64_t ldx, uint32_t* __restrict__ packed, int64_t n) {
+  __shared__ __attribute__((aligned(16))) uint32_t image[kWavesPerBlock][kPackRowsPerWave][kPackPitchDw];
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const int slot = lane >> 5, li = lane & 31;
+  const int64_t row0 = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave) * kPackRowsPerWave;
+  if (row0 >= n) return;  // whole wave exits together
+  uint4 raw[kPackRowsPerWave / 2];
+#pragma unroll
+  for (int p = 0; p < kPackRowsPerWave / 2; ++p) {
+    const int64_t r = row0 + 2 * p + slot;
+    raw[p] = r < n ? *reinterpret_cast<const uint4*>(x + r * ldx + 4 * li) : make_uint4(0u, 0u, 0u, 0u);
+  }
+#pragma unroll
+  for (int p = 0; p < kPackRowsPerWave / 2; ++p) {
+    uint32_t* dst = image[wave][2 * p + slot];
+    const uint32_t v[4] = {raw[p].x, raw[p].y, raw[p].z, raw[p].w};
+    const unsigned nib = (v[0] != 0u ? 1u : 0u) | (v[1] != 0u ? 2u : 0u) | (v[2] != 0u ? 4u : 0u) | (v[3] != 0u ? 8u : 0u);
+    const int g = li >> 3, sh = 4 * (li & 7);                        // mask dword of this lane's columns, bit offset in it
+    unsigned mw = nib << sh;
+    mw |= __shfl_xor(mw, 1);
+    mw |= __shfl_xor(mw, 2);
+    mw |= __shfl_xor(mw, 4);                                         // all 8 lanes of a group: the group's mask dword
+    uint4 m;
+    m.x = __shfl(mw, slot * 32);
+    m.y = __shfl(mw, slot * 32 + 8);
+    m.z = __shfl(mw, slot * 32 + 16);
+    m.w = __shfl(mw, slot * 32 + 24);
+    int pos = 4 + (g > 0 ? __popc(m.x) : 0) + (g > 1 ? __popc(m.y) : 0) + (g > 2 ? __popc(m.z) : 0) + __popc(mw & ((1u << sh) - 1u));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if ((nib >> i) & 1u) {
+        if (pos < kPackPitchDw) dst[pos] = v[i];                     // (an overflow row keeps what fits)
+        ++pos;
+      }
+    }
+    if (li == 0) *reinterpret_cast<uint4*>(dst) = m;
+  }
+  lds_wave_handoff();
+  const int rr = lane >> 4, q = 4 * (lane & 15);                     // this lane's 16 bytes of the wave's four images
+  const uint32_t* src = image[wave][rr];
+  const int k = mask_count(*reinterpret_cast<const uint4*>(src));
+  uint4 o = *reinterpret_cast<const uint4*>(src + q);
+  if (q + 0 >= 4 + k) o.x = 0u;                                      // never-written LDS behind the values
+  if (q + 1 >= 4 + k) o.y = 0u;
+  if (q + 2 >= 4 + k) o.z = 0u;
+  if (q + 3 >= 4 + k) o.w = 0u;
+  if (row0 + rr < n) *reinterpret_cast<uint4*>(packed + (row0 + rr) * kPackPitchDw + q) = o;
+}
+
+// segreduce_kernel<float, 4, 32, kModeSum, false> over packed rows: the same wave-per-row mapping, block remap, row_order, 64-incidence
+// column batches, kUnroll gathers per slot in flight and -- so that the result is BITWISE the dense kernel's -- for every output element
+// the same additions in the same order (incidence j + u * NS + slot to slot `slot`, acc = fmaf(1, v, acc) from +0 in incidence order,
+// the xor-shuffle slot sum).  A gather is one contiguous 256-byte access per slot (8 bytes per lane: two lines).  The row then goes
+// through LDS and every lane reads the mask back (one broadcast 16-byte read).  Lane li owns columns li, li + 32, li + 64, li + 96 --
+// bit li of each of the four mask dwords, not four neighbouring columns: the position of column li + 32 g is then (values of the dwords
+// below g) + popcount(dword g below bit li), two instructions, where neighbouring columns cost a rank inside the lane's nibble and a
+// select per column (measured: 75 vector instructions per gathered row pair and 1.02 ms per pass, vector-issue bound).
+// An empty column reads some dword and masks it to +0.  Rows above kPackCap occupied columns are read from the dense table in a branch
+// the wave takes only when a row of the step needs it.
+constexpr int kImagePad = 128;           // a position is at most 4 + 127: reads nobody uses may run this far past the last image
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void segreduce_packed_kernel(
+    const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const uint32_t* __restrict__ packed,
+    const float* __restrict__ x, int64_t ldx, float* __restrict__ out, int64_t ldo, int n_t, int mean,
+    const int32_t* __restrict__ row_order) {
+  constexpr int VEC = 4, LPR = 32, NS = 2, U = kUnroll;
+  __shared__ __attribute__((aligned(16))) uint32_t image[kWavesPerBlock * U * NS * kPackPitchDw + kImagePad];      // 16.5 KiB
+  const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
+  const int slot_row = static_cast<int>(blk) * kWavesPerBlock + (threadIdx.x >> 6);
+  if (slot_row >= n_t) return;  // whole wave exits together
+  const int row = row_order ? row_order[slot_row] : slot_row;
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const int slot = lane / LPR, li = lane % LPR;
+  const int start = rowptr[row], end = rowptr[row + 1];
+  const uint32_t below = (1u << li) - 1u;
+  uint32_t* const mine = image + (wave * U * NS + slot) * kPackPitchDw;       // image of gather u: mine + u * NS * kPackPitchDw
+  float acc[VEC];                                                             // acc[g]: column li + 32 g
+#pragma unroll
+  for (int g = 0; g < VEC; ++g) acc[g] = 0.f;
+
+  for (int base = start; base < end; base += kWave) {
+    const int n = min(kWave, end - base);
+    int my_col = 0;
+    if (lane < n) my_col = col[base + lane];
+    for (int j = 0; j < n; j += NS * U) {
+      uint2 raw[U];               // kept packed while in flight (8 B per lane and load)
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int jj = j + u * NS + slot;
+        const int src = __shfl(my_col, jj & (kWave - 1));
+        if (jj < n) raw[u] = *reinterpret_cast<const uint2*>(packed + static_cast<int64_t>(src) * kPackPitchDw + 2 * li);
+        else raw[u] = make_uint2(0u, 0u);                            // an empty mask: the row expands to zeros
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) *reinterpret_cast<uint2*>(mine + u * NS * kPackPitchDw + 2 * li) = raw[u];
+      lds_wave_handoff();
+      // expanded kExpand rows at a time: their mask reads, then their value reads, are independent LDS operations in flight together
+#pragma unroll
+      for (int u0 = 0; u0 < U; u0 += kExpand) {
+        if (j + u0 * NS >= n) break;                                 // wave-uniform: nothing but empty images from here on (exact: they add +0)
+        uint4 m[kExpand];
+#pragma unroll
+        for (int e = 0; e < kExpand; ++e) m[e] = *reinterpret_cast<const uint4*>(mine + (u0 + e) * NS * kPackPitchDw);
+        uint32_t v[kExpand][VEC];
+        bool over[kExpand];
+        bool any_over = false;
+#pragma unroll
+        for (int e = 0; e < kExpand; ++e) {
+          const uint32_t* r = mine + (u0 + e) * NS * kPackPitchDw;
+          const int c1 = 4 + __popc(m[e].x), c2 = c1 + __popc(m[e].y), c3 = c2 + __popc(m[e].z);
+          over[e] = c3 + __popc(m[e].w) > 4 + kPackCap;              // uniform over the slot: every lane of it read the same mask
+          any_over |= over[e];
+          v[e][0] = r[4 + __popc(m[e].x & below)] & all_ones_if_bit(m[e].x, li);
+          v[e][1] = r[c1 + __popc(m[e].y & below)] & all_ones_if_bit(m[e].y, li);
+          v[e][2] = r[c2 + __popc(m[e].z & below)] & all_ones_if_bit(m[e].z, li);
+          v[e][3] = r[c3 + __popc(m[e].w & below)] & all_ones_if_bit(m[e].w, li);
+        }
+        if (__any(any_over)) {                                       // wave-uniform, rare: a row did not fit, read it dense
+#pragma unroll
+          for (int e = 0; e < kExpand; ++e) {
+            const int src = __shfl(my_col, (j + (u0 + e) * NS + slot) & (kWave - 1));
+            if (over[e]) {
+              const uint32_t* xr = reinterpret_cast<const uint32_t*>(x + static_cast<int64_t>(src) * ldx) + li;
+#pragma unroll
+              for (int g = 0; g < VEC; ++g) v[e][g] = xr[32 * g];
+            }
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < kExpand; ++e)
+#pragma unroll
+          for (int g = 0; g < VEC; ++g) acc[g] = fmaf(1.f, __uint_as_float(v[e][g]), acc[g]);   // a skipped zero is an exact no-op of this sum
+      }
+      lds_wave_handoff();                                            // the next step's images overwrite these
+    }
+  }
+
+#pragma unroll
+  for (int off = LPR; off < kWave; off <<= 1)
+#pragma unroll
+    for (int g = 0; g < VEC; ++g) acc[g] += __shfl_xor(acc[g], off);
+
+  if (slot == 0) {
+    const float scale = mean ? 1.f / static_cast<float>(max(end - start, 1)) : 1.f;
+    float* o = out + static_cast<int64_t>(row) * ldo + li;
+#pragma unroll
+    for (int g = 0; g < VEC; ++g) o[32 * g] = acc[g] * scale;        // four stores of one 128-byte line each
+  }
+}
+
 // ---- host-side dispatch ------------------------------------------------------------------------
 
 template <typename T, int VEC, int LPR>
@@ -526,6 +697,50 @@ extern "C" int allset_sddmm_rowdot(int reduce, const int32_t* rowptr, const int3
   } else {
     sddmm_rowdot_kernel<kModeSum><<<grid, kBlock, 0, st>>>(rowptr, col, x, ldx, gout, ldg, nullptr, gw, nt, di, mean);
   }
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
+}
+
+static inline bool aligned256(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 255u) == 0; }
+
+extern "C" int allset_pack_rows_f32(const float* x, int64_t ldx, void* packed, int64_t n, int64_t d, void* stream) {
+  clear_error();
+  ALLSET_REQUIRE(n >= 0 && d >= 0, "pack_rows_f32: negative size");
+  ALLSET_REQUIRE(n < INT32_MAX, "pack_rows_f32: size exceeds int32");
+  if (d != 128) {
+    set_error("pack_rows_f32: built for d = 128 only (got %lld)", static_cast<long long>(d));
+    return ALLSET_ERR_UNSUPPORTED;
+  }
+  if (n == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(x && packed, "pack_rows_f32: null x/packed");
+  ALLSET_REQUIRE(ldx >= d && ldx % 4 == 0 && aligned16(x), "pack_rows_f32: rows of x must be 16-byte aligned (pointer and leading dimension)");
+  ALLSET_REQUIRE(aligned256(packed), "pack_rows_f32: the packed buffer must be 256-byte aligned");
+  const int64_t rows_per_block = static_cast<int64_t>(kWavesPerBlock) * kPackRowsPerWave;
+  const unsigned grid = static_cast<unsigned>((n + rows_per_block - 1) / rows_per_block);
+  pack_rows_kernel<<<grid, kBlock, 0, static_cast<hipStream_t>(stream)>>>(x, ldx, static_cast<uint32_t*>(packed), n);
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
+}
+
+extern "C" int allset_segreduce_packed_fwd(int reduce, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                                           const void* packed, const float* x, int64_t ldx, float* out, int64_t ldo, int64_t n_t,
+                                           int64_t n_s, int64_t d, void* stream) {
+  clear_error();
+  ALLSET_REQUIRE(reduce == ALLSET_SUM || reduce == ALLSET_MEAN, "segreduce_packed_fwd: reduce must be SUM or MEAN (got %d)", reduce);
+  ALLSET_REQUIRE(n_t >= 0 && n_s >= 0 && d >= 0, "segreduce_packed_fwd: negative size");
+  ALLSET_REQUIRE(n_t < INT32_MAX && n_s < INT32_MAX, "segreduce_packed_fwd: size exceeds int32");
+  if (d != 128) {
+    set_error("segreduce_packed_fwd: built for d = 128 only (got %lld)", static_cast<long long>(d));
+    return ALLSET_ERR_UNSUPPORTED;
+  }
+  if (n_t == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(rowptr && out, "segreduce_packed_fwd: null rowptr/out");
+  ALLSET_REQUIRE(n_s == 0 || (col && packed && x), "segreduce_packed_fwd: null col/packed/x with n_s > 0");
+  ALLSET_REQUIRE(ldx >= d && ldo >= d && ldx % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(out),
+                 "segreduce_packed_fwd: rows of x and out must be 16-byte aligned (pointers and leading dimensions)");
+  ALLSET_REQUIRE(aligned256(packed), "segreduce_packed_fwd: the packed buffer must be 256-byte aligned");
+  segreduce_packed_kernel<<<row_grid(n_t), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
+      rowptr, col, static_cast<const uint32_t*>(packed), x, ldx, out, ldo, static_cast<int>(n_t), reduce == ALLSET_MEAN, row_order);
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }

@@ -530,9 +530,17 @@ class _HaloExtremeMerge(torch.autograd.Function):
         return torch.where(won, g_c, torch.zeros_like(g_c)), None, None
 
 
-def _hip_deepsets(x, inc, norm, aggr):
+def _hip_deepsets(x, inc, norm, aggr, packed_rows=False):
     from . import functional as AF
-    return AF.deepsets_aggregate(x, inc, norm, aggr)
+    return AF.deepsets_aggregate(x, inc, norm, aggr, packed_rows=packed_rows)
+
+
+def _forward_aggregate(aggregate: Callable, conv) -> Callable:
+    """``aggregate`` for the forward aggregation behind ``conv.f_enc``: the package's own gets the conv's mostly-zero hint
+    (``HalfNLHconv.mostly_zero_enc``); an injected one keeps its four-argument signature."""
+    if aggregate is _hip_deepsets and conv.mostly_zero_enc():
+        return lambda x, inc, norm, aggr: _hip_deepsets(x, inc, norm, aggr, packed_rows=True)
+    return aggregate
 
 
 class HipPmaKernels:
@@ -605,27 +613,28 @@ def sharded_deepsets_layer(v2e_conv, e2v_conv, x_owned: Tensor, hg: ShardedHyper
     # ---- V -> E: dense on owned vertices, all-gather, local reduce over owned hyperedges
     # ``training`` must agree with the convs' own mode (the fused MLP kernels read conv.training)
     use_halo = hg.halo is not None and hg.halo_v2e is not None
+    agg_v2e, agg_e2v = _forward_aggregate(aggregate, v2e_conv), _forward_aggregate(aggregate, e2v_conv)
     with _bn_scope(vv, group):
         h = v2e_conv._mlp_act(v2e_conv.f_enc, x_owned, v2e_conv.dropout)
     if use_halo:                                               # only the rows the local hyperedges touch travel
-        e = aggregate(halo_gather(h, hg.halo), hg.halo_v2e, norm, aggr)
+        e = agg_v2e(halo_gather(h, hg.halo), hg.halo_v2e, norm, aggr)
     else:
         h_full = all_gather_rows(h, group)
-        e = aggregate(h_full, hg.v2e, norm, aggr)
+        e = agg_v2e(h_full, hg.v2e, norm, aggr)
     with _bn_scope(e.shape[0], group):
         e = v2e_conv._mlp_act(v2e_conv.f_dec, e, dropout)       # conv's relu (SetGNN's outer relu is idempotent) + dropout
         # ---- E -> V: dense on owned hyperedges, local partial sums for all vertices, reduce-scatter
         g = e2v_conv._mlp_act(e2v_conv.f_enc, e, e2v_conv.dropout)
     if aggr in ("max", "min") and use_halo:
-        v = _HaloExtremeMerge.apply(aggregate(g, hg.halo_e2v, norm, aggr), hg, aggr == "min")
+        v = _HaloExtremeMerge.apply(agg_e2v(g, hg.halo_e2v, norm, aggr), hg, aggr == "min")
     elif aggr in ("max", "min"):
         # local extreme over this rank's hyperedges (autograd routes to the local arg-extreme), then the key merge
-        partial = aggregate(g, hg.e2v, norm, aggr)
+        partial = agg_e2v(g, hg.e2v, norm, aggr)
         v = _ShardedExtremeMerge.apply(partial, hg.local_vertex_has_incidence(), hg, group, aggr == "min")
     elif use_halo:
-        v = halo_scatter_add(aggregate(g, hg.halo_e2v, norm, "add"), hg.halo)
+        v = halo_scatter_add(agg_e2v(g, hg.halo_e2v, norm, "add"), hg.halo)
     else:
-        partial = aggregate(g, hg.e2v, norm, "add")
+        partial = agg_e2v(g, hg.e2v, norm, "add")
         v = reduce_scatter_rows(partial, group)
     if aggr == "mean":
         v = v / hg.owned_vertex_degree(group).clamp(min=1).view(-1, 1)

@@ -107,14 +107,44 @@ def _routed(norm: Tensor, inc: Incidence, dst: bool) -> Tensor:
     return hit
 
 
+_PACKED_GATHER = True
+
+
+def set_packed_gather(on: bool) -> None:
+    """Module switch (default on; A/B runs and tests): whether a forward aggregation whose caller hints at a mostly-zero table
+    (``deepsets_aggregate(..., packed_rows=True)``) gathers packed nonzero rows.  The results are bitwise the
+    same either way."""
+    global _PACKED_GATHER
+    _PACKED_GATHER = bool(on)
+
+
+def packed_gather() -> bool:
+    return _PACKED_GATHER
+
+
+def _takes_packed(x: Tensor, w_dst: Optional[Tensor], inc: Incidence, reduce: int) -> bool:
+    """The packed path's conditions, from the arguments alone (no data pass, no sync: capturable): fp32, d = 128, contiguous
+    16-byte aligned rows, SUM / MEAN without weights, one wave per row without a split tail."""
+    if not (_PACKED_GATHER and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == 128 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0 and reduce in (SUM, MEAN) and w_dst is None and x.shape[0] > 0 and inc.n_dst > 0):
+        return False
+    csr = inc.by_dst
+    return _variant(csr, "segreduce", inc.n_dst, x) == 1 and not (0 < _split(csr, x) < inc.n_dst)
+
+
 class _SegReduce(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x: Tensor, w_dst: Optional[Tensor], w_src: Optional[Tensor], inc: Incidence, reduce: int):
+    def forward(ctx, x: Tensor, w_dst: Optional[Tensor], w_src: Optional[Tensor], inc: Incidence, reduce: int, packed_rows: bool = False):
         csr = inc.by_dst
         ext = reduce in (MAX, MIN)
-        out, arg = ops.segreduce(reduce, csr.rowptr, csr.col, w_dst, x, inc.n_dst, want_arg=ext,
-                                 variant=1 if ext else _variant(csr, "segreduce", inc.n_dst, x), row_order=csr.row_order,
-                                 split=_split(csr, x))
+        if packed_rows and _takes_packed(x, w_dst, inc, reduce):
+            # the packed table is a temporary of this forward (the unweighted backward never reads the gathered table)
+            out = ops.segreduce_packed(reduce, csr.rowptr, csr.col, ops.pack_rows(x), x, inc.n_dst, row_order=csr.row_order)
+            arg = None
+        else:
+            out, arg = ops.segreduce(reduce, csr.rowptr, csr.col, w_dst, x, inc.n_dst, want_arg=ext,
+                                     variant=1 if ext else _variant(csr, "segreduce", inc.n_dst, x), row_order=csr.row_order,
+                                     split=_split(csr, x))
         need_gw = w_dst is not None and ctx.needs_input_grad[1]
         ctx.inc, ctx.reduce, ctx.n_s, ctx.need_gw = inc, reduce, x.shape[0], need_gw
         ctx.save_for_backward(x if need_gw else None, w_dst, w_src, arg)
@@ -147,14 +177,17 @@ class _SegReduce(torch.autograd.Function):
         if ctx.need_gw:
             csr = inc.by_dst
             gw = ops.sddmm_rowdot(reduce, csr.rowptr, csr.col, x, gout, arg)
-        return gx, gw, None, None, None
+        return gx, gw, None, None, None, None
 
 
-def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None, aggr: str = "add") -> Tensor:
+def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None, aggr: str = "add",
+                       packed_rows: bool = False) -> Tensor:
     """``out[t] = reduce_{i: dst_i = t} norm_i * x[src_i]`` for ``aggr`` in add|sum|mean|max|min.
 
     ``norm`` is per incidence in the caller's edge-list order (int64 ones in the reference default,
     preprocessing.py:454); ``None`` or all-ones skips the weight stream.  Output has ``inc.n_dst`` rows.
+    ``packed_rows``: the caller's hint that ``x`` is mostly zeros (``dropout(relu(.))`` at p >= 0.5): where the packed gather is built
+    (``_takes_packed``) the forward gathers packed nonzero rows; same result bit for bit, and a wrong hint is only slower.
     """
     if aggr not in REDUCE_CODES:
         raise ValueError(f"unknown aggr {aggr!r}")
@@ -168,7 +201,7 @@ def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None,
         w_src = _routed(norm, inc, False).detach()        # (only the input gradient reads it; the weight gradient flows through w_dst)
     else:
         w_dst, w_src = inc.weights(norm)
-    return _SegReduce.apply(x, w_dst, w_src, inc, REDUCE_CODES[aggr])
+    return _SegReduce.apply(x, w_dst, w_src, inc, REDUCE_CODES[aggr], bool(packed_rows))
 
 
 # ---- exclude-self Deep Sets aggregation over the UNEXPANDED incidence (csrc/loo.hip) ------------------------

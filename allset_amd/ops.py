@@ -282,6 +282,42 @@ def segreduce(reduce: int, rowptr: Tensor, col: Tensor, w: Optional[Tensor], x: 
     return out, arg
 
 
+def pack_rows(x: Tensor) -> Tensor:
+    """``x`` f32[n, 128] -> int32[n, 64]: per row a 128-bit occupancy mask and the occupied elements (the format:
+    include/allset_hip_ext.h).  One streaming pass, no sync."""
+    dev = require_device(x)
+    _f32(x, "pack_rows")
+    x = _rowmajor(x)
+    n, d = x.shape
+    packed = torch.empty((n, _lib.PACK_PITCH_DW), dtype=torch.int32, device=dev)
+    with on_device(dev), _timed("pack_rows", dev, n * (4 * d + 4 * _lib.PACK_PITCH_DW)):
+        check(_lib.load().allset_pack_rows_f32(ptr(x), _ld(x), ptr(packed), n, d, stream_of(dev)), "allset_pack_rows_f32")
+    return packed
+
+
+def segreduce_packed(reduce: int, rowptr: Tensor, col: Tensor, packed: Tensor, x: Tensor, n_t: int,
+                     row_order: Optional[Tensor] = None) -> Tensor:
+    """``segreduce(reduce, rowptr, col, None, x, n_t, variant=1, row_order=row_order)[0]``, bit for bit, gathering
+    ``packed = pack_rows(x)`` (two lines per row instead of four); ``x`` itself is read only for rows above 60 occupied columns.
+    SUM / MEAN, fp32, d = 128."""
+    dev = require_device(rowptr, col, packed, x)
+    _f32(x, "segreduce_packed")
+    x = _rowmajor(x)
+    n_s, d = x.shape
+    if packed.dtype != torch.int32 or tuple(packed.shape) != (n_s, _lib.PACK_PITCH_DW) or not packed.is_contiguous():
+        raise _lib.AllSetHipError(f"segreduce_packed: packed must be contiguous int32[{n_s}, {_lib.PACK_PITCH_DW}] (ops.pack_rows)")
+    out = torch.empty((n_t, d), dtype=x.dtype, device=dev)
+    nnz = col.numel()
+    algo = nnz * (4 * _lib.PACK_PITCH_DW + 4) + (n_t + 1) * 4 + n_t * d * 4
+    with on_device(dev), _timed("segreduce_fwd", dev, algo):
+        if row_order is not None and row_order.numel() != n_t:
+            row_order = None                       # order was built for a different row count (prefix views)
+        check(_lib.load().allset_segreduce_packed_fwd(reduce, ptr(row_order), ptr(rowptr), ptr(col), ptr(packed), ptr(x), _ld(x),
+                                                      ptr(out), max(d, 1), n_t, n_s, d, stream_of(dev)),
+              "allset_segreduce_packed_fwd")
+    return out
+
+
 def segmax_bwd(rowptrT: Tensor, colT: Tensor, posT: Tensor, wT: Optional[Tensor], argext: Tensor, gout: Tensor,
                n_s: int) -> Tensor:
     dev = require_device(rowptrT, colT, posT, wT, argext, gout)

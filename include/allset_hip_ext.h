@@ -1192,6 +1192,33 @@ int allset_scan_collect(const int32_t* rowptr, const int32_t* col, const float* 
                         int64_t ldx, const float* s, const float* bias, int act, float p, uint64_t seed, const uint64_t* seed_base,
                         float* y, int64_t ldy, int64_t n_t, int64_t n_pos, int64_t d, int64_t width, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Packed nonzero rows for the forward Deep Sets gather.  Added under ABI 15, additions only.  fp32, d = 128 only
+ * (ALLSET_ERR_UNSUPPORTED otherwise).
+ *
+ * The format: a packed row is kPackPitchDw = 64 dwords (256 bytes, two 128-byte lines instead of the dense row's four) on a 256-byte
+ * pitch in a 256-byte aligned buffer.  Dwords 0..3 are a 128-bit occupancy mask: bit c (bit c % 32 of dword c / 32) is set iff the BIT
+ * PATTERN of element c is not 0x00000000, so -0.0, NaN and Inf count as values.  Dwords 4..4+k-1 hold the k occupied elements in column
+ * order, bit for bit.  A row with k > kPackCap = 60 is an overflow row: its mask is written in full, its values are not complete, and
+ * the gather reads that row from the dense table, which therefore stays allocated and is passed beside the packed one; popcount(mask) >
+ * kPackCap is the test, no flag is stored.  (This implementation writes zeros behind the values of a row that fits and the first 60
+ * values of an overflow row; readers may rely on neither.)  A table on which the caller's sparsity guess is wrong stays correct: an
+ * overflow row costs the gather the packed row's lines and then the dense row's four.  Only the first packed line (the mask) is needed
+ * for that decision, five lines against the dense gather's four; this kernel asks for both packed lines in its one 256-byte access
+ * before it knows, six against four.  A table with a fraction f of overflow rows therefore costs at most (2 + 4 f) / 4 of the dense
+ * gather's line requests: 3/2 at worst (5/4 for a reader that fetches the mask line alone), 1/2 at best.
+ *
+ * allset_pack_rows_f32: x f32[n, 128] (pitch ldx, a multiple of 4; 16-byte aligned) -> packed u32[n, 64].  One streaming pass, no
+ * counters, no sync.
+ * allset_segreduce_packed_fwd: allset_segreduce_fwd_ex's one-wave-per-row kernel (variant 1) for reduce = ALLSET_SUM / ALLSET_MEAN
+ * without weights, gathering `packed` (u32[n_s, 64]) and, for overflow rows only, x (f32[n_s, ldx]).  Every output element is produced
+ * by the same additions in the same order as allset_segreduce_fwd_ex's: the result is bitwise identical.  row_order int32[n_t] or NULL.
+ * ------------------------------------------------------------------------------------------- */
+enum { kPackPitchDw = 64, kPackCap = 60 };
+int allset_pack_rows_f32(const float* x, int64_t ldx, void* packed, int64_t n, int64_t d, void* stream);
+int allset_segreduce_packed_fwd(int reduce, const int32_t* row_order, const int32_t* rowptr, const int32_t* col, const void* packed,
+                                const float* x, int64_t ldx, float* out, int64_t ldo, int64_t n_t, int64_t n_s, int64_t d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
