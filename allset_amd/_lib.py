@@ -321,6 +321,10 @@ SIGNATURES = {
     # packed nonzero rows for the forward Deep Sets gather (under ABI 15, additions only; fp32, d = 128)
     "allset_pack_rows_f32": [_P, c_int64, _P, c_int64, c_int64, _P],
     "allset_segreduce_packed_fwd": [c_int, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P],
+    # the fused Linear forward that writes packed rows itself (under ABI 15, additions only; fused_fwd2.hip mode 3)
+    "allset_fused_linear_fwd_packed_supported": [c_int64, c_int64, c_int, c_float, c_float],
+    "allset_fused_linear_fwd_packed": [_P, c_int64, _P, _P, c_float, c_int, c_float, c_uint64, _P, _P, c_int, c_float, c_uint64, _P, _P,
+                                       c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

@@ -53,6 +53,11 @@ constexpr int kF2Sets = 4;                     // register sets of prefetched ro
 // waves -- PMA's folded attention logits riding along with its value projection (reference layers.py:128-130: the row is in the
 // staging lane's registers anyway; a row's 128 columns sit in the 16 lanes of a DPP row).  Until round 6 an auxiliary projection took
 // the symmetric bf16x6 kernel of fused_mlp.hip (0.35 ms per [1M, 128] launch against 0.20 here).
+//   3  the output leaves as PACKED NONZERO ROWS (include/allset_hip_ext.h, DESIGN.md 4.5: 128-bit occupancy mask + the occupied elements,
+//      256 bytes per row) -> `uo`, the format the forward Deep Sets gather reads, instead of the dense table: the epilogue packs each
+//      row it holds in registers anyway, so neither the dense write nor pack_rows_kernel's pass over it happens.  A row above kPackCap
+//      occupied columns also goes, dense, to row r of `y` (the overflow side table: nothing else of it is ever written).  Built for
+//      <HAS_LN, DROP_IN, DROP_OUT> = <true, true, true> only, in both arithmetics.
 template <bool HAS_LN, bool DROP_IN, bool DROP_OUT, bool D8, bool F16, int XM = 0, bool AUX = false>
 __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
     const float* __restrict__ x, int64_t ldx, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -63,7 +68,8 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
     const float* __restrict__ res = nullptr, int64_t ldres = 0, int relu_post = 0,
     const float* __restrict__ aux_w = nullptr, const float* __restrict__ aux_b = nullptr, float* __restrict__ aux_out = nullptr) {
   static_assert(!AUX || (XM == 0 && !DROP_IN && !HAS_LN), "auxiliary columns: the plain prologue only (behind a LayerNorm the fp16x3 form folds 2^Su into gamma / beta)");
-  static_assert(XM == 0 || F16, "the tail modes are built on the fp16x3 arithmetic only");
+  static_assert(XM == 0 || XM == 3 || F16, "the tail modes are built on the fp16x3 arithmetic only");
+  static_assert(XM != 3 || (HAS_LN && DROP_IN && DROP_OUT && !AUX), "mode 3: LayerNorm prologue, dropout in and out");
   static_assert(XM != 1 || (HAS_LN && !DROP_IN && !DROP_OUT), "mode 1: LayerNorm prologue, no dropout");
   static_assert(XM != 2 || (!HAS_LN && !DROP_IN), "mode 2: plain operand, LayerNorm in the epilogue");
   constexpr bool ROWSC = F16 && !HAS_LN;        // fp16x3 without a bound on the operand: one power of two per ROW, from its largest element
@@ -361,10 +367,11 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
           const float4 kp = keep4(seed_out, stage, hb, thr_out, keep_out);
           v.x *= kp.x; v.y *= kp.y; v.z *= kp.z; v.w *= kp.w;
         }
+        if constexpr (XM == 3) vv[hb] = v;        // (packed below, once both halves of the row are final)
 #ifdef ALLSET_ABL5_NOSTORE
         if (live && v.x == 123.456f)
 #else
-        if (live && XM != 2)
+        if (live && XM != 2 && XM != 3)
 #endif
           *reinterpret_cast<float4*>(yb + hb * dhy + yo) = v;
         if (mask_out != nullptr) {
@@ -378,6 +385,64 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
                                 (static_cast<uint32_t>((b2 >> sh) & 0xffu) << 16) | (static_cast<uint32_t>((b3 >> sh) & 0xffu) << 24);
           if (lane0 < 8 && 16 * (wave >> 2) < nrows)         // (a 16-row block entirely past n has no words in the buffer)
             mask_out[((stage * (R / 16) + (wave >> 2)) * (ND / 64) + hb) * 32 + (wave & 3) * 8 + lane0] = word;
+        }
+      }
+      if constexpr (XM == 3) {
+        // Packed row of lr (include/allset_hip_ext.h): occupancy = the BIT PATTERN is not zero (-0.0, NaN, Inf are values) -- not the
+        // v > 0 ballots of the activation mask above.  The 16 lanes of a DPP row hold the row; lane c's columns 64 hb + 4 c .. + 3 are
+        // nibble c % 8 of mask dword 2 hb + c / 8: an OR over the 8 lanes of a half row gives that dword (`own`), a row mirror the
+        // half row's other dword (`oth`).  Position of an element = 4 + occupied columns below it.
+        uint32_t u[2][4], own[2], oth[2];
+        const uint32_t sh = 4u * (c & 7);
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb) {
+          u[hb][0] = __float_as_uint(vv[hb].x); u[hb][1] = __float_as_uint(vv[hb].y);
+          u[hb][2] = __float_as_uint(vv[hb].z); u[hb][3] = __float_as_uint(vv[hb].w);
+          const uint32_t nib = (u[hb][0] != 0u ? 1u : 0u) | (u[hb][1] != 0u ? 2u : 0u) | (u[hb][2] != 0u ? 4u : 0u) | (u[hb][3] != 0u ? 8u : 0u);
+          float mw = __uint_as_float(nib << sh);                  // (dpp_row moves bits; nothing is computed on the float)
+          mw = __uint_as_float(__float_as_uint(mw) | __float_as_uint(dpp_row<0xB1>(mw)));
+          mw = __uint_as_float(__float_as_uint(mw) | __float_as_uint(dpp_row<0x4E>(mw)));
+          mw = __uint_as_float(__float_as_uint(mw) | __float_as_uint(dpp_row<0x141>(mw)));
+          own[hb] = __float_as_uint(mw);
+          oth[hb] = __float_as_uint(dpp_row<0x140>(mw));
+        }
+        const bool hi = c >= 8;
+        const uint32_t below = (1u << sh) - 1u;
+        const int cnt0 = __popc(own[0]) + __popc(oth[0]);
+        const int kocc = cnt0 + __popc(own[1]) + __popc(oth[1]);       // the row's occupied columns: uniform over its 16 lanes
+        int pos[2];
+        pos[0] = 4 + (hi ? __popc(oth[0]) : 0) + __popc(own[0] & below);
+        pos[1] = 4 + cnt0 + (hi ? __popc(oth[1]) : 0) + __popc(own[1] & below);
+        // The image of the wave's four rows is built in LDS IN PLACE of their rows of ytile[k % 2]: this wave alone reads those rows
+        // (every lane of it has them in vv by now -- a wave's LDS operations are served in issue order, the fence keeps the compiler
+        // from moving one across), the matrix waves write the OTHER tile during this tick and this one only after the tick's barrier,
+        // which this wave reaches with its image reads returned (they feed the store below).  A position is at most 4 + 127 < SPY: an
+        // overflow row's tail stays inside its own tile row (only dwords 0..63 of the image leave).  No extra LDS, no extra barrier.
+        uint32_t* im = reinterpret_cast<uint32_t*>(sY + (k & 1) * (R * SPY) + lr * SPY);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // In issue order: (1) the 16 lanes of a row clear dwords 0..63 of its image, so that what no value overwrites leaves as zeros;
+        // (2) the mask, which the lanes of the low half row hold in dword order (own, oth), to dwords 0..3 -- the high half's copy and
+        // (3) the zero of every empty column go to dwords >= 64 of the row, which never leave; every element is stored, none under a
+        // branch (eight exec-mask branches per stage cost more than the stores).
+        *reinterpret_cast<uint4*>(im + 4 * c) = make_uint4(0u, 0u, 0u, 0u);
+        *reinterpret_cast<uint4*>(im + (hi ? SPY - 4 : 0)) = make_uint4(own[0], oth[0], own[1], oth[1]);
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const bool occ = u[hb][i] != 0u;
+            im[occ ? pos[hb] : SPY - 1] = u[hb][i];
+            pos[hb] += occ ? 1 : 0;
+          }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // lane c takes dwords 4 c .. 4 c + 3 of its own row's image; the wave's four rows are 1 KB contiguous: one 16-byte store per lane
+        const uint4 o = *reinterpret_cast<const uint4*>(im + 4 * c);
+        if (live) *reinterpret_cast<uint4*>(reinterpret_cast<uint32_t*>(uo) + (stage * R + lr) * kPackPitchDw + 4 * c) = o;
+        if (live && kocc > kPackCap) {              // row-uniform, rare: the row did not fit -- the gather reads it from the side table
+          *reinterpret_cast<float4*>(yb + yo) = vv[0];
+          *reinterpret_cast<float4*>(yb + 256 + yo) = vv[1];
         }
       }
       if constexpr (XM == 2) {
@@ -618,12 +683,62 @@ int launch_fused_linear_fwd_roles(hipStream_t st, const float* x, int64_t ldx, c
   return 0;
 }
 
-// ---- the PMA tail (reference layers.py:153-157) folded into its two rFF Linears: modes 1 and 2 of the kernel above (fp16x3) -------
 static inline unsigned f2_grid(int64_t n) {
   const int64_t blocks = (n + kF2Rows - 1) / kF2Rows;
   return static_cast<unsigned>(blocks > 256 ? 256 : (blocks < 1 ? 1 : blocks));
 }
 
+// ---- mode 3: the Linear whose output leaves as packed nonzero rows (the last f_enc Linear in front of a forward Deep Sets gather) ----
+extern "C" int allset_fused_linear_fwd_packed_supported(int64_t K, int64_t N, int has_ln, float p_in, float p_out) {
+  return (K == 128 && N == 128 && has_ln && p_in > 0.f && p_in < 1.f && p_out > 0.f && p_out < 1.f) ? 1 : 0;
+}
+
+// packed[r] = pack(dropout_{p_out}(relu_out?(dropout_{p_in}(relu_in?(LayerNorm(x)))[r] W^T + bias)));  side[r, :] = that row, dense, for
+// the rows above kPackCap occupied columns ONLY (every other row of `side` is left untouched);  stats[r] = {mean, rstd};  mask_out: 1 bit
+// per element > 0, as allset_fused_linear_fwd writes it.  Bit for bit what allset_fused_linear_fwd_ex + allset_pack_rows_f32 give.
+extern "C" int allset_fused_linear_fwd_packed(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, int relu_in,
+                                              float p_in, uint64_t seed_in, const float* W, const float* bias, int relu_out, float p_out,
+                                              uint64_t seed_out, void* packed, float* side, int64_t ldside, float* stats, int64_t n,
+                                              int64_t K, int64_t N, const uint64_t* seed_base, uint32_t* mask_out, int arith,
+                                              void* stream) {
+  clear_error();
+  ALLSET_REQUIRE(n >= 0, "fused_linear_fwd_packed: negative size");
+  ALLSET_REQUIRE(arith == ALLSET_ARITH_AUTO || arith == ALLSET_ARITH_BF16X6 || arith == ALLSET_ARITH_FP16X3,
+                 "fused_linear_fwd_packed: arith must be ALLSET_ARITH_AUTO, ALLSET_ARITH_BF16X6 or ALLSET_ARITH_FP16X3");
+  if (!allset_fused_linear_fwd_packed_supported(K, N, gamma != nullptr, p_in, p_out)) {
+    set_error("fused_linear_fwd_packed: built for K = N = 128 behind a LayerNorm with dropout in and out only "
+              "(allset_fused_linear_fwd_packed_supported)");
+    return ALLSET_ERR_UNSUPPORTED;
+  }
+#ifdef ALLSET_NO_F16X3
+  if (arith == ALLSET_ARITH_FP16X3) { set_error("fused_linear_fwd_packed: this build has no fp16x3 arithmetic"); return ALLSET_ERR_UNSUPPORTED; }
+#endif
+  if (n == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(x && beta && W && packed && side && stats, "fused_linear_fwd_packed: null pointer");
+  ALLSET_REQUIRE(aligned16(x) && aligned16(side) && aligned16(W) && (reinterpret_cast<uintptr_t>(stats) & 7u) == 0,
+                 "fused_linear_fwd_packed: x / side / W must be 16-byte aligned, stats 8-byte aligned");
+  ALLSET_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 255u) == 0, "fused_linear_fwd_packed: the packed buffer must be 256-byte aligned");
+  ALLSET_REQUIRE(ldx >= K && ldx % 4 == 0 && ldside >= N && ldside % 4 == 0 && ldx < (1 << 24) && ldside < (1 << 24),
+                 "fused_linear_fwd_packed: rows must be 16-byte aligned, leading dimensions below 2^24");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool d8 = drop_is8(p_in) && drop_is8(p_out);
+#ifdef ALLSET_NO_F16X3
+  const bool f16 = false;
+#else
+  const bool f16 = arith != ALLSET_ARITH_BF16X6;
+#endif
+#define ALLSET_F2_PK(E8, H16)                                                                                                            \
+  fused_linear_fwd_roles_kernel<true, true, true, E8, H16, 3><<<f2_grid(n), kF2Block, 0, st>>>(                                             \
+      x, ldx, gamma, beta, eps, relu_in, p_in, seed_in, W, bias, relu_out, p_out, seed_out, side, ldside, stats, n, seed_base, mask_out, 0, 0, \
+      1.f / 128.f, nullptr, static_cast<float*>(packed), 0)
+  if (d8) { if (f16) ALLSET_F2_PK(true, true); else ALLSET_F2_PK(true, false); }
+  else    { if (f16) ALLSET_F2_PK(false, true); else ALLSET_F2_PK(false, false); }
+#undef ALLSET_F2_PK
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
+}
+
+// ---- the PMA tail (reference layers.py:153-157) folded into its two rFF Linears: modes 1 and 2 of the kernel above (fp16x3) -------
 extern "C" int allset_fused_linear_tail_supported(int64_t K, int64_t N) {
 #ifdef ALLSET_NO_F16X3
   (void)K; (void)N;

@@ -1207,6 +1207,72 @@ class _FusedNormLinear(torch.autograd.Function):
         return gx, dg, db, gw, gb, None, None, None, None, None, None, None
 
 
+class PackedRows:
+    """The output of a fused Linear that left as packed nonzero rows (``fused_norm_linear_packed``): what the forward Deep Sets gather
+    reads (``functional.deepsets_aggregate`` takes it in place of ``x``), and nothing else -- there is no dense table behind it.
+    ``packed``: int32[n, 64] (include/allset_hip_ext.h); ``_side``: the overflow side table f32[n, 128], UNINITIALISED except for the
+    rows above 60 occupied columns, and the autograd carrier: the gradient that flows back into it is the ordinary dense [n, 128]
+    gradient of the Linear's output.  Private: a caller must never read it as the activation."""
+
+    __slots__ = ("packed", "_side")
+
+    def __init__(self, packed: Tensor, side: Tensor):
+        self.packed, self._side = packed, side
+
+    @property
+    def shape(self):
+        return self._side.shape
+
+
+class _FusedNormLinearPacked(torch.autograd.Function):
+    """:class:`_FusedNormLinear` (row-major, LayerNorm prologue, dropout in and out) whose forward kernel packs its output rows
+    (fused_fwd2.hip mode 3) instead of writing the dense table; the same seeds in the same order, the same saved tensors (x, the row
+    statistics, the 1-bit mask), and ITS backward.  Returns (side, packed): see :class:`PackedRows`."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, weight, bias, eps, relu_in, p_in, relu_out, p_out):
+        from . import ops
+        seed_in = _draw_seed()
+        seed_out = _draw_seed()
+        base = _seed_base()
+        words = activation_mask_words(x.shape[0], weight.shape[0]) if any(ctx.needs_input_grad) else 0
+        mask = torch.empty(words, dtype=torch.int32, device=x.device) if words > 0 else None
+        packed, side, stats = ops.fused_linear_fwd_packed(x, weight, bias, gamma, beta, eps, relu_in, p_in, seed_in, relu_out, p_out,
+                                                          seed_out, base, mask, _arith_for(0, weight.shape[1], weight.shape[0], True, 0))
+        ctx.save_for_backward(x, stats, gamma, beta, weight, None, mask)
+        ctx.cfg = (bool(relu_in), float(p_in), seed_in, float(p_out), bias is not None, base)
+        ctx.layout = (0, 0)
+        ctx.params = (gamma, beta, weight, bias)
+        ctx.mark_non_differentiable(packed)
+        return side, packed
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, _g_packed=None):
+        return _FusedNormLinear.backward(ctx, gy)[:10]
+
+
+def fused_norm_linear_packed_supported(x: Tensor, gamma: Optional[Tensor], weight: Tensor, p_in: float, relu_out: bool, p_out: float) -> bool:
+    """:func:`fused_norm_linear_packed` is built for this call (from the arguments alone: no data pass, no sync)."""
+    from . import ops
+    N, K = weight.shape
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0 and gamma is not None and bool(relu_out)
+            and ops.fused_linear_fwd_packed_supported(K, N, True, p_in, p_out))
+
+
+def fused_norm_linear_packed(x: Tensor, gamma: Tensor, beta: Tensor, weight: Tensor, bias: Optional[Tensor], eps: float, relu_in: bool,
+                             p_in: float, relu_out: bool, p_out: float) -> PackedRows:
+    """:func:`fused_norm_linear` for the Linear in front of a forward Deep Sets gather: the output goes straight into the packed rows the
+    gather reads -- no dense table, no ``ops.pack_rows`` pass.  Bit for bit the rows ``pack_rows`` would make
+    of :func:`fused_norm_linear`'s output under the same seed counter."""
+    if not fused_norm_linear_packed_supported(x, gamma, weight, p_in, relu_out, p_out):
+        raise _lib.AllSetHipError("fused_norm_linear_packed: built for a [128, 128] Linear behind a LayerNorm with relu_out and both "
+                                  "dropouts active only (fused_norm_linear_packed_supported)")
+    side, packed = _FusedNormLinearPacked.apply(x, gamma, beta, weight, bias, float(eps), bool(relu_in), float(p_in), bool(relu_out),
+                                                float(p_out))
+    return PackedRows(packed, side)
+
+
 class _WideNormLinear(torch.autograd.Function):
     """The same layer as :class:`_FusedNormLinear` for widths beyond the LDS-resident-weight kernels (256, 512):
     forward = row statistics + one tiled bf16x6 GEMM with the prologue applied as the A operand is staged and the epilogue

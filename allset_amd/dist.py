@@ -596,6 +596,12 @@ def _valid_rows(lo: int, hi: int, n: int) -> int:
     return max(0, min(int(hi), int(n)) - int(lo))
 
 
+def _packs_enc(aggregate: Callable, conv, x: Tensor, inc, norm, aggr: str, group, use_halo: bool) -> bool:
+    """``conv.f_enc`` may write packed rows for the local gather over ``inc`` (``HalfNLHconv.packs_enc``): the package's own aggregation,
+    one rank and no halo exchange -- an all-gather or a halo gather of ``h`` needs the dense table."""
+    return bool(aggregate is _hip_deepsets and not use_halo and _skip_collective(group) and conv.packs_enc(x, inc, norm, aggr))
+
+
 def sharded_deepsets_layer(v2e_conv, e2v_conv, x_owned: Tensor, hg: ShardedHypergraph, aggr: str = "add",
                            dropout: float = 0.0, training: bool = False, group=None,
                            aggregate: Callable = _hip_deepsets, norm: Optional[Tensor] = None,
@@ -614,9 +620,12 @@ def sharded_deepsets_layer(v2e_conv, e2v_conv, x_owned: Tensor, hg: ShardedHyper
     # ``training`` must agree with the convs' own mode (the fused MLP kernels read conv.training)
     use_halo = hg.halo is not None and hg.halo_v2e is not None
     agg_v2e, agg_e2v = _forward_aggregate(aggregate, v2e_conv), _forward_aggregate(aggregate, e2v_conv)
+    pk_v2e = _packs_enc(aggregate, v2e_conv, x_owned, hg.v2e, norm, aggr, group, use_halo)
     with _bn_scope(vv, group):
-        h = v2e_conv._mlp_act(v2e_conv.f_enc, x_owned, v2e_conv.dropout)
-    if use_halo:                                               # only the rows the local hyperedges touch travel
+        h = v2e_conv._mlp_act(v2e_conv.f_enc, x_owned, v2e_conv.dropout, packed=pk_v2e)
+    if pk_v2e:                                                 # one rank: the owned block is the full table, gathered as packed rows
+        e = agg_v2e(h, hg.v2e, norm, aggr)
+    elif use_halo:                                             # only the rows the local hyperedges touch travel
         e = agg_v2e(halo_gather(h, hg.halo), hg.halo_v2e, norm, aggr)
     else:
         h_full = all_gather_rows(h, group)
@@ -624,7 +633,8 @@ def sharded_deepsets_layer(v2e_conv, e2v_conv, x_owned: Tensor, hg: ShardedHyper
     with _bn_scope(e.shape[0], group):
         e = v2e_conv._mlp_act(v2e_conv.f_dec, e, dropout)       # conv's relu (SetGNN's outer relu is idempotent) + dropout
         # ---- E -> V: dense on owned hyperedges, local partial sums for all vertices, reduce-scatter
-        g = e2v_conv._mlp_act(e2v_conv.f_enc, e, e2v_conv.dropout)
+        pk_e2v = aggr not in ("max", "min") and _packs_enc(aggregate, e2v_conv, e, hg.e2v, norm, "add", group, use_halo)
+        g = e2v_conv._mlp_act(e2v_conv.f_enc, e, e2v_conv.dropout, packed=pk_e2v)
     if aggr in ("max", "min") and use_halo:
         v = _HaloExtremeMerge.apply(agg_e2v(g, hg.halo_e2v, norm, aggr), hg, aggr == "min")
     elif aggr in ("max", "min"):

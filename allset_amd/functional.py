@@ -15,6 +15,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
+from .dense import PackedRows
 from ._lib import MAX, MEAN, MIN, REDUCE_CODES, SUM
 from .incidence import Incidence, LeaveOneOutIncidence
 
@@ -122,6 +123,62 @@ def packed_gather() -> bool:
     return _PACKED_GATHER
 
 
+_PACKED_EPILOGUE = "auto"
+# "auto": the fused Linear writes the packed rows itself from this many rows upward.  Below a few thousand rows both forms are bound
+# by their launches (DESIGN.md section 4.5 has the measured crossover); tests/test_gpu_packed_gather.py pins pack_rows at 500 rows.
+PACKED_EPILOGUE_MIN_ROWS = 16384
+
+
+def set_packed_epilogue(mode: str) -> None:
+    """Module switch beside :func:`set_packed_gather` (which still turns everything off): whether the last ``f_enc`` Linear in front
+    of a packed gather writes the packed rows from its own epilogue (``dense.fused_norm_linear_packed``) instead of a dense table
+    that ``ops.pack_rows`` then packs.  ``"auto"`` (default): from ``PACKED_EPILOGUE_MIN_ROWS`` rows upward; ``"on"``: at any size
+    (tests); ``"off"``: never.  The results are bitwise the same either way."""
+    global _PACKED_EPILOGUE
+    if mode not in ("auto", "on", "off"):
+        raise ValueError(f"set_packed_epilogue: mode must be 'auto', 'on' or 'off', got {mode!r}")
+    _PACKED_EPILOGUE = mode
+
+
+def packed_epilogue() -> str:
+    return _PACKED_EPILOGUE
+
+
+class _RowsToCome:
+    """What ``_takes_packed`` reads of a table that does not exist yet: the contiguous, aligned fp32 [n, 128] output of a Linear."""
+    dtype = torch.float32
+
+    def __init__(self, n: int):
+        self.shape = (int(n), 128)
+
+    def dim(self):
+        return 2
+
+    def is_contiguous(self):
+        return True
+
+    def data_ptr(self):
+        return 0
+
+    def element_size(self):
+        return 4
+
+    def stride(self, i):
+        return (128, 1)[i]
+
+
+def takes_packed_epilogue(n_rows: int, inc: Incidence, norm: Optional[Tensor], aggr: str) -> bool:
+    """Whether ``deepsets_aggregate(h, inc, norm, aggr, packed_rows=True)`` over the [n_rows, 128] fp32 output ``h`` of a Linear would
+    gather packed rows, and the switch lets the Linear write them itself -- from the arguments alone (no data pass, no sync), BEFORE
+    that Linear runs.  The caller adds the Linear's own conditions (``dense.fused_norm_linear_packed_supported``)."""
+    if _PACKED_EPILOGUE == "off" or (_PACKED_EPILOGUE == "auto" and n_rows < PACKED_EPILOGUE_MIN_ROWS) or aggr not in REDUCE_CODES:
+        return False
+    # (a norm not yet known to be all ones -- its first sighting or two, Incidence.weights -- keeps the dense table for that forward)
+    if not inc.known_unweighted(norm) or not (inc.src_extent <= n_rows <= inc.n_src):
+        return False
+    return _takes_packed(_RowsToCome(n_rows), None, inc, REDUCE_CODES[aggr])
+
+
 def _takes_packed(x: Tensor, w_dst: Optional[Tensor], inc: Incidence, reduce: int) -> bool:
     """The packed path's conditions, from the arguments alone (no data pass, no sync: capturable): fp32, d = 128, contiguous
     16-byte aligned rows, SUM / MEAN without weights, one wave per row without a split tail."""
@@ -134,10 +191,19 @@ def _takes_packed(x: Tensor, w_dst: Optional[Tensor], inc: Incidence, reduce: in
 
 class _SegReduce(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x: Tensor, w_dst: Optional[Tensor], w_src: Optional[Tensor], inc: Incidence, reduce: int, packed_rows: bool = False):
+    def forward(ctx, x: Tensor, w_dst: Optional[Tensor], w_src: Optional[Tensor], inc: Incidence, reduce: int, packed_rows: bool = False,
+                packed: Optional[Tensor] = None):
         csr = inc.by_dst
         ext = reduce in (MAX, MIN)
-        if packed_rows and _takes_packed(x, w_dst, inc, reduce):
+        if packed is not None:
+            # ``x`` is the overflow side table of a Linear that wrote ``packed`` itself (dense.PackedRows): mostly uninitialised, and
+            # read by the packed gather alone, for its overflow rows
+            if not _takes_packed(x, w_dst, inc, reduce):
+                raise _lib.AllSetHipError("deepsets_aggregate: packed rows came without a packed gather to read them "
+                                          "(functional.takes_packed_epilogue decides the route before the Linear runs)")
+            out = ops.segreduce_packed(reduce, csr.rowptr, csr.col, packed, x, inc.n_dst, row_order=csr.row_order)
+            arg = None
+        elif packed_rows and _takes_packed(x, w_dst, inc, reduce):
             # the packed table is a temporary of this forward (the unweighted backward never reads the gathered table)
             out = ops.segreduce_packed(reduce, csr.rowptr, csr.col, ops.pack_rows(x), x, inc.n_dst, row_order=csr.row_order)
             arg = None
@@ -177,7 +243,7 @@ class _SegReduce(torch.autograd.Function):
         if ctx.need_gw:
             csr = inc.by_dst
             gw = ops.sddmm_rowdot(reduce, csr.rowptr, csr.col, x, gout, arg)
-        return gx, gw, None, None, None, None
+        return gx, gw, None, None, None, None, None
 
 
 def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None, aggr: str = "add",
@@ -188,9 +254,13 @@ def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None,
     preprocessing.py:454); ``None`` or all-ones skips the weight stream.  Output has ``inc.n_dst`` rows.
     ``packed_rows``: the caller's hint that ``x`` is mostly zeros (``dropout(relu(.))`` at p >= 0.5): where the packed gather is built
     (``_takes_packed``) the forward gathers packed nonzero rows; same result bit for bit, and a wrong hint is only slower.
+    ``x`` may be a ``dense.PackedRows`` (a Linear that packed its own output, after ``takes_packed_epilogue``): gathered as it is.
     """
     if aggr not in REDUCE_CODES:
         raise ValueError(f"unknown aggr {aggr!r}")
+    packed = None
+    if isinstance(x, PackedRows):
+        x, packed = x._side, x.packed
     _lib.require_device(x)
     _check_rows(x, inc)
     if norm is not None and norm.requires_grad:
@@ -201,7 +271,7 @@ def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None,
         w_src = _routed(norm, inc, False).detach()        # (only the input gradient reads it; the weight gradient flows through w_dst)
     else:
         w_dst, w_src = inc.weights(norm)
-    return _SegReduce.apply(x, w_dst, w_src, inc, REDUCE_CODES[aggr], bool(packed_rows))
+    return _SegReduce.apply(x, w_dst, w_src, inc, REDUCE_CODES[aggr], bool(packed_rows), packed)
 
 
 # ---- exclude-self Deep Sets aggregation over the UNEXPANDED incidence (csrc/loo.hip) ------------------------

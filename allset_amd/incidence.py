@@ -173,6 +173,20 @@ class Incidence:
             self._wcache[key] = (weakref.ref(norm), hit, probed)
         return hit
 
+    def known_unweighted(self, norm: Optional[Tensor]) -> bool:
+        """``weights(norm)`` is known to be (None, None), for routes decided before the aggregation runs
+        (functional.takes_packed_epilogue).  An integer norm (the reference's default) is settled by ``weights`` itself, which probes it
+        on first sight whoever asks; for a floating-point norm this is a read of the cache alone -- no probe, no sync, and the cache's
+        count of sightings stays what it was."""
+        if norm is None:
+            return True
+        if norm.requires_grad or norm.numel() != self.nnz:
+            return False
+        if not norm.dtype.is_floating_point:
+            return self.weights(norm)[0] is None
+        entry = self._wcache.get((norm.data_ptr(), norm._version, norm.dtype, norm.numel()))
+        return entry is not None and entry[0]() is norm and entry[1][0] is None and entry[1][1] is None
+
 
 class LeaveOneOutIncidence:
     """The structure of the exclude-self aggregation over the UNEXPANDED V->E edge list.

@@ -238,8 +238,25 @@ class MLP(nn.Module):
                 all(dense.fused_linear_supported(lin.in_features, lin.out_features) for lin in self.lins) and
                 cb <= first.in_features // 2 and cb <= last.out_features // 2)
 
-    def forward(self, x, _post: Optional[float] = None, _in_cb: int = 0, _out_cb: int = 0, _pre: float = 0.0):
-        """``_post`` (internal): also apply ``dropout_p(relu(.))`` to the output -- the activation its callers
+    def packs_output(self, x: Tensor, post: Optional[float]) -> bool:
+        """``forward(x, _post=post, _packed_out=True)`` is built: the MLP takes the fused kernels (``_fusable``, no wide first Linear),
+        its last Linear sits behind a LayerNorm with both dropouts active, at the widths the packed epilogue is built for -- and no
+        forward hook is registered on the MLP (a hook must keep seeing the dense activation).  From the arguments alone."""
+        if post is None or not self.training or len(self.lins) < 2 or self._forward_hooks or self._forward_pre_hooks:
+            return False
+        if nn.modules.module._global_forward_hooks or nn.modules.module._global_forward_pre_hooks:
+            return False
+        if not _on_hip(x) or x.dtype != torch.float32 or self._wide_input(x) or not self._fusable(x):
+            return False
+        nm, lin = self.normalizations[-1], self.lins[-1]
+        if not isinstance(nm, nn.LayerNorm) or nm.weight is None or nm.bias is None:
+            return False
+        return dense.fused_norm_linear_packed_supported(x, nm.weight, lin.weight, float(self.dropout), True, float(post))
+
+    def forward(self, x, _post: Optional[float] = None, _in_cb: int = 0, _out_cb: int = 0, _pre: float = 0.0, _packed_out: bool = False):
+        """``_packed_out`` (internal, only after ``packs_output``): the last Linear writes packed nonzero rows and the result is a
+        ``dense.PackedRows`` for ``functional.deepsets_aggregate``.
+        ``_post`` (internal): also apply ``dropout_p(relu(.))`` to the output -- the activation its callers
         (``HalfNLHconv``) put right after the MLP -- inside the last Linear's epilogue.  ``_in_cb`` / ``_out_cb`` (internal, only
         after ``blockable``): the input / output is column-blocked [(C / cb) * n, cb].  ``_pre`` (internal, only after
         ``takes_pre_dropout``): a dropout in front of the MLP, applied inside its first kernel."""
@@ -247,6 +264,8 @@ class MLP(nn.Module):
         post_p = (float(_post) if self.training else 0.0) if _post is not None else None
         if _pre and not self._wide_input(x):
             raise ValueError("MLP.forward(_pre=...) needs takes_pre_dropout(x)")
+        if _packed_out and (_in_cb or _out_cb or _pre or not self.packs_output(x, _post)):
+            raise ValueError("MLP.forward(_packed_out=True) needs packs_output(x, _post)")
         if not (_in_cb or _out_cb) and self._wide_input(x):
             n0, lin0 = self.normalizations[0], self.lins[0]
             x = dense.input_norm_linear(x, n0.weight, n0.bias, lin0.weight, lin0.bias, n0.eps, float(_pre) if self.training else 0.0)
@@ -297,6 +316,9 @@ class MLP(nn.Module):
                         and dense.wide_stats_chain_supported(lin.weight.shape[1], lin.weight.shape[0], ln is not None, i > 0, p if i > 0 else 0.0)
                         and dense.wide_linear_supported(self.lins[i + 1].weight.shape[1], self.lins[i + 1].weight.shape[0], True, True, p)):
                     emit = (nxt.eps, True)
+                if is_last and _packed_out:
+                    return dense.fused_norm_linear_packed(x, ln.weight, ln.bias, lin.weight, lin.bias, ln.eps, relu_in=True, p_in=p,
+                                                          relu_out=True, p_out=post_p)
                 x = dense.fused_norm_linear(
                     x, ln.weight if ln is not None else None, ln.bias if ln is not None else None, lin.weight, lin.bias,
                     ln.eps if ln is not None else 1e-5, relu_in=i > 0, p_in=p if i > 0 else 0.0,
@@ -628,15 +650,24 @@ class HalfNLHconv(nn.Module):
             return relu_dropout(x, _post_dropout, self.training) if post else x
         if aggr is None:
             raise ValueError("aggr was not passed!")
-        x = self._mlp_act(self.f_enc, x, self.dropout, pre=_pre_dropout)
         inc = _as_incidence(edge_index, x.shape[0])
+        x = self._mlp_act(self.f_enc, x, self.dropout, pre=_pre_dropout, packed=self.packs_enc(x, inc, norm, aggr, _pre_dropout))
         x = AF.deepsets_aggregate(x, inc, norm, aggr, packed_rows=self.mostly_zero_enc())
         # relu(f_dec(.)); SetGNN's outer relu is idempotent on it, so its dropout can ride in the same pass
         return self._mlp_act(self.f_dec, x, _post_dropout if post else 0.0)
 
-    def _mlp_act(self, mlp, x, p, in_cb: int = 0, out_cb: int = 0, pre: float = 0.0):
+    def packs_enc(self, x: Tensor, inc, norm, aggr, pre: float = 0.0) -> bool:
+        """The fused route of DESIGN.md section 4.5: ``f_enc``'s last Linear writes the packed rows the forward gather over ``inc`` reads
+        (no dense table, no ``pack_rows`` pass).  From the arguments alone -- no data pass, no sync: the step still captures."""
+        return bool(self.mostly_zero_enc() and not pre and isinstance(self.f_enc, MLP) and x.dim() == 2
+                    and AF.takes_packed_epilogue(x.shape[0], inc, norm, aggr) and self.f_enc.packs_output(x, self.dropout))
+
+    def _mlp_act(self, mlp, x, p, in_cb: int = 0, out_cb: int = 0, pre: float = 0.0, packed: bool = False):
         """``dropout_p(relu(mlp(x)))``; the activation rides in the MLP's last fused kernel when there is one.
-        ``in_cb`` / ``out_cb``: column-blocked input / output (only after ``mlp.blockable``; dist.py)."""
+        ``in_cb`` / ``out_cb``: column-blocked input / output (only after ``mlp.blockable``; dist.py).  ``packed`` (only after
+        ``packs_enc``): the result is a ``dense.PackedRows``."""
         if isinstance(mlp, MLP):
+            if packed:
+                return mlp(x, _post=p, _pre=pre, _packed_out=True)
             return mlp(x, _post=p, _in_cb=in_cb, _out_cb=out_cb, _pre=pre)
         return relu_dropout(mlp(x), p, self.training)

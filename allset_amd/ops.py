@@ -295,6 +295,35 @@ def pack_rows(x: Tensor) -> Tensor:
     return packed
 
 
+def fused_linear_fwd_packed_supported(K: int, N: int, has_ln: bool, p_in: float, p_out: float) -> bool:
+    return bool(_lib.load().allset_fused_linear_fwd_packed_supported(int(K), int(N), int(has_ln), float(p_in), float(p_out)))
+
+
+def fused_linear_fwd_packed(x: Tensor, weight: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Tensor, eps: float, relu_in: bool,
+                            p_in: float, seed_in: int, relu_out: bool, p_out: float, seed_out: int, seed_base: Optional[Tensor],
+                            mask_out: Optional[Tensor], arith: int = 0) -> Tuple[Tensor, Tensor, Tensor]:
+    """The fused Linear forward (``dense.fused_linear_fwd`` behind a LayerNorm, dropout in and out) with ``pack_rows`` as its epilogue:
+    returns ``(packed int32[n, 64], side f32[n, N], stats)``.  ``side`` is UNINITIALISED except for the rows above 60 occupied columns
+    -- (packed, side) is what :func:`segreduce_packed` takes as (packed, x), and nothing else may read ``side``."""
+    dev = require_device(x, weight, bias, gamma, beta)
+    for t in (x, weight, bias, gamma, beta):
+        if t is not None:
+            _f32(t, "fused_linear_fwd_packed")
+    x = _rowmajor(x)
+    n, K = x.shape
+    N = weight.shape[0]
+    packed = torch.empty((n, _lib.PACK_PITCH_DW), dtype=torch.int32, device=dev)
+    side = torch.empty((n, N), dtype=torch.float32, device=dev)
+    stats = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    nparam = weight.numel() + N + 2 * K
+    with on_device(dev), _timed("fused_linear_fwd", dev, n * (4 * K + 4 * _lib.PACK_PITCH_DW) + 4 * nparam):
+        check(_lib.load().allset_fused_linear_fwd_packed(
+            ptr(x), _ld(x), ptr(gamma.contiguous()), ptr(beta.contiguous()), eps, int(relu_in), p_in, seed_in, ptr(weight.contiguous()),
+            ptr(bias.contiguous() if bias is not None else None), int(relu_out), p_out, seed_out, ptr(packed), ptr(side), max(N, 1),
+            ptr(stats), n, K, N, ptr(seed_base), ptr(mask_out), int(arith), stream_of(dev)), "allset_fused_linear_fwd_packed")
+    return packed, side, stats
+
+
 def segreduce_packed(reduce: int, rowptr: Tensor, col: Tensor, packed: Tensor, x: Tensor, n_t: int,
                      row_order: Optional[Tensor] = None) -> Tensor:
     """``segreduce(reduce, rowptr, col, None, x, n_t, variant=1, row_order=row_order)[0]``, bit for bit, gathering

@@ -1219,6 +1219,24 @@ int allset_pack_rows_f32(const float* x, int64_t ldx, void* packed, int64_t n, i
 int allset_segreduce_packed_fwd(int reduce, const int32_t* row_order, const int32_t* rowptr, const int32_t* col, const void* packed,
                                 const float* x, int64_t ldx, float* out, int64_t ldo, int64_t n_t, int64_t n_s, int64_t d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The fused Linear forward whose output leaves as packed nonzero rows (csrc/fused_fwd2.hip mode 3).  Added
+ * under ABI 15, additions only; detect with allset_fused_linear_fwd_packed_supported: 1 for K = N = 128 behind a LayerNorm prologue
+ * (has_ln) with 0 < p_in < 1 and 0 < p_out < 1 -- the last Linear of an f_enc in training -- else 0 (ALLSET_ERR_UNSUPPORTED).
+ *
+ * allset_fused_linear_fwd_packed: allset_fused_linear_fwd_ex (row-major operands, ALLSET_NORM_LAYER, no auxiliary columns) followed by
+ * allset_pack_rows_f32 of its y, in one kernel and without the dense y: `packed` u32[n, 64] (256-byte aligned) receives, bit for bit,
+ * the mask dwords of every row and the value dwords of every row that fits.  A row with more than kPackCap occupied columns is ALSO
+ * written, dense, to row r of `side` f32[n, ldside]; no other row of `side` is written (allocate it uninitialised: untouched rows
+ * cost no traffic), so (packed, side) is what allset_segreduce_packed_fwd takes as (packed, x).  stats, mask_out, the seeds and
+ * `arith`: as for allset_fused_linear_fwd_ex.
+ * ------------------------------------------------------------------------------------------- */
+int allset_fused_linear_fwd_packed_supported(int64_t K, int64_t N, int has_ln, float p_in, float p_out);
+int allset_fused_linear_fwd_packed(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, int relu_in,
+                                   float p_in, uint64_t seed_in, const float* W, const float* bias, int relu_out, float p_out,
+                                   uint64_t seed_out, void* packed, float* side, int64_t ldside, float* stats, int64_t n, int64_t K,
+                                   int64_t N, const uint64_t* seed_base, uint32_t* mask_out, int arith, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
