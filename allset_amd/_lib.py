@@ -22,6 +22,7 @@ SUM, MEAN, MAX, MIN = 0, 1, 2, 3
 F32, BF16 = 0, 1
 REDUCE_AS_TREE = 0x100
 PACK_PITCH_DW, PACK_CAP = 64, 60                              # include/allset_hip_ext.h kPackPitchDw / kPackCap
+CELLS_PER_ROW, CELL_CAP = 16, 48                              # include/allset_hip_ext.h kCellsPerRow / kCellCap
 ARITH_AUTO, ARITH_BF16X6, ARITH_FP16X3 = 0, 1, 2          # include/allset_hip_ext.h ALLSET_ARITH_*
 ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2                       # include/allset_hip_ext.h ALLSET_HCONV_ACT_*
 REDUCE_CODES = {"add": SUM, "sum": SUM, "mean": MEAN, "max": MAX, "min": MIN}
@@ -325,6 +326,12 @@ SIGNATURES = {
     "allset_fused_linear_fwd_packed_supported": [c_int64, c_int64, c_int, c_float, c_float],
     "allset_fused_linear_fwd_packed": [_P, c_int64, _P, _P, c_float, c_int, c_float, c_uint64, _P, _P, c_int, c_float, c_uint64, _P, _P,
                                        c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int, _P],
+    # cell rows, the second packed format of that gather (under ABI 15, additions only; fp32, d = 128; fused_fwd2.hip mode 4)
+    "allset_pack_cells_f32": [_P, c_int64, _P, c_int64, c_int64, _P],
+    "allset_segreduce_cells_fwd": [c_int, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P],
+    "allset_fused_linear_fwd_cells_supported": [c_int64, c_int64, c_int, c_float, c_float],
+    "allset_fused_linear_fwd_cells": [_P, c_int64, _P, _P, c_float, c_int, c_float, c_uint64, _P, _P, c_int, c_float, c_uint64, _P, _P,
+                                      c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(SIGNATURES) + ["allset_last_error"])
 

@@ -58,6 +58,9 @@ constexpr int kF2Sets = 4;                     // register sets of prefetched ro
 //      row it holds in registers anyway, so neither the dense write nor pack_rows_kernel's pass over it happens.  A row above kPackCap
 //      occupied columns also goes, dense, to row r of `y` (the overflow side table: nothing else of it is ever written).  Built for
 //      <HAS_LN, DROP_IN, DROP_OUT> = <true, true, true> only, in both arithmetics.
+//   4  mode 3 with the CELL layout of include/allset_hip_ext.h (16 cells of {v0, v1, v2, {col0, col1, col2, k}}: each occupied element
+//      with its column beside it, rank j in cell j % 16, slot j / 16), the format segreduce_cells_kernel gathers; rows above kCellCap
+//      occupied columns also go to the side table.  Same restrictions as mode 3.
 template <bool HAS_LN, bool DROP_IN, bool DROP_OUT, bool D8, bool F16, int XM = 0, bool AUX = false>
 __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
     const float* __restrict__ x, int64_t ldx, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -68,8 +71,8 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
     const float* __restrict__ res = nullptr, int64_t ldres = 0, int relu_post = 0,
     const float* __restrict__ aux_w = nullptr, const float* __restrict__ aux_b = nullptr, float* __restrict__ aux_out = nullptr) {
   static_assert(!AUX || (XM == 0 && !DROP_IN && !HAS_LN), "auxiliary columns: the plain prologue only (behind a LayerNorm the fp16x3 form folds 2^Su into gamma / beta)");
-  static_assert(XM == 0 || XM == 3 || F16, "the tail modes are built on the fp16x3 arithmetic only");
-  static_assert(XM != 3 || (HAS_LN && DROP_IN && DROP_OUT && !AUX), "mode 3: LayerNorm prologue, dropout in and out");
+  static_assert(XM == 0 || XM == 3 || XM == 4 || F16, "the tail modes are built on the fp16x3 arithmetic only");
+  static_assert((XM != 3 && XM != 4) || (HAS_LN && DROP_IN && DROP_OUT && !AUX), "modes 3 and 4: LayerNorm prologue, dropout in and out");
   static_assert(XM != 1 || (HAS_LN && !DROP_IN && !DROP_OUT), "mode 1: LayerNorm prologue, no dropout");
   static_assert(XM != 2 || (!HAS_LN && !DROP_IN), "mode 2: plain operand, LayerNorm in the epilogue");
   constexpr bool ROWSC = F16 && !HAS_LN;        // fp16x3 without a bound on the operand: one power of two per ROW, from its largest element
@@ -367,11 +370,11 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
           const float4 kp = keep4(seed_out, stage, hb, thr_out, keep_out);
           v.x *= kp.x; v.y *= kp.y; v.z *= kp.z; v.w *= kp.w;
         }
-        if constexpr (XM == 3) vv[hb] = v;        // (packed below, once both halves of the row are final)
+        if constexpr (XM == 3 || XM == 4) vv[hb] = v;        // (packed below, once both halves of the row are final)
 #ifdef ALLSET_ABL5_NOSTORE
         if (live && v.x == 123.456f)
 #else
-        if (live && XM != 2 && XM != 3)
+        if (live && XM != 2 && XM != 3 && XM != 4)
 #endif
           *reinterpret_cast<float4*>(yb + hb * dhy + yo) = v;
         if (mask_out != nullptr) {
@@ -387,7 +390,7 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
             mask_out[((stage * (R / 16) + (wave >> 2)) * (ND / 64) + hb) * 32 + (wave & 3) * 8 + lane0] = word;
         }
       }
-      if constexpr (XM == 3) {
+      if constexpr (XM == 3 || XM == 4) {
         // Packed row of lr (include/allset_hip_ext.h): occupancy = the BIT PATTERN is not zero (-0.0, NaN, Inf are values) -- not the
         // v > 0 ballots of the activation mask above.  The 16 lanes of a DPP row hold the row; lane c's columns 64 hb + 4 c .. + 3 are
         // nibble c % 8 of mask dword 2 hb + c / 8: an OR over the 8 lanes of a half row gives that dword (`own`), a row mirror the
@@ -421,6 +424,25 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
         uint32_t* im = reinterpret_cast<uint32_t*>(sY + (k & 1) * (R * SPY) + lr * SPY);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
+        if constexpr (XM == 4) {
+          // Cell rows.  In issue order: (1) lane c writes cell c empty -- value bits 0, its dummy column 128 + c in the three column
+          // bytes, k in the fourth --; (2) the element of rank j = pos - 4 goes to dword 4 (j % 16) + j / 16 and its column to byte
+          // 16 (j % 16) + 12 + j / 16; an empty column and a rank >= kCellCap go to the last dword of the tile row, which never leaves.
+          *reinterpret_cast<uint4*>(im + 4 * c) = make_uint4(0u, 0u, 0u, (128u + c) * 0x010101u | (static_cast<uint32_t>(kocc) << 24));
+          uint8_t* imb = reinterpret_cast<uint8_t*>(im);
+#pragma unroll
+          for (int hb = 0; hb < 2; ++hb) {
+            int j = pos[hb] - 4;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const bool put = u[hb][i] != 0u && j < kCellCap;
+              const int cl = 16 * (j & 15), sl = j >> 4;
+              *reinterpret_cast<uint32_t*>(imb + (put ? cl + 4 * sl : 4 * (SPY - 1))) = u[hb][i];
+              imb[put ? cl + 12 + sl : 4 * (SPY - 1)] = static_cast<uint8_t>(64 * hb + 4 * c + i);
+              j += u[hb][i] != 0u ? 1 : 0;
+            }
+          }
+        } else {
         // In issue order: (1) the 16 lanes of a row clear dwords 0..63 of its image, so that what no value overwrites leaves as zeros;
         // (2) the mask, which the lanes of the low half row hold in dword order (own, oth), to dwords 0..3 -- the high half's copy and
         // (3) the zero of every empty column go to dwords >= 64 of the row, which never leave; every element is stored, none under a
@@ -435,12 +457,13 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
             im[occ ? pos[hb] : SPY - 1] = u[hb][i];
             pos[hb] += occ ? 1 : 0;
           }
+        }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // lane c takes dwords 4 c .. 4 c + 3 of its own row's image; the wave's four rows are 1 KB contiguous: one 16-byte store per lane
         const uint4 o = *reinterpret_cast<const uint4*>(im + 4 * c);
         if (live) *reinterpret_cast<uint4*>(reinterpret_cast<uint32_t*>(uo) + (stage * R + lr) * kPackPitchDw + 4 * c) = o;
-        if (live && kocc > kPackCap) {              // row-uniform, rare: the row did not fit -- the gather reads it from the side table
+        if (live && kocc > (XM == 4 ? kCellCap : kPackCap)) {              // row-uniform, rare: the row did not fit -- the gather reads it from the side table
           *reinterpret_cast<float4*>(yb + yo) = vv[0];
           *reinterpret_cast<float4*>(yb + 256 + yo) = vv[1];
         }
@@ -734,6 +757,55 @@ extern "C" int allset_fused_linear_fwd_packed(const float* x, int64_t ldx, const
   if (d8) { if (f16) ALLSET_F2_PK(true, true); else ALLSET_F2_PK(true, false); }
   else    { if (f16) ALLSET_F2_PK(false, true); else ALLSET_F2_PK(false, false); }
 #undef ALLSET_F2_PK
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
+}
+
+// ---- mode 4: the same Linear writing cell rows (the format segreduce_cells_kernel gathers) ----
+extern "C" int allset_fused_linear_fwd_cells_supported(int64_t K, int64_t N, int has_ln, float p_in, float p_out) {
+  return allset_fused_linear_fwd_packed_supported(K, N, has_ln, p_in, p_out);
+}
+
+// allset_fused_linear_fwd_packed with cells[r] = pack_cells(...) and side[r, :] written for the rows above kCellCap occupied columns ONLY.
+// Bit for bit what allset_fused_linear_fwd_ex + allset_pack_cells_f32 give.
+extern "C" int allset_fused_linear_fwd_cells(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, int relu_in,
+                                             float p_in, uint64_t seed_in, const float* W, const float* bias, int relu_out, float p_out,
+                                             uint64_t seed_out, void* cells, float* side, int64_t ldside, float* stats, int64_t n,
+                                             int64_t K, int64_t N, const uint64_t* seed_base, uint32_t* mask_out, int arith,
+                                             void* stream) {
+  clear_error();
+  ALLSET_REQUIRE(n >= 0, "fused_linear_fwd_cells: negative size");
+  ALLSET_REQUIRE(arith == ALLSET_ARITH_AUTO || arith == ALLSET_ARITH_BF16X6 || arith == ALLSET_ARITH_FP16X3,
+                 "fused_linear_fwd_cells: arith must be ALLSET_ARITH_AUTO, ALLSET_ARITH_BF16X6 or ALLSET_ARITH_FP16X3");
+  if (!allset_fused_linear_fwd_cells_supported(K, N, gamma != nullptr, p_in, p_out)) {
+    set_error("fused_linear_fwd_cells: built for K = N = 128 behind a LayerNorm with dropout in and out only "
+              "(allset_fused_linear_fwd_cells_supported)");
+    return ALLSET_ERR_UNSUPPORTED;
+  }
+#ifdef ALLSET_NO_F16X3
+  if (arith == ALLSET_ARITH_FP16X3) { set_error("fused_linear_fwd_cells: this build has no fp16x3 arithmetic"); return ALLSET_ERR_UNSUPPORTED; }
+#endif
+  if (n == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(x && beta && W && cells && side && stats, "fused_linear_fwd_cells: null pointer");
+  ALLSET_REQUIRE(aligned16(x) && aligned16(side) && aligned16(W) && (reinterpret_cast<uintptr_t>(stats) & 7u) == 0,
+                 "fused_linear_fwd_cells: x / side / W must be 16-byte aligned, stats 8-byte aligned");
+  ALLSET_REQUIRE((reinterpret_cast<uintptr_t>(cells) & 255u) == 0, "fused_linear_fwd_cells: the cell buffer must be 256-byte aligned");
+  ALLSET_REQUIRE(ldx >= K && ldx % 4 == 0 && ldside >= N && ldside % 4 == 0 && ldx < (1 << 24) && ldside < (1 << 24),
+                 "fused_linear_fwd_cells: rows must be 16-byte aligned, leading dimensions below 2^24");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool d8 = drop_is8(p_in) && drop_is8(p_out);
+#ifdef ALLSET_NO_F16X3
+  const bool f16 = false;
+#else
+  const bool f16 = arith != ALLSET_ARITH_BF16X6;
+#endif
+#define ALLSET_F2_CL(E8, H16)                                                                                                            \
+  fused_linear_fwd_roles_kernel<true, true, true, E8, H16, 4><<<f2_grid(n), kF2Block, 0, st>>>(                                             \
+      x, ldx, gamma, beta, eps, relu_in, p_in, seed_in, W, bias, relu_out, p_out, seed_out, side, ldside, stats, n, seed_base, mask_out, 0, 0, \
+      1.f / 128.f, nullptr, static_cast<float*>(cells), 0)
+  if (d8) { if (f16) ALLSET_F2_CL(true, true); else ALLSET_F2_CL(true, false); }
+  else    { if (f16) ALLSET_F2_CL(false, true); else ALLSET_F2_CL(false, false); }
+#undef ALLSET_F2_CL
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }

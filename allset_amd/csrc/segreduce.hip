@@ -526,6 +526,217 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
   }
 }
 
+// ---- cell rows (include/allset_hip_ext.h: 16 cells of {v0, v1, v2, {col0, col1, col2, k}}, 256 bytes per row) ------------------------
+// The mask format's expansion pays for all 128 columns of a gathered row (a popcount, an LDS read at a computed address, a sign extract,
+// an AND per column: about 45 vector instructions per row pair).  A cell row carries each occupied element's
+// column beside it, so the lane that loaded a cell scatters the three values it holds into a dense LDS image of the row -- a byte
+// extract, an address and one ds_write_b32 each -- and the row is read back dense: the cost follows the occupied elements.
+#ifndef ALLSET_CELL_WAVES           // waves per SIMD the gather's registers are held to (8 images: LDS allows 8; 16 images: 4)
+#define ALLSET_CELL_WAVES 8
+#endif
+constexpr int kCellImageDw = 128 + kCellsPerRow;       // a row's image: its 128 columns + one pad dword per cell (the dummy columns)
+
+// pack_rows_kernel with the cell layout: the element of rank j goes to cell j % 16, slot j / 16.
+__global__ __launch_bounds__(kBlock) void pack_cells_kernel(const float* __restrict__ x, int64_t ldx, uint32_t* __restrict__ cells, int64_t n) {
+  __shared__ __attribute__((aligned(16))) uint32_t image[kWavesPerBlock][kPackRowsPerWave][kPackPitchDw];
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const int slot = lane >> 5, li = lane & 31;
+  const int64_t row0 = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave) * kPackRowsPerWave;
+  if (row0 >= n) return;  // whole wave exits together
+  uint4 raw[kPackRowsPerWave / 2];
+#pragma unroll
+  for (int p = 0; p < kPackRowsPerWave / 2; ++p) {
+    const int64_t r = row0 + 2 * p + slot;
+    raw[p] = r < n ? *reinterpret_cast<const uint4*>(x + r * ldx + 4 * li) : make_uint4(0u, 0u, 0u, 0u);
+  }
+#pragma unroll
+  for (int p = 0; p < kPackRowsPerWave / 2; ++p) {
+    uint32_t* dst = image[wave][2 * p + slot];
+    uint8_t* dstb = reinterpret_cast<uint8_t*>(dst);
+    const uint32_t v[4] = {raw[p].x, raw[p].y, raw[p].z, raw[p].w};
+    const unsigned nib = (v[0] != 0u ? 1u : 0u) | (v[1] != 0u ? 2u : 0u) | (v[2] != 0u ? 4u : 0u) | (v[3] != 0u ? 8u : 0u);
+    const int g = li >> 3, sh = 4 * (li & 7);                        // mask dword of this lane's columns, bit offset in it
+    unsigned mw = nib << sh;
+    mw |= __shfl_xor(mw, 1);
+    mw |= __shfl_xor(mw, 2);
+    mw |= __shfl_xor(mw, 4);                                         // all 8 lanes of a group: the group's mask dword
+    uint4 m;
+    m.x = __shfl(mw, slot * 32);
+    m.y = __shfl(mw, slot * 32 + 8);
+    m.z = __shfl(mw, slot * 32 + 16);
+    m.w = __shfl(mw, slot * 32 + 24);
+    int j = (g > 0 ? __popc(m.x) : 0) + (g > 1 ? __popc(m.y) : 0) + (g > 2 ? __popc(m.z) : 0) + __popc(mw & ((1u << sh) - 1u));
+    const uint32_t k = static_cast<uint32_t>(mask_count(m));
+    // every cell starts empty: value bits 0, its own dummy column in the three column bytes, k in the fourth
+    if (li < kCellsPerRow) *reinterpret_cast<uint4*>(dst + 4 * li) = make_uint4(0u, 0u, 0u, (128u + li) * 0x010101u | (k << 24));
+    lds_wave_handoff();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if ((nib >> i) & 1u) {
+        if (j < kCellCap) {                                          // (an overflow row keeps its first kCellCap elements)
+          dst[4 * (j & 15) + (j >> 4)] = v[i];
+          dstb[16 * (j & 15) + 12 + (j >> 4)] = static_cast<uint8_t>(4 * li + i);
+        }
+        ++j;
+      }
+    }
+  }
+  lds_wave_handoff();
+  const int rr = lane >> 4, q = 4 * (lane & 15);                     // this lane's cell of the wave's four images
+  if (row0 + rr < n) *reinterpret_cast<uint4*>(cells + (row0 + rr) * kPackPitchDw + q) = *reinterpret_cast<const uint4*>(image[wave][rr] + q);
+}
+
+// segreduce_kernel<float, 4, 32, kModeSum, false> over cell rows: the wave-per-row mapping, block remap, row_order and 64-incidence column
+// batches of segreduce_packed_kernel, and -- so that the result is BITWISE the dense kernel's -- for every output element the same
+// additions in the same order.  A load instruction gathers FOUR rows (16 lanes x 16 bytes: lane >> 4 the row, lane & 15 the cell); Q of
+// them are in flight per step (4 Q incidences) and go through LDS H at a time.  Incidence i of the step owns image i % (4 H), which is image
+// (u, slot) = (i >> 1, i & 1) of the dense kernel's assignment jj = j + u * NS + slot.  The images are zero between sub-steps: the lane that
+// holds a cell writes its three values at their columns (an unused slot's dummy column is a pad dword of its own), lane (slot, li) reads
+// columns 4 li .. 4 li + 3 of its slot's images in u order -- every dword of them is the dense row's, occupied or +0, and an image nobody
+// wrote adds +0 as the dense kernel's tail does -- and the writers clear what they wrote.  A row above kCellCap occupied columns is copied,
+// dense, from the side table into its image, in a branch the wave takes only when a row of the step needs it.
+// acc = fmaf(1, v, acc) as the dense kernel's machine code performs it: v_add_f32 with the gathered value as the FIRST operand.  The sum
+// is the same either way, the bits of a NaN are not: where two NaNs meet (Inf - Inf earlier in the row gives 0xffc00000, a gathered NaN
+// is usually 0x7fc00000) the instruction returns its first operand's, and "bitwise the dense kernel's" includes that.  The compiler
+// commutes a plain addition as it pleases, hence the instruction by name.
+__device__ __forceinline__ float add_value_first(uint32_t v, float acc) {
+  float r;
+  asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(v), "v"(acc));
+  return r;
+}
+
+template <int Q, int H>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ALLSET_CELL_WAVES, ALLSET_CELL_WAVES))) void segreduce_cells_kernel(
+    const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const uint4* __restrict__ cells,
+    const float* __restrict__ x, int64_t ldx, float* __restrict__ out, int64_t ldo, int n_t, int mean,
+    const int32_t* __restrict__ row_order) {
+  static_assert(Q % H == 0, "whole sub-steps");
+  constexpr int NI = 4 * H;                                           // images per wave: 8 -> 4.5 KiB, 18 KiB per workgroup
+  __shared__ __attribute__((aligned(16))) uint32_t image[kWavesPerBlock * NI * kCellImageDw];
+  const unsigned blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
+  const int slot_row = static_cast<int>(blk) * kWavesPerBlock + (threadIdx.x >> 6);
+  if (slot_row >= n_t) return;  // whole wave exits together
+  const int row = row_order ? row_order[slot_row] : slot_row;
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const int r4 = lane >> 4, cell = lane & 15;                         // as a loader: row of the instruction, cell of the row
+  const int slot = lane >> 5, li = lane & 31;                         // as a reader: the dense kernel's slot and 16-byte column group
+  const int start = rowptr[row], end = rowptr[row + 1];
+  uint32_t* const wimg = image + wave * NI * kCellImageDw;
+  for (int i = lane; i < NI * kCellImageDw / 4; i += kWave) reinterpret_cast<uint4*>(wimg)[i] = make_uint4(0u, 0u, 0u, 0u);
+  uint32_t* const wr = wimg + r4 * kCellImageDw;                      // image of load h of a sub-step: wr + 4 h * kCellImageDw
+  const uint32_t* const rd = wimg + slot * kCellImageDw + 4 * li;     // image (u, slot): rd + 2 u * kCellImageDw
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  lds_wave_handoff();
+
+  for (int base = start; base < end; base += kWave) {
+    const int n = min(kWave, end - base);
+    int my_col = 0;
+    if (lane < n) my_col = col[base + lane];
+    for (int j = 0; j < n; j += 4 * Q) {
+      uint4 raw[Q];
+      uint32_t meta[Q];
+      bool ok[Q];
+      {
+        int src[Q];                                                  // (the shuffles first: the loads then leave back to back)
+#pragma unroll
+        for (int q = 0; q < Q; ++q) src[q] = __shfl(my_col, (j + 4 * q + r4) & (kWave - 1));
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          ok[q] = j + 4 * q + r4 < n;                                // past the end: neither loaded nor scattered
+          meta[q] = 0u;                                              // (k = 0)
+          if (ok[q]) {
+            raw[q] = cells[static_cast<int64_t>(src[q]) * kCellsPerRow + cell];
+            meta[q] = raw[q].w;
+          }
+        }
+      }
+#pragma unroll
+      for (int q0 = 0; q0 < Q; q0 += H) {
+        if (q0 > 0 && j + 4 * q0 >= n) break;                        // wave-uniform: nothing was loaded from here on
+        bool over[H];
+        bool any_over = false;
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+          uint32_t* im = wr + 4 * h * kCellImageDw;
+          const uint32_t m = meta[q0 + h];
+          over[h] = (m >> 24) > static_cast<uint32_t>(kCellCap);
+          any_over |= over[h];
+          if (ok[q0 + h]) {
+            im[m & 0xffu] = raw[q0 + h].x;
+            im[(m >> 8) & 0xffu] = raw[q0 + h].y;
+            im[(m >> 16) & 0xffu] = raw[q0 + h].z;
+          }
+        }
+        any_over = __any(any_over);
+        if (any_over) {                                              // wave-uniform, rare: a row did not fit, its image is the dense row
+#pragma unroll
+          for (int h = 0; h < H; ++h) {
+            const int src = __shfl(my_col, (j + 4 * (q0 + h) + r4) & (kWave - 1));
+            if (over[h]) {
+              const uint4* xr = reinterpret_cast<const uint4*>(x + static_cast<int64_t>(src) * ldx) + cell;
+              uint4* im = reinterpret_cast<uint4*>(wr + 4 * h * kCellImageDw) + cell;
+              im[0] = xr[0];
+              im[16] = xr[16];
+            }
+          }
+        }
+        lds_wave_handoff();
+#pragma unroll
+        for (int u0 = 0; u0 < 2 * H; u0 += 2) {                      // two reads in flight (registers: 8 waves per SIMD need <= 64)
+          uint4 v[2];
+#pragma unroll
+          for (int e = 0; e < 2; ++e) v[e] = *reinterpret_cast<const uint4*>(rd + 2 * (u0 + e) * kCellImageDw);
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            acc[0] = add_value_first(v[e].x, acc[0]);
+            acc[1] = add_value_first(v[e].y, acc[1]);
+            acc[2] = add_value_first(v[e].z, acc[2]);
+            acc[3] = add_value_first(v[e].w, acc[3]);
+          }
+        }
+        lds_wave_handoff();
+        // the images are zero again for the next sub-step: every writer clears what it wrote
+#ifdef ALLSET_CELL_ZERO16           // ablation builds only (tools/cell_gather_bench.py): 16-byte zero stores over the whole images instead
+        for (int i = lane; i < NI * kCellImageDw / 4; i += kWave) reinterpret_cast<uint4*>(wimg)[i] = make_uint4(0u, 0u, 0u, 0u);
+#else
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+          uint32_t* im = wr + 4 * h * kCellImageDw;
+          const uint32_t m = meta[q0 + h];
+          if (ok[q0 + h]) {
+            im[m & 0xffu] = 0u;
+            im[(m >> 8) & 0xffu] = 0u;
+            im[(m >> 16) & 0xffu] = 0u;
+          }
+        }
+        if (any_over) {
+#pragma unroll
+          for (int h = 0; h < H; ++h) {
+            if (over[h]) {
+              uint4* im = reinterpret_cast<uint4*>(wr + 4 * h * kCellImageDw) + cell;
+              im[0] = make_uint4(0u, 0u, 0u, 0u);
+              im[16] = make_uint4(0u, 0u, 0u, 0u);
+            }
+          }
+        }
+#endif
+        lds_wave_handoff();
+      }
+    }
+  }
+
+#pragma unroll
+  for (int g = 0; g < 4; ++g) acc[g] = add_value_first(__float_as_uint(acc[g]), __shfl_xor(acc[g], 32));     // (own sum first, as there)
+
+  if (slot == 0) {
+    const float scale = mean ? 1.f / static_cast<float>(max(end - start, 1)) : 1.f;
+    int lo = lane;
+    asm volatile("" : "+v"(lo));                                     // the store's offset is formed here, not kept in registers across the loop
+    *reinterpret_cast<float4*>(out + static_cast<int64_t>(row) * ldo + 4 * lo) =
+        make_float4(acc[0] * scale, acc[1] * scale, acc[2] * scale, acc[3] * scale);
+  }
+}
+
 // ---- host-side dispatch ------------------------------------------------------------------------
 
 template <typename T, int VEC, int LPR>
@@ -741,6 +952,57 @@ extern "C" int allset_segreduce_packed_fwd(int reduce, const int32_t* row_order,
   ALLSET_REQUIRE(aligned256(packed), "segreduce_packed_fwd: the packed buffer must be 256-byte aligned");
   segreduce_packed_kernel<<<row_grid(n_t), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
       rowptr, col, static_cast<const uint32_t*>(packed), x, ldx, out, ldo, static_cast<int>(n_t), reduce == ALLSET_MEAN, row_order);
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
+}
+
+// segreduce_cells_kernel: load instructions (four rows each) in flight per step, and how many of them go through LDS together;
+// tools/cell_gather_bench.py rebuilds with other values
+#ifndef ALLSET_CELL_LOADS
+#define ALLSET_CELL_LOADS 4
+#endif
+#ifndef ALLSET_CELL_SUBSTEP
+#define ALLSET_CELL_SUBSTEP 2
+#endif
+
+extern "C" int allset_pack_cells_f32(const float* x, int64_t ldx, void* cells, int64_t n, int64_t d, void* stream) {
+  clear_error();
+  ALLSET_REQUIRE(n >= 0 && d >= 0, "pack_cells_f32: negative size");
+  ALLSET_REQUIRE(n < INT32_MAX, "pack_cells_f32: size exceeds int32");
+  if (d != 128) {
+    set_error("pack_cells_f32: built for d = 128 only (got %lld)", static_cast<long long>(d));
+    return ALLSET_ERR_UNSUPPORTED;
+  }
+  if (n == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(x && cells, "pack_cells_f32: null x/cells");
+  ALLSET_REQUIRE(ldx >= d && ldx % 4 == 0 && aligned16(x), "pack_cells_f32: rows of x must be 16-byte aligned (pointer and leading dimension)");
+  ALLSET_REQUIRE(aligned256(cells), "pack_cells_f32: the cell buffer must be 256-byte aligned");
+  const int64_t rows_per_block = static_cast<int64_t>(kWavesPerBlock) * kPackRowsPerWave;
+  const unsigned grid = static_cast<unsigned>((n + rows_per_block - 1) / rows_per_block);
+  pack_cells_kernel<<<grid, kBlock, 0, static_cast<hipStream_t>(stream)>>>(x, ldx, static_cast<uint32_t*>(cells), n);
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
+}
+
+extern "C" int allset_segreduce_cells_fwd(int reduce, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                                          const void* cells, const float* x, int64_t ldx, float* out, int64_t ldo, int64_t n_t,
+                                          int64_t n_s, int64_t d, void* stream) {
+  clear_error();
+  ALLSET_REQUIRE(reduce == ALLSET_SUM || reduce == ALLSET_MEAN, "segreduce_cells_fwd: reduce must be SUM or MEAN (got %d)", reduce);
+  ALLSET_REQUIRE(n_t >= 0 && n_s >= 0 && d >= 0, "segreduce_cells_fwd: negative size");
+  ALLSET_REQUIRE(n_t < INT32_MAX && n_s < INT32_MAX, "segreduce_cells_fwd: size exceeds int32");
+  if (d != 128) {
+    set_error("segreduce_cells_fwd: built for d = 128 only (got %lld)", static_cast<long long>(d));
+    return ALLSET_ERR_UNSUPPORTED;
+  }
+  if (n_t == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(rowptr && out, "segreduce_cells_fwd: null rowptr/out");
+  ALLSET_REQUIRE(n_s == 0 || (col && cells && x), "segreduce_cells_fwd: null col/cells/x with n_s > 0");
+  ALLSET_REQUIRE(ldx >= d && ldo >= d && ldx % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(out),
+                 "segreduce_cells_fwd: rows of x and out must be 16-byte aligned (pointers and leading dimensions)");
+  ALLSET_REQUIRE(aligned256(cells), "segreduce_cells_fwd: the cell buffer must be 256-byte aligned");
+  segreduce_cells_kernel<ALLSET_CELL_LOADS, ALLSET_CELL_SUBSTEP><<<row_grid(n_t), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
+      rowptr, col, static_cast<const uint4*>(cells), x, ldx, out, ldo, static_cast<int>(n_t), reduce == ALLSET_MEAN, row_order);
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }

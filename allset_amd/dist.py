@@ -611,6 +611,7 @@ def sharded_deepsets_layer(v2e_conv, e2v_conv, x_owned: Tensor, hg: ShardedHyper
     of the layer output.  ``v2e_conv`` / ``e2v_conv`` are :class:`allset_amd.layers.HalfNLHconv` (Deep Sets
     variant); their parameters are replicated, so parameter gradients must be all-reduced by the caller
     (``allreduce_grads``) -- each rank sees only its rows."""
+    from . import functional as AF
     if aggr not in ("add", "sum", "mean", "max", "min"):
         raise ValueError(f"aggr {aggr!r}")
     vv = _valid_rows(hg.v_lo, hg.v_hi, hg.n_v)                 # real (not pad) rows of this rank's vertex block; every local hyperedge is real
@@ -621,31 +622,34 @@ def sharded_deepsets_layer(v2e_conv, e2v_conv, x_owned: Tensor, hg: ShardedHyper
     use_halo = hg.halo is not None and hg.halo_v2e is not None
     agg_v2e, agg_e2v = _forward_aggregate(aggregate, v2e_conv), _forward_aggregate(aggregate, e2v_conv)
     pk_v2e = _packs_enc(aggregate, v2e_conv, x_owned, hg.v2e, norm, aggr, group, use_halo)
-    with _bn_scope(vv, group):
+    with _bn_scope(vv, group), AF.packed_direction("v2e"):
         h = v2e_conv._mlp_act(v2e_conv.f_enc, x_owned, v2e_conv.dropout, packed=pk_v2e)
-    if pk_v2e:                                                 # one rank: the owned block is the full table, gathered as packed rows
-        e = agg_v2e(h, hg.v2e, norm, aggr)
-    elif use_halo:                                             # only the rows the local hyperedges touch travel
-        e = agg_v2e(halo_gather(h, hg.halo), hg.halo_v2e, norm, aggr)
-    else:
-        h_full = all_gather_rows(h, group)
-        e = agg_v2e(h_full, hg.v2e, norm, aggr)
+    with AF.packed_direction("v2e"):
+        if pk_v2e:                                             # one rank: the owned block is the full table, gathered as packed rows
+            e = agg_v2e(h, hg.v2e, norm, aggr)
+        elif use_halo:                                         # only the rows the local hyperedges touch travel
+            e = agg_v2e(halo_gather(h, hg.halo), hg.halo_v2e, norm, aggr)
+        else:
+            h_full = all_gather_rows(h, group)
+            e = agg_v2e(h_full, hg.v2e, norm, aggr)
     with _bn_scope(e.shape[0], group):
         e = v2e_conv._mlp_act(v2e_conv.f_dec, e, dropout)       # conv's relu (SetGNN's outer relu is idempotent) + dropout
         # ---- E -> V: dense on owned hyperedges, local partial sums for all vertices, reduce-scatter
         pk_e2v = aggr not in ("max", "min") and _packs_enc(aggregate, e2v_conv, e, hg.e2v, norm, "add", group, use_halo)
-        g = e2v_conv._mlp_act(e2v_conv.f_enc, e, e2v_conv.dropout, packed=pk_e2v)
-    if aggr in ("max", "min") and use_halo:
-        v = _HaloExtremeMerge.apply(agg_e2v(g, hg.halo_e2v, norm, aggr), hg, aggr == "min")
-    elif aggr in ("max", "min"):
-        # local extreme over this rank's hyperedges (autograd routes to the local arg-extreme), then the key merge
-        partial = agg_e2v(g, hg.e2v, norm, aggr)
-        v = _ShardedExtremeMerge.apply(partial, hg.local_vertex_has_incidence(), hg, group, aggr == "min")
-    elif use_halo:
-        v = halo_scatter_add(agg_e2v(g, hg.halo_e2v, norm, "add"), hg.halo)
-    else:
-        partial = agg_e2v(g, hg.e2v, norm, "add")
-        v = reduce_scatter_rows(partial, group)
+        with AF.packed_direction("e2v"):
+            g = e2v_conv._mlp_act(e2v_conv.f_enc, e, e2v_conv.dropout, packed=pk_e2v)
+    with AF.packed_direction("e2v"):
+        if aggr in ("max", "min") and use_halo:
+            v = _HaloExtremeMerge.apply(agg_e2v(g, hg.halo_e2v, norm, aggr), hg, aggr == "min")
+        elif aggr in ("max", "min"):
+            # local extreme over this rank's hyperedges (autograd routes to the local arg-extreme), then the key merge
+            partial = agg_e2v(g, hg.e2v, norm, aggr)
+            v = _ShardedExtremeMerge.apply(partial, hg.local_vertex_has_incidence(), hg, group, aggr == "min")
+        elif use_halo:
+            v = halo_scatter_add(agg_e2v(g, hg.halo_e2v, norm, "add"), hg.halo)
+        else:
+            partial = agg_e2v(g, hg.e2v, norm, "add")
+            v = reduce_scatter_rows(partial, group)
     if aggr == "mean":
         v = v / hg.owned_vertex_degree(group).clamp(min=1).view(-1, 1)
     with _bn_scope(vv, group):

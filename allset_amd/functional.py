@@ -123,6 +123,49 @@ def packed_gather() -> bool:
     return _PACKED_GATHER
 
 
+# Per direction of a layer, as tools/cell_gather_bench.py decided it: the cell gather passed the kill criterion
+# over the E->V CSR and missed it over the V->E one (the mask gather's own repeats scatter too much there), so V->E keeps the mask rows.
+# ``None``: an aggregation whose caller named no direction (a bare ``HalfNLHconv``, ``deepsets_aggregate``).
+_PACKED_FORMAT = {"v2e": "mask", "e2v": "cells", None: "cells"}
+_PACKED_DIRECTION = None
+
+
+def set_packed_format(fmt: str, direction: Optional[str] = None) -> None:
+    """Module switch beside :func:`set_packed_gather`: which packed rows a forward aggregation gathers --
+    ``"cells"`` (every occupied element with its column beside it, expanded per occupied element) or ``"mask"`` (occupancy mask +
+    values, expanded per column).  ``direction``: ``"v2e"`` / ``"e2v"`` sets it for that half of a layer (:func:`packed_direction`),
+    ``None`` for every aggregation.  Every fall-back condition is the same for both formats, and so are the results, bit for bit."""
+    if fmt not in ("cells", "mask"):
+        raise ValueError(f"set_packed_format: format must be 'cells' or 'mask', got {fmt!r}")
+    if direction not in (None, "v2e", "e2v"):
+        raise ValueError(f"set_packed_format: direction must be None, 'v2e' or 'e2v', got {direction!r}")
+    for key in ((direction,) if direction is not None else tuple(_PACKED_FORMAT)):
+        _PACKED_FORMAT[key] = fmt
+
+
+def packed_format(direction: Optional[str] = None) -> str:
+    """The format of ``direction``, or of the direction the caller is in (:func:`packed_direction`)."""
+    return _PACKED_FORMAT[direction if direction is not None else _PACKED_DIRECTION]
+
+
+class packed_direction:
+    """``with packed_direction("v2e"):`` -- the aggregations inside belong to that half of a V->E->V layer and gather the packed
+    format chosen for it.  Host-side state only: nothing here touches the device, the step still captures."""
+
+    def __init__(self, direction: str):
+        if direction not in ("v2e", "e2v"):
+            raise ValueError(f"packed_direction: 'v2e' or 'e2v', got {direction!r}")
+        self.direction = direction
+
+    def __enter__(self):
+        global _PACKED_DIRECTION
+        self.was, _PACKED_DIRECTION = _PACKED_DIRECTION, self.direction
+
+    def __exit__(self, *exc):
+        global _PACKED_DIRECTION
+        _PACKED_DIRECTION = self.was
+
+
 _PACKED_EPILOGUE = "auto"
 # "auto": the fused Linear writes the packed rows itself from this many rows upward.  Below a few thousand rows both forms are bound
 # by their launches (DESIGN.md section 4.5 has the measured crossover); tests/test_gpu_packed_gather.py pins pack_rows at 500 rows.
@@ -192,7 +235,7 @@ def _takes_packed(x: Tensor, w_dst: Optional[Tensor], inc: Incidence, reduce: in
 class _SegReduce(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, w_dst: Optional[Tensor], w_src: Optional[Tensor], inc: Incidence, reduce: int, packed_rows: bool = False,
-                packed: Optional[Tensor] = None):
+                packed: Optional[Tensor] = None, packed_fmt: str = "mask"):
         csr = inc.by_dst
         ext = reduce in (MAX, MIN)
         if packed is not None:
@@ -201,11 +244,15 @@ class _SegReduce(torch.autograd.Function):
             if not _takes_packed(x, w_dst, inc, reduce):
                 raise _lib.AllSetHipError("deepsets_aggregate: packed rows came without a packed gather to read them "
                                           "(functional.takes_packed_epilogue decides the route before the Linear runs)")
-            out = ops.segreduce_packed(reduce, csr.rowptr, csr.col, packed, x, inc.n_dst, row_order=csr.row_order)
+            gather = ops.segreduce_cells if packed_fmt == "cells" else ops.segreduce_packed
+            out = gather(reduce, csr.rowptr, csr.col, packed, x, inc.n_dst, row_order=csr.row_order)
             arg = None
         elif packed_rows and _takes_packed(x, w_dst, inc, reduce):
             # the packed table is a temporary of this forward (the unweighted backward never reads the gathered table)
-            out = ops.segreduce_packed(reduce, csr.rowptr, csr.col, ops.pack_rows(x), x, inc.n_dst, row_order=csr.row_order)
+            if packed_format() == "cells":
+                out = ops.segreduce_cells(reduce, csr.rowptr, csr.col, ops.pack_cells(x), x, inc.n_dst, row_order=csr.row_order)
+            else:
+                out = ops.segreduce_packed(reduce, csr.rowptr, csr.col, ops.pack_rows(x), x, inc.n_dst, row_order=csr.row_order)
             arg = None
         else:
             out, arg = ops.segreduce(reduce, csr.rowptr, csr.col, w_dst, x, inc.n_dst, want_arg=ext,
@@ -243,7 +290,7 @@ class _SegReduce(torch.autograd.Function):
         if ctx.need_gw:
             csr = inc.by_dst
             gw = ops.sddmm_rowdot(reduce, csr.rowptr, csr.col, x, gout, arg)
-        return gx, gw, None, None, None, None, None
+        return gx, gw, None, None, None, None, None, None
 
 
 def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None, aggr: str = "add",
@@ -258,9 +305,9 @@ def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None,
     """
     if aggr not in REDUCE_CODES:
         raise ValueError(f"unknown aggr {aggr!r}")
-    packed = None
+    packed, packed_fmt = None, "mask"
     if isinstance(x, PackedRows):
-        x, packed = x._side, x.packed
+        x, packed, packed_fmt = x._side, x.packed, x.format
     _lib.require_device(x)
     _check_rows(x, inc)
     if norm is not None and norm.requires_grad:
@@ -271,7 +318,7 @@ def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None,
         w_src = _routed(norm, inc, False).detach()        # (only the input gradient reads it; the weight gradient flows through w_dst)
     else:
         w_dst, w_src = inc.weights(norm)
-    return _SegReduce.apply(x, w_dst, w_src, inc, REDUCE_CODES[aggr], bool(packed_rows), packed)
+    return _SegReduce.apply(x, w_dst, w_src, inc, REDUCE_CODES[aggr], bool(packed_rows), packed, packed_fmt)
 
 
 # ---- exclude-self Deep Sets aggregation over the UNEXPANDED incidence (csrc/loo.hip) ------------------------

@@ -317,8 +317,9 @@ class MLP(nn.Module):
                         and dense.wide_linear_supported(self.lins[i + 1].weight.shape[1], self.lins[i + 1].weight.shape[0], True, True, p)):
                     emit = (nxt.eps, True)
                 if is_last and _packed_out:
-                    return dense.fused_norm_linear_packed(x, ln.weight, ln.bias, lin.weight, lin.bias, ln.eps, relu_in=True, p_in=p,
-                                                          relu_out=True, p_out=post_p)
+                    packed_linear = dense.fused_norm_linear_cells if AF.packed_format() == "cells" else dense.fused_norm_linear_packed
+                    return packed_linear(x, ln.weight, ln.bias, lin.weight, lin.bias, ln.eps, relu_in=True, p_in=p, relu_out=True,
+                                         p_out=post_p)
                 x = dense.fused_norm_linear(
                     x, ln.weight if ln is not None else None, ln.bias if ln is not None else None, lin.weight, lin.bias,
                     ln.eps if ln is not None else 1e-5, relu_in=i > 0, p_in=p if i > 0 else 0.0,

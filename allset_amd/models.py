@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from torch.nn import Linear, Parameter
 
 from . import dense
+from . import functional as AF
 from .incidence import Incidence, LeaveOneOutIncidence, LooDirection
 from .layers import MLP, HalfNLHconv, relu_dropout
 
@@ -202,8 +203,10 @@ class SetGNN(nn.Module):
         if self.GPR:
             xs = [F.relu(self.MLP(x))]
             for i in range(len(self.V2EConvs)):
-                x = self.V2EConvs[i](x, v2e, norm, self.aggr, _post_dropout=self.dropout)   # relu + dropout fused
-                x = self.E2VConvs[i](x, e2v, norm, self.aggr)
+                with AF.packed_direction("v2e"):
+                    x = self.V2EConvs[i](x, v2e, norm, self.aggr, _post_dropout=self.dropout)   # relu + dropout fused
+                with AF.packed_direction("e2v"):
+                    x = self.E2VConvs[i](x, e2v, norm, self.aggr)
                 if self.E2VConvs[i].attention:     # (the Deep Sets conv ends in relu(f_dec(.)) already: layers.py, reference layers.py:634)
                     x = F.relu(x)
                 xs.append(x)
@@ -219,6 +222,8 @@ class SetGNN(nn.Module):
             x = F.dropout(x, p=0.2, training=self.training)
         for i in range(len(self.V2EConvs)):
             # x = dropout(relu(conv(x))) (models.py:475-481); relu + dropout ride in the conv's last fused pass
-            x = self.V2EConvs[i](x, v2e, norm, self.aggr, _post_dropout=self.dropout, _pre_dropout=pre if i == 0 else 0.0)
-            x = self.E2VConvs[i](x, e2v, norm, self.aggr, _post_dropout=self.dropout)
+            with AF.packed_direction("v2e"):
+                x = self.V2EConvs[i](x, v2e, norm, self.aggr, _post_dropout=self.dropout, _pre_dropout=pre if i == 0 else 0.0)
+            with AF.packed_direction("e2v"):
+                x = self.E2VConvs[i](x, e2v, norm, self.aggr, _post_dropout=self.dropout)
         return self.classifier(x)

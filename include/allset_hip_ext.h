@@ -1237,6 +1237,35 @@ int allset_fused_linear_fwd_packed(const float* x, int64_t ldx, const float* gam
                                    uint64_t seed_out, void* packed, float* side, int64_t ldside, float* stats, int64_t n, int64_t K,
                                    int64_t N, const uint64_t* seed_base, uint32_t* mask_out, int arith, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Cell rows: the second packed format of the forward Deep Sets gather.  Additions only.  fp32, d = 128 only
+ * (ALLSET_ERR_UNSUPPORTED otherwise).  The mask format above stays as it is.
+ *
+ * The format: a row is 256 bytes on a 256-byte pitch in a 256-byte aligned buffer, kCellsPerRow = 16 cells of 16 bytes.  Cell c holds
+ * the dwords {v0, v1, v2, meta}; meta holds the bytes {col0, col1, col2, k} (col0 the lowest byte).  k is the row's count of occupied
+ * columns, 0..128, the same in every cell; occupied means, as in the mask format, that the element's BIT PATTERN is not 0x00000000
+ * (-0.0, NaN and Inf are values).  The occupied element of rank j in column order goes to cell j % 16, slot j / 16: its bits to v<slot>,
+ * its column to col<slot>.  A row holds at most kCellCap = 48 elements.  An unused slot holds value bits 0 and the column byte 128 + c,
+ * a dummy column private to its cell: a reader that scatters every slot of cell c into an image of 128 + 16 dwords lands an unused one
+ * in pad dword c and never on a column.  k > kCellCap is an overflow row: its cells hold its first 48 elements, and the gather reads the
+ * row from the dense table, which is passed beside the cells as for the mask format.  Slot s is used by some cell iff k > 16 s.
+ *
+ * allset_pack_cells_f32: x f32[n, 128] (pitch ldx, a multiple of 4; 16-byte aligned) -> cells u32[n, 64].  One streaming pass.
+ * allset_segreduce_cells_fwd: allset_segreduce_packed_fwd over cell rows -- same arguments, same result, bitwise that of
+ * allset_segreduce_fwd_ex (variant 1, SUM / MEAN, no weights) over the dense table.
+ * allset_fused_linear_fwd_cells(_supported): allset_fused_linear_fwd_packed(_supported) writing cell rows (csrc/fused_fwd2.hip mode 4):
+ * bit for bit allset_fused_linear_fwd_ex followed by allset_pack_cells_f32; rows above kCellCap also go, dense, to `side`.
+ * ------------------------------------------------------------------------------------------- */
+enum { kCellsPerRow = 16, kCellCap = 48 };
+int allset_pack_cells_f32(const float* x, int64_t ldx, void* cells, int64_t n, int64_t d, void* stream);
+int allset_segreduce_cells_fwd(int reduce, const int32_t* row_order, const int32_t* rowptr, const int32_t* col, const void* cells,
+                               const float* x, int64_t ldx, float* out, int64_t ldo, int64_t n_t, int64_t n_s, int64_t d, void* stream);
+int allset_fused_linear_fwd_cells_supported(int64_t K, int64_t N, int has_ln, float p_in, float p_out);
+int allset_fused_linear_fwd_cells(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, int relu_in, float p_in,
+                                  uint64_t seed_in, const float* W, const float* bias, int relu_out, float p_out, uint64_t seed_out,
+                                  void* cells, float* side, int64_t ldside, float* stats, int64_t n, int64_t K, int64_t N,
+                                  const uint64_t* seed_base, uint32_t* mask_out, int arith, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
