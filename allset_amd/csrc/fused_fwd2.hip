@@ -55,7 +55,7 @@ constexpr int kF2Sets = 4;                     // register sets of prefetched ro
 // the symmetric bf16x6 kernel of fused_mlp.hip (0.35 ms per [1M, 128] launch against 0.20 here).
 //   3  the output leaves as PACKED NONZERO ROWS (include/allset_hip_ext.h, DESIGN.md 4.5: 128-bit occupancy mask + the occupied elements,
 //      256 bytes per row) -> `uo`, the format the forward Deep Sets gather reads, instead of the dense table: the epilogue packs each
-//      row it holds in registers anyway, so neither the dense write nor pack_rows_kernel's pass over it happens.  A row above kPackCap
+//      row it holds in registers anyway, so neither the dense write nor pack_kernel's pass over it happens.  A row above kPackCap
 //      occupied columns also goes, dense, to row r of `y` (the overflow side table: nothing else of it is ever written).  Built for
 //      <HAS_LN, DROP_IN, DROP_OUT> = <true, true, true> only, in both arithmetics.
 //   4  mode 3 with the CELL layout of include/allset_hip_ext.h (16 cells of {v0, v1, v2, {col0, col1, col2, k}}: each occupied element
@@ -648,13 +648,18 @@ int fused_linear_fwd_roles_supported(int64_t K, int64_t N, int has_aux) {
   return (K == 128 && N == 128) ? 1 : 0;
 }
 
+// one persistent workgroup per CU
+static inline unsigned f2_grid(int64_t n) {
+  const int64_t blocks = (n + kF2Rows - 1) / kF2Rows;
+  return static_cast<unsigned>(blocks > 256 ? 256 : (blocks < 1 ? 1 : blocks));
+}
+
 // The plain Linear (no norm, no dropout, row-major operands) with four auxiliary output columns: y = relu_out?(relu_in?(x) W^T + b),
 // aux_out = relu_in?(x) aux_w^T + aux_b
 int launch_fused_linear_fwd_roles_aux(hipStream_t st, const float* x, int64_t ldx, int relu_in, const float* W, const float* bias,
                                       int relu_out, float* y, int64_t ldy, int64_t n, uint32_t* mask_out, const float* aux_w,
                                       const float* aux_b, float* aux_out, int arith) {
-  const int64_t blocks = (n + kF2Rows - 1) / kF2Rows;
-  const unsigned grid = static_cast<unsigned>(blocks > 256 ? 256 : (blocks < 1 ? 1 : blocks));
+  const unsigned grid = f2_grid(n);
 #define ALLSET_F2_AUX(H16)                                                                                                             \
   fused_linear_fwd_roles_kernel<false, false, false, false, H16, 0, true><<<grid, kF2Block, 0, st>>>(                                   \
       x, ldx, nullptr, nullptr, 1e-5f, relu_in, 0.f, 0, W, bias, relu_out, 0.f, 0, y, ldy, nullptr, n, nullptr, mask_out, 0, 0, 1.f / 128.f, \
@@ -672,8 +677,7 @@ int launch_fused_linear_fwd_roles(hipStream_t st, const float* x, int64_t ldx, c
                                   int relu_in, float p_in, uint64_t seed_in, const float* W, const float* bias, int relu_out,
                                   float p_out, uint64_t seed_out, float* y, int64_t ldy, float* stats, int64_t n,
                                   const uint64_t* seed_base, uint32_t* mask_out, int64_t xcb, int64_t ycb, float ln_inv, int arith) {
-  const int64_t blocks = (n + kF2Rows - 1) / kF2Rows;
-  const unsigned grid = static_cast<unsigned>(blocks > 256 ? 256 : (blocks < 1 ? 1 : blocks));      // one persistent workgroup per CU
+  const unsigned grid = f2_grid(n);
   // the dropout resolution is a function of p alone (common.h drop_threshold): 8 bits per element when p * 256 is an integer
   const bool d8 = drop_is8(p_in) && drop_is8(p_out);
   // fp16x3 arithmetic: behind a true LayerNorm prologue (its bound on the operand gives one scale per launch) and -- round 5 -- without
@@ -706,14 +710,58 @@ int launch_fused_linear_fwd_roles(hipStream_t st, const float* x, int64_t ldx, c
   return 0;
 }
 
-static inline unsigned f2_grid(int64_t n) {
-  const int64_t blocks = (n + kF2Rows - 1) / kF2Rows;
-  return static_cast<unsigned>(blocks > 256 ? 256 : (blocks < 1 ? 1 : blocks));
-}
-
-// ---- mode 3: the Linear whose output leaves as packed nonzero rows (the last f_enc Linear in front of a forward Deep Sets gather) ----
+// ---- modes 3 and 4: the Linear whose output leaves as packed nonzero rows (the last f_enc Linear in front of a forward Deep Sets gather) --
+// -- mask rows (XM = 3, the format segreduce_packed_kernel gathers) or cell rows (XM = 4, segreduce_cells_kernel's)
 extern "C" int allset_fused_linear_fwd_packed_supported(int64_t K, int64_t N, int has_ln, float p_in, float p_out) {
   return (K == 128 && N == 128 && has_ln && p_in > 0.f && p_in < 1.f && p_out > 0.f && p_out < 1.f) ? 1 : 0;
+}
+
+extern "C" int allset_fused_linear_fwd_cells_supported(int64_t K, int64_t N, int has_ln, float p_in, float p_out) {
+  return allset_fused_linear_fwd_packed_supported(K, N, has_ln, p_in, p_out);
+}
+
+// `fn`: the exported function's name for the messages; `supported`: ITS query
+template <int XM>
+static int fused_linear_fwd_packed_impl(const char* fn, int (*supported)(int64_t, int64_t, int, float, float), const float* x, int64_t ldx,
+                                        const float* gamma, const float* beta, float eps, int relu_in, float p_in, uint64_t seed_in,
+                                        const float* W, const float* bias, int relu_out, float p_out, uint64_t seed_out, void* packed,
+                                        float* side, int64_t ldside, float* stats, int64_t n, int64_t K, int64_t N,
+                                        const uint64_t* seed_base, uint32_t* mask_out, int arith, void* stream) {
+  static_assert(XM == 3 || XM == 4, "the two packed epilogues");
+  clear_error();
+  ALLSET_REQUIRE(n >= 0, "%s: negative size", fn);
+  ALLSET_REQUIRE(arith == ALLSET_ARITH_AUTO || arith == ALLSET_ARITH_BF16X6 || arith == ALLSET_ARITH_FP16X3,
+                 "%s: arith must be ALLSET_ARITH_AUTO, ALLSET_ARITH_BF16X6 or ALLSET_ARITH_FP16X3", fn);
+  if (!supported(K, N, gamma != nullptr, p_in, p_out)) {
+    set_error("%s: built for K = N = 128 behind a LayerNorm with dropout in and out only (allset_%s_supported)", fn, fn);
+    return ALLSET_ERR_UNSUPPORTED;
+  }
+#ifdef ALLSET_NO_F16X3
+  if (arith == ALLSET_ARITH_FP16X3) { set_error("%s: this build has no fp16x3 arithmetic", fn); return ALLSET_ERR_UNSUPPORTED; }
+#endif
+  if (n == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(x && beta && W && packed && side && stats, "%s: null pointer", fn);
+  ALLSET_REQUIRE(aligned16(x) && aligned16(side) && aligned16(W) && (reinterpret_cast<uintptr_t>(stats) & 7u) == 0,
+                 "%s: x / side / W must be 16-byte aligned, stats 8-byte aligned", fn);
+  ALLSET_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 255u) == 0, "%s: the packed buffer must be 256-byte aligned", fn);
+  ALLSET_REQUIRE(ldx >= K && ldx % 4 == 0 && ldside >= N && ldside % 4 == 0 && ldx < (1 << 24) && ldside < (1 << 24),
+                 "%s: rows must be 16-byte aligned, leading dimensions below 2^24", fn);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool d8 = drop_is8(p_in) && drop_is8(p_out);
+#ifdef ALLSET_NO_F16X3
+  const bool f16 = false;
+#else
+  const bool f16 = arith != ALLSET_ARITH_BF16X6;
+#endif
+#define ALLSET_F2_PK(E8, H16)                                                                                                            \
+  fused_linear_fwd_roles_kernel<true, true, true, E8, H16, XM><<<f2_grid(n), kF2Block, 0, st>>>(                                            \
+      x, ldx, gamma, beta, eps, relu_in, p_in, seed_in, W, bias, relu_out, p_out, seed_out, side, ldside, stats, n, seed_base, mask_out, 0, 0, \
+      1.f / 128.f, nullptr, static_cast<float*>(packed), 0)
+  if (d8) { if (f16) ALLSET_F2_PK(true, true); else ALLSET_F2_PK(true, false); }
+  else    { if (f16) ALLSET_F2_PK(false, true); else ALLSET_F2_PK(false, false); }
+#undef ALLSET_F2_PK
+  ALLSET_LAUNCH_CHECK();
+  return ALLSET_OK;
 }
 
 // packed[r] = pack(dropout_{p_out}(relu_out?(dropout_{p_in}(relu_in?(LayerNorm(x)))[r] W^T + bias)));  side[r, :] = that row, dense, for
@@ -724,46 +772,9 @@ extern "C" int allset_fused_linear_fwd_packed(const float* x, int64_t ldx, const
                                               uint64_t seed_out, void* packed, float* side, int64_t ldside, float* stats, int64_t n,
                                               int64_t K, int64_t N, const uint64_t* seed_base, uint32_t* mask_out, int arith,
                                               void* stream) {
-  clear_error();
-  ALLSET_REQUIRE(n >= 0, "fused_linear_fwd_packed: negative size");
-  ALLSET_REQUIRE(arith == ALLSET_ARITH_AUTO || arith == ALLSET_ARITH_BF16X6 || arith == ALLSET_ARITH_FP16X3,
-                 "fused_linear_fwd_packed: arith must be ALLSET_ARITH_AUTO, ALLSET_ARITH_BF16X6 or ALLSET_ARITH_FP16X3");
-  if (!allset_fused_linear_fwd_packed_supported(K, N, gamma != nullptr, p_in, p_out)) {
-    set_error("fused_linear_fwd_packed: built for K = N = 128 behind a LayerNorm with dropout in and out only "
-              "(allset_fused_linear_fwd_packed_supported)");
-    return ALLSET_ERR_UNSUPPORTED;
-  }
-#ifdef ALLSET_NO_F16X3
-  if (arith == ALLSET_ARITH_FP16X3) { set_error("fused_linear_fwd_packed: this build has no fp16x3 arithmetic"); return ALLSET_ERR_UNSUPPORTED; }
-#endif
-  if (n == 0) return ALLSET_OK;
-  ALLSET_REQUIRE(x && beta && W && packed && side && stats, "fused_linear_fwd_packed: null pointer");
-  ALLSET_REQUIRE(aligned16(x) && aligned16(side) && aligned16(W) && (reinterpret_cast<uintptr_t>(stats) & 7u) == 0,
-                 "fused_linear_fwd_packed: x / side / W must be 16-byte aligned, stats 8-byte aligned");
-  ALLSET_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 255u) == 0, "fused_linear_fwd_packed: the packed buffer must be 256-byte aligned");
-  ALLSET_REQUIRE(ldx >= K && ldx % 4 == 0 && ldside >= N && ldside % 4 == 0 && ldx < (1 << 24) && ldside < (1 << 24),
-                 "fused_linear_fwd_packed: rows must be 16-byte aligned, leading dimensions below 2^24");
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool d8 = drop_is8(p_in) && drop_is8(p_out);
-#ifdef ALLSET_NO_F16X3
-  const bool f16 = false;
-#else
-  const bool f16 = arith != ALLSET_ARITH_BF16X6;
-#endif
-#define ALLSET_F2_PK(E8, H16)                                                                                                            \
-  fused_linear_fwd_roles_kernel<true, true, true, E8, H16, 3><<<f2_grid(n), kF2Block, 0, st>>>(                                             \
-      x, ldx, gamma, beta, eps, relu_in, p_in, seed_in, W, bias, relu_out, p_out, seed_out, side, ldside, stats, n, seed_base, mask_out, 0, 0, \
-      1.f / 128.f, nullptr, static_cast<float*>(packed), 0)
-  if (d8) { if (f16) ALLSET_F2_PK(true, true); else ALLSET_F2_PK(true, false); }
-  else    { if (f16) ALLSET_F2_PK(false, true); else ALLSET_F2_PK(false, false); }
-#undef ALLSET_F2_PK
-  ALLSET_LAUNCH_CHECK();
-  return ALLSET_OK;
-}
-
-// ---- mode 4: the same Linear writing cell rows (the format segreduce_cells_kernel gathers) ----
-extern "C" int allset_fused_linear_fwd_cells_supported(int64_t K, int64_t N, int has_ln, float p_in, float p_out) {
-  return allset_fused_linear_fwd_packed_supported(K, N, has_ln, p_in, p_out);
+  return fused_linear_fwd_packed_impl<3>("fused_linear_fwd_packed", allset_fused_linear_fwd_packed_supported, x, ldx, gamma, beta, eps,
+                                         relu_in, p_in, seed_in, W, bias, relu_out, p_out, seed_out, packed, side, ldside, stats, n, K, N,
+                                         seed_base, mask_out, arith, stream);
 }
 
 // allset_fused_linear_fwd_packed with cells[r] = pack_cells(...) and side[r, :] written for the rows above kCellCap occupied columns ONLY.
@@ -773,41 +784,9 @@ extern "C" int allset_fused_linear_fwd_cells(const float* x, int64_t ldx, const 
                                              uint64_t seed_out, void* cells, float* side, int64_t ldside, float* stats, int64_t n,
                                              int64_t K, int64_t N, const uint64_t* seed_base, uint32_t* mask_out, int arith,
                                              void* stream) {
-  clear_error();
-  ALLSET_REQUIRE(n >= 0, "fused_linear_fwd_cells: negative size");
-  ALLSET_REQUIRE(arith == ALLSET_ARITH_AUTO || arith == ALLSET_ARITH_BF16X6 || arith == ALLSET_ARITH_FP16X3,
-                 "fused_linear_fwd_cells: arith must be ALLSET_ARITH_AUTO, ALLSET_ARITH_BF16X6 or ALLSET_ARITH_FP16X3");
-  if (!allset_fused_linear_fwd_cells_supported(K, N, gamma != nullptr, p_in, p_out)) {
-    set_error("fused_linear_fwd_cells: built for K = N = 128 behind a LayerNorm with dropout in and out only "
-              "(allset_fused_linear_fwd_cells_supported)");
-    return ALLSET_ERR_UNSUPPORTED;
-  }
-#ifdef ALLSET_NO_F16X3
-  if (arith == ALLSET_ARITH_FP16X3) { set_error("fused_linear_fwd_cells: this build has no fp16x3 arithmetic"); return ALLSET_ERR_UNSUPPORTED; }
-#endif
-  if (n == 0) return ALLSET_OK;
-  ALLSET_REQUIRE(x && beta && W && cells && side && stats, "fused_linear_fwd_cells: null pointer");
-  ALLSET_REQUIRE(aligned16(x) && aligned16(side) && aligned16(W) && (reinterpret_cast<uintptr_t>(stats) & 7u) == 0,
-                 "fused_linear_fwd_cells: x / side / W must be 16-byte aligned, stats 8-byte aligned");
-  ALLSET_REQUIRE((reinterpret_cast<uintptr_t>(cells) & 255u) == 0, "fused_linear_fwd_cells: the cell buffer must be 256-byte aligned");
-  ALLSET_REQUIRE(ldx >= K && ldx % 4 == 0 && ldside >= N && ldside % 4 == 0 && ldx < (1 << 24) && ldside < (1 << 24),
-                 "fused_linear_fwd_cells: rows must be 16-byte aligned, leading dimensions below 2^24");
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool d8 = drop_is8(p_in) && drop_is8(p_out);
-#ifdef ALLSET_NO_F16X3
-  const bool f16 = false;
-#else
-  const bool f16 = arith != ALLSET_ARITH_BF16X6;
-#endif
-#define ALLSET_F2_CL(E8, H16)                                                                                                            \
-  fused_linear_fwd_roles_kernel<true, true, true, E8, H16, 4><<<f2_grid(n), kF2Block, 0, st>>>(                                             \
-      x, ldx, gamma, beta, eps, relu_in, p_in, seed_in, W, bias, relu_out, p_out, seed_out, side, ldside, stats, n, seed_base, mask_out, 0, 0, \
-      1.f / 128.f, nullptr, static_cast<float*>(cells), 0)
-  if (d8) { if (f16) ALLSET_F2_CL(true, true); else ALLSET_F2_CL(true, false); }
-  else    { if (f16) ALLSET_F2_CL(false, true); else ALLSET_F2_CL(false, false); }
-#undef ALLSET_F2_CL
-  ALLSET_LAUNCH_CHECK();
-  return ALLSET_OK;
+  return fused_linear_fwd_packed_impl<4>("fused_linear_fwd_cells", allset_fused_linear_fwd_cells_supported, x, ldx, gamma, beta, eps,
+                                         relu_in, p_in, seed_in, W, bias, relu_out, p_out, seed_out, cells, side, ldside, stats, n, K, N,
+                                         seed_base, mask_out, arith, stream);
 }
 
 // ---- the PMA tail (reference layers.py:153-157) folded into its two rFF Linears: modes 1 and 2 of the kernel above (fp16x3) -------

@@ -358,7 +358,7 @@ __global__ __launch_bounds__(kBlock) void sddmm_rowdot_vec_kernel(
 // ---- packed nonzero rows (include/allset_hip_ext.h: 128-bit occupancy mask + the occupied elements, 256 bytes per row) --------
 // The forward aggregations gather dropout(relu(.)) tables, about 3/4 zeros: a packed row is two 128-byte lines where the dense row is
 // four, and what bounds the gather is the count of line requests.
-constexpr int kPackRowsPerWave = 4;      // pack_rows_kernel: two rows per 16-byte load instruction, two of them in flight
+constexpr int kPackRowsPerWave = 4;      // pack_kernel:      two rows per 16-byte load instruction, two of them in flight
 constexpr int kExpand = 2;               // segreduce_packed_kernel: gathered rows per slot expanded through LDS together (and skipped together)
 
 // the LDS hand-off between lanes of ONE wave (the LDS serves a wave's operations in order): keeps the compiler from moving accesses across
@@ -375,9 +375,11 @@ __device__ __forceinline__ uint32_t all_ones_if_bit(uint32_t m, int b) {
 __device__ __forceinline__ int mask_count(const uint4& m) { return __popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w); }
 
 // Half a wave per row, 16 bytes per lane (columns 4 li .. 4 li + 3): the mask dwords are OR-reduced over the 8 lanes that share one, the
-// values are scattered into an LDS image of the row at 4 + (occupied columns below), and the wave's four images leave in ONE coalesced
-// 16-byte store per lane (1 KiB).
-__global__ __launch_bounds__(kBlock) void pack_rows_kernel(const float* __restrict__ x, int64_t ldx, uint32_t* __restrict__ packed, int64_t n) {
+// values are scattered into an LDS image of the row, and the wave's four images leave in ONE coalesced 16-byte store per lane (1 KiB).
+// The image is the format's (include/allset_hip_ext.h).  Mask rows: the mask in dwords 0 .. 3, the element of rank j at 4 + j.  Cell rows
+// (CELLS): the element of rank j in cell j % 16, slot j / 16, its column in the cell's fourth dword.
+template <bool CELLS>
+__global__ __launch_bounds__(kBlock) void pack_kernel(const float* __restrict__ x, int64_t ldx, uint32_t* __restrict__ packed, int64_t n) {
   __shared__ __attribute__((aligned(16))) uint32_t image[kWavesPerBlock][kPackRowsPerWave][kPackPitchDw];
   const int wave = threadIdx.x >> 6, lane = lane_id();
   const int slot = lane >> 5, li = lane & 31;
@@ -404,25 +406,47 @@ __global__ __launch_bounds__(kBlock) void pack_rows_kernel(const float* __restri
     m.y = __shfl(mw, slot * 32 + 8);
     m.z = __shfl(mw, slot * 32 + 16);
     m.w = __shfl(mw, slot * 32 + 24);
-    int pos = 4 + (g > 0 ? __popc(m.x) : 0) + (g > 1 ? __popc(m.y) : 0) + (g > 2 ? __popc(m.z) : 0) + __popc(mw & ((1u << sh) - 1u));
+    // rank of this lane's first occupied column among the row's
+    int j = (g > 0 ? __popc(m.x) : 0) + (g > 1 ? __popc(m.y) : 0) + (g > 2 ? __popc(m.z) : 0) + __popc(mw & ((1u << sh) - 1u));
+    if constexpr (CELLS) {
+      uint8_t* dstb = reinterpret_cast<uint8_t*>(dst);
+      const uint32_t k = static_cast<uint32_t>(mask_count(m));
+      // every cell starts empty: value bits 0, its own dummy column in the three column bytes, k in the fourth
+      if (li < kCellsPerRow) *reinterpret_cast<uint4*>(dst + 4 * li) = make_uint4(0u, 0u, 0u, (128u + li) * 0x010101u | (k << 24));
+      lds_wave_handoff();
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if ((nib >> i) & 1u) {
-        if (pos < kPackPitchDw) dst[pos] = v[i];                     // (an overflow row keeps what fits)
-        ++pos;
+      for (int i = 0; i < 4; ++i) {
+        if ((nib >> i) & 1u) {
+          if (j < kCellCap) {                                        // (an overflow row keeps its first kCellCap elements)
+            dst[4 * (j & 15) + (j >> 4)] = v[i];
+            dstb[16 * (j & 15) + 12 + (j >> 4)] = static_cast<uint8_t>(4 * li + i);
+          }
+          ++j;
+        }
       }
+    } else {
+      int pos = 4 + j;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if ((nib >> i) & 1u) {
+          if (pos < kPackPitchDw) dst[pos] = v[i];                   // (an overflow row keeps what fits)
+          ++pos;
+        }
+      }
+      if (li == 0) *reinterpret_cast<uint4*>(dst) = m;
     }
-    if (li == 0) *reinterpret_cast<uint4*>(dst) = m;
   }
   lds_wave_handoff();
   const int rr = lane >> 4, q = 4 * (lane & 15);                     // this lane's 16 bytes of the wave's four images
   const uint32_t* src = image[wave][rr];
-  const int k = mask_count(*reinterpret_cast<const uint4*>(src));
   uint4 o = *reinterpret_cast<const uint4*>(src + q);
-  if (q + 0 >= 4 + k) o.x = 0u;                                      // never-written LDS behind the values
-  if (q + 1 >= 4 + k) o.y = 0u;
-  if (q + 2 >= 4 + k) o.z = 0u;
-  if (q + 3 >= 4 + k) o.w = 0u;
+  if constexpr (!CELLS) {
+    const int k = mask_count(*reinterpret_cast<const uint4*>(src));
+    if (q + 0 >= 4 + k) o.x = 0u;                                    // never-written LDS behind the values
+    if (q + 1 >= 4 + k) o.y = 0u;
+    if (q + 2 >= 4 + k) o.z = 0u;
+    if (q + 3 >= 4 + k) o.w = 0u;
+  }
   if (row0 + rr < n) *reinterpret_cast<uint4*>(packed + (row0 + rr) * kPackPitchDw + q) = o;
 }
 
@@ -535,56 +559,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 #define ALLSET_CELL_WAVES 8
 #endif
 constexpr int kCellImageDw = 128 + kCellsPerRow;       // a row's image: its 128 columns + one pad dword per cell (the dummy columns)
-
-// pack_rows_kernel with the cell layout: the element of rank j goes to cell j % 16, slot j / 16.
-__global__ __launch_bounds__(kBlock) void pack_cells_kernel(const float* __restrict__ x, int64_t ldx, uint32_t* __restrict__ cells, int64_t n) {
-  __shared__ __attribute__((aligned(16))) uint32_t image[kWavesPerBlock][kPackRowsPerWave][kPackPitchDw];
-  const int wave = threadIdx.x >> 6, lane = lane_id();
-  const int slot = lane >> 5, li = lane & 31;
-  const int64_t row0 = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave) * kPackRowsPerWave;
-  if (row0 >= n) return;  // whole wave exits together
-  uint4 raw[kPackRowsPerWave / 2];
-#pragma unroll
-  for (int p = 0; p < kPackRowsPerWave / 2; ++p) {
-    const int64_t r = row0 + 2 * p + slot;
-    raw[p] = r < n ? *reinterpret_cast<const uint4*>(x + r * ldx + 4 * li) : make_uint4(0u, 0u, 0u, 0u);
-  }
-#pragma unroll
-  for (int p = 0; p < kPackRowsPerWave / 2; ++p) {
-    uint32_t* dst = image[wave][2 * p + slot];
-    uint8_t* dstb = reinterpret_cast<uint8_t*>(dst);
-    const uint32_t v[4] = {raw[p].x, raw[p].y, raw[p].z, raw[p].w};
-    const unsigned nib = (v[0] != 0u ? 1u : 0u) | (v[1] != 0u ? 2u : 0u) | (v[2] != 0u ? 4u : 0u) | (v[3] != 0u ? 8u : 0u);
-    const int g = li >> 3, sh = 4 * (li & 7);                        // mask dword of this lane's columns, bit offset in it
-    unsigned mw = nib << sh;
-    mw |= __shfl_xor(mw, 1);
-    mw |= __shfl_xor(mw, 2);
-    mw |= __shfl_xor(mw, 4);                                         // all 8 lanes of a group: the group's mask dword
-    uint4 m;
-    m.x = __shfl(mw, slot * 32);
-    m.y = __shfl(mw, slot * 32 + 8);
-    m.z = __shfl(mw, slot * 32 + 16);
-    m.w = __shfl(mw, slot * 32 + 24);
-    int j = (g > 0 ? __popc(m.x) : 0) + (g > 1 ? __popc(m.y) : 0) + (g > 2 ? __popc(m.z) : 0) + __popc(mw & ((1u << sh) - 1u));
-    const uint32_t k = static_cast<uint32_t>(mask_count(m));
-    // every cell starts empty: value bits 0, its own dummy column in the three column bytes, k in the fourth
-    if (li < kCellsPerRow) *reinterpret_cast<uint4*>(dst + 4 * li) = make_uint4(0u, 0u, 0u, (128u + li) * 0x010101u | (k << 24));
-    lds_wave_handoff();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if ((nib >> i) & 1u) {
-        if (j < kCellCap) {                                          // (an overflow row keeps its first kCellCap elements)
-          dst[4 * (j & 15) + (j >> 4)] = v[i];
-          dstb[16 * (j & 15) + 12 + (j >> 4)] = static_cast<uint8_t>(4 * li + i);
-        }
-        ++j;
-      }
-    }
-  }
-  lds_wave_handoff();
-  const int rr = lane >> 4, q = 4 * (lane & 15);                     // this lane's cell of the wave's four images
-  if (row0 + rr < n) *reinterpret_cast<uint4*>(cells + (row0 + rr) * kPackPitchDw + q) = *reinterpret_cast<const uint4*>(image[wave][rr] + q);
-}
 
 // segreduce_kernel<float, 4, 32, kModeSum, false> over cell rows: the wave-per-row mapping, block remap, row_order and 64-incidence column
 // batches of segreduce_packed_kernel, and -- so that the result is BITWISE the dense kernel's -- for every output element the same
@@ -914,44 +888,24 @@ extern "C" int allset_sddmm_rowdot(int reduce, const int32_t* rowptr, const int3
 
 static inline bool aligned256(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 255u) == 0; }
 
-extern "C" int allset_pack_rows_f32(const float* x, int64_t ldx, void* packed, int64_t n, int64_t d, void* stream) {
+// ---- the two packed formats' entry points: one body each, the exported name for the messages, the format for the kernel ------------
+static int pack_impl(const char* fn, bool cells, const float* x, int64_t ldx, void* packed, int64_t n, int64_t d, void* stream) {
   clear_error();
-  ALLSET_REQUIRE(n >= 0 && d >= 0, "pack_rows_f32: negative size");
-  ALLSET_REQUIRE(n < INT32_MAX, "pack_rows_f32: size exceeds int32");
+  ALLSET_REQUIRE(n >= 0 && d >= 0, "%s: negative size", fn);
+  ALLSET_REQUIRE(n < INT32_MAX, "%s: size exceeds int32", fn);
   if (d != 128) {
-    set_error("pack_rows_f32: built for d = 128 only (got %lld)", static_cast<long long>(d));
+    set_error("%s: built for d = 128 only (got %lld)", fn, static_cast<long long>(d));
     return ALLSET_ERR_UNSUPPORTED;
   }
   if (n == 0) return ALLSET_OK;
-  ALLSET_REQUIRE(x && packed, "pack_rows_f32: null x/packed");
-  ALLSET_REQUIRE(ldx >= d && ldx % 4 == 0 && aligned16(x), "pack_rows_f32: rows of x must be 16-byte aligned (pointer and leading dimension)");
-  ALLSET_REQUIRE(aligned256(packed), "pack_rows_f32: the packed buffer must be 256-byte aligned");
+  ALLSET_REQUIRE(x && packed, "%s: null x/packed", fn);
+  ALLSET_REQUIRE(ldx >= d && ldx % 4 == 0 && aligned16(x), "%s: rows of x must be 16-byte aligned (pointer and leading dimension)", fn);
+  ALLSET_REQUIRE(aligned256(packed), "%s: the packed buffer must be 256-byte aligned", fn);
   const int64_t rows_per_block = static_cast<int64_t>(kWavesPerBlock) * kPackRowsPerWave;
   const unsigned grid = static_cast<unsigned>((n + rows_per_block - 1) / rows_per_block);
-  pack_rows_kernel<<<grid, kBlock, 0, static_cast<hipStream_t>(stream)>>>(x, ldx, static_cast<uint32_t*>(packed), n);
-  ALLSET_LAUNCH_CHECK();
-  return ALLSET_OK;
-}
-
-extern "C" int allset_segreduce_packed_fwd(int reduce, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
-                                           const void* packed, const float* x, int64_t ldx, float* out, int64_t ldo, int64_t n_t,
-                                           int64_t n_s, int64_t d, void* stream) {
-  clear_error();
-  ALLSET_REQUIRE(reduce == ALLSET_SUM || reduce == ALLSET_MEAN, "segreduce_packed_fwd: reduce must be SUM or MEAN (got %d)", reduce);
-  ALLSET_REQUIRE(n_t >= 0 && n_s >= 0 && d >= 0, "segreduce_packed_fwd: negative size");
-  ALLSET_REQUIRE(n_t < INT32_MAX && n_s < INT32_MAX, "segreduce_packed_fwd: size exceeds int32");
-  if (d != 128) {
-    set_error("segreduce_packed_fwd: built for d = 128 only (got %lld)", static_cast<long long>(d));
-    return ALLSET_ERR_UNSUPPORTED;
-  }
-  if (n_t == 0) return ALLSET_OK;
-  ALLSET_REQUIRE(rowptr && out, "segreduce_packed_fwd: null rowptr/out");
-  ALLSET_REQUIRE(n_s == 0 || (col && packed && x), "segreduce_packed_fwd: null col/packed/x with n_s > 0");
-  ALLSET_REQUIRE(ldx >= d && ldo >= d && ldx % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(out),
-                 "segreduce_packed_fwd: rows of x and out must be 16-byte aligned (pointers and leading dimensions)");
-  ALLSET_REQUIRE(aligned256(packed), "segreduce_packed_fwd: the packed buffer must be 256-byte aligned");
-  segreduce_packed_kernel<<<row_grid(n_t), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
-      rowptr, col, static_cast<const uint32_t*>(packed), x, ldx, out, ldo, static_cast<int>(n_t), reduce == ALLSET_MEAN, row_order);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (cells) pack_kernel<true><<<grid, kBlock, 0, st>>>(x, ldx, static_cast<uint32_t*>(packed), n);
+  else       pack_kernel<false><<<grid, kBlock, 0, st>>>(x, ldx, static_cast<uint32_t*>(packed), n);
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
 }
@@ -965,44 +919,49 @@ extern "C" int allset_segreduce_packed_fwd(int reduce, const int32_t* row_order,
 #define ALLSET_CELL_SUBSTEP 2
 #endif
 
-extern "C" int allset_pack_cells_f32(const float* x, int64_t ldx, void* cells, int64_t n, int64_t d, void* stream) {
+static int segreduce_packed_impl(const char* fn, bool cells, int reduce, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                                 const void* packed, const float* x, int64_t ldx, float* out, int64_t ldo, int64_t n_t, int64_t n_s,
+                                 int64_t d, void* stream) {
   clear_error();
-  ALLSET_REQUIRE(n >= 0 && d >= 0, "pack_cells_f32: negative size");
-  ALLSET_REQUIRE(n < INT32_MAX, "pack_cells_f32: size exceeds int32");
+  ALLSET_REQUIRE(reduce == ALLSET_SUM || reduce == ALLSET_MEAN, "%s: reduce must be SUM or MEAN (got %d)", fn, reduce);
+  ALLSET_REQUIRE(n_t >= 0 && n_s >= 0 && d >= 0, "%s: negative size", fn);
+  ALLSET_REQUIRE(n_t < INT32_MAX && n_s < INT32_MAX, "%s: size exceeds int32", fn);
   if (d != 128) {
-    set_error("pack_cells_f32: built for d = 128 only (got %lld)", static_cast<long long>(d));
+    set_error("%s: built for d = 128 only (got %lld)", fn, static_cast<long long>(d));
     return ALLSET_ERR_UNSUPPORTED;
   }
-  if (n == 0) return ALLSET_OK;
-  ALLSET_REQUIRE(x && cells, "pack_cells_f32: null x/cells");
-  ALLSET_REQUIRE(ldx >= d && ldx % 4 == 0 && aligned16(x), "pack_cells_f32: rows of x must be 16-byte aligned (pointer and leading dimension)");
-  ALLSET_REQUIRE(aligned256(cells), "pack_cells_f32: the cell buffer must be 256-byte aligned");
-  const int64_t rows_per_block = static_cast<int64_t>(kWavesPerBlock) * kPackRowsPerWave;
-  const unsigned grid = static_cast<unsigned>((n + rows_per_block - 1) / rows_per_block);
-  pack_cells_kernel<<<grid, kBlock, 0, static_cast<hipStream_t>(stream)>>>(x, ldx, static_cast<uint32_t*>(cells), n);
+  if (n_t == 0) return ALLSET_OK;
+  ALLSET_REQUIRE(rowptr && out, "%s: null rowptr/out", fn);
+  ALLSET_REQUIRE(n_s == 0 || (col && packed && x), "%s: null col/packed/x with n_s > 0", fn);
+  ALLSET_REQUIRE(ldx >= d && ldo >= d && ldx % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(out),
+                 "%s: rows of x and out must be 16-byte aligned (pointers and leading dimensions)", fn);
+  ALLSET_REQUIRE(aligned256(packed), "%s: the packed buffer must be 256-byte aligned", fn);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int nt = static_cast<int>(n_t), mean = reduce == ALLSET_MEAN;
+  if (cells) segreduce_cells_kernel<ALLSET_CELL_LOADS, ALLSET_CELL_SUBSTEP><<<row_grid(n_t), kBlock, 0, st>>>(
+                 rowptr, col, static_cast<const uint4*>(packed), x, ldx, out, ldo, nt, mean, row_order);
+  else       segreduce_packed_kernel<<<row_grid(n_t), kBlock, 0, st>>>(
+                 rowptr, col, static_cast<const uint32_t*>(packed), x, ldx, out, ldo, nt, mean, row_order);
   ALLSET_LAUNCH_CHECK();
   return ALLSET_OK;
+}
+
+extern "C" int allset_pack_rows_f32(const float* x, int64_t ldx, void* packed, int64_t n, int64_t d, void* stream) {
+  return pack_impl("pack_rows_f32", false, x, ldx, packed, n, d, stream);
+}
+
+extern "C" int allset_pack_cells_f32(const float* x, int64_t ldx, void* cells, int64_t n, int64_t d, void* stream) {
+  return pack_impl("pack_cells_f32", true, x, ldx, cells, n, d, stream);
+}
+
+extern "C" int allset_segreduce_packed_fwd(int reduce, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
+                                           const void* packed, const float* x, int64_t ldx, float* out, int64_t ldo, int64_t n_t,
+                                           int64_t n_s, int64_t d, void* stream) {
+  return segreduce_packed_impl("segreduce_packed_fwd", false, reduce, row_order, rowptr, col, packed, x, ldx, out, ldo, n_t, n_s, d, stream);
 }
 
 extern "C" int allset_segreduce_cells_fwd(int reduce, const int32_t* row_order, const int32_t* rowptr, const int32_t* col,
                                           const void* cells, const float* x, int64_t ldx, float* out, int64_t ldo, int64_t n_t,
                                           int64_t n_s, int64_t d, void* stream) {
-  clear_error();
-  ALLSET_REQUIRE(reduce == ALLSET_SUM || reduce == ALLSET_MEAN, "segreduce_cells_fwd: reduce must be SUM or MEAN (got %d)", reduce);
-  ALLSET_REQUIRE(n_t >= 0 && n_s >= 0 && d >= 0, "segreduce_cells_fwd: negative size");
-  ALLSET_REQUIRE(n_t < INT32_MAX && n_s < INT32_MAX, "segreduce_cells_fwd: size exceeds int32");
-  if (d != 128) {
-    set_error("segreduce_cells_fwd: built for d = 128 only (got %lld)", static_cast<long long>(d));
-    return ALLSET_ERR_UNSUPPORTED;
-  }
-  if (n_t == 0) return ALLSET_OK;
-  ALLSET_REQUIRE(rowptr && out, "segreduce_cells_fwd: null rowptr/out");
-  ALLSET_REQUIRE(n_s == 0 || (col && cells && x), "segreduce_cells_fwd: null col/cells/x with n_s > 0");
-  ALLSET_REQUIRE(ldx >= d && ldo >= d && ldx % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(out),
-                 "segreduce_cells_fwd: rows of x and out must be 16-byte aligned (pointers and leading dimensions)");
-  ALLSET_REQUIRE(aligned256(cells), "segreduce_cells_fwd: the cell buffer must be 256-byte aligned");
-  segreduce_cells_kernel<ALLSET_CELL_LOADS, ALLSET_CELL_SUBSTEP><<<row_grid(n_t), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
-      rowptr, col, static_cast<const uint4*>(cells), x, ldx, out, ldo, static_cast<int>(n_t), reduce == ALLSET_MEAN, row_order);
-  ALLSET_LAUNCH_CHECK();
-  return ALLSET_OK;
+  return segreduce_packed_impl("segreduce_cells_fwd", true, reduce, row_order, rowptr, col, cells, x, ldx, out, ldo, n_t, n_s, d, stream);
 }

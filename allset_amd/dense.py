@@ -1210,16 +1210,17 @@ class _FusedNormLinear(torch.autograd.Function):
 class PackedRows:
     """The output of a fused Linear that left as packed nonzero rows (``fused_norm_linear_packed``): what the forward Deep Sets gather
     reads (``functional.deepsets_aggregate`` takes it in place of ``x``), and nothing else -- there is no dense table behind it.
-    ``packed``: int32[n, 64] (include/allset_hip_ext.h) in the format ``format`` names -- ``"mask"`` (occupancy mask + values) or
-    ``"cells"`` (16 cells of three values with their columns); ``_side``: the overflow side table f32[n, 128], UNINITIALISED except
-    for the rows above the format's capacity (60 / 48 occupied columns), and the autograd carrier: the gradient that flows back into
-    it is the ordinary dense [n, 128] gradient of the Linear's output.  Private: a caller must never read it as the activation."""
+    ``packed``: int32[n, 64] (include/allset_hip_ext.h) in the format ``format`` names (``ops.PACKED_FORMATS``) -- ``"mask"`` (occupancy
+    mask + values) or ``"cells"`` (16 cells of three values with their columns); ``_side``: the overflow side table f32[n, 128],
+    UNINITIALISED except for the rows above the format's capacity (60 / 48 occupied columns), and the autograd carrier: the gradient
+    that flows back into it is the ordinary dense [n, 128] gradient of the Linear's output.  Private: a caller must never read it as the
+    activation."""
 
     __slots__ = ("packed", "_side", "format")
 
-    def __init__(self, packed: Tensor, side: Tensor, format: str = "mask"):
-        if format not in ("mask", "cells"):
-            raise ValueError(f"PackedRows: format must be 'mask' or 'cells', got {format!r}")
+    def __init__(self, packed: Tensor, side: Tensor, format: str):
+        from . import ops
+        ops.packed_format_entry(format, "PackedRows")
         self.packed, self._side, self.format = packed, side, format
 
     @property
@@ -1228,21 +1229,21 @@ class PackedRows:
 
 
 class _FusedNormLinearPacked(torch.autograd.Function):
-    """:class:`_FusedNormLinear` (row-major, LayerNorm prologue, dropout in and out) whose forward kernel packs its output rows
-    (fused_fwd2.hip mode 3, or mode 4 for ``cells``) instead of writing the dense table; the same seeds in the same order, the same
-    saved tensors (x, the row statistics, the 1-bit mask), and ITS backward.  Returns (side, packed): see :class:`PackedRows`."""
+    """:class:`_FusedNormLinear` (row-major, LayerNorm prologue, dropout in and out) whose forward kernel packs its output rows in the
+    format ``fmt`` (fused_fwd2.hip mode 3 for ``"mask"``, mode 4 for ``"cells"``) instead of writing the dense table; the same seeds in
+    the same order, the same saved tensors (x, the row statistics, the 1-bit mask), and ITS backward.  Returns (side, packed): see
+    :class:`PackedRows`."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, weight, bias, eps, relu_in, p_in, relu_out, p_out, cells=False):
+    def forward(ctx, x, gamma, beta, weight, bias, eps, relu_in, p_in, relu_out, p_out, fmt):
         from . import ops
         seed_in = _draw_seed()
         seed_out = _draw_seed()
         base = _seed_base()
         words = activation_mask_words(x.shape[0], weight.shape[0]) if any(ctx.needs_input_grad) else 0
         mask = torch.empty(words, dtype=torch.int32, device=x.device) if words > 0 else None
-        fwd = ops.fused_linear_fwd_cells if cells else ops.fused_linear_fwd_packed
-        packed, side, stats = fwd(x, weight, bias, gamma, beta, eps, relu_in, p_in, seed_in, relu_out, p_out, seed_out, base, mask,
-                                  _arith_for(0, weight.shape[1], weight.shape[0], True, 0))
+        packed, side, stats = ops.fused_linear_fwd_packed(x, weight, bias, gamma, beta, eps, relu_in, p_in, seed_in, relu_out, p_out, seed_out,
+                                                          base, mask, _arith_for(0, weight.shape[1], weight.shape[0], True, 0), fmt=fmt)
         ctx.save_for_backward(x, stats, gamma, beta, weight, None, mask)
         ctx.cfg = (bool(relu_in), float(p_in), seed_in, float(p_out), bias is not None, base)
         ctx.layout = (0, 0)
@@ -1256,41 +1257,26 @@ class _FusedNormLinearPacked(torch.autograd.Function):
         return _FusedNormLinear.backward(ctx, gy)[:10] + (None,)
 
 
-def fused_norm_linear_packed_supported(x: Tensor, gamma: Optional[Tensor], weight: Tensor, p_in: float, relu_out: bool, p_out: float) -> bool:
+def fused_norm_linear_packed_supported(x: Tensor, gamma: Optional[Tensor], weight: Tensor, p_in: float, relu_out: bool, p_out: float,
+                                       format: str) -> bool:
     """:func:`fused_norm_linear_packed` is built for this call (from the arguments alone: no data pass, no sync)."""
     from . import ops
     N, K = weight.shape
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0 and gamma is not None and bool(relu_out)
-            and ops.fused_linear_fwd_packed_supported(K, N, True, p_in, p_out))
+            and ops.fused_linear_fwd_packed_supported(K, N, True, p_in, p_out, fmt=format))
 
 
 def fused_norm_linear_packed(x: Tensor, gamma: Tensor, beta: Tensor, weight: Tensor, bias: Optional[Tensor], eps: float, relu_in: bool,
-                             p_in: float, relu_out: bool, p_out: float) -> PackedRows:
+                             p_in: float, relu_out: bool, p_out: float, format: str) -> PackedRows:
     """:func:`fused_norm_linear` for the Linear in front of a forward Deep Sets gather: the output goes straight into the packed rows the
-    gather reads -- no dense table, no ``ops.pack_rows`` pass.  Bit for bit the rows ``pack_rows`` would make
-    of :func:`fused_norm_linear`'s output under the same seed counter."""
-    if not fused_norm_linear_packed_supported(x, gamma, weight, p_in, relu_out, p_out):
+    gather reads, in the format ``format`` -- no dense table, no ``ops.pack_rows`` pass.  Bit for bit the rows
+    ``ops.pack_rows(., fmt=format)`` would make of :func:`fused_norm_linear`'s output under the same seed counter."""
+    if not fused_norm_linear_packed_supported(x, gamma, weight, p_in, relu_out, p_out, format):
         raise _lib.AllSetHipError("fused_norm_linear_packed: built for a [128, 128] Linear behind a LayerNorm with relu_out and both "
                                   "dropouts active only (fused_norm_linear_packed_supported)")
     side, packed = _FusedNormLinearPacked.apply(x, gamma, beta, weight, bias, float(eps), bool(relu_in), float(p_in), bool(relu_out),
-                                                float(p_out))
-    return PackedRows(packed, side)
-
-
-def fused_norm_linear_cells(x: Tensor, gamma: Tensor, beta: Tensor, weight: Tensor, bias: Optional[Tensor], eps: float, relu_in: bool,
-                            p_in: float, relu_out: bool, p_out: float) -> PackedRows:
-    """:func:`fused_norm_linear_packed` writing cell rows (fused_fwd2.hip mode 4; same conditions,
-    ``fused_norm_linear_packed_supported``): bit for bit the rows ``ops.pack_cells`` would make of :func:`fused_norm_linear`'s output
-    under the same seed counter."""
-    from . import ops
-    N, K = weight.shape
-    if not (fused_norm_linear_packed_supported(x, gamma, weight, p_in, relu_out, p_out)
-            and ops.fused_linear_fwd_cells_supported(K, N, True, p_in, p_out)):
-        raise _lib.AllSetHipError("fused_norm_linear_cells: built for a [128, 128] Linear behind a LayerNorm with relu_out and both "
-                                  "dropouts active only (fused_norm_linear_packed_supported)")
-    side, packed = _FusedNormLinearPacked.apply(x, gamma, beta, weight, bias, float(eps), bool(relu_in), float(p_in), bool(relu_out),
-                                                float(p_out), True)
-    return PackedRows(packed, side, "cells")
+                                                float(p_out), format)
+    return PackedRows(packed, side, format)
 
 
 class _WideNormLinear(torch.autograd.Function):

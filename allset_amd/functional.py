@@ -135,8 +135,7 @@ def set_packed_format(fmt: str, direction: Optional[str] = None) -> None:
     ``"cells"`` (every occupied element with its column beside it, expanded per occupied element) or ``"mask"`` (occupancy mask +
     values, expanded per column).  ``direction``: ``"v2e"`` / ``"e2v"`` sets it for that half of a layer (:func:`packed_direction`),
     ``None`` for every aggregation.  Every fall-back condition is the same for both formats, and so are the results, bit for bit."""
-    if fmt not in ("cells", "mask"):
-        raise ValueError(f"set_packed_format: format must be 'cells' or 'mask', got {fmt!r}")
+    ops.packed_format_entry(fmt, "set_packed_format")
     if direction not in (None, "v2e", "e2v"):
         raise ValueError(f"set_packed_format: direction must be None, 'v2e' or 'e2v', got {direction!r}")
     for key in ((direction,) if direction is not None else tuple(_PACKED_FORMAT)):
@@ -235,24 +234,20 @@ def _takes_packed(x: Tensor, w_dst: Optional[Tensor], inc: Incidence, reduce: in
 class _SegReduce(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, w_dst: Optional[Tensor], w_src: Optional[Tensor], inc: Incidence, reduce: int, packed_rows: bool = False,
-                packed: Optional[Tensor] = None, packed_fmt: str = "mask"):
+                packed: Optional[Tensor] = None, packed_fmt: Optional[str] = None):
         csr = inc.by_dst
         ext = reduce in (MAX, MIN)
-        if packed is not None:
-            # ``x`` is the overflow side table of a Linear that wrote ``packed`` itself (dense.PackedRows): mostly uninitialised, and
-            # read by the packed gather alone, for its overflow rows
-            if not _takes_packed(x, w_dst, inc, reduce):
-                raise _lib.AllSetHipError("deepsets_aggregate: packed rows came without a packed gather to read them "
-                                          "(functional.takes_packed_epilogue decides the route before the Linear runs)")
-            gather = ops.segreduce_cells if packed_fmt == "cells" else ops.segreduce_packed
-            out = gather(reduce, csr.rowptr, csr.col, packed, x, inc.n_dst, row_order=csr.row_order)
-            arg = None
-        elif packed_rows and _takes_packed(x, w_dst, inc, reduce):
-            # the packed table is a temporary of this forward (the unweighted backward never reads the gathered table)
-            if packed_format() == "cells":
-                out = ops.segreduce_cells(reduce, csr.rowptr, csr.col, ops.pack_cells(x), x, inc.n_dst, row_order=csr.row_order)
-            else:
-                out = ops.segreduce_packed(reduce, csr.rowptr, csr.col, ops.pack_rows(x), x, inc.n_dst, row_order=csr.row_order)
+        # ``packed`` came with ``x`` (dense.PackedRows): ``x`` is the overflow side table of a Linear that wrote the rows itself -- mostly
+        # uninitialised, and read by the packed gather alone, for its overflow rows
+        if packed is not None and not _takes_packed(x, w_dst, inc, reduce):
+            raise _lib.AllSetHipError("deepsets_aggregate: packed rows came without a packed gather to read them "
+                                      "(functional.takes_packed_epilogue decides the route before the Linear runs)")
+        if packed is not None or (packed_rows and _takes_packed(x, w_dst, inc, reduce)):
+            fmt = packed_fmt if packed is not None else packed_format()
+            if packed is None:
+                # the packed table is a temporary of this forward (the unweighted backward never reads the gathered table)
+                packed = ops.pack_rows(x, fmt=fmt)
+            out = ops.segreduce_packed(reduce, csr.rowptr, csr.col, packed, x, inc.n_dst, row_order=csr.row_order, fmt=fmt)
             arg = None
         else:
             out, arg = ops.segreduce(reduce, csr.rowptr, csr.col, w_dst, x, inc.n_dst, want_arg=ext,
@@ -305,7 +300,7 @@ def deepsets_aggregate(x: Tensor, inc: Incidence, norm: Optional[Tensor] = None,
     """
     if aggr not in REDUCE_CODES:
         raise ValueError(f"unknown aggr {aggr!r}")
-    packed, packed_fmt = None, "mask"
+    packed, packed_fmt = None, None
     if isinstance(x, PackedRows):
         x, packed, packed_fmt = x._side, x.packed, x.format
     _lib.require_device(x)

@@ -251,7 +251,8 @@ class MLP(nn.Module):
         nm, lin = self.normalizations[-1], self.lins[-1]
         if not isinstance(nm, nn.LayerNorm) or nm.weight is None or nm.bias is None:
             return False
-        return dense.fused_norm_linear_packed_supported(x, nm.weight, lin.weight, float(self.dropout), True, float(post))
+        return dense.fused_norm_linear_packed_supported(x, nm.weight, lin.weight, float(self.dropout), True, float(post),
+                                                        AF.packed_format())
 
     def forward(self, x, _post: Optional[float] = None, _in_cb: int = 0, _out_cb: int = 0, _pre: float = 0.0, _packed_out: bool = False):
         """``_packed_out`` (internal, only after ``packs_output``): the last Linear writes packed nonzero rows and the result is a
@@ -317,9 +318,8 @@ class MLP(nn.Module):
                         and dense.wide_linear_supported(self.lins[i + 1].weight.shape[1], self.lins[i + 1].weight.shape[0], True, True, p)):
                     emit = (nxt.eps, True)
                 if is_last and _packed_out:
-                    packed_linear = dense.fused_norm_linear_cells if AF.packed_format() == "cells" else dense.fused_norm_linear_packed
-                    return packed_linear(x, ln.weight, ln.bias, lin.weight, lin.bias, ln.eps, relu_in=True, p_in=p, relu_out=True,
-                                         p_out=post_p)
+                    return dense.fused_norm_linear_packed(x, ln.weight, ln.bias, lin.weight, lin.bias, ln.eps, relu_in=True, p_in=p,
+                                                          relu_out=True, p_out=post_p, format=AF.packed_format())
                 x = dense.fused_norm_linear(
                     x, ln.weight if ln is not None else None, ln.bias if ln is not None else None, lin.weight, lin.bias,
                     ln.eps if ln is not None else 1e-5, relu_in=i > 0, p_in=p if i > 0 else 0.0,

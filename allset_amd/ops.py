@@ -282,29 +282,51 @@ def segreduce(reduce: int, rowptr: Tensor, col: Tensor, w: Optional[Tensor], x: 
     return out, arg
 
 
-def pack_rows(x: Tensor) -> Tensor:
-    """``x`` f32[n, 128] -> int32[n, 64]: per row a 128-bit occupancy mask and the occupied elements (the format:
-    include/allset_hip_ext.h).  One streaming pass, no sync."""
+# The two packed-row formats of the forward Deep Sets gather (include/allset_hip_ext.h): "mask" rows (a 128-bit
+# occupancy mask + the occupied elements) and "cells" rows (16 cells of three elements with their columns and the row's count).  Per
+# format: the occupied columns a row holds (a row above ``cap`` is read from the dense table instead) and its C entry points -- the pack
+# pass, the gather, the fused Linear that writes the rows from its epilogue and that Linear's ``_supported`` query.  Everything that
+# takes a format name looks it up here (:func:`packed_format_entry`).
+PACKED_FORMATS = {
+    "mask": dict(cap=_lib.PACK_CAP, pack="allset_pack_rows_f32", gather="allset_segreduce_packed_fwd",
+                 linear="allset_fused_linear_fwd_packed", supported="allset_fused_linear_fwd_packed_supported"),
+    "cells": dict(cap=_lib.CELL_CAP, pack="allset_pack_cells_f32", gather="allset_segreduce_cells_fwd",
+                  linear="allset_fused_linear_fwd_cells", supported="allset_fused_linear_fwd_cells_supported"),
+}
+
+
+def packed_format_entry(fmt: str, who: str) -> dict:
+    """The table entry of ``fmt``; anything else is a ``ValueError`` in ``who``'s name."""
+    if not isinstance(fmt, str) or fmt not in PACKED_FORMATS:
+        raise ValueError(f"{who}: format must be {' or '.join(repr(k) for k in PACKED_FORMATS)}, got {fmt!r}")
+    return PACKED_FORMATS[fmt]
+
+
+def pack_rows(x: Tensor, *, fmt: str) -> Tensor:
+    """``x`` f32[n, 128] -> int32[n, 64]: every row in the packed format ``fmt`` (:data:`PACKED_FORMATS`).  One streaming pass, no sync."""
+    sym = packed_format_entry(fmt, "pack_rows")["pack"]
     dev = require_device(x)
     _f32(x, "pack_rows")
     x = _rowmajor(x)
     n, d = x.shape
     packed = torch.empty((n, _lib.PACK_PITCH_DW), dtype=torch.int32, device=dev)
     with on_device(dev), _timed("pack_rows", dev, n * (4 * d + 4 * _lib.PACK_PITCH_DW)):
-        check(_lib.load().allset_pack_rows_f32(ptr(x), _ld(x), ptr(packed), n, d, stream_of(dev)), "allset_pack_rows_f32")
+        check(getattr(_lib.load(), sym)(ptr(x), _ld(x), ptr(packed), n, d, stream_of(dev)), sym)
     return packed
 
 
-def fused_linear_fwd_packed_supported(K: int, N: int, has_ln: bool, p_in: float, p_out: float) -> bool:
-    return bool(_lib.load().allset_fused_linear_fwd_packed_supported(int(K), int(N), int(has_ln), float(p_in), float(p_out)))
+def fused_linear_fwd_packed_supported(K: int, N: int, has_ln: bool, p_in: float, p_out: float, *, fmt: str) -> bool:
+    sym = packed_format_entry(fmt, "fused_linear_fwd_packed_supported")["supported"]
+    return bool(getattr(_lib.load(), sym)(int(K), int(N), int(has_ln), float(p_in), float(p_out)))
 
 
 def fused_linear_fwd_packed(x: Tensor, weight: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Tensor, eps: float, relu_in: bool,
                             p_in: float, seed_in: int, relu_out: bool, p_out: float, seed_out: int, seed_base: Optional[Tensor],
-                            mask_out: Optional[Tensor], arith: int = 0) -> Tuple[Tensor, Tensor, Tensor]:
-    """The fused Linear forward (``dense.fused_linear_fwd`` behind a LayerNorm, dropout in and out) with ``pack_rows`` as its epilogue:
-    returns ``(packed int32[n, 64], side f32[n, N], stats)``.  ``side`` is UNINITIALISED except for the rows above 60 occupied columns
-    -- (packed, side) is what :func:`segreduce_packed` takes as (packed, x), and nothing else may read ``side``."""
+                            mask_out: Optional[Tensor], arith: int = 0, *, fmt: str) -> Tuple[Tensor, Tensor, Tensor]:
+    """The fused Linear forward (``dense.fused_linear_fwd`` behind a LayerNorm, dropout in and out) with ``pack_rows(., fmt=fmt)`` as its
+    epilogue: returns ``(packed int32[n, 64], side f32[n, N], stats)``.  ``side`` is UNINITIALISED except for the rows above the format's
+    capacity -- (packed, side) is what :func:`segreduce_packed` takes as (packed, x), and nothing else may read ``side``."""
+    sym = packed_format_entry(fmt, "fused_linear_fwd_packed")["linear"]
     dev = require_device(x, weight, bias, gamma, beta)
     for t in (x, weight, bias, gamma, beta):
         if t is not None:
@@ -317,18 +339,19 @@ def fused_linear_fwd_packed(x: Tensor, weight: Tensor, bias: Optional[Tensor], g
     stats = torch.empty((n, 2), dtype=torch.float32, device=dev)
     nparam = weight.numel() + N + 2 * K
     with on_device(dev), _timed("fused_linear_fwd", dev, n * (4 * K + 4 * _lib.PACK_PITCH_DW) + 4 * nparam):
-        check(_lib.load().allset_fused_linear_fwd_packed(
+        check(getattr(_lib.load(), sym)(
             ptr(x), _ld(x), ptr(gamma.contiguous()), ptr(beta.contiguous()), eps, int(relu_in), p_in, seed_in, ptr(weight.contiguous()),
             ptr(bias.contiguous() if bias is not None else None), int(relu_out), p_out, seed_out, ptr(packed), ptr(side), max(N, 1),
-            ptr(stats), n, K, N, ptr(seed_base), ptr(mask_out), int(arith), stream_of(dev)), "allset_fused_linear_fwd_packed")
+            ptr(stats), n, K, N, ptr(seed_base), ptr(mask_out), int(arith), stream_of(dev)), sym)
     return packed, side, stats
 
 
 def segreduce_packed(reduce: int, rowptr: Tensor, col: Tensor, packed: Tensor, x: Tensor, n_t: int,
-                     row_order: Optional[Tensor] = None) -> Tensor:
+                     row_order: Optional[Tensor] = None, *, fmt: str) -> Tensor:
     """``segreduce(reduce, rowptr, col, None, x, n_t, variant=1, row_order=row_order)[0]``, bit for bit, gathering
-    ``packed = pack_rows(x)`` (two lines per row instead of four); ``x`` itself is read only for rows above 60 occupied columns.
-    SUM / MEAN, fp32, d = 128."""
+    ``packed = pack_rows(x, fmt=fmt)`` (two lines per row instead of four); ``x`` itself is read only for rows above the format's
+    capacity.  SUM / MEAN, fp32, d = 128."""
+    sym = packed_format_entry(fmt, "segreduce_packed")["gather"]
     dev = require_device(rowptr, col, packed, x)
     _f32(x, "segreduce_packed")
     x = _rowmajor(x)
@@ -341,72 +364,8 @@ def segreduce_packed(reduce: int, rowptr: Tensor, col: Tensor, packed: Tensor, x
     with on_device(dev), _timed("segreduce_fwd", dev, algo):
         if row_order is not None and row_order.numel() != n_t:
             row_order = None                       # order was built for a different row count (prefix views)
-        check(_lib.load().allset_segreduce_packed_fwd(reduce, ptr(row_order), ptr(rowptr), ptr(col), ptr(packed), ptr(x), _ld(x),
-                                                      ptr(out), max(d, 1), n_t, n_s, d, stream_of(dev)),
-              "allset_segreduce_packed_fwd")
-    return out
-
-
-def pack_cells(x: Tensor) -> Tensor:
-    """``x`` f32[n, 128] -> int32[n, 64]: per row 16 cells of three occupied elements with their columns and the row's count (the
-    cell format: include/allset_hip_ext.h).  One streaming pass, no sync."""
-    dev = require_device(x)
-    _f32(x, "pack_cells")
-    x = _rowmajor(x)
-    n, d = x.shape
-    cells = torch.empty((n, _lib.PACK_PITCH_DW), dtype=torch.int32, device=dev)
-    with on_device(dev), _timed("pack_rows", dev, n * (4 * d + 4 * _lib.PACK_PITCH_DW)):
-        check(_lib.load().allset_pack_cells_f32(ptr(x), _ld(x), ptr(cells), n, d, stream_of(dev)), "allset_pack_cells_f32")
-    return cells
-
-
-def fused_linear_fwd_cells_supported(K: int, N: int, has_ln: bool, p_in: float, p_out: float) -> bool:
-    return bool(_lib.load().allset_fused_linear_fwd_cells_supported(int(K), int(N), int(has_ln), float(p_in), float(p_out)))
-
-
-def fused_linear_fwd_cells(x: Tensor, weight: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Tensor, eps: float, relu_in: bool,
-                           p_in: float, seed_in: int, relu_out: bool, p_out: float, seed_out: int, seed_base: Optional[Tensor],
-                           mask_out: Optional[Tensor], arith: int = 0) -> Tuple[Tensor, Tensor, Tensor]:
-    """:func:`fused_linear_fwd_packed` with ``pack_cells`` as the epilogue: ``(cells int32[n, 64], side f32[n, N], stats)``; ``side``
-    is UNINITIALISED except for the rows above 48 occupied columns -- (cells, side) is what :func:`segreduce_cells` takes."""
-    dev = require_device(x, weight, bias, gamma, beta)
-    for t in (x, weight, bias, gamma, beta):
-        if t is not None:
-            _f32(t, "fused_linear_fwd_cells")
-    x = _rowmajor(x)
-    n, K = x.shape
-    N = weight.shape[0]
-    cells = torch.empty((n, _lib.PACK_PITCH_DW), dtype=torch.int32, device=dev)
-    side = torch.empty((n, N), dtype=torch.float32, device=dev)
-    stats = torch.empty((n, 2), dtype=torch.float32, device=dev)
-    nparam = weight.numel() + N + 2 * K
-    with on_device(dev), _timed("fused_linear_fwd", dev, n * (4 * K + 4 * _lib.PACK_PITCH_DW) + 4 * nparam):
-        check(_lib.load().allset_fused_linear_fwd_cells(
-            ptr(x), _ld(x), ptr(gamma.contiguous()), ptr(beta.contiguous()), eps, int(relu_in), p_in, seed_in, ptr(weight.contiguous()),
-            ptr(bias.contiguous() if bias is not None else None), int(relu_out), p_out, seed_out, ptr(cells), ptr(side), max(N, 1),
-            ptr(stats), n, K, N, ptr(seed_base), ptr(mask_out), int(arith), stream_of(dev)), "allset_fused_linear_fwd_cells")
-    return cells, side, stats
-
-
-def segreduce_cells(reduce: int, rowptr: Tensor, col: Tensor, cells: Tensor, x: Tensor, n_t: int,
-                    row_order: Optional[Tensor] = None) -> Tensor:
-    """:func:`segreduce_packed` over ``cells = pack_cells(x)``: the same result, bit for bit; ``x`` itself is read only for rows above
-    48 occupied columns.  SUM / MEAN, fp32, d = 128."""
-    dev = require_device(rowptr, col, cells, x)
-    _f32(x, "segreduce_cells")
-    x = _rowmajor(x)
-    n_s, d = x.shape
-    if cells.dtype != torch.int32 or tuple(cells.shape) != (n_s, _lib.PACK_PITCH_DW) or not cells.is_contiguous():
-        raise _lib.AllSetHipError(f"segreduce_cells: cells must be contiguous int32[{n_s}, {_lib.PACK_PITCH_DW}] (ops.pack_cells)")
-    out = torch.empty((n_t, d), dtype=x.dtype, device=dev)
-    nnz = col.numel()
-    algo = nnz * (4 * _lib.PACK_PITCH_DW + 4) + (n_t + 1) * 4 + n_t * d * 4
-    with on_device(dev), _timed("segreduce_fwd", dev, algo):
-        if row_order is not None and row_order.numel() != n_t:
-            row_order = None                       # order was built for a different row count (prefix views)
-        check(_lib.load().allset_segreduce_cells_fwd(reduce, ptr(row_order), ptr(rowptr), ptr(col), ptr(cells), ptr(x), _ld(x),
-                                                     ptr(out), max(d, 1), n_t, n_s, d, stream_of(dev)),
-              "allset_segreduce_cells_fwd")
+        check(getattr(_lib.load(), sym)(reduce, ptr(row_order), ptr(rowptr), ptr(col), ptr(packed), ptr(x), _ld(x),
+                                        ptr(out), max(d, 1), n_t, n_s, d, stream_of(dev)), sym)
     return out
 
 

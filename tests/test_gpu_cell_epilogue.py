@@ -1,5 +1,5 @@
 """GPU: the fused Linear forward that writes cell rows from its own epilogue (csrc/fused_fwd2.hip mode 4) against
-the pair it replaces -- the dense kernel's output and ``ops.pack_cells`` of it -- and the layers under the three routes of the forward
+the pair it replaces -- the dense kernel's output and ``ops.pack_rows(., fmt="cells")`` of it -- and the layers under the three routes of the forward
 gather: cell rows, mask rows, dense.  Every comparison is an equality of bit patterns."""
 import numpy as np
 import pytest
@@ -36,7 +36,7 @@ def _params(table, device):
 
 
 def _cells_linear(x, W, bias, gamma, beta, arith, mask, device):
-    """ops.fused_linear_fwd_cells through the C entry point, with a side table the test filled beforehand."""
+    """ops.fused_linear_fwd_packed(..., fmt="cells") through the C entry point, with a side table the test filled beforehand."""
     from allset_amd import _lib
     n = x.shape[0]
     cells = torch.empty(n, fmt.PITCH_DW, dtype=torch.int32, device=device)
@@ -62,7 +62,7 @@ def test_cell_epilogue_equals_linear_then_pack_cells(arith, table, device):
         with dense.arithmetic(arith):
             y, stats = dense.fused_linear_fwd(x, W, bias, gamma, beta, 1e-5, True, 0.5, 101, True, 0.5, 202, None, m_ref)
             cells, side, stats_new = _cells_linear(x, W, bias, gamma, beta, dense._arith_for(0, 128, 128, True, 0), m_new, device)
-        want = ops.pack_cells(y)
+        want = ops.pack_rows(y, fmt="cells")
         assert torch.equal(cells, want), (n, "cell rows")
         assert torch.equal(want.cpu(), torch.from_numpy(fmt.encode_cells(y.cpu().numpy()).view(np.int32))), (n, "the reference's own rows")
         k = (_bits(y) != 0).sum(1)
@@ -89,8 +89,8 @@ def test_gather_over_the_cell_epilogue_is_the_dense_gather(table, device):
     x = torch.randn(n_s, 128, generator=torch.Generator().manual_seed(3)).to(device)
     mask = torch.zeros(dense.activation_mask_words(n_s, 128), dtype=torch.int32, device=device)
     y, _ = dense.fused_linear_fwd(x, W, bias, gamma, beta, 1e-5, True, 0.5, 101, True, 0.5, 202, None, mask)
-    cells, side, _ = ops.fused_linear_fwd_cells(x, W, bias, gamma, beta, 1e-5, True, 0.5, 101, True, 0.5, 202, None, mask,
-                                                dense._arith_for(0, 128, 128, True, 0))
+    cells, side, _ = ops.fused_linear_fwd_packed(x, W, bias, gamma, beta, 1e-5, True, 0.5, 101, True, 0.5, 202, None, mask,
+                                                 dense._arith_for(0, 128, 128, True, 0), fmt="cells")
     g = torch.Generator().manual_seed(9)
     deg = torch.randint(0, 40, (301,), generator=g)
     rowptr = torch.zeros(302, dtype=torch.int32)
@@ -98,7 +98,7 @@ def test_gather_over_the_cell_epilogue_is_the_dense_gather(table, device):
     col = torch.randint(0, n_s, (int(rowptr[-1]),), generator=g).to(torch.int32)
     rowptr, col = rowptr.to(device), col.to(device)
     want, _ = ops.segreduce(0, rowptr, col, None, y, 301, variant=1)
-    assert torch.equal(_bits(ops.segreduce_cells(0, rowptr, col, cells, side, 301)), _bits(want))
+    assert torch.equal(_bits(ops.segreduce_packed(0, rowptr, col, cells, side, 301, fmt="cells")), _bits(want))
 
 
 # ---- layer level: cell rows, mask rows and the dense gather give the same training step ----------------------------------------
@@ -179,15 +179,15 @@ def test_default_routes_of_the_sharded_layer(device, monkeypatch):
     steps, n_v = _layer_steps(device)
     step, _ = steps["sharded"]
     calls = []
-    for name in ("segreduce_packed", "segreduce_cells", "fused_linear_fwd_packed", "fused_linear_fwd_cells", "pack_rows", "pack_cells"):
-        monkeypatch.setattr(ops, name, (lambda fn, name: lambda *a, **k: (calls.append(name), fn(*a, **k))[1])(getattr(ops, name), name))
+    for name in ("segreduce_packed", "fused_linear_fwd_packed", "pack_rows"):
+        monkeypatch.setattr(ops, name, (lambda fn, name: lambda *a, **k: (calls.append((name, k["fmt"])), fn(*a, **k))[1])(getattr(ops, name), name))
     was = AF.packed_epilogue()
     AF.set_packed_epilogue("on")
     try:
         step(torch.randn(n_v, 128, device=device))
     finally:
         AF.set_packed_epilogue(was)
-    assert calls == ["fused_linear_fwd_packed", "segreduce_packed", "fused_linear_fwd_cells", "segreduce_cells"]
+    assert calls == [("fused_linear_fwd_packed", "mask"), ("segreduce_packed", "mask"), ("fused_linear_fwd_packed", "cells"), ("segreduce_packed", "cells")]
 
 
 def test_every_route_replays_the_same_from_a_graph(device):

@@ -78,7 +78,7 @@ def test_pack_cells_matches_the_numpy_reference(strided, device):
             xd = buf[:, :128]                                            # ldx = 192 > 128
         else:
             xd = torch.from_numpy(x).to(device)
-        got = ops.pack_cells(xd).cpu()
+        got = ops.pack_rows(xd, fmt="cells").cpu()
         assert got.shape == (n, fmt.PITCH_DW) and got.dtype == torch.int32
         assert torch.equal(got, ref), n                                  # every byte is defined, overflow rows included
 
@@ -96,7 +96,7 @@ def test_segreduce_cells_is_bitwise_the_dense_and_the_mask_gather(reduce, ordere
     assert set(LENGTHS) <= set((rowptr[1:] - rowptr[:-1]).tolist())
     rowptr, col = rowptr.to(device), col.to(device)
     xd = torch.from_numpy(_source_table(specials)).to(device)
-    cells, packed = ops.pack_cells(xd), ops.pack_rows(xd)
+    cells, packed = ops.pack_rows(xd, fmt="cells"), ops.pack_rows(xd, fmt="mask")
     side = torch.full_like(xd, 7.0)                                      # only the overflow rows of the side table may be read
     over = (_bits(xd) != 0).sum(1) > fmt.CAP
     side[over] = xd[over]
@@ -104,8 +104,8 @@ def test_segreduce_cells_is_bitwise_the_dense_and_the_mask_gather(reduce, ordere
         order = torch.randperm(n_t, generator=torch.Generator().manual_seed(n_t)).to(torch.int32).to(device) if ordered else None
         rp = rowptr[:n_t + 1]
         want, _ = ops.segreduce(reduce, rp, col, None, xd, n_t, variant=1, row_order=order)
-        got = ops.segreduce_cells(reduce, rp, col, cells, side, n_t, row_order=order)
-        mask = ops.segreduce_packed(reduce, rp, col, packed, xd, n_t, row_order=order)
+        got = ops.segreduce_packed(reduce, rp, col, cells, side, n_t, row_order=order, fmt="cells")
+        mask = ops.segreduce_packed(reduce, rp, col, packed, xd, n_t, row_order=order, fmt="mask")
         assert torch.equal(_bits(got), _bits(want)), n_t
         if specials is not True:
             assert torch.equal(_bits(got), _bits(mask)), n_t
@@ -115,7 +115,7 @@ def test_segreduce_cells_is_bitwise_the_dense_and_the_mask_gather(reduce, ordere
         empty = (rp[1:] - rp[:-1]) == 0
         assert not _bits(got)[empty].any()                               # empty rows write +0
     if reduce == SUM and not ordered and specials is False:                   # and the dense kernel is right about a sum (float64 on the host)
-        got = ops.segreduce_cells(SUM, rowptr, col, cells, side, N_ROWS).cpu().double()
+        got = ops.segreduce_packed(SUM, rowptr, col, cells, side, N_ROWS, fmt="cells").cpu().double()
         ref = torch.zeros(N_ROWS, 128, dtype=torch.float64)
         ref.index_add_(0, torch.repeat_interleave(torch.arange(N_ROWS), (rowptr[1:] - rowptr[:-1]).cpu().long()), xd.cpu().double()[col.cpu().long()])
         torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-5)
@@ -125,11 +125,11 @@ def test_a_single_source_row_gathered_many_times(device):
     """Every incidence of a step the same row: the four rows of a load instruction and the images of a sub-step all hold one row."""
     from allset_amd import ops
     x = torch.from_numpy(fmt.make_table((48, 49), seed=5, specials=False)).to(device)
-    cells = ops.pack_cells(x)
+    cells = ops.pack_rows(x, fmt="cells")
     rowptr = torch.tensor([0, 130, 147], dtype=torch.int32, device=device)
     col = torch.cat([torch.zeros(130, dtype=torch.int32), torch.ones(17, dtype=torch.int32)]).to(device)
     want, _ = ops.segreduce(SUM, rowptr, col, None, x, 2, variant=1)
-    assert torch.equal(_bits(ops.segreduce_cells(SUM, rowptr, col, cells, x, 2)), _bits(want))
+    assert torch.equal(_bits(ops.segreduce_packed(SUM, rowptr, col, cells, x, 2, fmt="cells")), _bits(want))
 
 
 # ---- dispatch: the hint takes the cell path at the built shape, everything else keeps today's route --------------------------------

@@ -54,9 +54,9 @@ def _pair(table, arith, p, n, device):
         m_new = torch.zeros(words, dtype=torch.int32, device=device)
         with dense.arithmetic(arith):
             y, stats = dense.fused_linear_fwd(x, W, bias, gamma, beta, 1e-5, True, p, 101, True, p_out, 202, None, m_ref)
-            packed_ref = ops.pack_rows(y)
+            packed_ref = ops.pack_rows(y, fmt="mask")
             packed, side, stats_new = ops.fused_linear_fwd_packed(x, W, bias, gamma, beta, 1e-5, True, p, 101, True, p_out, 202, None, m_new,
-                                                                  dense._arith_for(0, 128, 128, True, 0))
+                                                                  dense._arith_for(0, 128, 128, True, 0), fmt="mask")
         r = dict(y=y, stats=stats, packed_ref=packed_ref, m_ref=m_ref, packed=packed, side=side, stats_new=stats_new, m_new=m_new)
         if key[1:] != ("fp16x3", 0.5, 32 * 256 + 1):                 # (only what the gather test below reads again is kept)
             return r
@@ -99,7 +99,7 @@ def test_gather_over_the_fused_output_is_the_dense_gather(table, device):
     rowptr, col = _csr(300, n_s, seed=7)
     rowptr, col = rowptr.to(device), col.to(device)
     want, _ = ops.segreduce(SUM, rowptr, col, None, r["y"], 300, variant=1)
-    got = ops.segreduce_packed(SUM, rowptr, col, r["packed"], r["side"], 300)
+    got = ops.segreduce_packed(SUM, rowptr, col, r["packed"], r["side"], 300, fmt="mask")
     assert torch.equal(_bits(got), _bits(want))
 
 

@@ -46,7 +46,7 @@ def test_pack_rows_matches_the_encoder(n, strided, device):
             assert xd.stride(0) == 192
         else:
             xd = x.to(device)
-        got = ops.pack_rows(xd).cpu()
+        got = ops.pack_rows(xd, fmt="mask").cpu()
         assert got.shape == (n, fmt.PITCH_DW) and got.dtype == torch.int32
         assert torch.equal(got[:, :4], ref[:, :4])                   # masks, overflow rows included
         k = torch.tensor(ks)
@@ -94,18 +94,18 @@ def test_segreduce_packed_is_bitwise_the_dense_gather(reduce, ordered, n_s, devi
     rowptr, col = rowptr.to(device), col.to(device)
     for name, x in _tables(n_s).items():
         xd = x.to(device)
-        packed = ops.pack_rows(xd)
+        packed = ops.pack_rows(xd, fmt="mask")
         for n_t in (300, 299):                                       # 299: not a multiple of the 4 rows of a workgroup
             order = torch.randperm(n_t, generator=torch.Generator().manual_seed(n_t)).to(torch.int32).to(device) if ordered else None
             rp = rowptr[:n_t + 1]
             want, _ = ops.segreduce(reduce, rp, col, None, xd, n_t, variant=1, row_order=order)
-            got = ops.segreduce_packed(reduce, rp, col, packed, xd, n_t, row_order=order)
+            got = ops.segreduce_packed(reduce, rp, col, packed, xd, n_t, row_order=order, fmt="mask")
             assert torch.equal(_bits(got), _bits(want)), (name, n_t)
             empty = (rp[1:] - rp[:-1]) == 0
             assert not _bits(got)[empty].any()                       # empty rows write +0
     if n_s == 300 and not ordered and reduce == SUM:                # and the dense kernel is right about a sum (float64 on the host)
         x = _tables(n_s)["mix10"]
-        got = ops.segreduce_packed(SUM, rowptr, col, ops.pack_rows(x.to(device)), x.to(device), 300).cpu().double()
+        got = ops.segreduce_packed(SUM, rowptr, col, ops.pack_rows(x.to(device), fmt="mask"), x.to(device), 300, fmt="mask").cpu().double()
         ref = torch.zeros(300, 128, dtype=torch.float64)
         ref.index_add_(0, torch.repeat_interleave(torch.arange(300), (rowptr[1:] - rowptr[:-1]).cpu().long()), x.double()[col.cpu().long()])
         torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-5)

@@ -2,8 +2,8 @@
 """The cell-row forward gather against the mask-row one at the headline shape: 1M x 1M, degree 16, d = 128,
 the table relu + dropout 0.5 of random normals.  Times (HIP events, median / min / max of --iters launches after --warmup)
 
-  * pack_rows against pack_cells;
-  * segreduce_packed (mask rows) against segreduce_cells (cell rows) over both CSRs of the incidence -- V->E, where every row has
+  * pack_rows writing mask rows against cell rows;
+  * segreduce_packed over mask rows against cell rows, over both CSRs of the incidence -- V->E, where every row has
     `degree` incidences, and E->V, where the row lengths scatter around it;
   * the fused Linear that writes mask rows (csrc/fused_fwd2.hip mode 3) against the one that writes cell rows (mode 4);
   * with --variants DIR: the cell gather rebuilt with other step shapes (loads in flight / loads per LDS sub-step / waves per SIMD)
@@ -73,7 +73,7 @@ def gpu_step(cold: bool) -> dict:
     x = torch.relu(torch.randn(n, D, device=dev, generator=g))
     x = x * (torch.rand(n, D, device=dev, generator=g) >= 0.5).float() * 2.0
     occupied = (x != 0).sum(1)
-    packed, cells = ops.pack_rows(x), ops.pack_cells(x)
+    packed, cells = ops.pack_rows(x, fmt="mask"), ops.pack_rows(x, fmt="cells")
     dirs = (("V->E", inc.by_dst), ("E->V", inc.by_src))
     stream = torch.cuda.current_stream().cuda_stream
     P_, I64, I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
@@ -94,8 +94,8 @@ def gpu_step(cold: bool) -> dict:
     equal = True
     for _, csr in dirs:
         want, _ = ops.segreduce(0, csr.rowptr, csr.col, None, x, n, variant=1, row_order=csr.row_order)
-        for got in [ops.segreduce_packed(0, csr.rowptr, csr.col, packed, x, n, row_order=csr.row_order),
-                    ops.segreduce_cells(0, csr.rowptr, csr.col, cells, x, n, row_order=csr.row_order)] + \
+        for got in [ops.segreduce_packed(0, csr.rowptr, csr.col, packed, x, n, row_order=csr.row_order, fmt="mask"),
+                    ops.segreduce_packed(0, csr.rowptr, csr.col, cells, x, n, row_order=csr.row_order, fmt="cells")] + \
                    [run_variant(lib, csr) for lib in variants.values()]:
             equal = equal and bool(torch.equal(got.view(torch.int32), want.view(torch.int32)))
         del want, got
@@ -112,10 +112,10 @@ def gpu_step(cold: bool) -> dict:
                 ts.append(s.elapsed_time(e))
         return {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
 
-    res = {"pack rows": timeit(lambda: ops.pack_rows(x)), "pack cells": timeit(lambda: ops.pack_cells(x))}
+    res = {"pack rows": timeit(lambda: ops.pack_rows(x, fmt="mask")), "pack cells": timeit(lambda: ops.pack_rows(x, fmt="cells"))}
     for name, csr in dirs:
-        res["mask " + name] = timeit(lambda: ops.segreduce_packed(0, csr.rowptr, csr.col, packed, x, n, row_order=csr.row_order))
-        res["cells " + name] = timeit(lambda: ops.segreduce_cells(0, csr.rowptr, csr.col, cells, x, n, row_order=csr.row_order))
+        res["mask " + name] = timeit(lambda: ops.segreduce_packed(0, csr.rowptr, csr.col, packed, x, n, row_order=csr.row_order, fmt="mask"))
+        res["cells " + name] = timeit(lambda: ops.segreduce_packed(0, csr.rowptr, csr.col, cells, x, n, row_order=csr.row_order, fmt="cells"))
         for vname, lib in variants.items():
             res[f"cells {name} [{vname}]"] = timeit(lambda: run_variant(lib, csr))
 
@@ -126,12 +126,12 @@ def gpu_step(cold: bool) -> dict:
     gamma, beta = torch.ones(D, device=dev), torch.zeros(D, device=dev)
     mask = torch.empty(dense.activation_mask_words(n, D), dtype=torch.int32, device=dev)
     arith = dense._arith_for(0, D, D, True, 0)
-    lin = {"linear mask rows": lambda: ops.fused_linear_fwd_packed(xl, W, bias, gamma, beta, 1e-5, True, P, 101, True, P, 202, None, mask, arith),
-           "linear cell rows": lambda: ops.fused_linear_fwd_cells(xl, W, bias, gamma, beta, 1e-5, True, P, 101, True, P, 202, None, mask, arith)}
+    lin = {"linear mask rows": lambda: ops.fused_linear_fwd_packed(xl, W, bias, gamma, beta, 1e-5, True, P, 101, True, P, 202, None, mask, arith, fmt="mask"),
+           "linear cell rows": lambda: ops.fused_linear_fwd_packed(xl, W, bias, gamma, beta, 1e-5, True, P, 101, True, P, 202, None, mask, arith, fmt="cells")}
     y = dense.fused_linear_fwd(xl, W, bias, gamma, beta, 1e-5, True, P, 101, True, P, 202, None, mask)[0]
     lc, side, _ = lin["linear cell rows"]()
     over = (y.view(torch.int32) != 0).sum(1) > 48
-    rows_equal = bool(torch.equal(lc, ops.pack_cells(y))) and bool(torch.equal(side.view(torch.int32)[over], y.view(torch.int32)[over]))
+    rows_equal = bool(torch.equal(lc, ops.pack_rows(y, fmt="cells"))) and bool(torch.equal(side.view(torch.int32)[over], y.view(torch.int32)[over]))
     del y, lc, side
     for name, fn in lin.items():
         res[name] = timeit(fn)
@@ -151,7 +151,7 @@ def table(rows) -> str:
         out.append(f"[{r['step']}] n = {n}, nnz = {nnz}, d = {D}; occupied columns per row: mean {r['occupied_mean']:.1f}, max "
                    f"{r['occupied_max']}; rows above 48 (cell overflow): {r['over48']} = {r['over48'] / n:.2e} of the table, above 60 (mask "
                    f"overflow): {r['over60']}; every gather bitwise equal to the dense one: {r['bitwise_equal']}")
-        out.append(f"  the Linear's output: rows above 48: {r['linear_over48']}; mode-4 rows equal to pack_cells of the dense output, side table "
+        out.append(f"  the Linear's output: rows above 48: {r['linear_over48']}; mode-4 rows equal to the packed cell rows of the dense output, side table "
                    f"holds the overflow rows: {r['linear_rows_equal']}")
         out.append(f"  E->V row lengths: max {r['ev_max_degree']} (V->E: all {nnz // n})")
         out.append(f"  {'kernel':<58}{'median ms':>10}{'min':>9}{'max':>9}{'G lines/s':>11}")
@@ -165,7 +165,7 @@ def table(rows) -> str:
             gain = mask["median"] - cell["median"]
             out.append(f"  {d}: cell gather {cell['median']:.3f} ms against mask gather {mask['median']:.3f} ms: gain {gain:+.3f} ms, mask spread "
                        f"(max - min of {args.iters}) {spread:.3f} ms, criterion gain > 3 x spread: {'PASS' if gain > 3 * spread else 'FAIL'}")
-        out.append(f"  pack_cells against pack_rows: {k['pack cells']['median'] - k['pack rows']['median']:+.3f} ms; the Linear writing cell rows "
+        out.append(f"  packing cell rows against mask rows: {k['pack cells']['median'] - k['pack rows']['median']:+.3f} ms; the Linear writing cell rows "
                    f"against mask rows: {k['linear cell rows']['median'] - k['linear mask rows']['median']:+.3f} ms per launch")
     return "\n".join(out) + "\n"
 

@@ -53,7 +53,7 @@ def _time_pair(n: int, scrub, check_gather: bool) -> dict:
         return dense.fused_linear_fwd(x, W, bias, gamma, beta, 1e-5, True, P, 101, True, P, 202, None, mask)[0]
 
     def lin_packed():
-        return ops.fused_linear_fwd_packed(x, W, bias, gamma, beta, 1e-5, True, P, 101, True, P, 202, None, mask, arith)
+        return ops.fused_linear_fwd_packed(x, W, bias, gamma, beta, 1e-5, True, P, 101, True, P, 202, None, mask, arith, fmt="mask")
 
     def timeit(fn):
         ts = []
@@ -67,7 +67,7 @@ def _time_pair(n: int, scrub, check_gather: bool) -> dict:
         return {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
 
     y = lin_dense()
-    packed_ref = ops.pack_rows(y)
+    packed_ref = ops.pack_rows(y, fmt="mask")
     packed, side, _ = lin_packed()
     occupied = (y.view(torch.int32) != 0).sum(1)
     fits = occupied <= 60
@@ -82,13 +82,13 @@ def _time_pair(n: int, scrub, check_gather: bool) -> dict:
         equal = True
         for csr in (inc.by_dst, inc.by_src):
             want, _ = ops.segreduce(0, csr.rowptr, csr.col, None, y, n, variant=1, row_order=csr.row_order)
-            got = ops.segreduce_packed(0, csr.rowptr, csr.col, packed, side, n, row_order=csr.row_order)
+            got = ops.segreduce_packed(0, csr.rowptr, csr.col, packed, side, n, row_order=csr.row_order, fmt="mask")
             equal = equal and bool(torch.equal(got.view(torch.int32), want.view(torch.int32)))
             del want, got
         res["gather_equal"] = equal
         del hg, inc
-    res["kernels"] = {"linear dense": timeit(lin_dense), "pack rows": timeit(lambda: ops.pack_rows(y)),
-                      "linear + pack": timeit(lambda: ops.pack_rows(lin_dense())), "linear packed": timeit(lin_packed)}
+    res["kernels"] = {"linear dense": timeit(lin_dense), "pack rows": timeit(lambda: ops.pack_rows(y, fmt="mask")),
+                      "linear + pack": timeit(lambda: ops.pack_rows(lin_dense(), fmt="mask")), "linear packed": timeit(lin_packed)}
     return res
 
 

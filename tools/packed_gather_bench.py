@@ -43,13 +43,13 @@ def gpu_step(cold: bool) -> dict:
     x = torch.relu(torch.randn(n, D, device=dev, generator=g))
     x = x * (torch.rand(n, D, device=dev, generator=g) >= 0.5).float() * 2.0
     occupied = (x != 0).sum(1)
-    packed = ops.pack_rows(x)
+    packed = ops.pack_rows(x, fmt="mask")
     # V->E: every row has exactly `degree` incidences; E->V (the transposed CSR): the rows' lengths scatter around it
     dirs = (("V->E", inc.by_dst), ("E->V", inc.by_src))
     equal = True
     for _, csr in dirs:
         want, _ = ops.segreduce(0, csr.rowptr, csr.col, None, x, n, variant=1, row_order=csr.row_order)
-        got = ops.segreduce_packed(0, csr.rowptr, csr.col, packed, x, n, row_order=csr.row_order)
+        got = ops.segreduce_packed(0, csr.rowptr, csr.col, packed, x, n, row_order=csr.row_order, fmt="mask")
         equal = equal and bool(torch.equal(got.view(torch.int32), want.view(torch.int32)))
         del want, got
     scrub = torch.empty(1 << 28, dtype=torch.float32, device=dev) if cold else None      # 1 GiB
@@ -65,10 +65,10 @@ def gpu_step(cold: bool) -> dict:
                 ts.append(s.elapsed_time(e))
         return {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
 
-    res = {"pack": timeit(lambda: ops.pack_rows(x))}
+    res = {"pack": timeit(lambda: ops.pack_rows(x, fmt="mask"))}
     for name, csr in dirs:
         res["dense " + name] = timeit(lambda: ops.segreduce(0, csr.rowptr, csr.col, None, x, n, variant=1, row_order=csr.row_order))
-        res["packed " + name] = timeit(lambda: ops.segreduce_packed(0, csr.rowptr, csr.col, packed, x, n, row_order=csr.row_order))
+        res["packed " + name] = timeit(lambda: ops.segreduce_packed(0, csr.rowptr, csr.col, packed, x, n, row_order=csr.row_order, fmt="mask"))
     deg = inc.by_src.rowptr[1:] - inc.by_src.rowptr[:-1]
     return {"step": "cold" if cold else "hot", "n": n, "nnz": nnz, "bitwise_equal": equal,
             "occupied_mean": float(occupied.float().mean()), "occupied_max": int(occupied.max()),
