@@ -97,7 +97,8 @@ static int adam_impl(int dtype, void* const* params, const void* const* grads, v
   AdamTable tb;
   int32_t chunks = 0;
   for (int64_t k = 0; k < count; ++k) {
-    ALLSET_REQUIRE(numel[k] >= 0 && params[k] && grads[k] && exp_avg[k] && exp_avg_sq[k] && steps[k], "adam_step: null tensor %lld", static_cast<long long>(k));
+    // (a zero-element tensor has no storage: its pointers are NULL, it gets no chunk and no workgroup reads them)
+    ALLSET_REQUIRE(numel[k] >= 0 && (numel[k] == 0 || (params[k] && grads[k] && exp_avg[k] && exp_avg_sq[k] && steps[k])), "adam_step: null tensor %lld", static_cast<long long>(k));
     tb.p[k] = params[k]; tb.g[k] = grads[k]; tb.m[k] = exp_avg[k]; tb.v[k] = exp_avg_sq[k]; tb.step[k] = steps[k];
     tb.numel[k] = numel[k];
     tb.first_chunk[k] = chunks;

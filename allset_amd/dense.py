@@ -357,8 +357,7 @@ def ln_bwd(gy: Tensor, x: Tensor, stats: Tensor, gamma: Tensor, relu_in: bool, p
     lib = _lib.load()
     npart = c_int64(0)
     if x.dtype == torch.bfloat16:
-        if gy.dtype != torch.bfloat16:
-            gy = gy.to(torch.bfloat16)
+        _check_dtype(torch.bfloat16, gy, gamma)   # (a cast of gy here would be a second rounding of the gradient: refused, as ln_res_bwd does)
         check(lib.allset_ln_bwd_bf16_partials(n, d, byref(npart)), "allset_ln_bwd_bf16_partials")
         partials = torch.empty((npart.value, 2, d), dtype=torch.float32, device=dev)
         gx = torch.empty((n, d), dtype=x.dtype, device=dev) if want_gx else None

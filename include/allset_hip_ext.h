@@ -118,7 +118,8 @@ int allset_linear_bf16_bwd_bits(const void* gy, int64_t ldg, const void* bits, c
 /* torch.optim.Adam's update (reference train.py:469; non-amsgrad, L2 weight decay) for up to allset_adam_max_tensors() fp32
  * tensors in ONE launch.  params / grads / exp_avg / exp_avg_sq / numel: HOST arrays of `count` device pointers / sizes (read
  * during the call); steps: one DEVICE float per tensor holding its t >= 1, which the caller increments before each call (so a
- * captured graph advances the bias corrections on replay).  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps). */
+ * captured graph advances the bias corrections on replay).  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+ * A tensor with numel 0 may carry NULL pointers: it is skipped. */
 int allset_adam_max_tensors(void);
 int allset_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                      const float* const* steps, const int64_t* numel, int64_t count, float lr, float beta1, float beta2, float eps,

@@ -1422,22 +1422,31 @@ def test_linear_with_widths_that_are_not_multiples_of_four(n, I, O, device):
 
 
 def test_fused_adam_bf16_parameters(device):
-    """bf16 parameters (moments in bf16, fp32 arithmetic, one rounding per stored value) against torch.optim.Adam on the same bf16
-    tensors: one step agrees to a bf16 ulp of the parameter; the fallback list is empty (one launch)."""
+    """bf16 parameters (moments in bf16, fp32 arithmetic, one rounding per stored value): each of three steps against the float64
+    restatement of csrc/optim.hip's header, started from the state the device held before that step, under the bounds derived in
+    tests/bf16_dense_cases.py ``adam_within`` (half a bf16 ulp plus the fp32 arithmetic's share; the trajectory as a whole moves by
+    about lr per step, so a tolerance on its end point could not tell the kernel from one that did nothing); one launch, no fallback."""
+    import bf16_dense_cases as dc
     from allset_amd.optim import FusedAdam
     g = torch.Generator().manual_seed(11)
     pa = [torch.randn(256, 256, generator=g).to(torch.bfloat16).to(device).requires_grad_(True),
           torch.randn(256, generator=g).to(torch.bfloat16).to(device).requires_grad_(True)]
-    pb = [p.detach().clone().requires_grad_(True) for p in pa]
-    oa, ob = FusedAdam(pa, lr=1e-2), torch.optim.Adam(pb, lr=1e-2)
-    for _ in range(3):
-        for a, b in zip(pa, pb):
-            gr = torch.randn(a.shape, generator=g).to(torch.bfloat16).to(device)
-            a.grad, b.grad = gr.clone(), gr.clone()
-        oa.step(); ob.step()
-    for a, b in zip(pa, pb):
-        torch.testing.assert_close(a.float(), b.float(), rtol=2 ** -6, atol=2e-2)
-        assert oa.state[a]["exp_avg"].dtype == torch.bfloat16
+    hyper = dict(lr=1e-2, betas=(0.9, 0.999), eps=1e-8)
+    oa = FusedAdam(pa, **hyper)
+    for step in range(1, 4):
+        before = []
+        for a in pa:
+            a.grad = torch.randn(a.shape, generator=g).to(torch.bfloat16).to(device)
+            st = oa.state[a]
+            m, v = (st[k].detach().cpu().double() for k in ("exp_avg", "exp_avg_sq")) if st else (torch.zeros(a.shape, dtype=torch.float64),) * 2
+            before.append((a.detach().cpu().double().clone(), a.grad.cpu().double(), m.clone(), v.clone()))
+        oa.step()
+        for a, (p, gr, m, v) in zip(pa, before):
+            ref = dc.adam_reference(p, gr, m, v, step, wd=0.0, **hyper)
+            st = oa.state[a]
+            assert st["exp_avg"].dtype == torch.bfloat16 and float(st["step"]) == step
+            for got, which in ((st["exp_avg"], "m"), (st["exp_avg_sq"], "v"), (a.detach(), "p")):
+                dc.assert_adam(got, ref, which, True, f"step {step}")
 
 
 @pytest.mark.parametrize("n,C", [(1, 3), (2708, 7), (50000, 40), (300, 67)])
