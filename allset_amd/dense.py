@@ -16,7 +16,7 @@ from typing import Optional, Tuple
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _lib, _memo
 from ._lib import check, ptr, require_device, stream_of, on_device
 from .ops import _ld, _rowmajor, _timed
 
@@ -456,30 +456,26 @@ class _Planes:
 # ---- the plane images of a whole step, built by ONE launch ------------------------------------------------------------------------
 # A training step at the reference's tuned widths (MLP_hidden 256 / 512) rebuilds the fp16 plane images of W (forward) and W^T
 # (backward-data) of every wide Linear -- weights change every step -- each a ~5-us launch in front of its GEMM.  All weights are known
-# when the forward starts: `prefetch_wide_planes` builds every image a model will ask for in one batched launch and
-# `gemm_x6_planes` serves them.  An entry is keyed by the weight's storage, shape, version and the weight epoch (bumped by every
-# optimizer step that writes parameters behind torch's back: allset_amd.optim.FusedAdam), consumed ONCE, and dropped by the next prefetch.
-class _PlaneStore:
-    entries: dict = {}
-    epoch = 0
+# when the forward starts: inside `with prefetch_wide_planes(...)` every image the model will ask for exists, built by one batched launch;
+# `_WideNormLinear.forward` takes its two (W^T rides to the backward on the autograd context).  An image belongs to that one forward and
+# its autograd graph: held per weight OBJECT, handed out once, gone when the scope exits.
+_step_planes: Optional[dict] = None      # inside prefetch_wide_planes: (id(W), transpose) -> (W, W._version, _Planes)
 
 
-def weights_changed() -> None:
-    """Parameters were updated in place by something torch's version counters do not see (a raw-pointer optimizer kernel)."""
-    _PlaneStore.epoch += 1
-    _PlaneStore.entries = {}
+@contextlib.contextmanager
+def prefetch_wide_planes(weights, with_transposed: bool):
+    """``weights``: fp32 [out, in] weight tensors of Linears on the tiled wide path; inside, planes(W) -- and planes(W^T) when a backward
+    will follow -- of all of them exist, built with one launch (fp16-plane arithmetic only; whatever it does not take is built on demand).
+    A forward of another model inside gets a scope of its own, and this one is put back behind it."""
+    global _step_planes
+    outer, _step_planes = _step_planes, _build_wide_planes(weights, with_transposed) if (weights and wide_f16()) else None
+    try:
+        yield
+    finally:
+        _step_planes = outer
 
 
-def _plane_key(W: Tensor, transpose: bool):
-    return (W.data_ptr(), tuple(W.shape), W.stride(0), W._version, _PlaneStore.epoch, bool(transpose))
-
-
-def prefetch_wide_planes(weights, with_transposed: bool) -> None:
-    """``weights``: fp32 [out, in] weight tensors of Linears on the tiled wide path; builds planes(W) -- and planes(W^T) when a backward
-    will follow -- of all of them with one launch (fp16-plane arithmetic only; anything it does not take is built on demand as before)."""
-    _PlaneStore.entries = {}
-    if not weights or not wide_f16():
-        return
+def _build_wide_planes(weights, with_transposed: bool) -> Optional[dict]:
     import ctypes
     lib = _lib.load()
     cap = int(lib.allset_gemm_f16x3_planes_batch_max())
@@ -493,9 +489,10 @@ def prefetch_wide_planes(weights, with_transposed: bool) -> None:
             if nbytes > 0:
                 todo.append((W, tr, N, K, nbytes))
     if not todo:
-        return
+        return None
     dev = todo[0][0].device
     todo = [t for t in todo if t[0].device == dev]
+    images = {}
     for k0 in range(0, len(todo), cap):
         chunk = todo[k0:k0 + cap]
         bufs = [torch.empty(t[4], dtype=torch.uint8, device=dev) for t in chunk]
@@ -507,9 +504,14 @@ def prefetch_wide_planes(weights, with_transposed: bool) -> None:
                 (ctypes.c_int64 * n)(*[t[2] for t in chunk]), (ctypes.c_int64 * n)(*[t[3] for t in chunk]), n, stream_of(dev)),
                 "allset_gemm_f16x3_planes_batched")
         for t, b in zip(chunk, bufs):
-            # the entry keeps the weight tensor ALIVE: while an image waits here its key (an address) cannot come to mean another tensor
-            # (a dead model's weight freed, a new model's weight of the same shape allocated in its place, version 0 again)
-            _PlaneStore.entries[_plane_key(t[0], t[1])] = (_Planes(b, True), t[0])
+            images[(id(t[0]), t[1])] = (t[0], t[0]._version, _Planes(b, True))      # (holds W: its id stays its own)
+    return images
+
+
+def prefetched_planes(W: Tensor, transpose: bool) -> Optional["_Planes"]:
+    """This step's prebuilt fp16 image of ``W`` / ``W^T``: once, inside the scope that built it, for that very tensor as it was then."""
+    hit = _step_planes.pop((id(W), bool(transpose)), None) if _step_planes else None
+    return hit[2] if (hit is not None and hit[0] is W and hit[1] == W._version) else None
 
 
 def gemm_x6_planes(W: Tensor, transpose: bool, f16: Optional[bool] = None) -> "_Planes":
@@ -519,10 +521,6 @@ def gemm_x6_planes(W: Tensor, transpose: bool, f16: Optional[bool] = None) -> "_
     _check_f32(W)
     W = _rowmajor(W)
     f16 = wide_f16() if f16 is None else bool(f16)            # (callers that know their prologue pass f16 themselves)
-    if f16 and _PlaneStore.entries:
-        hit = _PlaneStore.entries.pop(_plane_key(W, transpose), None)       # built by this step's prefetch launch; used once
-        if hit is not None:
-            return hit[0]
     N, K = (W.shape[1], W.shape[0]) if transpose else (W.shape[0], W.shape[1])
     lib = _lib.load()
     nbytes = int((lib.allset_gemm_f16x3_plane_bytes if f16 else lib.allset_gemm_x6_plane_bytes)(N, K))
@@ -1298,7 +1296,9 @@ class _WideNormLinear(torch.autograd.Function):
         # the fp32 output twice -- 2 GB per Linear at [1M, 256]); widths that are not multiples of 64 keep y
         words = activation_mask_words(x.shape[0], weight.shape[0]) if (keep_y and x.shape[0] > 0) else 0
         mask = torch.empty(words, dtype=torch.int32, device=x.device) if words > 0 else None
-        y = gemm_x6(x, gemm_x6_planes(weight, False, f16=wide_f16(gamma is not None)), weight.shape[0], bias, relu_in=relu_in, stats=stats, gamma=gamma,
+        f16 = wide_f16(gamma is not None)         # (both images of the step's prefetch are taken NOW: the backward reads no module state)
+        planes, ctx.planes_t = (prefetched_planes(weight, False), prefetched_planes(weight, True)) if f16 else (None, None)
+        y = gemm_x6(x, planes or gemm_x6_planes(weight, False, f16=f16), weight.shape[0], bias, relu_in=relu_in, stats=stats, gamma=gamma,
                     beta=beta, p_in=p_in, seed_in=seed_in, relu_out=relu_out, p_out=p_out, seed_out=seed_out, seed_base=base,
                     mask_out=mask, stats_out=stats_y, stats_eps=emit[0] if emit is not None else 1e-5,
                     stats_relu=bool(emit[1]) if emit is not None else False)
@@ -1333,14 +1333,14 @@ class _WideNormLinear(torch.autograd.Function):
         need_x = ctx.needs_input_grad[0]
         if need_x or (gamma is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])):
             # gradient of the Linear's input u = dropout(LN(relu(x))): (gy * epilogue mask) @ W
+            planes_t = ctx.planes_t if (ctx.planes_t is not None and wide_f16()) else gemm_x6_planes(weight, True)
             if gamma is not None and weight.shape[1] <= 256:
                 # one kernel: the Linear's input gradient never leaves the chip, the LayerNorm backward is the GEMM's epilogue
-                gx, dg, db = gemm_x6_lnb(gy, gemm_x6_planes(weight, True), x, stats, gamma, relu_in, p_in, seed_in, mask_y=y,
+                gx, dg, db = gemm_x6_lnb(gy, planes_t, x, stats, gamma, relu_in, p_in, seed_in, mask_y=y,
                                          p_mask=p_out, seed_base=base, mask_bits=mask,
                                          defer_to=(p_g, p_bt) if (dfr and need[1] and need[2]) else None)
                 return gx, dg, db, gw, gb, None, None, None, None, None, None, None
             # (behind a bare relu -- p_in == 0 there, see wide_linear_supported -- the mask by the sign of x is the GEMM's epilogue)
-            planes_t = gemm_x6_planes(weight, True)
             sgn = x if (gamma is None and relu_in and planes_t.f16 and x.stride(-1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
                         and _lib.load().allset_gemm_wide_sgn_supported(_lib.ARITH_FP16X3, weight.shape[1], weight.shape[0])) else None
             gu = gemm_x6(gy, planes_t, weight.shape[1], None, mask_y=y, p_mask=p_out, mask_bits=mask, sgn_x=sgn)
@@ -2354,30 +2354,16 @@ class SparseRows:
         self.colptr[1:] = torch.cumsum(torch.bincount(cols, minlength=d), 0).to(torch.int32)
 
 
-_SPARSE_ROWS = {}           # data_ptr -> (weakref to the tensor, version, shape, SparseRows or None)
 SPARSE_MAX_DENSITY = 0.10   # above this fraction of non-zeros the GEMM path wins
 
 
-def sparse_rows(x: Tensor) -> Optional[SparseRows]:
-    """The cached :class:`SparseRows` of ``x`` when at most 10 % of it is non-zero, else None.  Built on first sight of the tensor
-    (one host read-back; keyed on identity and version, so an in-place update rebuilds it) -- never during graph capture: a tensor
-    first seen there takes the dense path."""
-    import weakref
-    key = x.data_ptr()
-    hit = _SPARSE_ROWS.get(key)
-    if hit is not None:
-        ref, ver, shape, sp = hit
-        if ref() is x and ver == x._version and shape == tuple(x.shape):
-            return sp
-    if torch.cuda.is_current_stream_capturing():
-        return None
-    if len(_SPARSE_ROWS) > 64:
-        for k in [k for k, v in _SPARSE_ROWS.items() if v[0]() is None]:
-            del _SPARSE_ROWS[k]
-    nnz = int(torch.count_nonzero(x))
-    sp = SparseRows(x) if (x.numel() > 0 and nnz <= SPARSE_MAX_DENSITY * x.numel()) else None
-    _SPARSE_ROWS[key] = (weakref.ref(x), x._version, tuple(x.shape), sp)
-    return sp
+def sparse_rows(x: Tensor, build: bool = True) -> Optional[SparseRows]:
+    """The :class:`SparseRows` of ``x`` when at most 10 % of it is non-zero, else None.  Built on first sight of the tensor (one host
+    read-back) and kept on it (``_memo``: an in-place update rebuilds it; it is freed with ``x``, so a graph whose kernels read it holds it:
+    graphs.py) -- never during graph capture, where a tensor first seen takes the dense path, nor with ``build=False``."""
+    if not build or (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+        return _memo.lookup(x, "sparse_rows", default=None)
+    return _memo.get(x, "sparse_rows", (), lambda: SparseRows(x) if (x.numel() > 0 and int(torch.count_nonzero(x)) <= SPARSE_MAX_DENSITY * x.numel()) else None)
 
 
 class _SparseInputNormLinear(torch.autograd.Function):

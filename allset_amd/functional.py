@@ -14,7 +14,7 @@ from typing import Optional, Tuple
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib, ops
+from . import _lib, _memo, ops
 from .dense import PackedRows
 from ._lib import MAX, MEAN, MIN, REDUCE_CODES, SUM
 from .incidence import Incidence, LeaveOneOutIncidence
@@ -91,8 +91,8 @@ class _RouteWeights(torch.autograd.Function):
 def _routed(norm: Tensor, inc: Incidence, dst: bool) -> Tensor:
     """``norm`` (edge-list order, requires grad) in the order of ``inc.by_dst`` / ``inc.by_src``.
 
-    A NON-LEAF norm (SetGNN's ``Importance * norm``, a fresh tensor per forward) caches the routed copy on itself per
-    (CSR object, version, grad mode): the V->E and E->V convs of a layer share one routing and autograd sums their gradients; the
+    A NON-LEAF norm (SetGNN's ``Importance * norm``, a fresh tensor per forward) keeps the routed copy on itself (``_memo``) per
+    (CSR object, grad mode): the V->E and E->V convs of a layer share one routing and autograd sums their gradients; the
     cache dies with that forward's tensor.  A LEAF (an ``nn.Parameter`` handed straight to ``deepsets_aggregate``) is never
     cached: it outlives the forward, the optimizer updates it in place, a hit would replay the first call's values and graph
     (and keep it alive through AccumulateGrad -> tensor -> cache).  Routing is one gather, 0.2 ms at nnz = 16M."""
@@ -100,12 +100,7 @@ def _routed(norm: Tensor, inc: Incidence, dst: bool) -> Tensor:
     perm, inv = (inc.perm_dst_long(), inc.inv_perm_dst()) if dst else (inc.perm_src_long(), inc.inv_perm_src())
     if norm.grad_fn is None:
         return _RouteWeights.apply(norm.reshape(-1).to(torch.float32), perm, inv)
-    cache = norm.__dict__.setdefault("_allset_routed", {})
-    key = (id(csr), norm._version, torch.is_grad_enabled())
-    hit = cache.get(key)
-    if hit is None:
-        hit = cache[key] = _RouteWeights.apply(norm.reshape(-1).to(torch.float32), perm, inv)
-    return hit
+    return _memo.get(norm, "routed", (id(csr), torch.is_grad_enabled()), lambda: _RouteWeights.apply(norm.reshape(-1).to(torch.float32), perm, inv))
 
 
 _PACKED_GATHER = True

@@ -7,7 +7,8 @@ same loop -- same arithmetic, one graph launch per epoch.
 
 What makes capture possible here:
   * every kernel of the path is stream-ordered with no host read-back once the incidence is built
-    (``models.SetGNN._incidences`` caches the CSR pair on the first call, which must happen BEFORE capture);
+    (``models.SetGNN._incidences`` builds the CSR pair on the first call, which must happen BEFORE capture, and keeps it on
+    ``data.edge_index``: the graph holds ``data``, so the pair lives as long as the graph);
   * dropout masks come from a device-resident counter (``dense.device_seed_counter``): the kernels read it when they
     start and the graph advances it once per step (in the launch that reduces the parameter gradients), so every replay
     draws fresh masks although the host-side seeds were frozen at capture;
@@ -44,6 +45,11 @@ def _side_stream_warmup(fn: Callable[[], None], iters: int) -> "torch.cuda.Strea
     return s
 
 
+# (the captured kernels may read data.x through its non-zero structure, dense.sparse_rows, which lives on that tensor and is dropped by an
+#  in-place update: a graph keeps what it captured alive -- None: it took the dense kernels -- and refuses to replay over newer features)
+_STALE = "data.x was updated in place after capture; the captured kernels read its non-zero structure as it was then"
+
+
 class GraphedForward:
     """Eval-mode forward of ``model`` on a fixed ``data`` captured as one graph.
 
@@ -67,6 +73,7 @@ class GraphedForward:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=st):
                 self.out = model(data)
+        self._sp, self._x_version = (dense.sparse_rows(data.x, build=False) if constant_features else None), data.x._version
         model.train(was_training)
 
     def __call__(self, x: Optional[Tensor] = None) -> Tensor:
@@ -75,6 +82,8 @@ class GraphedForward:
                 raise AllSetHipError("GraphedForward(constant_features=True): the captured kernels read the features' non-zero structure; "
                                      "capture with constant_features=False to replace them between replays")
             self.data.x.copy_(x)
+        if self._sp is not None and self.data.x._version != self._x_version:
+            raise AllSetHipError(_STALE)
         self.graph.replay()
         return self.out
 
@@ -157,6 +166,7 @@ class GraphedTrainStep:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=st):
                 self.loss = one_step()
+        self._sp, self._x_version = dense.sparse_rows(data.x, build=False), data.x._version
         if restore:
             with torch.no_grad():
                 for p, snap in zip(params, p_snap):
@@ -168,5 +178,7 @@ class GraphedTrainStep:
                     b.copy_(snap)
 
     def __call__(self) -> Tensor:
+        if self._sp is not None and self.data.x._version != self._x_version:
+            raise AllSetHipError(_STALE)
         self.graph.replay()
         return self.loss

@@ -14,12 +14,11 @@ Layout (all int32, device resident):
 """
 from __future__ import annotations
 
-import weakref
 from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _lib, ops
+from . import _lib, _memo, ops
 from .ops import CSR
 
 Tensor = torch.Tensor
@@ -41,7 +40,7 @@ class Incidence:
         self.device = by_dst.rowptr.device
         self._pos_dst_of_src: Optional[Tensor] = None     # by_src position -> by_dst position
         self._inv_cnt: Dict[str, Tensor] = {}
-        self._wcache: Dict[Tuple, Tuple[weakref.ref, Tuple[Optional[Tensor], Optional[Tensor]]]] = {}
+        self._routed: Optional[Tuple] = None              # weights(): (_memo.Stamp of the norm, its routed pair, probed for all ones)
         self._reversed: Optional["Incidence"] = None
 
     # ---- construction ---------------------------------------------------------------------
@@ -137,25 +136,23 @@ class Incidence:
     def weights(self, norm: Optional[Tensor]) -> Tuple[Optional[Tensor], Optional[Tensor]]:
         """Route the reference's per-incidence ``norm`` (edge-list order; int64 ones by default,
         preprocessing.py:454) into (by_dst order, by_src order) f32 arrays.  All-ones -> (None, None):
-        (integer norms on first sight, a persistent floating-point tensor from its second use on) the kernels then skip the weight stream.  Cached per (storage, version) for non-grad norms, and only while
-        that very tensor object is alive: a temporary recomputed per forward (``Importance * norm`` under
-        ``no_grad``) is usually handed the previous temporary's address with ``_version`` 0 by the caching
-        allocator, so an address match alone would return the FIRST evaluation's weights for ever."""
+        (integer norms on first sight, a persistent floating-point tensor from its second use on) the kernels then skip the weight stream.
+        Kept for non-grad norms while a ``_memo.Stamp`` holds: a temporary recomputed per forward (``Importance * norm`` under ``no_grad``)
+        usually gets the previous temporary's address with ``_version`` 0, and an address match alone served the FIRST weights for ever."""
         if norm is None:
             return None, None
         if norm.numel() != self.nnz:
             raise ValueError(f"norm has {norm.numel()} entries for {self.nnz} incidences")
         if norm.requires_grad:
             raise RuntimeError("weights(): a norm that requires grad is routed inside functional.deepsets_aggregate")
-        key = (norm.data_ptr(), norm._version, norm.dtype, norm.numel())
-        entry = self._wcache.get(key)
-        hit = entry[1] if (entry is not None and entry[0]() is norm) else None
+        entry = self._routed if (self._routed is not None and self._routed[0].holds(norm)) else None
+        hit = entry[1] if entry is not None else None
         if hit is not None and not entry[2] and not _capturing(norm):
             # A floating-point norm seen a SECOND time as the very same live tensor is persistent (``torch.ones(nnz)`` kept by the
             # caller), not a per-forward temporary: probe it once now.  All ones -> the weight stream is skipped from here on.
             if bool((norm.reshape(-1) == 1).all()):
                 hit = (None, None)
-            self._wcache[key] = (entry[0], hit, True)
+            self._routed = (entry[0], hit, True)
         if hit is None:
             flat = norm.reshape(-1)
             # The all-ones probe (a host sync) on FIRST sight is for the reference's DEFAULT norm only: int64 ones
@@ -167,11 +164,12 @@ class Incidence:
             if probed and bool((flat == 1).all()):
                 hit = (None, None)
             else:
-                f = flat.to(torch.float32)
-                hit = (f.index_select(0, self.perm_dst_long()), f.index_select(0, self.perm_src_long()))
-            self._wcache.clear()
-            self._wcache[key] = (weakref.ref(norm), hit, probed)
+                hit = self._route(flat.to(torch.float32))
+            self._routed = (_memo.Stamp(norm), hit, probed)
         return hit
+
+    def _route(self, f: Tensor) -> Tuple[Tensor, Tensor]:
+        return f.index_select(0, self.perm_dst_long()), f.index_select(0, self.perm_src_long())
 
     def known_unweighted(self, norm: Optional[Tensor]) -> bool:
         """``weights(norm)`` is known to be (None, None), for routes decided before the aggregation runs
@@ -184,8 +182,8 @@ class Incidence:
             return False
         if not norm.dtype.is_floating_point:
             return self.weights(norm)[0] is None
-        entry = self._wcache.get((norm.data_ptr(), norm._version, norm.dtype, norm.numel()))
-        return entry is not None and entry[0]() is norm and entry[1][0] is None and entry[1][1] is None
+        entry = self._routed
+        return entry is not None and entry[0].holds(norm) and entry[1][0] is None and entry[1][1] is None
 
 
 class LeaveOneOutIncidence:
@@ -323,26 +321,10 @@ def _rowptr_of(counts: Tensor, dev) -> Tensor:
     return rowptr
 
 
-# ---------------------------------------------------------------------------------------------
-# cache: edge_index tensor -> Incidence, keyed on storage identity + version (the reference hands the
-# same data.edge_index to every forward; models.py:450)
-# ---------------------------------------------------------------------------------------------
-
 def _capturing(t: Tensor) -> bool:
     return t.is_cuda and torch.cuda.is_current_stream_capturing()
 
 
-_CACHE: Dict[Tuple, Tuple[weakref.ref, Incidence]] = {}
-_CACHE_LIMIT = 16
-
-
 def cached_incidence(edge_index: Tensor, n_src: Optional[int], n_dst: Optional[int] = None) -> Incidence:
-    key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), str(edge_index.device), n_src, n_dst)
-    hit = _CACHE.get(key)
-    if hit is not None and hit[0]() is edge_index:            # the live tensor itself, not a recycled address
-        return hit[1]
-    inc = Incidence.from_edge_index(edge_index, n_src=n_src, n_dst=n_dst)
-    if len(_CACHE) >= _CACHE_LIMIT:
-        _CACHE.pop(next(iter(_CACHE)))
-    _CACHE[key] = (weakref.ref(edge_index), inc)
-    return inc
+    """Built on first sight of ``edge_index`` and kept on that tensor (the reference hands every forward the same one, models.py:450)."""
+    return _memo.get(edge_index, "incidence", (n_src, n_dst), lambda: Incidence.from_edge_index(edge_index, n_src=n_src, n_dst=n_dst))

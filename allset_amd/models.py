@@ -13,15 +13,14 @@ reference (models.py:453-456, layers.py:174,656) do not exist after the first ca
 """
 from __future__ import annotations
 
-import weakref
-from typing import Dict, Tuple
+from typing import Tuple
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn import Linear, Parameter
 
-from . import dense
+from . import _memo, dense
 from . import functional as AF
 from .incidence import Incidence, LeaveOneOutIncidence, LooDirection
 from .layers import MLP, HalfNLHconv, relu_dropout
@@ -108,8 +107,6 @@ class SetGNN(nn.Module):
             if self.GPR:
                 self.MLP._raw_input = True
 
-        self._inc_cache: Dict[Tuple, Tuple[weakref.ref, Tuple[Incidence, Incidence]]] = {}
-
     def reset_parameters(self):
         for group in (self.V2EConvs, self.E2VConvs, self.bnV2Es, self.bnE2Vs):
             for layer in group:
@@ -122,56 +119,41 @@ class SetGNN(nn.Module):
             nn.init.ones_(self.Importance)
 
     # ---- incidence handling ---------------------------------------------------------------------
-    def _incidences(self, edge_index: torch.Tensor, n_v: int) -> Tuple[Incidence, Incidence]:
-        """(V->E, E->V) incidences for ``data.edge_index``; built on first sight of the tensor.
+    @staticmethod
+    def _rebased(edge_index: torch.Tensor, key: Tuple, build):
+        """``build()`` on first sight of ``edge_index``, kept on that tensor (``_memo``: whoever holds ``data`` holds its incidences).
+        Mirrors reference models.py:453-454: hyperedge ids are re-based IN PLACE so that they start at 0 (train.py hands them over starting
+        at n_V; after the first call the tensor is unchanged, as in the reference where subtracting min()==0 is a no-op)."""
+        def rebase_and_build():
+            if edge_index.numel() > 0:
+                cidx = int(edge_index[1].min())          # one-time host sync (reference: every forward)
+                if cidx != 0:
+                    edge_index[1] -= cidx                # reference side effect, kept (SURVEY A.2 Q2)
+            return build()
+        return _memo.get(edge_index, "setgnn", key, rebase_and_build)
 
-        Mirrors reference models.py:453-454: hyperedge ids are re-based IN PLACE so that they start at
-        0 (train.py hands them over starting at n_V; after the first call the tensor is unchanged, as in
-        the reference where subtracting min()==0 is a no-op).
-        """
-        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), n_v)
-        hit = self._inc_cache.get(key)
-        if hit is not None and hit[0]() is edge_index:        # same live tensor object, not merely a reused address
-            return hit[1]
-        if edge_index.numel() > 0:
-            cidx = int(edge_index[1].min())          # one-time host sync (reference: every forward)
-            if cidx != 0:
-                edge_index[1] -= cidx                # reference side effect, kept (SURVEY A.2 Q2)
-        v2e = Incidence.from_edge_index(edge_index, n_src=n_v)    # n_E = max hyperedge id + 1 (Q1)
-        e2v = v2e.reversed()                                      # n_V' = max vertex id + 1 (Q1)
-        self._inc_cache.clear()
-        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), n_v)
-        self._inc_cache[key] = (weakref.ref(edge_index), (v2e, e2v))
-        return v2e, e2v
+    def _incidences(self, edge_index: torch.Tensor, n_v: int) -> Tuple[Incidence, Incidence]:
+        """(V->E, E->V) incidences for ``data.edge_index``."""
+        def build():
+            v2e = Incidence.from_edge_index(edge_index, n_src=n_v)    # n_E = max hyperedge id + 1 (Q1)
+            return v2e, v2e.reversed()                                # n_V' = max vertex id + 1 (Q1)
+        return self._rebased(edge_index, (n_v,), build)
 
     def _loo_incidences(self, edge_index: torch.Tensor, n_v: int, normtype: str, attention: bool = False
                         ) -> Tuple[LooDirection, LooDirection]:
         """The (V->E, E->V) pair for exclude-self data that kept its UNEXPANDED edge list (``preprocessing.exclude_self``): one
-        :class:`LeaveOneOutIncidence`, built on first sight of the tensor and cached exactly as ``_incidences`` caches the plain pair
-        (hyperedge ids re-based in place, as there)."""
-        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), n_v, "loo", normtype, attention)
-        hit = self._inc_cache.get(key)
-        if hit is not None and hit[0]() is edge_index:
-            return hit[1]
-        if edge_index.numel() > 0:
-            cidx = int(edge_index[1].min())
-            if cidx != 0:
-                edge_index[1] -= cidx
-        loo = LeaveOneOutIncidence.from_edge_index(edge_index, n_v=n_v)
-        if attention and edge_index.is_cuda:
-            loo.merge_incidence()                                  # (its one-time host syncs happen here, not inside a captured forward)
-        pair = (LooDirection(loo, "v2e", normtype, attention), LooDirection(loo, "e2v", normtype, attention))
-        self._inc_cache.clear()
-        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), n_v, "loo", normtype, attention)
-        self._inc_cache[key] = (weakref.ref(edge_index), pair)
-        return pair
+        :class:`LeaveOneOutIncidence`."""
+        def build():
+            loo = LeaveOneOutIncidence.from_edge_index(edge_index, n_v=n_v)
+            if attention and edge_index.is_cuda:
+                loo.merge_incidence()                              # (its one-time host syncs happen here, not inside a captured forward)
+            return LooDirection(loo, "v2e", normtype, attention), LooDirection(loo, "e2v", normtype, attention)
+        return self._rebased(edge_index, ("loo", n_v, normtype, attention), build)
 
-    def _prefetch_planes(self, x: torch.Tensor) -> None:
+    def _prefetch_planes(self, x: torch.Tensor):
         """At dataset scale every launch is a link of the step's dependent chain: the fp16 plane images of all wide (256 / 512-wide)
-        Linears of the convs -- W for the forward, W^T too when a backward will follow -- in one launch up front (dense.prefetch_wide_planes;
-        at benchmark scale the ten 5-us launches do not matter and the images are built where they are used)."""
-        if not (x.is_cuda and x.dtype == torch.float32 and x.shape[0] <= 65536):
-            return
+        Linears of the convs -- W for the forward, W^T too when a backward will follow -- in one launch up front, for this forward and its
+        backward alone (dense.prefetch_wide_planes; at benchmark scale the ten 5-us launches do not matter: built where they are used)."""
         ws = getattr(self, "_wide_weights", None)
         if ws is None:
             ws = []
@@ -180,8 +162,8 @@ class SetGNN(nn.Module):
                     if isinstance(m, nn.Linear) and dense.wide_linear_supported(m.in_features, m.out_features, False):
                         ws.append(m.weight)
             self._wide_weights = ws
-        # (always: an empty list drops whatever an earlier forward left unconsumed)
-        dense.prefetch_wide_planes(ws, with_transposed=torch.is_grad_enabled() and any(w.requires_grad for w in ws))
+        ws = ws if (x.is_cuda and x.dtype == torch.float32 and x.shape[0] <= 65536) else []
+        return dense.prefetch_wide_planes(ws, with_transposed=torch.is_grad_enabled() and any(w.requires_grad for w in ws))
 
     def forward(self, data):
         """``data.x`` [n_V, F] float32, ``data.edge_index`` int64 [2, nnz] (row 0 vertex ids, row 1
@@ -199,31 +181,31 @@ class SetGNN(nn.Module):
             if self.LearnMask:
                 norm = self.Importance * norm
             v2e, e2v = self._incidences(edge_index, x.shape[0])
-        self._prefetch_planes(x)
-        if self.GPR:
-            xs = [F.relu(self.MLP(x))]
+        with self._prefetch_planes(x):
+            if self.GPR:
+                xs = [F.relu(self.MLP(x))]
+                for i in range(len(self.V2EConvs)):
+                    with AF.packed_direction("v2e"):
+                        x = self.V2EConvs[i](x, v2e, norm, self.aggr, _post_dropout=self.dropout)   # relu + dropout fused
+                    with AF.packed_direction("e2v"):
+                        x = self.E2VConvs[i](x, e2v, norm, self.aggr)
+                    if self.E2VConvs[i].attention:     # (the Deep Sets conv ends in relu(f_dec(.)) already: layers.py, reference layers.py:634)
+                        x = F.relu(x)
+                    xs.append(x)
+                    x = relu_dropout(x, self.dropout, self.training)     # x >= 0 already: the dropout alone, from the counter hash (no mask tensor)
+                # reference models.py:468-470: x = GPRweights(stack(xs, -1)).squeeze() -- a Linear(L+1 -> 1) over the stacked layer
+                # outputs, i.e. a weighted sum of them.  Written as that sum: as a matmul it is an [n*d, L+1] x [L+1, 1] product,
+                # which the library runs as a strided-batched GEMM with K = L+1 -- 19 SECONDS per step at n = 1M, d = 128
+                # (tools/model_step_profile.py with MODEL_ARGS=All_num_layers=2,GPR=1); same arithmetic, same parameter.
+                return self.classifier(_WeightedSum.apply(self.GPRweights.weight, *xs))
+            # hard-coded input dropout (models.py:473); on raw features without gradient it rides in the first conv's first kernel
+            pre = 0.2 if (self.training and len(self.V2EConvs) and self.V2EConvs[0].takes_pre_dropout(x)) else 0.0
+            if not pre:
+                x = F.dropout(x, p=0.2, training=self.training)
             for i in range(len(self.V2EConvs)):
+                # x = dropout(relu(conv(x))) (models.py:475-481); relu + dropout ride in the conv's last fused pass
                 with AF.packed_direction("v2e"):
-                    x = self.V2EConvs[i](x, v2e, norm, self.aggr, _post_dropout=self.dropout)   # relu + dropout fused
+                    x = self.V2EConvs[i](x, v2e, norm, self.aggr, _post_dropout=self.dropout, _pre_dropout=pre if i == 0 else 0.0)
                 with AF.packed_direction("e2v"):
-                    x = self.E2VConvs[i](x, e2v, norm, self.aggr)
-                if self.E2VConvs[i].attention:     # (the Deep Sets conv ends in relu(f_dec(.)) already: layers.py, reference layers.py:634)
-                    x = F.relu(x)
-                xs.append(x)
-                x = relu_dropout(x, self.dropout, self.training)     # x >= 0 already: the dropout alone, from the counter hash (no mask tensor)
-            # reference models.py:468-470: x = GPRweights(stack(xs, -1)).squeeze() -- a Linear(L+1 -> 1) over the stacked layer
-            # outputs, i.e. a weighted sum of them.  Written as that sum: as a matmul it is an [n*d, L+1] x [L+1, 1] product,
-            # which the library runs as a strided-batched GEMM with K = L+1 -- 19 SECONDS per step at n = 1M, d = 128
-            # (tools/model_step_profile.py with MODEL_ARGS=All_num_layers=2,GPR=1); same arithmetic, same parameter.
-            return self.classifier(_WeightedSum.apply(self.GPRweights.weight, *xs))
-        # hard-coded input dropout (models.py:473); on raw features without gradient it rides in the first conv's first kernel
-        pre = 0.2 if (self.training and len(self.V2EConvs) and self.V2EConvs[0].takes_pre_dropout(x)) else 0.0
-        if not pre:
-            x = F.dropout(x, p=0.2, training=self.training)
-        for i in range(len(self.V2EConvs)):
-            # x = dropout(relu(conv(x))) (models.py:475-481); relu + dropout ride in the conv's last fused pass
-            with AF.packed_direction("v2e"):
-                x = self.V2EConvs[i](x, v2e, norm, self.aggr, _post_dropout=self.dropout, _pre_dropout=pre if i == 0 else 0.0)
-            with AF.packed_direction("e2v"):
-                x = self.E2VConvs[i](x, e2v, norm, self.aggr, _post_dropout=self.dropout)
-        return self.classifier(x)
+                    x = self.E2VConvs[i](x, e2v, norm, self.aggr, _post_dropout=self.dropout)
+            return self.classifier(x)

@@ -1839,43 +1839,105 @@ def test_wide_forward_writes_the_next_layers_row_statistics(n, arith, device):
 
 
 def test_prefetched_plane_images_equal_the_on_demand_ones_and_are_never_stale(device):
-    """``dense.prefetch_wide_planes`` (one launch for the fp16 plane images of W and W^T of every wide Linear of a step) hands
-    ``gemm_x6_planes`` bit-identical images, each exactly once; an in-place update of a weight (torch's version counter) or
-    ``dense.weights_changed()`` (what ``FusedAdam.step`` calls: its kernel writes through raw pointers) makes the next request rebuild."""
+    """Inside ``with dense.prefetch_wide_planes(...)`` (one launch for the fp16 plane images of W and W^T of every wide Linear of a step)
+    ``dense.prefetched_planes`` hands out images bit-identical to ``gemm_x6_planes``'s, each exactly once and only for the very weight
+    object as it was when they were built (its version counter is checked at hand-out); when the scope exits -- on an exception too --
+    nothing is left to serve, and ``gemm_x6_planes`` itself never serves anything but its own build."""
     from allset_amd import dense
     g = torch.Generator().manual_seed(4)
     ws = [torch.randn(256, 256, generator=g).to(device), torch.randn(512, 256, generator=g).to(device),
           (torch.randn(512, 512, generator=g) * 1e-3).to(device)]
+
+    def on_demand_is_its_own_build(w):
+        for tr in (False, True):
+            assert dense.prefetched_planes(w, tr) is None
+            assert torch.equal(dense.gemm_x6_planes(w, tr).buf, dense.gemm_x6_planes(w, tr, f16=True).buf)
     with dense.arithmetic("auto"):
         ref = {(i, tr): dense.gemm_x6_planes(w, tr).buf.clone() for i, w in enumerate(ws) for tr in (False, True)}
-        dense.prefetch_wide_planes(ws, with_transposed=True)
-        assert len(dense._PlaneStore.entries) == 6
-        for i, w in enumerate(ws):
-            for tr in (False, True):
-                got = dense.gemm_x6_planes(w, tr)
-                assert got.f16 and torch.equal(got.buf, ref[(i, tr)])
-        assert not dense._PlaneStore.entries                       # consumed once
-        dense.prefetch_wide_planes(ws, with_transposed=False)
-        assert len(dense._PlaneStore.entries) == 3
-        ws[0].mul_(2.0)                                            # version bump: the prebuilt image of ws[0] must not be served
-        fresh = dense.gemm_x6_planes(ws[0], False)
-        assert not torch.equal(fresh.buf, ref[(0, False)]) and len(dense._PlaneStore.entries) == 3
-        dense.weights_changed()
-        assert not dense._PlaneStore.entries
-        # an image left unconsumed must never be served for ANOTHER tensor that comes to live at the same address (a dead model's
-        # weight freed, a new model's allocated in its place: the hypothesis sweep of test_gpu_random_shapes.py found exactly that)
+        with dense.prefetch_wide_planes(ws, with_transposed=True):
+            assert len(dense._step_planes) == 6
+            for i, w in enumerate(ws):
+                for tr in (False, True):
+                    got = dense.prefetched_planes(w, tr)
+                    assert got.f16 and torch.equal(got.buf, ref[(i, tr)])
+                    assert torch.equal(dense.gemm_x6_planes(w, tr).buf, ref[(i, tr)])   # (the builder is pure: the same bytes again)
+            assert not dense._step_planes                          # handed out once ...
+            for w in ws:
+                for tr in (False, True):
+                    assert dense.prefetched_planes(w, tr) is None  # ... a second request builds on demand
+        assert dense._step_planes is None
+        with dense.prefetch_wide_planes(ws, with_transposed=False):
+            assert len(dense._step_planes) == 3
+            assert dense.prefetched_planes(ws[0].clone(), False) is None       # equal contents, another object
+            ws[0].mul_(2.0)                                        # version bump: the prebuilt image of ws[0] must not be served
+            assert dense.prefetched_planes(ws[0], False) is None
+            fresh = dense.gemm_x6_planes(ws[0], False)
+            assert not torch.equal(fresh.buf, ref[(0, False)])
+            # another model's forward inside gets a scope of its own, and this one is put back behind it
+            with dense.prefetch_wide_planes([ws[2]], with_transposed=True):
+                assert len(dense._step_planes) == 2 and dense.prefetched_planes(ws[1], False) is None
+            assert len(dense._step_planes) == 2
+            assert torch.equal(dense.prefetched_planes(ws[1], False).buf, ref[(1, False)])
+        assert dense._step_planes is None
+        # an image left unconsumed is served to NOBODY once the scope has exited -- not to the tensor it was built for (which may have
+        # been rewritten through .data since), not to another tensor that comes to live at the same address (a dead model's weight
+        # freed, a new model's allocated in its place: the hypothesis sweep of test_gpu_random_shapes.py found exactly that)
         w_old = torch.randn(256, 256, generator=g).to(device)
-        dense.prefetch_wide_planes([w_old], with_transposed=False)
-        addr = w_old.data_ptr()
+        with pytest.raises(ZeroDivisionError):
+            with dense.prefetch_wide_planes([w_old] + ws, with_transposed=True):
+                assert len(dense._step_planes) == 8
+                1 / 0
+        assert dense._step_planes is None
+        w_old.data.uniform_(-1.0, 1.0)                             # (no version counter moves)
+        on_demand_is_its_own_build(w_old)
         del w_old
-        w_new = torch.randn(256, 256, generator=g).to(device)             # (the store keeps w_old alive, so this is another block ...)
-        assert w_new.data_ptr() != addr
-        assert torch.equal(dense.gemm_x6_planes(w_new, False).buf, dense.gemm_x6_planes(w_new, False, f16=True).buf)
-        dense.prefetch_wide_planes([], with_transposed=False)             # (... until the next prefetch drops it)
-        assert not dense._PlaneStore.entries
+        w_new = torch.randn(256, 256, generator=g).to(device)      # (nothing keeps w_old alive: usually the same block)
+        for w in [w_new] + ws:
+            on_demand_is_its_own_build(w)
         with dense.arithmetic("strict"):
-            dense.prefetch_wide_planes(ws, with_transposed=True)   # the exact-split arithmetic builds its bf16 planes where they are used
-            assert not dense._PlaneStore.entries
+            with dense.prefetch_wide_planes(ws, with_transposed=True):   # the exact-split arithmetic builds its bf16 planes where they are used
+                assert dense._step_planes is None
+                assert all(dense.prefetched_planes(w, tr) is None for w in ws for tr in (False, True))
+
+
+def test_wide_linear_after_a_forward_without_backward_and_a_data_write_uses_fresh_planes(device):
+    """A grad-enabled ``model(data)`` with no backward used to leave the W^T plane images of its prefetch behind; ``weight.data.
+    uniform_()`` (the reference's ``glorot``, layers.py:31-34) moves no version counter, so a later layer-level forward + backward of
+    that Linear's MLP computed ``grad_x`` against the OLD W^T.  Images now end with the forward that built them: output, ``grad_x`` and
+    every parameter gradient against the float64 torch composition."""
+    import cases
+    from types import SimpleNamespace
+    from allset_amd import SetGNN, dense
+    case = cases.build_case("wide256_pma_h4")
+    torch.manual_seed(11)
+    with dense.arithmetic("auto"):
+        model = SetGNN(case["args"]).to(device).eval()
+        model.reset_parameters()
+        data = SimpleNamespace(x=torch.from_numpy(case["x"]).to(device), edge_index=torch.from_numpy(case["edge_index"]).clone().to(device),
+                               norm=torch.from_numpy(case["norm"]).to(device))
+        model(data)                                                # grad enabled, no backward
+        rff = model.E2VConvs[0].prop.rFF                           # Linear(256, 256) -> relu -> Linear(256, 256), no normalisation
+        assert all(tuple(lin.weight.shape) == (256, 256) and dense.wide_linear_supported(256, 256, False) for lin in rff.lins)
+        assert all(isinstance(nm, torch.nn.Identity) for nm in rff.normalizations)
+        s = 1.0 / 16
+        rff.lins[0].weight.data.uniform_(-s, s)
+        x = torch.randn(50, 256, generator=torch.Generator().manual_seed(12)).to(device).requires_grad_(True)
+        G = torch.randn(50, 256, generator=torch.Generator().manual_seed(13)).to(device)
+        model.zero_grad()
+        y = rff(x)
+        (y * G).sum().backward()
+    xd = x.detach().double().requires_grad_(True)
+    prm = [(lin.weight.detach().double().requires_grad_(True), lin.bias.detach().double().requires_grad_(True)) for lin in rff.lins]
+    yd = xd
+    for i, (w, b) in enumerate(prm):
+        yd = torch.nn.functional.linear(torch.relu(yd) if i > 0 else yd, w, b)
+    (yd * G.double()).sum().backward()
+    pairs = [("y", y.detach(), yd.detach()), ("grad_x", x.grad, xd.grad)]
+    for i, (lin, (w, b)) in enumerate(zip(rff.lins, prm)):
+        pairs += [(f"gW{i}", lin.weight.grad, w.grad), (f"gb{i}", lin.bias.grad, b.grad)]
+    for what, got, exp in pairs:
+        print(what, float((got.double() - exp).abs().max()), float(exp.abs().max()))
+        torch.testing.assert_close(got.double(), exp, rtol=1e-4, atol=1e-4 * float(exp.abs().max()), msg=lambda m, what=what: f"{what}: {m}")
 
 
 @pytest.mark.parametrize("n,O,I", [(300, 256, 256), (4391, 512, 512), (129, 384, 256), (1, 128, 512), (3327, 512, 260)])

@@ -257,6 +257,77 @@ def test_sparse_rows_cache_follows_the_tensor(device):
     dense_again[rows, b.col.long()] = b.val
     assert torch.equal(dense_again, x)
     assert torch.equal(b.val[b.posT.long()], x[b.rowT.long(), torch.repeat_interleave(torch.arange(500, device=device), (b.colptr[1:] - b.colptr[:-1]).long())])
+    twin = x.clone()                                        # equal contents, another tensor object: a structure of its own
+    c = dense.sparse_rows(twin)
+    assert c is not None and c is not b and c.nnz == b.nnz and dense.sparse_rows(x) is b
+    import gc
+    import weakref
+    w = weakref.ref(b)
+    del a, b, x                                             # the structure lives on its tensor and nowhere else
+    gc.collect()
+    assert w() is None and dense.sparse_rows(twin) is c
+
+
+def _sparse_feature_data(device, seed):
+    """200 vertices with 500 bag-of-words features (2 % non-zero), 40 hyperedges; AllDeepSets with a LayerNorm on the input."""
+    import cases
+    from types import SimpleNamespace
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.rand(200, 500, generator=g) < 0.02).float()
+    pairs = sorted({(int(v), int(e)) for v, e in zip(torch.randint(0, 200, (900,), generator=g), torch.randint(0, 40, (900,), generator=g))}
+                   | {(v, v % 40) for v in range(200)})
+    ei = torch.tensor(pairs, dtype=torch.int64).t().contiguous()
+    ei = torch.stack([ei[0], ei[1] + 200])
+    data = SimpleNamespace(x=x.to(device), edge_index=ei.to(device), norm=torch.ones(ei.shape[1], device=device))
+    return data, cases.make_args("ds_add", 500, 64, 5, All_num_layers=1, Classifier_hidden=64)
+
+
+def test_a_graph_keeps_the_structures_it_captured_alive(device, monkeypatch):
+    """``GraphedForward(..., constant_features=True)`` on sparse features replays kernels that read the features' ``SparseRows`` and the
+    incidence CSRs of ITS data.  Both live on the data's tensors (which the graph holds) and the graph holds the ``SparseRows`` itself:
+    an eager forward of the same model on other data in between frees neither, and the next replay is bit-identical."""
+    from allset_amd import SetGNN, dense
+    from allset_amd.graphs import GraphedForward
+    data_a, args = _sparse_feature_data(device, 1)
+    data_b, _ = _sparse_feature_data(device, 2)
+    torch.manual_seed(7)
+    model = SetGNN(args).to(device).eval()
+    model.reset_parameters()
+    taken = []
+    real_apply = dense._SparseInputNormLinear.apply
+    monkeypatch.setattr(dense._SparseInputNormLinear, "apply", staticmethod(lambda *a: taken.append(1) or real_apply(*a)))
+    gf = GraphedForward(model, data_a, constant_features=True)
+    assert taken and gf._sp is not None and gf._sp is dense.sparse_rows(data_a.x)          # the capture read the non-zeros
+    first = gf().clone()
+    with torch.no_grad(), dense.constant_features():
+        eager_a = model(data_a)
+        other = model(data_b)                                   # other data: new incidences, a new SparseRows
+    assert torch.equal(eager_a, first) and not torch.equal(other, first)
+    torch.cuda.synchronize()
+    assert torch.equal(gf(), first)
+
+
+def test_a_graph_refuses_to_replay_over_features_updated_in_place(device, monkeypatch):
+    """After ``data.x[0, 0] = 5.0`` the ``SparseRows`` the capture read describes the old features (and the tensor has dropped it):
+    ``gf()`` raises before anything is replayed.  A capture that took the dense kernels is not concerned."""
+    from allset_amd import SetGNN
+    from allset_amd._lib import AllSetHipError
+    from allset_amd.graphs import GraphedForward
+    data, args = _sparse_feature_data(device, 1)
+    torch.manual_seed(7)
+    model = SetGNN(args).to(device).eval()
+    model.reset_parameters()
+    gf = GraphedForward(model, data, constant_features=True)
+    gd = GraphedForward(model, data)
+    assert gf._sp is not None and gd._sp is None
+    gf(), gd()
+    replays = []
+    monkeypatch.setattr(gf.graph, "replay", lambda: replays.append(1))
+    data.x[0, 0] = 5.0
+    with pytest.raises(AllSetHipError):
+        gf()
+    assert not replays
+    gd()                                                        # reads data.x itself
 
 
 @pytest.mark.parametrize("n,d,O,H", [(3312, 3703, 128, 4), (300, 1433, 64, 4), (517, 3703, 128, 1), (64, 300, 64, 3), (1, 256, 128, 4),

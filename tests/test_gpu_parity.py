@@ -90,7 +90,7 @@ def test_learnmask_eval_follows_importance_between_no_grad_forwards(device):
 
 def test_incidence_cache_rebuilds_for_a_new_graph_at_a_recycled_address(device):
     """A second hypergraph with the same number of incidences whose edge_index lands at the freed address of the first
-    must not be aggregated over the first one's CSR (SetGNN._inc_cache / cached_incidence keep a weakref)."""
+    must not be aggregated over the first one's CSR (the pair lives on the edge_index object it was built from: allset_amd._memo)."""
     from types import SimpleNamespace
     from allset_amd import SetGNN
     from oracle import allset_oracle as oracle
