@@ -395,27 +395,54 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
         // v > 0 ballots of the activation mask above.  The 16 lanes of a DPP row hold the row; lane c's columns 64 hb + 4 c .. + 3 are
         // nibble c % 8 of mask dword 2 hb + c / 8: an OR over the 8 lanes of a half row gives that dword (`own`), a row mirror the
         // half row's other dword (`oth`).  Position of an element = 4 + occupied columns below it.
-        uint32_t u[2][4], own[2], oth[2];
+        uint32_t u[2][4], own[2] = {0u, 0u}, oth[2] = {0u, 0u};
+        int pos[2], kocc;
         const uint32_t sh = 4u * (c & 7);
+        const bool hi = c >= 8;
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb) {
           u[hb][0] = __float_as_uint(vv[hb].x); u[hb][1] = __float_as_uint(vv[hb].y);
           u[hb][2] = __float_as_uint(vv[hb].z); u[hb][3] = __float_as_uint(vv[hb].w);
-          const uint32_t nib = (u[hb][0] != 0u ? 1u : 0u) | (u[hb][1] != 0u ? 2u : 0u) | (u[hb][2] != 0u ? 4u : 0u) | (u[hb][3] != 0u ? 8u : 0u);
-          float mw = __uint_as_float(nib << sh);                  // (dpp_row moves bits; nothing is computed on the float)
-          mw = __uint_as_float(__float_as_uint(mw) | __float_as_uint(dpp_row<0xB1>(mw)));
-          mw = __uint_as_float(__float_as_uint(mw) | __float_as_uint(dpp_row<0x4E>(mw)));
-          mw = __uint_as_float(__float_as_uint(mw) | __float_as_uint(dpp_row<0x141>(mw)));
-          own[hb] = __float_as_uint(mw);
-          oth[hb] = __float_as_uint(dpp_row<0x140>(mw));
         }
-        const bool hi = c >= 8;
-        const uint32_t below = (1u << sh) - 1u;
-        const int cnt0 = __popc(own[0]) + __popc(oth[0]);
-        const int kocc = cnt0 + __popc(own[1]) + __popc(oth[1]);       // the row's occupied columns: uniform over its 16 lanes
-        int pos[2];
-        pos[0] = 4 + (hi ? __popc(oth[0]) : 0) + __popc(own[0] & below);
-        pos[1] = 4 + cnt0 + (hi ? __popc(oth[1]) : 0) + __popc(own[1] & below);
+        if constexpr (XM == 4) {
+          // Cell rows carry no mask, only ranks: the lane's counts of the two half rows ride in one register (at most 64 each: a byte
+          // apiece) through one inclusive scan over the DPP row (row_shr 1, 2, 4, 8; a lane the shift leaves without a source adds 0)
+          // and one butterfly sum for the totals -- 8 DPP adds where the two masks take 8 DPP moves, 6 popcounts and the nibbles.
+          int n2[2];
+#pragma unroll
+          for (int hb = 0; hb < 2; ++hb)
+            n2[hb] = ((u[hb][0] != 0u ? 1 : 0) + (u[hb][1] != 0u ? 1 : 0)) + ((u[hb][2] != 0u ? 1 : 0) + (u[hb][3] != 0u ? 1 : 0));
+          const int pk = n2[0] | (n2[1] << 8);
+          int inc = pk, tot = pk;
+          inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);
+          inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);
+          inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);
+          inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, true);
+          tot += __builtin_amdgcn_update_dpp(0, tot, 0xB1, 0xf, 0xf, false);
+          tot += __builtin_amdgcn_update_dpp(0, tot, 0x4E, 0xf, 0xf, false);
+          tot += __builtin_amdgcn_update_dpp(0, tot, 0x141, 0xf, 0xf, false);
+          tot += __builtin_amdgcn_update_dpp(0, tot, 0x140, 0xf, 0xf, false);
+          const int exc = inc - pk, cnt0 = tot & 0xff;
+          kocc = cnt0 + (tot >> 8);
+          pos[0] = 4 + (exc & 0xff);
+          pos[1] = 4 + cnt0 + (exc >> 8);
+        } else {
+#pragma unroll
+          for (int hb = 0; hb < 2; ++hb) {
+            const uint32_t nib = (u[hb][0] != 0u ? 1u : 0u) | (u[hb][1] != 0u ? 2u : 0u) | (u[hb][2] != 0u ? 4u : 0u) | (u[hb][3] != 0u ? 8u : 0u);
+            float mw = __uint_as_float(nib << sh);                  // (dpp_row moves bits; nothing is computed on the float)
+            mw = __uint_as_float(__float_as_uint(mw) | __float_as_uint(dpp_row<0xB1>(mw)));
+            mw = __uint_as_float(__float_as_uint(mw) | __float_as_uint(dpp_row<0x4E>(mw)));
+            mw = __uint_as_float(__float_as_uint(mw) | __float_as_uint(dpp_row<0x141>(mw)));
+            own[hb] = __float_as_uint(mw);
+            oth[hb] = __float_as_uint(dpp_row<0x140>(mw));
+          }
+          const uint32_t below = (1u << sh) - 1u;
+          const int cnt0 = __popc(own[0]) + __popc(oth[0]);
+          kocc = cnt0 + __popc(own[1]) + __popc(oth[1]);               // the row's occupied columns: uniform over its 16 lanes
+          pos[0] = 4 + (hi ? __popc(oth[0]) : 0) + __popc(own[0] & below);
+          pos[1] = 4 + cnt0 + (hi ? __popc(oth[1]) : 0) + __popc(own[1] & below);
+        }
         // The image of the wave's four rows is built in LDS IN PLACE of their rows of ytile[k % 2]: this wave alone reads those rows
         // (every lane of it has them in vv by now -- a wave's LDS operations are served in issue order, the fence keeps the compiler
         // from moving one across), the matrix waves write the OTHER tile during this tick and this one only after the tick's barrier,
@@ -425,21 +452,27 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if constexpr (XM == 4) {
-          // Cell rows.  In issue order: (1) lane c writes cell c empty -- value bits 0, its dummy column 128 + c in the three column
-          // bytes, k in the fourth --; (2) the element of rank j = pos - 4 goes to dword 4 (j % 16) + j / 16 and its column to byte
-          // 16 (j % 16) + 12 + j / 16; an empty column and a rank >= kCellCap go to the last dword of the tile row, which never leaves.
-          *reinterpret_cast<uint4*>(im + 4 * c) = make_uint4(0u, 0u, 0u, (128u + c) * 0x010101u | (static_cast<uint32_t>(kocc) << 24));
-          uint8_t* imb = reinterpret_cast<uint8_t*>(im);
+          // Cell rows, staged IN RANK ORDER: the element of rank j = pos - 4 goes to dword j of the tile row and its column to dword
+          // 64 + j (one running position per half row, as in mode 3; the two stores share an address register).  Nobody reads dwords
+          // kCellCap .. kCellCap + 3 or their twins 64 above: an empty column goes to the first of them, and a half row's running
+          // position starts at most there (one clamp per half row, not per element), so a rank >= kCellCap lands among the four.
+          // In issue order: (1) lane c writes its own three slots -- ranks c, 16 + c, 32 + c -- empty: value bits 0, dummy column
+          // 128 + c; (2) the elements.  Lane c then builds cell c in registers from those six dwords (below): nothing is scattered
+          // into a cell image and none is read back.
+          static_assert(kCellCap == 48 && kCellCap + 3 < 64 && 64 + kCellCap + 3 < SPY, "three slots per cell; the staged columns sit 64 dwords above the values");
+          const uint32_t dcol = 128u + c;
+#pragma unroll
+          for (int s = 0; s < 3; ++s) { im[16 * s + c] = 0u; im[64 + 16 * s + c] = dcol; }
 #pragma unroll
           for (int hb = 0; hb < 2; ++hb) {
-            int j = pos[hb] - 4;
+            int j = min(pos[hb] - 4, kCellCap);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-              const bool put = u[hb][i] != 0u && j < kCellCap;
-              const int cl = 16 * (j & 15), sl = j >> 4;
-              *reinterpret_cast<uint32_t*>(imb + (put ? cl + 4 * sl : 4 * (SPY - 1))) = u[hb][i];
-              imb[put ? cl + 12 + sl : 4 * (SPY - 1)] = static_cast<uint8_t>(64 * hb + 4 * c + i);
-              j += u[hb][i] != 0u ? 1 : 0;
+              const bool occ = u[hb][i] != 0u;
+              const int at = occ ? j : kCellCap;
+              im[at] = u[hb][i];
+              im[64 + at] = static_cast<uint32_t>(64 * hb + 4 * c + i);
+              j += occ ? 1 : 0;
             }
           }
         } else {
@@ -460,8 +493,13 @@ __global__ __launch_bounds__(kF2Block) void fused_linear_fwd_roles_kernel(
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        // lane c takes dwords 4 c .. 4 c + 3 of its own row's image; the wave's four rows are 1 KB contiguous: one 16-byte store per lane
-        const uint4 o = *reinterpret_cast<const uint4*>(im + 4 * c);
+        // lane c takes dwords 4 c .. 4 c + 3 of its own row's image (cell rows: cell c = its three staged values, then their columns
+        // as bytes with k on top); the wave's four rows are 1 KB contiguous: one 16-byte store per lane
+        uint4 o;
+        if constexpr (XM == 4)
+          o = make_uint4(im[c], im[16 + c], im[32 + c], (im[64 + c] | (im[80 + c] << 8)) | ((im[96 + c] | (static_cast<uint32_t>(kocc) << 8)) << 16));
+        else
+          o = *reinterpret_cast<const uint4*>(im + 4 * c);
         if (live) *reinterpret_cast<uint4*>(reinterpret_cast<uint32_t*>(uo) + (stage * R + lr) * kPackPitchDw + 4 * c) = o;
         if (live && kocc > (XM == 4 ? kCellCap : kPackCap)) {              // row-uniform, rare: the row did not fit -- the gather reads it from the side table
           *reinterpret_cast<float4*>(yb + yo) = vv[0];

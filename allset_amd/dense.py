@@ -1246,11 +1246,14 @@ class _FusedNormLinearPacked(torch.autograd.Function):
         ctx.layout = (0, 0)
         ctx.params = (gamma, beta, weight, bias)
         ctx.mark_non_differentiable(packed)
+        ctx.set_materialize_grads(False)     # (packed never carries a gradient: no int32 [n, 64] zero-fill for it in every backward)
         return side, packed
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy, _g_packed=None):
+        if gy is None:                       # nothing downstream used the rows
+            return (None,) * 11
         return _FusedNormLinear.backward(ctx, gy)[:10] + (None,)
 
 
@@ -1308,11 +1311,14 @@ class _WideNormLinear(torch.autograd.Function):
         if emit is None:
             return y
         ctx.mark_non_differentiable(stats_y)
+        ctx.set_materialize_grads(False)     # (stats_y never carries a gradient: no [n, 2] zero-fill for it in every backward)
         return y, stats_y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy, _g_stats=None):
+        if gy is None:                       # nothing downstream used y
+            return (None,) * 12
         x, stats, gamma, beta, weight, y, mask = ctx.saved_tensors
         relu_in, p_in, seed_in, p_out, has_bias, base = ctx.cfg
         if x.shape[0] == 0:                     # no rows: every gradient is zero (empty tensors carry no row statistics)
@@ -2579,6 +2585,7 @@ class _SyncBatchNorm(torch.autograd.Function):
         y = xhat * weight.float() + bias.float() if weight is not None else xhat
         ctx.save_for_backward(xhat, weight, rstd, count)
         ctx.cfg = (int(valid), group, bias is not None)
+        # (gradients stay materialised: the backward all-reduces, so a rank whose y went unused must still take part, with zeros)
         ctx.mark_non_differentiable(mean, var, count)
         return y.to(x.dtype), mean, var, count
 
@@ -2700,11 +2707,14 @@ class _BatchNormLinear(torch.autograd.Function):
         ctx.save_for_backward(x, stats, a, b, weight, mask, mean, rstd, bn_weight)
         ctx.cfg = (bool(relu_in), float(p_in), seed_in, float(p_out), base, keep_y)
         ctx.mark_non_differentiable(mean, var)
+        ctx.set_materialize_grads(False)     # (mean, var never carry a gradient: no [d] zero-fills for them in every backward)
         return y, mean, var
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, gy, _gm, _gv):
+    def backward(ctx, gy, _gm=None, _gv=None):
+        if gy is None:                       # nothing downstream used y
+            return (None,) * 10
         x, stats, a, b, weight, mask, mean, rstd, bn_weight = ctx.saved_tensors
         relu_in, p_in, seed_in, p_out, base, keep_y = ctx.cfg
         if keep_y and mask is None:
