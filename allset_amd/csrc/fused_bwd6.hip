@@ -46,10 +46,16 @@ constexpr int kSVWaves = 8;
 constexpr int kSTop = 13;                      // a scaled row's largest element lies in [2^13, 2^14)
 constexpr int kSEMin = 20;                     // floor of the biased row exponent (rows below 2^-107 are treated as that small)
 
-// max(|a.x|, |a.y|, |a.z|, |a.w|, m) in plain fmaxf / fabsf (wgrad_f16.hip wf_amax4 is the v_max3_f32 asm form)
+// max(|a.x|, |a.y|, |a.z|, |a.w|, m): two v_max3_f32 with |x| source modifiers (the form of wgrad_f16.hip wf_amax4; plain fmaxf /
+// fabsf compiled to four v_max_f32).  A maximum is exact, so the result is the same number.
 __device__ __forceinline__ float amax4(float4 a, float m) {
-  return fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))), m);
+  asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a.x), "v"(a.y));
+  asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a.z), "v"(a.w));
+  return m;
 }
+// Compile-time switch of the vector role's stage code: Full = the stage is known to hold all its rows and its addresses come from the
+// running scalars (the main trips); otherwise the stage may be partial or past the end and everything is rebuilt from k (the edges).
+template <bool B> struct StageTag { static constexpr bool full = B; };
 // 2^(field - 127) for a biased exponent field in [0, 254] (0 -> 0.0), no branch (wgrad_f16.hip wf_pow2 also maps fields < 0 to 0.0)
 __device__ __forceinline__ float pow2_field(int field) { return __uint_as_float(static_cast<uint32_t>(field) << 23); }
 #ifdef ALLSET_ABL6_NOBAR            // ablation builds only (tools/bwd_f16x3_ablation.py): timing without the barriers, results wrong
@@ -241,16 +247,68 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
         ml[1] = make_float2(pma_m[row * pma_heads + pt_h1], pma_l[row * pma_heads + pt_h1]);
       }
     };
+    // ---- The main trips' addressing (no PT / PT2).  A vector wave pays for every instruction of its stream, scalar ones included
+    // (DESIGN.md 6.3), and the stage's address is data-independent: stage k of the workgroup lies gridDim.x * R rows behind stage
+    // k - 1.  So each operand has ONE 64-bit scalar base that one add per stage advances by a launch constant, and ONE 32-bit lane
+    // offset (row of the stage x leading dimension + the layout's column offset) computed here, before the loop.  Only a
+    // workgroup's last stage can be partial (and only in the workgroup that owns the globally last one): the main trips cover full
+    // stages alone -- no rows_left, no row clamp, no valid / live select, no store predicate -- and the edges (the first S0, the
+    // last three to five stages) run the general code above and below.  Requests run two stages ahead of S0 / S2a, so the main trips
+    // end where their last request is for the workgroup's last FULL stage: no request of theirs needs a clamp or a zero stride.
+    constexpr bool FAST = !PT && !PT2;
+    const bool hasP = (n % R) != 0 && stage_of(T - 1) == n_stages - 1;
+    const int Tf = __builtin_amdgcn_readfirstlane(static_cast<int>(T) - (hasP ? 1 : 0));        // this workgroup's full stages (a scalar: the loop's compare stays off the vector pipe)
+    const uint32_t og = static_cast<uint32_t>(lr) * static_cast<uint32_t>(ldg) * 4u + cog0;
+    const uint32_t ox = static_cast<uint32_t>(lr) * static_cast<uint32_t>(ldx) * 4u + cox0;
+    const uint32_t ogx = static_cast<uint32_t>(lr) * static_cast<uint32_t>(ldgx) * 4u + cogx0;
+    const uint32_t oacc = static_cast<uint32_t>(lr) * static_cast<uint32_t>(ldacc) * 4u + 16u * c;
+    const uint32_t om = static_cast<uint32_t>((((lr >> 4) * (OD / 64)) * 32 + ((lr & 15) >> 2) * 8 + (lr & 3) * 2 + (c >> 3)) * 4);
+    const uint32_t ost = static_cast<uint32_t>(lr) * 8u;
+    const int64_t gstep = static_cast<int64_t>(gridDim.x) * R;      // rows between two stages of the workgroup
+    const int64_t stride_g = gstep * ldg * 4, stride_x = gstep * ldx * 4, stride_gx = gstep * ldgx * 4, stride_acc = gstep * ldacc * 4;
+    const int64_t stride_m = gstep * (OD / 32) * 4, stride_st = gstep * 8;        // mask: 4 dwords per row; stats: 2 floats per row
+    // request side: the base of the main trips' FIRST request.  Before them stages 0 and 1 are requested and the first S0 has asked
+    // for gy of stage 2: S0(1) asks for gy of the workgroup's stage 3, S2a(0) for x of stage 2
+    const char* gyq = reinterpret_cast<const char*>(gy) + (stage_of(0) * R * ldg * 4 + 3 * stride_g);
+    const char* mq = reinterpret_cast<const char*>(mask) + (stage_of(0) * R * (OD / 32) * 4 + 3 * stride_m);
+    const char* xq = reinterpret_cast<const char*>(x) + (stage_of(0) * R * ldx * 4 + 2 * stride_x);
+    const char* stq = reinterpret_cast<const char*>(stats) + (stage_of(0) * R * 8 + 2 * stride_st);
+    // consumer side: stage k itself, from stage 0 of the workgroup on
+    char* gxp = reinterpret_cast<char*>(gx) + stage_of(0) * R * ldgx * 4;
+    const char* accp = reinterpret_cast<const char*>(acc_in) + stage_of(0) * R * ldacc * 4;
+    uint64_t squad = static_cast<uint64_t>(stage_of(0)) * (R * ID / 4);       // the hash's quad index of the stage's first element
+    const uint64_t stride_q = static_cast<uint64_t>(gridDim.x) * (R * ID / 4);
+    // (the lane offset passes through an empty asm at its use: hoisted out of the loop as a 64-bit pair, the load loses its
+    // scalar-base + 32-bit-offset form and pays a 64-bit vector add per request)
+    auto here = [](uint32_t o) -> uint32_t { __asm__ volatile("" : "+v"(o)); return o; };
+    auto request_gy_full = [&](float4 (&ag)[2], uint32_t (&am)[2]) {        // called from S0(k): the request for stage k + 2
+#pragma unroll
+      for (int hb = 0; hb < 2; ++hb) {
+        ag[hb] = *reinterpret_cast<const float4*>(gyq + hb * dhg + here(og));
+        if constexpr (HAS_MASK) am[hb] = *reinterpret_cast<const uint32_t*>(mq + hb * 128 + here(om));
+      }
+      gyq += stride_g;
+      if constexpr (HAS_MASK) mq += stride_m;
+    };
+    auto request_x_full = [&](float4 (&xr)[2], float2& st) {               // called from S2a(k): the request for stage k + 2
+#pragma unroll
+      for (int hb = 0; hb < 2; ++hb) xr[hb] = *reinterpret_cast<const float4*>(xq + hb * dhx + here(ox));
+      if constexpr (HAS_LN) st = *reinterpret_cast<const float2*>(stq + here(ost));
+      xq += stride_x;
+      if constexpr (HAS_LN) stq += stride_st;
+    };
     int eNext = kSEMin, eCur = kSEMin;            // biased row exponent of ga: stage k + 1 (written by S0), stage k (read by S2b)
     int Erun = 2 * kSEMin;                        // the largest q_r over the stages up to the one S2b is working on
     int quK = kSEMin;                             // eu_r of stage k (S2a -> S2b)
     // ---- S0(k): ga = gy under the forward's epilogue mask, scaled to the row's window, two fp16 planes into ga[k % 3]
     const float keep2 = (PT2 && p2 > 0.f) ? 1.f / (1.f - p2) : 1.f;
     const uint32_t thr2 = drop_threshold(p2);
-    auto S0 = [&](int64_t k, float4 (&ag)[2], uint32_t (&am)[2], float4 (&sg)[2], float2& st2) {
-      const int nrows = rows_left(stage_of(k));
-      const bool valid = lr < nrows;
-      uint8_t* img = sGA + (k % 3) * IMG;
+    // (tag: StageTag<true> in the main trips -- see "the main trips' addressing" above; b3 = k % 3, the ga image the stage goes to)
+    auto S0 = [&](auto tag, int64_t k, int b3, float4 (&ag)[2], uint32_t (&am)[2], float4 (&sg)[2], float2& st2) {
+      constexpr bool FULL = decltype(tag)::full;
+      static_assert(!FULL || FAST, "the full-stage path is not built for PT / PT2");
+      const bool valid = FULL ? true : lr < rows_left(stage_of(k));
+      uint8_t* img = sGA + b3 * IMG;
       float4 v[2];
       float amax = 0.f;
       if constexpr (PT2) {
@@ -342,7 +400,8 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
         *reinterpret_cast<uint2*>(img + 1 * PLANE + wo) = make_uint2(l0, l1);
       }
       __builtin_amdgcn_sched_barrier(0);
-      request_gy(k + 2, ag, am);                  // into the set just consumed: two stages ahead
+      if constexpr (FULL) request_gy_full(ag, am);
+      else request_gy(k + 2, ag, am);             // into the set just consumed: two stages ahead
       request_s2(k + 2, sg, st2);
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -352,13 +411,15 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
     uint32_t xbK = 0;          // "raw x > 0" flags, bit 4 hb + q
     float rstdK = 1.f, meanK = 0.f;
     float4 grK[2]; float2 mlK[2];                    // PT: the residual branch's row / the softmax statistics of stage k (S2a -> S2b)
-    auto S2a = [&](int64_t k, float4 (&xr)[2], float2& st) {
+    auto S2a = [&](auto tag, int64_t k, float4 (&xr)[2], float2& st) {
+      constexpr bool FULL = decltype(tag)::full;
       request_gres(k, grK); request_ml(k, mlK);       // (PT; no-ops otherwise)
-      const int64_t stage = stage_of(k);
-      const uint64_t stage_pair = static_cast<uint64_t>(stage) * (R * ID / 2);
+      // the hash's index of the stage's first element: stage * 1024 quads = stage * 2048 pairs (FULL: the running value, the same number)
+      uint64_t stage_quad, stage_pair;
+      if constexpr (FULL) { stage_quad = squad; stage_pair = squad << 1; if constexpr (DROP_IN) squad += stride_q; }
+      else { stage_quad = static_cast<uint64_t>(stage_of(k)) * (R * ID / 4); stage_pair = static_cast<uint64_t>(stage_of(k)) * (R * ID / 2); }
       const uint32_t stage_pair_lo = static_cast<uint32_t>(stage_pair);
       const uint32_t hi_term = __umul24(static_cast<uint32_t>(stage_pair >> 32), 0x5EBCA7U) + static_cast<uint32_t>(seed_in >> 32);
-      const uint64_t stage_quad = static_cast<uint64_t>(stage) * (R * ID / 4);
       const uint32_t stage_quad_lo = static_cast<uint32_t>(stage_quad);
       const uint32_t hi_term_q = __umul24(static_cast<uint32_t>(stage_quad >> 32), 0x5EBCA7U) + static_cast<uint32_t>(seed_in >> 32);
       xbK = 0;
@@ -418,14 +479,16 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
         sE[(k & 3) * kSVWaves + wave] = qw;
       }
       __builtin_amdgcn_sched_barrier(0);
-      request_x(k + 2, xr, st);                   // x is consumed: the request for two stages ahead goes out a tick earlier
+      if constexpr (FULL) request_x_full(xr, st);
+      else request_x(k + 2, xr, st);              // x is consumed: the request for two stages ahead goes out a tick earlier
       __builtin_amdgcn_sched_barrier(0);
     };
     // ---- S2b(k): gu -> LayerNorm backward -> gx; then u, scaled against the workgroup's largest row exponent, into u[k % 2]
-    auto S2b = [&](int64_t k) {
-      const int64_t stage = stage_of(k);
-      const int nrows = rows_left(stage);
-      const bool live = lr < nrows;
+    auto S2b = [&](auto tag, int64_t k, int b2) {         // b2 = k % 2, the u image the stage goes to
+      constexpr bool FULL = decltype(tag)::full;
+      const int64_t stage = FULL ? 0 : stage_of(k);         // (FULL: the running bases stand for it)
+      const int nrows = FULL ? R : rows_left(stage);
+      const bool live = FULL ? true : lr < nrows;
       Erun = max(Erun, stage_emax(k));
       const float inv_sa = pow2_field(eCur - kSTop) * keep_in;  // undoes the row scale of ga (the wave's W scale is undone by S1); x the dropout's 1 / keep
       const int ffield = 267 + eCur - Erun;
@@ -438,9 +501,12 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
       if constexpr (HAS_ACC) {
         const int lrc = min(lr, max(nrows, 1) - 1);
 #pragma unroll
-        for (int hb = 0; hb < 2; ++hb)
-          acc[hb] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(acc_in + stage * R * ldacc) +
-                                                     static_cast<uint32_t>(lrc) * static_cast<uint32_t>(ldacc) * 4u + 256 * hb + 16 * c);
+        for (int hb = 0; hb < 2; ++hb) {
+          if constexpr (FULL) acc[hb] = *reinterpret_cast<const float4*>(accp + 256 * hb + here(oacc));
+          else acc[hb] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(acc_in + stage * R * ldacc) +
+                                                          static_cast<uint32_t>(lrc) * static_cast<uint32_t>(ldacc) * 4u + 256 * hb + 16 * c);
+        }
+        if constexpr (FULL) accp += stride_acc;
       }
 #pragma unroll
       for (int hb = 0; hb < 2; ++hb) {
@@ -470,14 +536,18 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
       const float rstd = rstdK;
       const float ptSd = PT ? 1.f / rstd : 0.f, ptMean = PT ? meanK : 0.f;
       float ptDot[2] = {0.f, 0.f};
-      uint8_t* img = sU + (k % 2) * IMG;
+      uint8_t* img = sU + b2 * IMG;
 #pragma unroll
       for (int hb = 0; hb < 2; ++hb) {
         const float4 xh = xhK[hb];
         float4 o = v[hb];
-        if constexpr (HAS_LN)
-          o = make_float4(rstd * (v[hb].x - s1 - xh.x * s2), rstd * (v[hb].y - s1 - xh.y * s2),
-                          rstd * (v[hb].z - s1 - xh.z * s2), rstd * (v[hb].w - s1 - xh.w * s2));
+        if constexpr (HAS_LN) {
+          // (v = gu gamma, rounded: behind the empty asm the compiler cannot fold that product into "- s1" as an FMA, which it did in
+          // one of the two stage paths and not in the other -- the rows of the two paths must be the same bits)
+          __asm__("" : "+v"(o.x), "+v"(o.y), "+v"(o.z), "+v"(o.w));
+          o = make_float4(rstd * (o.x - s1 - xh.x * s2), rstd * (o.y - s1 - xh.y * s2),
+                          rstd * (o.z - s1 - xh.z * s2), rstd * (o.w - s1 - xh.w * s2));
+        }
         if (RELU_IN) {
           const uint32_t xb = xbK >> (4 * hb);
           o.x = (xb & 1u) ? o.x : 0.f; o.y = (xb & 2u) ? o.y : 0.f; o.z = (xb & 4u) ? o.z : 0.f; o.w = (xb & 8u) ? o.w : 0.f;
@@ -488,8 +558,11 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
 #else
         if (live)
 #endif
-          *reinterpret_cast<float4*>(reinterpret_cast<char*>(gx + stage * R * ldgx) +
-                                     hb * dhgx + (static_cast<uint32_t>(lr) * static_cast<uint32_t>(ldgx) * 4u + cogx0)) = o;
+        {
+          if constexpr (FULL) *reinterpret_cast<float4*>(gxp + hb * dhgx + here(ogx)) = o;
+          else *reinterpret_cast<float4*>(reinterpret_cast<char*>(gx + stage * R * ldgx) +
+                                          hb * dhgx + (static_cast<uint32_t>(lr) * static_cast<uint32_t>(ldgx) * 4u + cogx0)) = o;
+        }
         if constexpr (PT) {
           const float kz = live ? 1.f : 0.f;
           dcv[hb].x = fmaf(o.x, kz, dcv[hb].x); dcv[hb].y = fmaf(o.y, kz, dcv[hb].y); dcv[hb].z = fmaf(o.z, kz, dcv[hb].z); dcv[hb].w = fmaf(o.w, kz, dcv[hb].w);
@@ -531,6 +604,7 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
         if (w1) *reinterpret_cast<float2*>(pma_stats + (row * pma_heads + pt_h1) * 2) =
             make_float2(mlK[1].y > 0.f ? mlK[1].x + __logf(mlK[1].y + 1e-16f) : 3.402823466e+38f, d1);
       }
+      if constexpr (FULL) gxp += stride_gx;
       eCur = eNext;                               // S0(k + 1) ran in the previous tick
     };
 
@@ -540,37 +614,68 @@ __global__ __launch_bounds__(kSBlock) void fused_linear_bwd_f16x3_kernel(
     request_gy(1, agS[1], amS[1]);
     request_s2(1, sgS[1], s2S[1]);
     request_x(1, xrS[1], stS[1]);
-    S0(0, agS[0], amS[0], sgS[0], s2S[0]);
+    constexpr StageTag<false> edge{};
+    constexpr StageTag<true> full{};
+    S0(edge, 0, 0, agS[0], amS[0], sgS[0], s2S[0]);
     eCur = eNext;
     ALLSET_TICK();
     // Two stages per trip: stage k lives in register set 0, stage k + 1 in set 1; no conditional half inside the trip (fused_bwd4.hip:
     // the compiler's s_waitcnt insertion); an odd last stage is peeled off.
     int64_t k = 0;
     ALLSET_MARK(3);
+    if constexpr (FAST) {
+      // The main trips: every stage they touch (k, k + 1, the S0 of k + 2, the requests up to k + 4) is full, and both halves are
+      // the same code.
+      int kf = 0, b3 = 1;                   // b3 = (kf + 1) % 3 without the division
+      for (; kf + 4 < Tf; kf += 2) {
+        S0(full, kf + 1, b3, agS[1], amS[1], sgS[1], s2S[1]);
+        S2a(full, kf, xrS[0], stS[0]);
+        ALLSET_MARK(0);
+        ALLSET_TICK();
+        ALLSET_MARK(1);
+        S2b(full, kf, 0);
+        ALLSET_MARK(2);
+        ALLSET_TICK();
+        ALLSET_MARK(3);
+        b3 = b3 == 2 ? 0 : b3 + 1;
+        S0(full, kf + 2, b3, agS[0], amS[0], sgS[0], s2S[0]);
+        S2a(full, kf + 1, xrS[1], stS[1]);
+        ALLSET_MARK(0);
+        ALLSET_TICK();
+        ALLSET_MARK(1);
+        S2b(full, kf + 1, 1);
+        ALLSET_MARK(2);
+        ALLSET_TICK();
+        ALLSET_MARK(3);
+        b3 = b3 == 2 ? 0 : b3 + 1;
+      }
+      k = kf;
+    }
+    // The edges: the general code, for the stages the main trips left (three to five of them; all stages with PT / PT2)
     for (; k + 1 < T; k += 2) {
-      S0(k + 1, agS[1], amS[1], sgS[1], s2S[1]);
-      S2a(k, xrS[0], stS[0]);
+      S0(edge, k + 1, static_cast<int>((k + 1) % 3), agS[1], amS[1], sgS[1], s2S[1]);
+      S2a(edge, k, xrS[0], stS[0]);
       ALLSET_MARK(0);
       ALLSET_TICK();
       ALLSET_MARK(1);
-      S2b(k);
+      S2b(edge, k, 0);
       ALLSET_MARK(2);
       ALLSET_TICK();
       ALLSET_MARK(3);
-      if (k + 2 < T) S0(k + 2, agS[0], amS[0], sgS[0], s2S[0]);
-      S2a(k + 1, xrS[1], stS[1]);
+      if (k + 2 < T) S0(edge, k + 2, static_cast<int>((k + 2) % 3), agS[0], amS[0], sgS[0], s2S[0]);
+      S2a(edge, k + 1, xrS[1], stS[1]);
       ALLSET_MARK(0);
       ALLSET_TICK();
       ALLSET_MARK(1);
-      S2b(k + 1);
+      S2b(edge, k + 1, 1);
       ALLSET_MARK(2);
       ALLSET_TICK();
       ALLSET_MARK(3);
     }
     if (k < T) {                            // odd stage count: the last stage, in set 0
-      S2a(k, xrS[0], stS[0]);
+      S2a(edge, k, xrS[0], stS[0]);
       ALLSET_TICK();
-      S2b(k);
+      S2b(edge, k, 0);
       ALLSET_TICK();
     }
     ALLSET_TICK();                        // (the matrix waves' last weight-gradient step)

@@ -2,9 +2,11 @@
 """Ablation of fused_linear_bwd_f16x3_kernel (csrc/fused_bwd6.hip; tools/bwd_roles_ablation.py is the same for fused_bwd4.hip): variants without the workgroup barriers (results wrong,
 timing only), without the MFMAs, without the gx stores, with per-segment cycle counters, each timed at [1M,128] x [128,128].
 Run on the GPU box: python tools/bwd_f16x3_ablation.py [--light] [--only <substring>] [-DFLAG ...]
+ALLSET_ABL_SO_DIR=<dir>: where the variants' libraries go (default /tmp); with ALLSET_ABL_REUSE=1 a library already there is loaded as it
+is, so that the variants can be compiled ahead of the run (the name is bwdf16x3_<variant name, non-word characters as _>.so).
 (the comparison arms of rounds 2-3 -- the pair / stage / three-waves kernels and their ablation scripts -- live in
 the git history before round 5, tools/micro/retired/, as they were when they lost their A/B; the library no longer builds them.)"""
-import ctypes, os, statistics, subprocess, sys
+import ctypes, os, re, statistics, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
@@ -29,8 +31,9 @@ if "--only" in sys.argv:
     key = sys.argv[sys.argv.index("--only") + 1]
     variants = [v for v in variants if key in v[0]]
 for name, flags in variants:
-    so = f"/tmp/bwdf16x3_{abs(hash(name))}.so"
-    subprocess.run(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950"] + ([] if "-DSLP" in flags else ["-fno-slp-vectorize"]) + ["-shared", "-fPIC",
+    so = os.path.join(os.environ.get("ALLSET_ABL_SO_DIR", "/tmp"), "bwdf16x3_" + re.sub(r"\W+", "_", name) + ".so")
+    if not (os.environ.get("ALLSET_ABL_REUSE") == "1" and os.path.exists(so)):
+      subprocess.run(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950"] + ([] if "-DSLP" in flags else ["-fno-slp-vectorize"]) + ["-shared", "-fPIC",
                     "-I", os.path.join(ROOT, "include"), "-o", so] + flags + src, check=True)
     lib = ctypes.CDLL(so)
     fn = lib.allset_fused_linear_bwd_all
