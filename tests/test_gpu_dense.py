@@ -1449,10 +1449,11 @@ def test_fused_adam_bf16_parameters(device):
                 dc.assert_adam(got, ref, which, True, f"step {step}")
 
 
-@pytest.mark.parametrize("n,C", [(1, 3), (2708, 7), (50000, 40), (300, 67)])
+@pytest.mark.parametrize("n,C", [(1, 3), (2708, 7), (50000, 40), (300, 67), (256 * 256 + 300, 5)])
 def test_split_metrics_match_the_reference_evaluate(n, C, device):
     """allset_split_metrics against the reference's evaluate() (train.py:169-199): eval_acc and NLLLoss(log_softmax) per split,
-    including rows in no split and an exact tie (first maximum wins, as torch.argmax)."""
+    including rows in no split and an exact tie (first maximum wins, as torch.argmax).  The last case is 300 rows past one sweep of
+    the kernel's 256 x 256 threads: the first 300 threads take a second row."""
     from allset_amd.losses import split_ids, split_metrics
     g = torch.Generator().manual_seed(n * 3 + C)
     logits = (3 * torch.randn(n, C, generator=g)).to(device)
