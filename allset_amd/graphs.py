@@ -120,7 +120,8 @@ class GraphedTrainStep:
     Capture needs a few real warm-up steps (allocator, autograd and optimizer state must exist before recording).
     With ``restore=True`` (default) parameters and optimizer state are put back afterwards -- in place, the graph holds
     their addresses -- so the first replay is step 1 of training, not step ``warmup + 1``: state the optimizer created
-    during warm-up is zeroed, which is Adam's initial state.
+    during warm-up is zeroed, which is Adam's initial state (an fp32 master weight of ``FusedAdam(master_weights=True)`` is set to the
+    restored parameter instead).
     """
 
     def __init__(self, model: torch.nn.Module, data, loss_fn: Callable[[Tensor], Tensor],
@@ -172,8 +173,14 @@ class GraphedTrainStep:
                 for p, snap in zip(params, p_snap):
                     p.copy_(snap)
                     for k, v in optimizer.state.get(p, {}).items():
-                        if torch.is_tensor(v):
-                            v.copy_(s_snap[p][k]) if k in s_snap[p] else v.zero_()
+                        if not torch.is_tensor(v):
+                            continue
+                        if k in s_snap[p]:
+                            v.copy_(s_snap[p][k])
+                        elif k == "master":          # FusedAdam(master_weights=True): an fp32 master created during warm-up starts
+                            v.copy_(snap)            # as the parameter it belongs to, not as zero
+                        else:
+                            v.zero_()
                 for b, snap in b_snap:
                     b.copy_(snap)
 

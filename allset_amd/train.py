@@ -21,6 +21,8 @@ preprocessing branch, the ``--UniGNN_*`` flags below, the default one-group Adam
 
     python -m allset_amd.train --method AllSetTransformer --dname synthetic --epochs 50 --runs 2 --heads 4 \\
         --MLP_hidden 128 --All_num_layers 1
+    python -m allset_amd.train --method AllSetTransformer --dtype bf16 --heads 4 --MLP_hidden 128 --dname synthetic \\
+        --epochs 50 --runs 2             # bf16 model, fp32 master weights
     python -m allset_amd.train --method HCHA --dname synthetic --epochs 50 --runs 2      # HGNN: --method HGNN --HCHA_symdegnorm
     python -m allset_amd.train --method HCHA --HCHA_use_attention --heads 2 --dname synthetic --epochs 50 --runs 2
     python -m allset_amd.train --method UniGCNII --dname synthetic --epochs 50 --runs 2 --All_num_layers 4
@@ -465,6 +467,8 @@ def make_optimizer(args, model):
     if args.method in UNIGNN_METHODS:
         return FusedAdam([dict(params=model.reg_params, weight_decay=0.01), dict(params=model.non_reg_params, weight_decay=5e-4)],
                          lr=0.01)
+    if getattr(args, 'dtype', 'fp32') == 'bf16':            # bf16 model: fp32 master weights and moments
+        return FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd, master_weights=True)
     return FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd)
 
 
@@ -536,6 +540,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="the reference's processed file <root>/<dname>/processed/data.pt (or its directory)")
     p.add_argument('--seed', default=None, type=int, help='seed numpy/torch (the reference fixes no seeds, README.md:60)')
     p.add_argument('--res_root', default='hyperparameter_tunning')
+    p.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'],
+                   help='bf16: mixed-precision training -- the model and the features in bfloat16 (the bf16 kernels), fp32 master weights '
+                        'and Adam moments in the optimizer, loss and metrics on fp32 logits (DESIGN.md section 24).  Built for --method '
+                        'AllSetTransformer / AllDeepSets with --normalization ln')
     p.add_argument('--hip_graph', default=-1, type=int, choices=[-1, 0, 1],
                    help='1: capture the training step, the eval forward and the metrics as hipGraphs (allset_amd/graphs.py); '
                         '0: eager launches; -1 (default): graphs where the loop is launch-bound (at most 200k vertices), eager '
@@ -637,6 +645,8 @@ def exclude_self_path(args) -> str:
     everything else (AllSetTransformer without that flag, the default method, among it) and under ``--exclude_self_expand``."""
     if getattr(args, 'exclude_self_expand', False) or args.LearnMask:
         return 'expand'
+    if getattr(args, 'dtype', 'fp32') == 'bf16':            # the leave-one-out kernels take fp32 rows (DESIGN.md section 19)
+        return 'expand'
     if args.method == 'AllSetTransformer' and getattr(args, 'exclude_self_loo_attention', False):
         # the PMA convs pool MLP_hidden-wide rows with args.heads heads and ignore norm (so any normtype); GPR keeps the expansion
         if getattr(args, 'GPR', False):
@@ -666,6 +676,9 @@ def run(args) -> dict:
         raise RuntimeError("allset_amd has no CPU path for the aggregation kernels: run with --cuda 0 on an MI355X")
     device = torch.device(f'cuda:{args.cuda}')
     model, data = model.to(device), data.to(device)
+    if getattr(args, 'dtype', 'fp32') == 'bf16':            # (every run's reset_parameters() then initialises the bf16 tensors in place)
+        model = model.to(torch.bfloat16)
+        data.x = data.x.to(torch.bfloat16)                  # once: the features are constants of the run
     if args.method in UNIGNN_METHODS + UNIGNN_CONV_METHODS:       # (reference train.py:438-440)
         args.UniGNN_degV = args.UniGNN_degV.to(device)
         args.UniGNN_degE = args.UniGNN_degE.to(device)
@@ -687,6 +700,7 @@ def run(args) -> dict:
 
 
 def _run_loop(args, model, data, splits, device, logger, runtimes, num_params):
+    train_loss = []                                        # [runs][epochs]: the training step's loss, as hist[:, 6] held it
     for r in range(args.runs):
         t0 = time.time()
         split_idx = {k: v.to(device) for k, v in splits[r].items()}
@@ -709,7 +723,7 @@ def _run_loop(args, model, data, splits, device, logger, runtimes, num_params):
             from .graphs import GraphedForward, GraphedTrainStep
             graphed_step = graphed_eval = None
             try:
-                graphed_step = GraphedTrainStep(model, data, lambda logits: nll_log_softmax(logits, y_all, train_mask, n_train), optimizer)
+                graphed_step = GraphedTrainStep(model, data, lambda logits: nll_log_softmax(logits.float(), y_all, train_mask, n_train), optimizer)
                 graphed_eval = GraphedForward(model, data, constant_features=True)    # (the same data.x every epoch)
             except (RuntimeError, AllSetHipError) as exc:     # capture-time failures only (an op that synchronises, an unsupported
                 if args.hip_graph == 1:                       # launch); shape / dtype bugs in the model are TypeError / ValueError
@@ -730,7 +744,7 @@ def _run_loop(args, model, data, splits, device, logger, runtimes, num_params):
         if use_graph:                          # the metrics of the replayed forward and the step's loss as a third small graph
             from .graphs import GraphedCallable
             graphed_metrics = GraphedCallable(
-                lambda: torch.cat([split_metrics(graphed_eval.out, y_all, sp, counts), graphed_step.loss.detach().reshape(1)]), device)
+                lambda: torch.cat([split_metrics(graphed_eval.out.float(), y_all, sp, counts), graphed_step.loss.detach().reshape(1)]), device)
         refresh_rv = getattr(model, 'refresh_projections', None) if not getattr(model, 'fast', True) else None
         for epoch in range(args.epochs):
             if use_graph:
@@ -749,14 +763,14 @@ def _run_loop(args, model, data, splits, device, logger, runtimes, num_params):
             else:
                 model.train()
                 optimizer.zero_grad()
-                loss = nll_log_softmax(model(data), y_all, train_mask, n_train)
+                loss = nll_log_softmax(model(data).float(), y_all, train_mask, n_train)
                 # every parameter-gradient partial of the backward pass reduced by ONE launch (dense.deferred_param_grads)
                 with dense.deferred_param_grads():
                     loss.backward()
                 optimizer.step()
                 model.eval()
                 with torch.no_grad(), dense.constant_features():      # (the same data.x every epoch: raw sparse features from their non-zeros)
-                    logits = model(data)
+                    logits = model(data).float()
                 loss = loss.detach()
             with torch.no_grad():
                 hist[epoch, :6] = split_metrics(logits, y_all, sp, counts)
@@ -765,8 +779,10 @@ def _run_loop(args, model, data, splits, device, logger, runtimes, num_params):
                 m = hist[epoch].tolist()
                 print(f'Epoch: {epoch:02d}, Train Loss: {m[6]:.4f}, Valid Loss: {m[4]:.4f}, Test  Loss: {m[5]:.4f}, '
                       f'Train Acc: {100 * m[0]:.2f}%, Valid Acc: {100 * m[1]:.2f}%, Test  Acc: {100 * m[2]:.2f}%')
-        for row in hist[:, :3].tolist():                   # one read-back per run
-            logger.add_result(r, tuple(row))
+        rows = hist.tolist()                               # one read-back per run
+        for row in rows:
+            logger.add_result(r, tuple(row[:3]))
+        train_loss.append([row[6] for row in rows])
         runtimes.append(time.time() - t0)
     avg_time, std_time = float(np.mean(runtimes)), float(np.std(runtimes))
     best_val, best_test = logger.print_statistics()
@@ -781,7 +797,7 @@ def _run_loop(args, model, data, splits, device, logger, runtimes, num_params):
                 f',{avg_time // 60}min{(avg_time % 60):.2f}s\n')
     with open(f'{args.res_root}/all_args_{args.dname}_noise_{args.feature_noise}.csv', 'a+') as f:
         f.write(str(args) + '\n')
-    return dict(best_val=best_val, best_test=best_test, num_params=num_params, avg_time=avg_time, csv=filename)
+    return dict(best_val=best_val, best_test=best_test, num_params=num_params, avg_time=avg_time, csv=filename, train_loss=train_loss)
 
 
 def parse_args(argv=None):
@@ -791,6 +807,16 @@ def parse_args(argv=None):
     if args.CE_implicit and args.method == 'CEGAT':
         parser.error("--CE_implicit is not built for --method CEGAT: its attention logit leaky_relu(a_l x_i + a_r x_j) does not factorise "
                      "over a hyperedge, so CEGAT needs the explicit clique expansion (use --method CEGCN, or drop the flag)")
+    if args.dtype == 'bf16':
+        if args.method not in ALLSET_METHODS:
+            parser.error(f"--dtype bf16 is built for --method {' / '.join(ALLSET_METHODS)} only: the kernels of {args.method!r} are fp32 "
+                         "(use --dtype fp32)")
+        if args.normalization != 'ln':
+            parser.error("--dtype bf16 is built for --normalization ln only (the bf16 LayerNorm kernels; BatchNorm statistics and "
+                         "the norm-free MLP are fp32 paths): use --normalization ln or --dtype fp32")
+        if args.exclude_self_loo_attention:
+            parser.error("--dtype bf16 does not go with --exclude_self_loo_attention: the leave-one-out softmax is built for fp32 rows; "
+                         "plain --exclude_self (the expansion) is supported in bf16")
     return args
 
 
