@@ -9,6 +9,9 @@ Dropout masks are a counter-based hash of (seed, element index): the seed is dra
 from __future__ import annotations
 
 import contextlib
+import ctypes
+import functools
+import math
 import os
 from ctypes import byref, c_int64
 from typing import Optional, Tuple
@@ -130,29 +133,103 @@ def _deferrable(part: Tensor, *params, M: Optional[int] = None) -> bool:
                for p in real)
 
 
-def _defer(part: Tensor, sections, M: Optional[int] = None) -> None:
-    """``sections``: (parameter or None, offset into the summed row, shape).  A parameter named twice in one scope (shared weights)
-    accumulates."""
-    secs = [(p, off, tuple(shape)) for p, off, shape in sections if p is not None]
-    _Deferred.pending.append((part, part.shape[1] if M is None else M, secs))
-
-
-def _defer_or_reduce(part: Tensor, sections, defer: bool):
-    """``sections``: [(parameter or None, offset, shape)] of one partial buffer [P, M].  Inside ``deferred_param_grads()`` (and with
-    ``defer``) the buffer is queued and every section comes back None; otherwise one reduction launch and the sections as views."""
-    part2 = part.reshape(part.shape[0], -1)
-    params = [p for p, _, _ in sections]
-    if defer and any(p is not None for p in params) and _deferrable(part2, *params):
-        _defer(part2, sections)
-        return [None] * len(sections)
-    red = reduce_partials(part2).reshape(-1)
-    out = []
-    for _, off, shape in sections:
-        numel = 1
-        for v in shape:
-            numel *= v
-        out.append(red[off:off + numel].view(shape))
+def _row(*fields):
+    """Section table ``[(key, offset, shape)]`` of a partial row whose fields lie side by side: ``fields`` = (key, shape) in row order;
+    a field with key None is columns nobody wants (a bias slot the kernel keeps without a bias).  The table functions below are pure
+    functions of the widths and cached: a table is read, never changed."""
+    out, off = [], 0
+    for key, shape in fields:
+        if key is not None:
+            out.append((key, off, tuple(shape)))
+        off += math.prod(shape)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def _ln_sections(d: int, colb_shape=None):
+    """Row of the LayerNorm backward kernels (``ln_bwd``, ``gemm_x6_lnb``, ``ln_res_bwd[_pma]``): dgamma | dbeta [| dcolb]."""
+    return _row(("gamma", (d,)), ("beta", (d,)), *((("colb", colb_shape),) if colb_shape is not None else ()))
+
+
+@functools.lru_cache(maxsize=None)
+def _wgrad_sections(O: int, I: int, want_bias: bool = True, aux: bool = False):
+    """Row of the weight-gradient kernels (``wgrad_fused``, ``wgrad_bf16_ex2``), packed: gW [| gb] [| four auxiliary rows, their bias]."""
+    return _row(("weight", (O, I)), *((("bias", (O,)),) if want_bias else ()), *((("aux_w", (4, I)), ("aux_b", (4,))) if aux else ()))
+
+
+@functools.lru_cache(maxsize=None)
+def _one_pass_sections(O: int, I: int, want_bias: bool = True, ln: int = 0, colb_shape=None, aux: bool = False):
+    """Row of the one-pass Linear backward kernels (``fused_linear_bwd_all[_aux]``, ``_pma_tail``, ``_ln_pro``, ``linear_narrow_bwd``):
+    gW | gb (the slot stays without a bias) [| dgamma, dbeta of width ``ln``] [| dcolb] [| four auxiliary rows, their bias]."""
+    return _row(("weight", (O, I)), ("bias" if want_bias else None, (O,)), *((("gamma", (ln,)), ("beta", (ln,))) if ln else ()),
+                *((("colb", colb_shape),) if colb_shape is not None else ()), *((("aux_w", (4, I)), ("aux_b", (4,))) if aux else ()))
+
+
+def _finish_partials(part: Tensor, sections, params=None, *, out_dtype: torch.dtype = torch.float32, queue: bool = True) -> list:
+    """THE end of every backward launcher: ``part`` [P, stride] (or [P, a, b]) fp32 partials, ``sections`` its row layout
+    ``[(key, offset, shape)]``, ``params`` = {key: Parameter} for the sections that are parameters' gradients (:func:`_queue_params`).
+    Returns one entry per section: a view of the reduced row, or None where the section was queued.
+
+    Queued (inside ``deferred_param_grads()``, with ``queue``, when :func:`_deferrable`): the parameter sections -- a prefix
+    [0, M_main) of the row -- for the scope's one batched launch; sections behind them that belong to no parameter are reduced at once
+    with the association the WHOLE buffer's reduction has (``reduce_partials_slice``).  Otherwise ONE reduction of the whole buffer:
+    ``reduce_partials``, or for bf16 ``reduce_partials_to`` (summed and rounded in one launch) where that kernel takes the shape."""
+    if part.dim() != 2:
+        part = part.reshape(part.shape[0], -1)
+    P, M = part.shape
+    own = []                                     # the parameters of the leading sections, in row order
+    if params:                                   # (once per backward node of an eager step: a plain loop; ``is`` -- ``==`` on a
+        for sec in sections:                     # Parameter is a tensor operation)
+            q = params.get(sec[0])
+            if q is None:
+                break
+            own.append(q)
+        if len(own) != len(params) and len(own) != sum(q is not None for q in params.values()):
+            raise _lib.AllSetHipError(f"parameters {[k for k, q in params.items() if q is not None]} are not the leading sections of a "
+                                      f"partial row of sections {[k for k, _, _ in sections]}")
+    n_own = len(own)
+    if queue and n_own:
+        rest = sections[n_own:]
+        M_main = rest[0][1] if rest else M
+        if _deferrable(part, *own, M=M_main):
+            _Deferred.pending.append((part, M_main, [(q, sec[1], sec[2]) for q, sec in zip(own, sections)]))
+            if not rest:
+                return [None] * n_own
+            red = reduce_partials_slice(part, M_main, rest[-1][1] + math.prod(rest[-1][2]) - M_main, out_dtype)
+            return [None] * n_own + [red[off - M_main:off - M_main + math.prod(shape)].view(shape) for _, off, shape in rest]
+    if out_dtype == torch.float32:
+        red = reduce_partials(part) if part.is_contiguous() else reduce_partials_to(part, M, out_dtype)
+    elif M % 4 == 0 and P <= 4096:
+        red = reduce_partials_to(part, M, out_dtype)
+    else:
+        red = reduce_partials(part).to(out_dtype)
+    return [red[off:off + math.prod(shape)].view(shape) for _, off, shape in sections]
+
+
+def _by_key(sections, grads) -> dict:
+    return {sec[0]: g for sec, g in zip(sections, grads)}
+
+
+def _queue_params(ctx, index):
+    """May this backward node queue?  ``ctx.params`` = {key: parameter object as the node received it, or None}, ``index`` = {key:
+    position in ``needs_input_grad``} of the parameters asked about.  Those that are present, under their keys, when the node runs
+    inside ``deferred_param_grads()`` and every one of them wants its gradient; None otherwise."""
+    params = getattr(ctx, "params", None)
+    if not _Deferred.active or params is None:
+        return None
+    need, out = ctx.needs_input_grad, {}
+    for k, i in index.items():
+        q = params[k]
+        if q is not None:
+            if not need[i]:
+                return None
+            out[k] = q
+    return out
+
+
+def _pick(params, **keys):
+    """{launcher key: params[node key]} for a node that feeds several launchers; None stays None."""
+    return None if params is None else {k: params[name] for k, name in keys.items() if name in params}
 
 
 def flush_param_grads(bump_i64: Optional[Tensor] = None, bump_f32=None) -> None:
@@ -164,7 +241,6 @@ def flush_param_grads(bump_i64: Optional[Tensor] = None, bump_f32=None) -> None:
     section as an entry of its own whose sum the kernel adds to the existing gradient: no ``add_`` launch per such parameter."""
     pend, _Deferred.pending = _Deferred.pending, []
     lib = _lib.load()
-    import ctypes
     dev = pend[0][0].device if pend else (bump_i64.device if bump_i64 is not None else None)
     later = []
     # flat entry list: (partial pointer, P, row stride, M, dtype, base in that dtype's output buffer, accumuland pointer or 0)
@@ -184,9 +260,7 @@ def flush_param_grads(bump_i64: Optional[Tensor] = None, bump_f32=None) -> None:
         dt = sections[0][0].dtype if sections else torch.float32
         whole = None
         for p, off, shape in sections:
-            numel = 1
-            for v in shape:
-                numel *= v
+            numel = math.prod(shape)
             g_old = p.grad
             if id(p) in seen:
                 if whole is None:
@@ -295,7 +369,6 @@ def reduce_partials_slice(part: Tensor, col0: int, M: int, dtype: torch.dtype) -
     if not lib.allset_reduce_partials_is_tree(P, width) or lib.allset_reduce_partials_is_tree(P, M) \
             or not lib.allset_reduce_partials_batchable(P, M):
         return reduce_partials_to(view, M, dtype)
-    import ctypes
     dev = part.device
     out = torch.empty(M, dtype=dtype, device=dev)
     flags = (ctypes.c_int32 * 1)((_lib.BF16 if dtype == torch.bfloat16 else _lib.F32) | _lib.REDUCE_AS_TREE)
@@ -350,7 +423,8 @@ def ln_bf16_supported(d: int) -> bool:
 
 
 def ln_bwd(gy: Tensor, x: Tensor, stats: Tensor, gamma: Tensor, relu_in: bool, p: float, seed: int,
-           seed_base: Optional[Tensor] = None, want_gx: bool = True, defer_to=None) -> Tuple[Optional[Tensor], Tensor, Tensor]:
+           seed_base: Optional[Tensor] = None, want_gx: bool = True, params=None) -> Tuple[Optional[Tensor], Tensor, Tensor]:
+    """(gx, dgamma, dbeta).  ``params``: see :func:`_finish_partials` (keys gamma, beta)."""
     dev = require_device(gy, x, stats, gamma)
     gy, x = _rowmajor(gy), _rowmajor(x)
     n, d = x.shape
@@ -365,11 +439,9 @@ def ln_bwd(gy: Tensor, x: Tensor, stats: Tensor, gamma: Tensor, relu_in: bool, p
             check(lib.allset_ln_bwd_bf16(ptr(gy), _ld(gy), ptr(x), _ld(x), ptr(stats), ptr(gamma.contiguous()), int(relu_in), p,
                                          seed, ptr(gx), max(d, 1), ptr(partials), npart.value, n, d, ptr(seed_base),
                                          stream_of(dev)), "allset_ln_bwd_bf16")
-        if (2 * d) % 4 == 0 and npart.value <= 4096:
-            red = reduce_partials_to(partials.view(npart.value, 2 * d), 2 * d, torch.bfloat16).view(2, d)
-            return gx, red[0], red[1]
-        red = reduce_partials(partials)
-        return gx, red[0].to(torch.bfloat16), red[1].to(torch.bfloat16)
+        # (kept as it was: the bf16 LayerNorm backward reduces at once, though the rule could queue bf16 parameters)
+        dg, db = _finish_partials(partials, _ln_sections(d), params, out_dtype=torch.bfloat16, queue=False)
+        return gx, dg, db
     check(lib.allset_ln_bwd_partials(n, d, byref(npart)), "allset_ln_bwd_partials")
     partials = torch.empty((npart.value, 2, d), dtype=torch.float32, device=dev)
     gx = torch.empty((n, d), dtype=x.dtype, device=dev) if want_gx else None
@@ -378,9 +450,8 @@ def ln_bwd(gy: Tensor, x: Tensor, stats: Tensor, gamma: Tensor, relu_in: bool, p
                                 seed, ptr(gx), max(d, 1), ptr(partials), npart.value, n, d, ptr(seed_base),
                                 stream_of(dev)),
               "allset_ln_bwd")
-    dg_, db_ = _defer_or_reduce(partials, [(defer_to[0] if defer_to else None, 0, (d,)), (defer_to[1] if defer_to else None, d, (d,))],
-                                defer_to is not None)
-    return gx, dg_, db_
+    dg, db = _finish_partials(partials, _ln_sections(d), params)
+    return gx, dg, db
 
 
 def wgrad(ga: Tensor, u: Tensor, want_bias: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
@@ -588,7 +659,7 @@ def gemm_x6(A: Tensor, planes: Tensor, N: int, bias: Optional[Tensor] = None, *,
 
 def gemm_x6_lnb(G: Tensor, planes_t: Tensor, x: Tensor, stats: Tensor, gamma: Tensor, relu_in: bool, p: float, seed: int,
                 mask_y: Optional[Tensor] = None, p_mask: float = 0.0, seed_base: Optional[Tensor] = None,
-                mask_bits: Optional[Tensor] = None, defer_to=None) -> Tuple[Tensor, Tensor, Tensor]:
+                mask_bits: Optional[Tensor] = None, params=None) -> Tuple[Tensor, Tensor, Tensor]:
     """Backward-data of a wide Linear fused with the LayerNorm backward of its input (include/allset_hip.h
     allset_gemm_x6_lnb): returns (gx, dgamma, dbeta).  ``planes_t``: ``gemm_x6_planes(weight, True)``; N = x.shape[1] <= 256."""
     planes_t, f16 = planes_t.buf, planes_t.f16
@@ -608,9 +679,8 @@ def gemm_x6_lnb(G: Tensor, planes_t: Tensor, x: Tensor, stats: Tensor, gamma: Te
                                        _ld(mask_y) if mask_y is not None else 0, ptr(mask_bits), p_mask, ptr(planes_t),
                                        ptr(x), _ld(x), ptr(stats), ptr(gamma.contiguous()), int(relu_in), p, seed, ptr(gx), max(N, 1),
                                        ptr(partials), npart, n, N, K, ptr(seed_base), stream_of(dev)), "allset_gemm_wide_lnb")
-    dg_, db_ = _defer_or_reduce(partials, [(defer_to[0] if defer_to else None, 0, (N,)), (defer_to[1] if defer_to else None, N, (N,))],
-                                defer_to is not None)
-    return gx, dg_, db_
+    dg, db = _finish_partials(partials, _ln_sections(N), params)
+    return gx, dg, db
 
 
 # ---- arithmetic of the fused Linear kernels (include/allset_hip_ext.h ALLSET_ARITH_*) ---------------------------------------------
@@ -772,20 +842,18 @@ def fused_linear_bwd_all_blocked(gy: Tensor, gy_cb: int, mask: Optional[Tensor],
             0, int(relu_in), p_in, seed_in, ptr(gx), x_cb if x_cb else max(I, 1), x_cb, ptr(part_ln), ptr(part_w),
             ptr(part_b if want_bias else None), P, n, O, I, ptr(seed_base), ptr(None), 0, M,
             _arith_for(1, I, O, stats is not None, 0), stream_of(dev)), "allset_fused_linear_bwd_all_ex")
-    red = reduce_partials(part)
-    gw = red[:O * I].view(O, I)
-    gb = red[O * I:O * I + O] if want_bias else None
-    if stats is None:
-        return gx, None, None, gw, gb
-    return gx, red[O * I + O:O * I + O + I], red[O * I + O + I:O * I + O + 2 * I], gw, gb
+    sections = _one_pass_sections(O, I, want_bias, ln=I if stats is not None else 0)
+    g = _by_key(sections, _finish_partials(part, sections))           # (kept as it was: the blocked form takes no parameters)
+    return gx, g.get("gamma"), g.get("beta"), g["weight"], g.get("bias")
 
 
 def wgrad_fused(gy: Tensor, y: Optional[Tensor], p_out: float, x: Tensor, stats: Optional[Tensor],
                 gamma: Optional[Tensor], beta: Optional[Tensor], relu_in: bool, p_in: float, seed_in: int,
-                want_bias: bool = True, seed_base: Optional[Tensor] = None, mask: Optional[Tensor] = None, defer_to=None
+                want_bias: bool = True, seed_base: Optional[Tensor] = None, mask: Optional[Tensor] = None, params=None
                 ) -> Tuple[Tensor, Optional[Tensor]]:
     """Weight/bias gradient of the fused Linear with both operands recomputed on the fly (csrc/dense.hip).
-    ``mask`` (from ``fused_linear_fwd(mask_out=...)``) replaces ``y`` as the source of the epilogue mask."""
+    ``mask`` (from ``fused_linear_fwd(mask_out=...)``) replaces ``y`` as the source of the epilogue mask.  ``params``: see
+    :func:`_finish_partials` (keys weight, bias)."""
     dev = require_device(gy, y, x, stats, gamma, beta, mask)
     gy, x = _rowmajor(gy), _rowmajor(x)
     if y is not None:
@@ -803,21 +871,19 @@ def wgrad_fused(gy: Tensor, y: Optional[Tensor], p_out: float, x: Tensor, stats:
             check(lib.allset_wgrad_f16x3(ptr(gy), _ld(gy), ptr(mask), p_out, ptr(x), _ld(x), ptr(stats), ptr(gamma.contiguous()),
                                          ptr(beta.contiguous()), int(relu_in), p_in, seed_in, ptr(part), M, int(want_bias), ns.value,
                                          n, O, I, ptr(seed_base), stream_of(dev)), "allset_wgrad_f16x3")
-        gw_, gb_ = _defer_or_reduce(part, [(defer_to[0] if defer_to else None, 0, (O, I)),
-                                           ((defer_to[1] if defer_to else None) if want_bias else None, O * I, (O,))], defer_to is not None)
-        return gw_, (gb_ if want_bias else None)
-    check(lib.allset_wgrad_slices(n, O, I, byref(ns)), "allset_wgrad_slices")
-    # one partial buffer [slices, gW | gb] and one reduction launch (O and I are multiples of 4, checked by the kernel)
-    part = torch.empty((ns.value, M), dtype=torch.float32, device=dev)
-    with on_device(dev), _timed("wgrad_fused", dev, n * (O * (2 if (y is not None and mask is None) else 1) + I) * 4):
-        check(lib.allset_wgrad_fused_ex(ptr(gy), _ld(gy), ptr(y), _ld(y) if y is not None else 0, p_out, ptr(x), _ld(x),
-                                        ptr(stats), ptr(gamma.contiguous() if gamma is not None else None),
-                                        ptr(beta.contiguous() if beta is not None else None), int(relu_in), p_in, seed_in,
-                                        ptr(part), M, int(want_bias), ns.value, n, O, I, ptr(seed_base), ptr(mask),
-                                        stream_of(dev)), "allset_wgrad_fused_ex")
-    gw_, gb_ = _defer_or_reduce(part, [(defer_to[0] if defer_to else None, 0, (O, I)),
-                                       ((defer_to[1] if defer_to else None) if want_bias else None, O * I, (O,))], defer_to is not None)
-    return gw_, (gb_ if want_bias else None)
+    else:
+        check(lib.allset_wgrad_slices(n, O, I, byref(ns)), "allset_wgrad_slices")
+        # one partial buffer [slices, gW | gb] and one reduction launch (O and I are multiples of 4, checked by the kernel)
+        part = torch.empty((ns.value, M), dtype=torch.float32, device=dev)
+        with on_device(dev), _timed("wgrad_fused", dev, n * (O * (2 if (y is not None and mask is None) else 1) + I) * 4):
+            check(lib.allset_wgrad_fused_ex(ptr(gy), _ld(gy), ptr(y), _ld(y) if y is not None else 0, p_out, ptr(x), _ld(x),
+                                            ptr(stats), ptr(gamma.contiguous() if gamma is not None else None),
+                                            ptr(beta.contiguous() if beta is not None else None), int(relu_in), p_in, seed_in,
+                                            ptr(part), M, int(want_bias), ns.value, n, O, I, ptr(seed_base), ptr(mask),
+                                            stream_of(dev)), "allset_wgrad_fused_ex")
+    sections = _wgrad_sections(O, I, want_bias)
+    g = _by_key(sections, _finish_partials(part, sections, params))
+    return g["weight"], g.get("bias")
 
 
 def fused_linear_bwd(gy: Tensor, y: Optional[Tensor], p_out: float, weight: Tensor, x: Tensor, stats: Optional[Tensor],
@@ -889,10 +955,9 @@ def one_pass_preferred(O: int, I: int) -> bool:
 def fused_linear_bwd_all(gy: Tensor, mask: Optional[Tensor], p_out: float, weight: Tensor, x: Tensor, stats: Optional[Tensor],
                          gamma: Optional[Tensor], beta: Optional[Tensor], relu_in: bool, p_in: float, seed_in: int,
                          seed_base: Optional[Tensor] = None, acc_in: Optional[Tensor] = None, want_bias: bool = True,
-                         norm_mode: int = 0, defer_to=None) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor], Tensor, Optional[Tensor]]:
+                         norm_mode: int = 0, params=None) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor], Tensor, Optional[Tensor]]:
     """(gx, dgamma, dbeta, gW, gb) of the fused Linear from ONE pass over gy and x (include/allset_hip.h
-    allset_fused_linear_bwd_all).  ``defer_to`` = the (gamma, beta, weight, bias) PARAMETERS: inside ``deferred_param_grads()`` their
-    gradients are queued for the batched reduction and come back as None."""
+    allset_fused_linear_bwd_all).  ``params``: see :func:`_finish_partials` (keys weight, bias, gamma, beta)."""
     dev = require_device(gy, mask, weight, x, stats, gamma, beta, acc_in)
     _check_f32(gy, weight, x, stats, gamma, beta, acc_in)
     gy, x = _rowmajor(gy), _rowmajor(x)
@@ -915,46 +980,29 @@ def fused_linear_bwd_all(gy: Tensor, mask: Optional[Tensor], p_out: float, weigh
     flat = part.view(-1)
     part_w, part_b = flat, flat[O * I:]
     part_ln = flat[O * I + O:] if stats is not None else None
-    if norm_mode:
-        if acc_in is not None or stats is None:
-            raise _lib.AllSetHipError("fused_linear_bwd_all: the column-affine prologue takes stats / gamma / beta and no acc_in")
-        with on_device(dev), _timed("fused_linear_bwd_all", dev, n * (O + 2 * I) * 4):
-            check(lib.allset_fused_linear_bwd_all_ex(
-                ptr(gy), _ld(gy), 0, ptr(mask), p_out, ptr(weight), ptr(x), _ld(x), 0, ptr(stats), ptr(gamma.contiguous()),
-                ptr(beta.contiguous()), int(norm_mode), int(relu_in), p_in, seed_in, ptr(gx), max(I, 1), 0, ptr(part_ln), ptr(part_w),
-                ptr(part_b if want_bias else None), P, n, O, I, ptr(seed_base), ptr(None), 0, M,
-                _arith_for(1, I, O, True, norm_mode), stream_of(dev)), "allset_fused_linear_bwd_all_ex")
-        red = reduce_partials(part)
-        return (gx, red[O * I + O:O * I + O + I], red[O * I + O + I:O * I + O + 2 * I], red[:O * I].view(O, I),
-                red[O * I:O * I + O] if want_bias else None)
+    if norm_mode and (acc_in is not None or stats is None):
+        raise _lib.AllSetHipError("fused_linear_bwd_all: the column-affine prologue takes stats / gamma / beta and no acc_in")
     with on_device(dev), _timed("fused_linear_bwd_all", dev, n * (O + 2 * I) * 4):
         check(lib.allset_fused_linear_bwd_all_ex(
             ptr(gy), _ld(gy), 0, ptr(mask), p_out, ptr(weight), ptr(x), _ld(x), 0, ptr(stats),
             ptr(gamma.contiguous() if gamma is not None else None), ptr(beta.contiguous() if beta is not None else None),
-            0, int(relu_in), p_in, seed_in, ptr(gx), max(I, 1), 0, ptr(part_ln), ptr(part_w), ptr(part_b if want_bias else None), P, n, O, I,
-            ptr(seed_base), ptr(acc_in), _ld(acc_in) if acc_in is not None else 0, M,
-            _arith_for(1, I, O, stats is not None, 0), stream_of(dev)), "allset_fused_linear_bwd_all_ex")
-    if defer_to is not None and _deferrable(part, *defer_to):
-        g_p, b_p, w_p, bias_p = defer_to
-        _defer(part, [(w_p, 0, (O, I)), (bias_p if want_bias else None, O * I, (O,)),
-                      (g_p if stats is not None else None, O * I + O, (I,)), (b_p if stats is not None else None, O * I + O + I, (I,))])
-        return gx, None, None, None, None
-    red = reduce_partials(part)
-    gw = red[:O * I].view(O, I)
-    gb = red[O * I:O * I + O] if want_bias else None
-    if stats is None:
-        return gx, None, None, gw, gb
-    return gx, red[O * I + O:O * I + O + I], red[O * I + O + I:O * I + O + 2 * I], gw, gb
+            int(norm_mode), int(relu_in), p_in, seed_in, ptr(gx), max(I, 1), 0, ptr(part_ln), ptr(part_w), ptr(part_b if want_bias else None),
+            P, n, O, I, ptr(seed_base), ptr(acc_in), _ld(acc_in) if acc_in is not None else 0, M,
+            _arith_for(1, I, O, stats is not None, norm_mode), stream_of(dev)), "allset_fused_linear_bwd_all_ex")
+    sections = _one_pass_sections(O, I, want_bias, ln=I if stats is not None else 0)
+    # (kept as it was: the column-affine prologue never queues, though the rule could)
+    g = _by_key(sections, _finish_partials(part, sections, params, queue=not norm_mode))
+    return gx, g.get("gamma"), g.get("beta"), g["weight"], g.get("bias")
 
 
 def fused_linear_bwd_all_aux_supported(O: int, I: int) -> bool:
     return bool(_lib.load().allset_fused_linear_bwd_all_aux_supported(int(O), int(I)))
 
 
-def fused_linear_bwd_all_aux(gy: Tensor, weight: Tensor, x: Tensor, aux_g: Tensor, aux_w: Tensor, defer_to=None
+def fused_linear_bwd_all_aux(gy: Tensor, weight: Tensor, x: Tensor, aux_g: Tensor, aux_w: Tensor, params=None
                              ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """(gx, gW, gb, gaux_w [4, I], gaux_b [4]) of the plain Linear with four auxiliary output columns, from ONE pass over gy and x
-    (include/allset_hip.h allset_fused_linear_bwd_all_aux)."""
+    (include/allset_hip.h allset_fused_linear_bwd_all_aux).  ``params``: see :func:`_finish_partials` (keys weight, bias)."""
     dev = require_device(gy, weight, x, aux_g, aux_w)
     _check_f32(gy, weight, x, aux_g, aux_w)
     gy, x = _rowmajor(gy), _rowmajor(x)
@@ -972,14 +1020,11 @@ def fused_linear_bwd_all_aux(gy: Tensor, weight: Tensor, x: Tensor, aux_g: Tenso
         check(lib.allset_fused_linear_bwd_all_aux(ptr(gy), _ld(gy), ptr(weight), ptr(x), _ld(x), ptr(aux_g), ptr(aux_w), ptr(gx),
                                                   max(I, 1), ptr(part), M, P, n, O, I, stream_of(dev)),
               "allset_fused_linear_bwd_all_aux")
-    o = O * I
-    if defer_to is not None and (o + O) % 4 == 0 and defer_to[1] is not None and _deferrable(part, *defer_to, M=o + O):
-        # (weight, bias) PARAMETERS: queued; the four auxiliary rows (their weight is a folded tensor, not a parameter) reduce at once
-        _defer(part, [(defer_to[0], 0, (O, I)), (defer_to[1], o, (O,))], M=o + O)
-        redx = reduce_partials_slice(part, o + O, 4 * I + 4, torch.float32)
-        return gx, None, None, redx[:4 * I].view(4, I), redx[4 * I:4 * I + 4]
-    red = reduce_partials(part)
-    return gx, red[:o].view(O, I), red[o:o + O], red[o + O:o + O + 4 * I].view(4, I), red[o + O + 4 * I:o + O + 4 * I + 4]
+    sections = _one_pass_sections(O, I, aux=True)
+    # (kept as it was: without a bias PARAMETER nothing is queued, though the rule could queue the weight alone.  The four auxiliary
+    # rows -- their weight is a folded tensor, not a parameter -- reduce at once either way)
+    gw, gb, gwa, gba = _finish_partials(part, sections, params, queue=bool(params) and params.get("bias") is not None)
+    return gx, gw, gb, gwa, gba
 
 
 def wgrad_supported(ga: Tensor, u: Tensor) -> bool:
@@ -1102,7 +1147,7 @@ class _Linear(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
-        ctx.params = (weight, bias)
+        ctx.params = {"weight": weight, "bias": bias}
         return torch.nn.functional.linear(x, weight, bias)
 
     @staticmethod
@@ -1113,9 +1158,9 @@ class _Linear(torch.autograd.Function):
         gx = gw = gb = None
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         if need_w and linear_narrow_supported(gy, x, weight):          # a classifier head: one kernel for all three gradients
-            defer = ctx.params if (not ctx.has_bias or need_b) else None
-            gx, gw, gb = linear_narrow_bwd(gy, x, weight, ctx.needs_input_grad[0], defer_to=defer)
-            return gx, gw, gb if need_b else None
+            gx, gw, gb = linear_narrow_bwd(gy, x, weight, ctx.needs_input_grad[0], want_bias=need_b,
+                                           params=_queue_params(ctx, {"weight": 1, "bias": 2}))
+            return gx, gw, gb
         if ctx.needs_input_grad[0]:
             gx = gy @ weight
         if need_w or need_b:
@@ -1161,7 +1206,7 @@ class _FusedNormLinear(torch.autograd.Function):
         ctx.save_for_backward(x, stats, gamma, beta, weight, y if (keep_y and mask is None) else None, mask)
         ctx.cfg = (bool(relu_in), float(p_in), seed_in, float(p_out), bias is not None, base)
         ctx.layout = (int(in_cb), int(out_cb))
-        ctx.params = (gamma, beta, weight, bias)     # (the objects themselves: deferred_param_grads assigns their .grad)
+        ctx.params = {"gamma": gamma, "beta": beta, "weight": weight, "bias": bias}     # (the objects themselves: deferred_param_grads assigns their .grad)
         return y
 
     @staticmethod
@@ -1190,10 +1235,8 @@ class _FusedNormLinear(torch.autograd.Function):
                 fused_linear_bwd_all_supported(weight.shape[0], weight.shape[1], gamma is not None, p_in > 0.0, relu_in,
                                                mask is not None)):
             # everything from one read of gy and x
-            need = ctx.needs_input_grad
-            defer = ctx.params if (_Deferred.active and (gamma is None or (need[1] and need[2])) and (not has_bias or need[4])) else None
             gx, dg, db, gw, gb = fused_linear_bwd_all(gy, mask, p_out, weight, x, stats, gamma, beta, relu_in, p_in, seed_in,
-                                                      base, want_bias=need_b, defer_to=defer)
+                                                      base, want_bias=need_b, params=_queue_params(ctx, {"gamma": 1, "beta": 2, "weight": 3, "bias": 4}))
             return gx, dg, db, gw, gb, None, None, None, None, None, None, None
         if ctx.needs_input_grad[3] or need_b:
             gw, gb = wgrad_fused(gy, y, p_out, x, stats, gamma, beta, relu_in, p_in, seed_in, want_bias=need_b,
@@ -1244,7 +1287,7 @@ class _FusedNormLinearPacked(torch.autograd.Function):
         ctx.save_for_backward(x, stats, gamma, beta, weight, None, mask)
         ctx.cfg = (bool(relu_in), float(p_in), seed_in, float(p_out), bias is not None, base)
         ctx.layout = (0, 0)
-        ctx.params = (gamma, beta, weight, bias)
+        ctx.params = {"gamma": gamma, "beta": beta, "weight": weight, "bias": bias}
         ctx.mark_non_differentiable(packed)
         ctx.set_materialize_grads(False)     # (packed never carries a gradient: no int32 [n, 64] zero-fill for it in every backward)
         return side, packed
@@ -1307,7 +1350,7 @@ class _WideNormLinear(torch.autograd.Function):
                     stats_relu=bool(emit[1]) if emit is not None else False)
         ctx.save_for_backward(x, stats, gamma, beta, weight, y if (keep_y and mask is None) else None, mask)
         ctx.cfg = (bool(relu_in), float(p_in), seed_in, float(p_out), bias is not None, base)
-        ctx.params = (gamma, beta, weight, bias)     # (the objects themselves: deferred_param_grads assigns their .grad)
+        ctx.params = {"gamma": gamma, "beta": beta, "weight": weight, "bias": bias}     # (the objects themselves: deferred_param_grads assigns their .grad)
         if emit is None:
             return y
         ctx.mark_non_differentiable(stats_y)
@@ -1330,12 +1373,11 @@ class _WideNormLinear(torch.autograd.Function):
         gy = gy.contiguous()
         gx = dg = db = gw = gb = None
         need_b = has_bias and ctx.needs_input_grad[4]
-        need = ctx.needs_input_grad
-        p_g, p_bt, p_w, p_b = ctx.params
-        dfr = _Deferred.active
+        # (kept as it was: two buffers, two decisions -- (weight, bias) may queue while (gamma, beta) do not, and the other way round)
+        q_w, q_ln = _queue_params(ctx, {"weight": 3, "bias": 4}), _queue_params(ctx, {"gamma": 1, "beta": 2})
         if ctx.needs_input_grad[3] or need_b:
             gw, gb = wgrad_fused(gy, y, p_out, x, stats, gamma, beta, relu_in, p_in, seed_in, want_bias=need_b, seed_base=base, mask=mask,
-                                 defer_to=(p_w, p_b) if (dfr and need[3] and (not has_bias or need[4])) else None)
+                                 params=q_w)
         need_x = ctx.needs_input_grad[0]
         if need_x or (gamma is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])):
             # gradient of the Linear's input u = dropout(LN(relu(x))): (gy * epilogue mask) @ W
@@ -1344,7 +1386,7 @@ class _WideNormLinear(torch.autograd.Function):
                 # one kernel: the Linear's input gradient never leaves the chip, the LayerNorm backward is the GEMM's epilogue
                 gx, dg, db = gemm_x6_lnb(gy, planes_t, x, stats, gamma, relu_in, p_in, seed_in, mask_y=y,
                                          p_mask=p_out, seed_base=base, mask_bits=mask,
-                                         defer_to=(p_g, p_bt) if (dfr and need[1] and need[2]) else None)
+                                         params=q_ln)
                 return gx, dg, db, gw, gb, None, None, None, None, None, None, None
             # (behind a bare relu -- p_in == 0 there, see wide_linear_supported -- the mask by the sign of x is the GEMM's epilogue)
             sgn = x if (gamma is None and relu_in and planes_t.f16 and x.stride(-1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
@@ -1352,7 +1394,7 @@ class _WideNormLinear(torch.autograd.Function):
             gu = gemm_x6(gy, planes_t, weight.shape[1], None, mask_y=y, p_mask=p_out, mask_bits=mask, sgn_x=sgn)
             if gamma is not None:
                 gx, dg, db = ln_bwd(gu, x, stats, gamma, relu_in, p_in, seed_in, base, want_gx=need_x,
-                                    defer_to=(p_g, p_bt) if (dfr and need[1] and need[2]) else None)
+                                    params=q_ln)
             elif relu_in and sgn is None:       # (rows of x that are not 16-byte aligned: the elementwise pass)
                 gx = torch.empty_like(x)
                 with torch.cuda.device(x.device), _timed("relu_dropout_bwd", x.device, 3 * x.numel() * 4):
@@ -1438,11 +1480,10 @@ def ln_res_fwd(x: Tensor, colb: Optional[Tensor], res: Optional[Tensor], gamma: 
 
 
 def ln_res_bwd(gy: Tensor, x: Tensor, colb: Optional[Tensor], res: Optional[Tensor], stats: Tensor, gamma: Tensor,
-               beta: Tensor, relu_out: bool, p: float, seed: int, seed_base: Optional[Tensor] = None, defer_to=None
+               beta: Tensor, relu_out: bool, p: float, seed: int, seed_base: Optional[Tensor] = None, params=None
                ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """(gs, dgamma, dbeta, dcolb); gs is the gradient of x and of res.  bf16 activations: the three parameter
-    gradients are accumulated in fp32 and cast back.  ``defer_to`` = the (gamma, beta, colb-or-None) PARAMETERS (fp32): inside
-    ``deferred_param_grads()`` their gradients are queued and come back as None."""
+    gradients are accumulated in fp32 and cast back.  ``params``: see :func:`_finish_partials` (keys gamma, beta, colb)."""
     dev = require_device(gy, x, colb, res, stats, gamma, beta)
     bf16 = x.dtype == torch.bfloat16
     if bf16:
@@ -1463,18 +1504,19 @@ def ln_res_bwd(gy: Tensor, x: Tensor, colb: Optional[Tensor], res: Optional[Tens
         check(fn(ptr(gy), _ld(gy), ptr(x), _ld(x), ptr(colb.contiguous() if colb is not None else None), ptr(res),
                  _ld(res) if res is not None else 0, ptr(stats), ptr(gamma.contiguous()), ptr(beta.contiguous()), int(relu_out), p,
                  seed, ptr(gs), max(d, 1), ptr(partials), npart.value, n, d, ptr(seed_base), stream_of(dev)), name)
-    if not bf16 and defer_to is not None:
-        dg_, db_, dc_ = _defer_or_reduce(partials, [(defer_to[0], 0, (d,)), (defer_to[1], d, (d,)),
-                                                    (defer_to[2] if colb is not None else None, 2 * d,
-                                                     tuple(defer_to[2].shape) if (colb is not None and defer_to[2] is not None) else (d,))], True)
-        return gs, dg_, db_, dc_
-    if bf16 and (3 * d) % 4 == 0 and npart.value <= 4096:
-        red = reduce_partials_to(partials.view(npart.value, 3 * d), 3 * d, torch.bfloat16).view(3, d)   # summed and rounded in one launch
-    else:
-        red = reduce_partials(partials)
-        if bf16:
-            red = red.to(torch.bfloat16)
-    return gs, red[0], red[1], red[2]
+    dg, db, dc = _finish_ln_res(partials, d, colb, params, x.dtype)
+    return gs, dg, db, dc
+
+
+def _finish_ln_res(partials: Tensor, d: int, colb: Optional[Tensor], params, dtype: torch.dtype):
+    """(dgamma, dbeta, dcolb) from the [P, 3, d] partials of ``ln_res_bwd`` / ``ln_res_bwd_pma``.  The third row is summed without a
+    colb too (callers outside a node read it); a node that passes ``params`` and has no colb does not want it.  A colb PARAMETER gets
+    its gradient in its own shape."""
+    c_p = params.get("colb") if params else None
+    sections = _ln_sections(d, (tuple(c_p.shape) if c_p is not None else (d,)) if (colb is not None or not params) else None)
+    # (kept as it was: bf16 reduces at once -- summed and rounded in one launch -- though the rule could queue bf16 parameters)
+    grads = _finish_partials(partials, sections, params, out_dtype=dtype, queue=dtype == torch.float32)
+    return (*grads, None)[:3]
 
 
 def ln_res_bwd_pma_supported(d: int, heads: int, dtype: torch.dtype = torch.float32) -> bool:
@@ -1484,7 +1526,7 @@ def ln_res_bwd_pma_supported(d: int, heads: int, dtype: torch.dtype = torch.floa
 
 
 def ln_res_bwd_pma(gy: Tensor, x: Tensor, colb: Tensor, stats: Tensor, gamma: Tensor, beta: Tensor, m: Tensor, l: Tensor,
-                   defer_to=None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+                   params=None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """Backward of ``LayerNorm(x + colb)`` where ``x`` is PMA's pooled output, with the attention-backward statistics written by
     the same pass: returns (gs, dgamma, dbeta, dcolb, pma_stats [n, H, 2]) -- include/allset_hip.h allset_ln_res_bwd_pma.
     fp32, or bf16 activations and parameters (fp32 statistics)."""
@@ -1513,17 +1555,8 @@ def ln_res_bwd_pma(gy: Tensor, x: Tensor, colb: Tensor, stats: Tensor, gamma: Te
         check(fn(ptr(gy), _ld(gy), ptr(x), _ld(x), ptr(colb.contiguous()), ptr(stats), ptr(gamma.contiguous()),
                  ptr(beta.contiguous()), ptr(gs), max(d, 1), ptr(partials), npart.value, n, d,
                  ptr(m.contiguous()), ptr(l.contiguous()), ptr(pstats), H, stream_of(dev)), name)
-    if not bf16 and defer_to is not None:        # (gamma, beta, att_r) PARAMETERS: queued inside deferred_param_grads()
-        dg_, db_, dc_ = _defer_or_reduce(partials, [(defer_to[0], 0, (d,)), (defer_to[1], d, (d,)),
-                                                    (defer_to[2], 2 * d, tuple(defer_to[2].shape) if defer_to[2] is not None else (d,))], True)
-        return gs, dg_, db_, dc_, pstats
-    if bf16 and (3 * d) % 4 == 0 and npart.value <= 4096:
-        red = reduce_partials_to(partials.view(npart.value, 3 * d), 3 * d, torch.bfloat16).view(3, d)
-    else:
-        red = reduce_partials(partials)
-        if bf16:
-            red = red.to(torch.bfloat16)
-    return gs, red[0], red[1], red[2], pstats
+    dg, db, dc = _finish_ln_res(partials, d, colb, params, x.dtype)
+    return gs, dg, db, dc, pstats
 
 
 class _LayerNormRes(torch.autograd.Function):
@@ -1536,7 +1569,7 @@ class _LayerNormRes(torch.autograd.Function):
         y, stats = ln_res_fwd(x, cb, res, gamma, beta, eps, relu_out, p, seed, base)
         ctx.save_for_backward(x, cb, res, stats, gamma, beta)
         ctx.cfg = (bool(relu_out), float(p), seed, base, colb.shape if colb is not None else None)
-        ctx.params = (gamma, beta, colb)
+        ctx.params = {"gamma": gamma, "beta": beta, "colb": colb}
         return y
 
     @staticmethod
@@ -1544,10 +1577,8 @@ class _LayerNormRes(torch.autograd.Function):
     def backward(ctx, gy):
         x, cb, res, stats, gamma, beta = ctx.saved_tensors
         relu_out, p, seed, base, cshape = ctx.cfg
-        need = ctx.needs_input_grad
-        dfr = _Deferred.active and need[3] and need[4] and (cshape is None or need[1]) and x.dtype == torch.float32
         gs, dg, db, dc = ln_res_bwd(gy.contiguous(), x, cb, res, stats, gamma, beta, relu_out, p, seed, base,
-                                    defer_to=ctx.params if dfr else None)
+                                    params=_queue_params(ctx, {"gamma": 3, "beta": 4, "colb": 1}))
         return (gs, (dc.reshape(cshape) if (cshape is not None and dc is not None) else None), (gs if res is not None else None), dg, db,
                 None, None, None)
 
@@ -1581,7 +1612,7 @@ class _PmaProject(torch.autograd.Function):
             alpha = torch.nn.functional.linear(x, w_a, b_a)
         ctx.save_for_backward(x, w_v, w4)
         ctx.cfg = (b_v is not None, b_a is not None, aux, H)
-        ctx.params = (w_v, b_v)
+        ctx.params = {"weight": w_v, "bias": b_v}
         return x_v, alpha
 
     @staticmethod
@@ -1595,8 +1626,7 @@ class _PmaProject(torch.autograd.Function):
                 and fused_linear_bwd_all_aux_supported(w_v.shape[0], w_v.shape[1])):
             # one pass: both gradient branches of x, the projection's weight / bias gradient and the logit columns' own
             g4 = g_alpha if H == 4 else torch.cat([g_alpha, g_alpha.new_zeros(g_alpha.shape[0], 4 - H)], dim=1)
-            defer = ctx.params if (_Deferred.active and has_bv and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]) else None
-            gx, gwv, gbv, gwa4, gba4 = fused_linear_bwd_all_aux(g_v, w_v, x, g4, w4, defer_to=defer)
+            gx, gwv, gbv, gwa4, gba4 = fused_linear_bwd_all_aux(g_v, w_v, x, g4, w4, params=_queue_params(ctx, {"weight": 1, "bias": 2}))
             return (gx, gwv, gbv if has_bv else None, gwa4[:H] if H < 4 else gwa4,
                     (gba4[:H] if H < 4 else gba4) if has_ba else None)
         if ctx.needs_input_grad[0]:
@@ -1636,7 +1666,7 @@ class _PmaResidualFF(torch.autograd.Function):
         y, stats = ln_res_fwd(out, None, z, gamma, beta, eps, relu_post, p, seed, base)
         ctx.save_for_backward(out, y1, z, mask, stats, w1, w2, gamma, beta)
         ctx.cfg = (bool(relu_post), float(p), seed, base, b1 is not None, b2 is not None)
-        ctx.params = (gamma, beta)
+        ctx.params = {"gamma": gamma, "beta": beta}
         return y
 
     @staticmethod
@@ -1644,11 +1674,9 @@ class _PmaResidualFF(torch.autograd.Function):
     def backward(ctx, gy):
         out, y1, z, mask, stats, w1, w2, gamma, beta = ctx.saved_tensors
         relu_post, p, seed, base, has_b1, has_b2 = ctx.cfg
-        need = ctx.needs_input_grad
-        prm = getattr(ctx, "params", None)
-        dfr = _Deferred.active and prm is not None and need[5] and need[6] and out.dtype == torch.float32
+        # (kept as it was: only the LayerNorm pair may queue; the Linear-gradient buffers below pass no parameters)
         gs, dg, db, _ = ln_res_bwd(gy.contiguous(), out, None, z, stats, gamma, beta, relu_post, p, seed, base,
-                                   defer_to=(prm[0], prm[1], None) if dfr else None)
+                                   params=_queue_params(ctx, {"gamma": 5, "beta": 6}))
         zy = None if mask is not None else z
         if mask is not None and gs.shape[0] > 0 and one_pass_preferred(w2.shape[0], w2.shape[1]) and one_pass_preferred(w1.shape[0], w1.shape[1]):
             # round 3: the split-role one-pass kernel covers both Linears (relu prologue + mask; plain + acc_in): two launches
@@ -1733,10 +1761,11 @@ def fused_linear_bwd_pma_tail_supported(heads: int) -> bool:
 
 
 def fused_linear_bwd_pma_tail(gy: Tensor, weight: Tensor, pooled: Tensor, colb: Optional[Tensor], stats: Tensor, gamma: Tensor, beta: Tensor,
-                              gres: Tensor, m: Tensor, l: Tensor, want_bias: bool = True, defer_to=None):
+                              gres: Tensor, m: Tensor, l: Tensor, want_bias: bool = True, params=None):
     """``(g_pooled, dgamma0, dbeta0, dcolb, gW, gb, pma_stats)``: the backward of the PMA tail's first rFF Linear with the residual
     branch's gradient added in front of ln0's backward, ln0's backward, and the pooling's backward statistics -- ONE pass
-    (include/allset_hip_ext.h allset_fused_linear_bwd_pma_tail; until round 6: fused_linear_bwd_all(acc_in) + ln_res_bwd_pma)."""
+    (include/allset_hip_ext.h allset_fused_linear_bwd_pma_tail; until round 6: fused_linear_bwd_all(acc_in) + ln_res_bwd_pma).
+    ``params``: see :func:`_finish_partials` (keys weight, bias, gamma, beta, colb)."""
     dev = require_device(gy, weight, pooled, colb, stats, gamma, beta, gres, m, l)
     _check_f32(gy, weight, pooled, colb, stats, gamma, beta, gres, m, l)
     gy, pooled, gres = _rowmajor(gy), _rowmajor(pooled), _rowmajor(gres)
@@ -1756,16 +1785,11 @@ def fused_linear_bwd_pma_tail(gy: Tensor, weight: Tensor, pooled: Tensor, colb: 
             ptr(gy), _ld(gy), ptr(weight.contiguous()), ptr(pooled), _ld(pooled), ptr(colb.contiguous() if colb is not None else None),
             ptr(stats), ptr(gamma.contiguous()), ptr(beta.contiguous()), ptr(gres), _ld(gres), ptr(gx), max(I, 1), ptr(part), M, P,
             ptr(m.contiguous()), ptr(l.contiguous()), ptr(pstats), H, n, O, I, stream_of(dev)), "allset_fused_linear_bwd_pma_tail")
-    o = O * I
-    if defer_to is not None and colb is not None and _deferrable(part, *defer_to):
-        # (weight, bias, gamma0, beta0, att_r) PARAMETERS: queued for the batched reduction of deferred_param_grads()
-        w_p, b_p, g_p, bt_p, c_p = defer_to
-        _defer(part, [(w_p, 0, (O, I)), (b_p if want_bias else None, o, (O,)), (g_p, o + O, (I,)), (bt_p, o + O + I, (I,)),
-                      (c_p, o + O + 2 * I, tuple(c_p.shape))])
-        return gx, None, None, None, None, None, pstats
-    red = reduce_partials(part)
-    return (gx, red[o + O:o + O + I], red[o + O + I:o + O + 2 * I], red[o + O + 2 * I:o + O + 3 * I], red[:o].view(O, I),
-            red[o:o + O] if want_bias else None, pstats)
+    c_p = params.get("colb") if params else None
+    sections = _one_pass_sections(O, I, want_bias, ln=I, colb_shape=tuple(c_p.shape) if c_p is not None else (I,))
+    # (kept as it was: without a colb nothing is queued, though the rule could)
+    g = _by_key(sections, _finish_partials(part, sections, params, queue=colb is not None))
+    return gx, g["gamma"], g["beta"], g["colb"], g["weight"], g.get("bias"), pstats
 
 
 def fused_linear_bwd_ln_pro_supported() -> bool:
@@ -1774,9 +1798,10 @@ def fused_linear_bwd_ln_pro_supported() -> bool:
 
 def fused_linear_bwd_ln_pro(gy: Tensor, s: Tensor, stats2: Tensor, gamma2: Tensor, beta2: Tensor, relu_post: bool, p: float, seed: int,
                             seed_base: Optional[Tensor], mask: Tensor, weight: Tensor, x: Tensor, relu_in: bool, want_bias: bool = True,
-                            defer_to=None):
+                            params=None):
     """``(gs, dgamma2, dbeta2, gx, gW, gb)``: ln1's backward (on the saved sum ``s``) as the gy prologue of the second rFF Linear's
-    one-pass backward (include/allset_hip_ext.h allset_fused_linear_bwd_ln_pro; until round 6: ln_res_bwd + fused_linear_bwd_all)."""
+    one-pass backward (include/allset_hip_ext.h allset_fused_linear_bwd_ln_pro; until round 6: ln_res_bwd + fused_linear_bwd_all).
+    ``params``: see :func:`_finish_partials` (keys weight, bias, gamma, beta)."""
     dev = require_device(gy, s, stats2, gamma2, beta2, mask, weight, x)
     _check_f32(gy, s, stats2, gamma2, beta2, weight, x)
     gy, s, x = _rowmajor(gy), _rowmajor(s), _rowmajor(x)
@@ -1795,13 +1820,9 @@ def fused_linear_bwd_ln_pro(gy: Tensor, s: Tensor, stats2: Tensor, gamma2: Tenso
             ptr(gy), _ld(gy), ptr(s), _ld(s), ptr(stats2), ptr(gamma2.contiguous()), ptr(beta2.contiguous()), int(relu_post), float(p), int(seed),
             ptr(seed_base), ptr(mask), ptr(weight.contiguous()), ptr(x), _ld(x), int(relu_in), ptr(gs), max(O, 1), ptr(gx), max(I, 1), ptr(part), M, P,
             n, O, I, stream_of(dev)), "allset_fused_linear_bwd_ln_pro")
-    o = O * I
-    if defer_to is not None and _deferrable(part, *defer_to):
-        w_p, b_p, g_p, bt_p = defer_to         # (weight, bias, gamma1, beta1) PARAMETERS
-        _defer(part, [(w_p, 0, (O, I)), (b_p if want_bias else None, o, (O,)), (g_p, o + O, (O,)), (bt_p, o + 2 * O, (O,))])
-        return gs, None, None, gx, None, None
-    red = reduce_partials(part)
-    return gs, red[o + O:o + 2 * O], red[o + 2 * O:o + 3 * O], gx, red[:o].view(O, I), (red[o:o + O] if want_bias else None)
+    sections = _one_pass_sections(O, I, want_bias, ln=O)
+    g = _by_key(sections, _finish_partials(part, sections, params))
+    return gs, g["gamma"], g["beta"], gx, g["weight"], g.get("bias")
 
 
 def pma_tail_bwd(saved, cfg, gy: Tensor, m: Optional[Tensor] = None, l: Optional[Tensor] = None, params=None):
@@ -1810,15 +1831,14 @@ def pma_tail_bwd(saved, cfg, gy: Tensor, m: Optional[Tensor] = None, l: Optional
     statistics written by the same pass when the softmax statistics ``(m, l)`` are given."""
     pooled, cb, stats0, g0, b0, out, y1, mask, s, stats1, w1, w2, g1, bt1 = saved
     relu_post, p, seed, base, has_b1, has_b2 = cfg
-    # ``params`` = (att_r, g0, b0, w1, b1, w2, b2, g1, bt1) as the node received them: inside deferred_param_grads() the two one-pass
-    # kernels' parameter gradients are queued for the batched reduction and come back as None
-    d1 = (params[5], params[6], params[7], params[8]) if params is not None else None
-    d0 = (params[3], params[4], params[1], params[2], params[0]) if params is not None else None
+    # ``params`` = the node's parameters by name (through :func:`_queue_params`): each one-pass kernel takes its own
+    q1 = _pick(params, weight="w2", bias="b2", gamma="g1", beta="bt1")
+    q0 = _pick(params, weight="w1", bias="b1", gamma="g0", beta="b0", colb="att_r")
     if fused_linear_bwd_ln_pro_supported():
         # ln1's backward inside the second Linear's one-pass backward (csrc/fused_bwd6.hip PT2): one pass instead of two
         gs, dg1, db1, gh, gw2, gb2 = fused_linear_bwd_ln_pro(gy.contiguous(), s, stats1, g1, bt1, relu_post, p, seed, base, mask, w2, y1, True,
-                                                             want_bias=has_b2, defer_to=d1)
-    else:
+                                                             want_bias=has_b2, params=q1)
+    else:                                         # (kept as it was, here and below: the fallbacks and the dummy-head form pass no parameters)
         gs, dg1, db1, _ = ln_res_bwd(gy.contiguous(), s, None, None, stats1, g1, bt1, relu_post, p, seed, base)
         gh, _, _, gw2, gb2 = fused_linear_bwd_all(gs, mask, 0.0, w2, y1, None, None, None, True, 0.0, 0, want_bias=has_b2)
     if m is None and fused_linear_bwd_pma_tail_supported(1):
@@ -1829,7 +1849,7 @@ def pma_tail_bwd(saved, cfg, gy: Tensor, m: Optional[Tensor] = None, l: Optional
     if m is not None and fused_linear_bwd_pma_tail_supported(m.shape[1]):
         # the first Linear's backward, ln0's backward and the pooling's statistics in ONE pass (csrc/fused_bwd6.hip PT)
         g_pooled, dg0, db0, dc, gw1, gb1, pstats = fused_linear_bwd_pma_tail(gh, w1, pooled, cb, stats0, g0, b0, gs, m, l, want_bias=has_b1,
-                                                                             defer_to=d0)
+                                                                             params=q0)
         return g_pooled, dc, dg0, db0, gw1, gb1, gw2, gb2, dg1, db1, pstats
     gout, _, _, gw1, gb1 = fused_linear_bwd_all(gh, None, 0.0, w1, out, None, None, None, False, 0.0, 0, acc_in=gs, want_bias=has_b1)
     if m is not None:
@@ -1840,15 +1860,7 @@ def pma_tail_bwd(saved, cfg, gy: Tensor, m: Optional[Tensor] = None, l: Optional
     return g_pooled, dc, dg0, db0, gw1, gb1, gw2, gb2, dg1, db1, pstats
 
 
-def tail_defer_params(ctx, idx):
-    """``ctx.params`` (att_r, g0, b0, w1, b1, w2, b2, g1, bt1) when the node runs inside ``deferred_param_grads()`` and every one of
-    them (inputs ``idx`` of the node) wants its gradient; None otherwise."""
-    if not _Deferred.active or getattr(ctx, "params", None) is None:
-        return None
-    if not all(ctx.needs_input_grad[i] for i, q in zip(idx, ctx.params) if q is not None):
-        return None
-    return ctx.params
-
+_TAIL_INPUTS = dict(att_r=1, g0=2, b0=3, w1=5, b1=6, w2=7, b2=8, g1=9, bt1=10)      # (positions in _PmaTail.forward; its ctx.params has these names)
 
 class _PmaTail(torch.autograd.Function):
     """``dropout_p(relu_post?(ln1(out + relu(rFF(out)))))`` with ``out = ln0(pooled + att_r)`` as one autograd node on two forward
@@ -1859,14 +1871,14 @@ class _PmaTail(torch.autograd.Function):
         y, saved, cfg = pma_tail_fwd(pooled, att_r.reshape(-1), g0, b0, eps0, w1, b1, w2, b2, g1, bt1, eps1, relu_post, p)
         ctx.save_for_backward(*saved)
         ctx.cfg, ctx.cshape = cfg, att_r.shape
-        ctx.params = (att_r, g0, b0, w1, b1, w2, b2, g1, bt1)
+        ctx.params = dict(att_r=att_r, g0=g0, b0=b0, w1=w1, b1=b1, w2=w2, b2=b2, g1=g1, bt1=bt1)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
         g_pooled, dc, dg0, db0, gw1, gb1, gw2, gb2, dg1, db1, _ = pma_tail_bwd(ctx.saved_tensors, ctx.cfg, gy,
-                                                                               params=tail_defer_params(ctx, (1, 2, 3, 5, 6, 7, 8, 9, 10)))
+                                                                               params=_queue_params(ctx, _TAIL_INPUTS))
         return g_pooled, (dc.reshape(ctx.cshape) if dc is not None else None), dg0, db0, None, gw1, gb1, gw2, gb2, dg1, db1, None, None, None
 
 
@@ -2023,12 +2035,10 @@ def wgrad_bf16_ex2_supported(O: int, I: int, bits: bool, aux: bool) -> bool:
 
 
 def wgrad_bf16_ex2(ga: Tensor, u: Tensor, bits: Optional[Tensor] = None, g4: Optional[Tensor] = None, want_bias: bool = True,
-                   defer_to=None):
+                   params=None):
     """``(gW, gb[, gWa [4, I], gba [4]])`` of a bf16 Linear in one pass over ``ga`` and ``u``: ``bits`` = the relu bit mask of the
     Linear's output (``ga`` is the gradient BEFORE the mask), ``g4`` = the fp32 [n, 4] gradient of four auxiliary output columns.
-    Results bf16 (summed in fp32, rounded once by the reduction).  ``defer_to`` = the (weight, bias) PARAMETERS: inside
-    ``deferred_param_grads()`` gW / gb are queued for the batched reduction and come back as None (the auxiliary rows, whose
-    weights are not parameters, are reduced at once)."""
+    Results bf16 (summed in fp32, rounded once by the reduction).  ``params``: see :func:`_finish_partials` (keys weight, bias)."""
     dev = require_device(ga, u)
     _check_dtype(torch.bfloat16, ga, u)
     ga, u = _rowmajor(ga), _rowmajor(u)
@@ -2045,23 +2055,9 @@ def wgrad_bf16_ex2(ga: Tensor, u: Tensor, bits: Optional[Tensor] = None, g4: Opt
     with on_device(dev), _timed("wgrad", dev, nbytes):
         check(lib.allset_wgrad_bf16_ex2(ptr(ga), _ld(ga), ptr(bits), ptr(g4), ptr(u), _ld(u), ptr(part), M, int(want_bias), ns.value,
                                         n, O, I, stream_of(dev)), "allset_wgrad_bf16_ex2")
-    M_main = O * I + (O if want_bias else 0)
-    if defer_to is not None and M_main % 4 == 0 and _deferrable(part, defer_to[0], defer_to[1] if want_bias else None, M=M_main):
-        _defer(part, [(defer_to[0], 0, (O, I)), (defer_to[1] if want_bias else None, O * I, (O,))], M=M_main)
-        if g4 is None:
-            return None, None
-        redx = reduce_partials_slice(part, M_main, 4 * I + 4, torch.bfloat16)
-        return None, None, redx[:4 * I].view(4, I), redx[4 * I:]
-    red = reduce_partials_to(part, M, torch.bfloat16)
-    gw = red[:O * I].view(O, I)
-    off = O * I
-    gb = None
-    if want_bias:
-        gb = red[off:off + O]
-        off += O
-    if g4 is None:
-        return gw, gb
-    return gw, gb, red[off:off + 4 * I].view(4, I), red[off + 4 * I:off + 4 * I + 4]
+    sections = _wgrad_sections(O, I, want_bias, aux=g4 is not None)
+    g = _by_key(sections, _finish_partials(part, sections, params, out_dtype=torch.bfloat16))
+    return (g["weight"], g.get("bias")) + ((g["aux_w"], g["aux_b"]) if g4 is not None else ())
 
 
 class _LinearBf16(torch.autograd.Function):
@@ -2082,7 +2078,7 @@ class _LinearBf16(torch.autograd.Function):
             ctx.save_for_backward(x, weight, y if relu_out else None)
         ctx.has_bias = bias is not None
         ctx.use_bits = use_bits
-        ctx.params = (weight, bias)               # (the objects themselves: deferred_param_grads assigns their .grad)
+        ctx.params = {"weight": weight, "bias": bias}               # (the objects themselves: deferred_param_grads assigns their .grad)
         return y
 
     @staticmethod
@@ -2096,8 +2092,7 @@ class _LinearBf16(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 gx = linear_bf16_bwd_bits(gy, weight, y)
             if need_w:
-                defer = ctx.params if (_Deferred.active and ctx.needs_input_grad[1] and (not ctx.has_bias or ctx.needs_input_grad[2])) else None
-                gw, gb = wgrad_bf16_ex2(gy, x, bits=y, want_bias=ctx.has_bias, defer_to=defer)
+                gw, gb = wgrad_bf16_ex2(gy, x, bits=y, want_bias=ctx.has_bias, params=_queue_params(ctx, {"weight": 1, "bias": 2}))
             return gx, gw, gb, None
         ga = gy
         if ctx.needs_input_grad[0]:
@@ -2125,7 +2120,7 @@ class _PmaProjectBf16(torch.autograd.Function):
         x_v, a4 = linear_bf16_fwd(x, w_v, b_v, False, w4, b4)
         ctx.save_for_backward(x, w_v, w4)
         ctx.cfg = (b_v is not None, b_a is not None, H)
-        ctx.params = (w_v, b_v)
+        ctx.params = {"weight": w_v, "bias": b_v}
         return x_v, (a4 if H == 4 else a4[:, :H].contiguous())
 
     @staticmethod
@@ -2144,8 +2139,7 @@ class _PmaProjectBf16(torch.autograd.Function):
                 and g_v.stride(0) % 8 == 0 and x.stride(1) == 1 and x.stride(0) % 8 == 0:
             # the four logit rows ride in the value projection's weight-gradient pass (one read of x instead of two)
             g4 = g_alpha if H == 4 else torch.cat([g_alpha, g_alpha.new_zeros(g_alpha.shape[0], 4 - H)], dim=1)
-            defer = ctx.params if (_Deferred.active and ctx.needs_input_grad[1] and (not has_bv or ctx.needs_input_grad[2])) else None
-            gwv, gbv, gwa4, gba4 = wgrad_bf16_ex2(g_v, x, g4=g4, want_bias=has_bv, defer_to=defer)
+            gwv, gbv, gwa4, gba4 = wgrad_bf16_ex2(g_v, x, g4=g4, want_bias=has_bv, params=_queue_params(ctx, {"weight": 1, "bias": 2}))
             gwa, gba = gwa4[:H], (gba4[:H] if has_ba else None)
             return gx, gwv, gbv, gwa, gba
         if need_v:
@@ -2184,7 +2178,7 @@ class _PmaResidualFFBf16(torch.autograd.Function):
         y, stats = ln_res_fwd(out, None, z, gamma, beta, eps, relu_post, p, seed, base)
         ctx.save_for_backward(out, h, z, stats, w1, w2, gamma, beta, mh, mz)
         ctx.cfg = (bool(relu_post), float(p), seed, base, b1 is not None, b2 is not None)
-        ctx.params = (w1, b1, w2, b2, gamma, beta)
+        ctx.params = dict(w1=w1, b1=b1, w2=w2, b2=b2, gamma=gamma, beta=beta)
         return y
 
     @staticmethod
@@ -2192,15 +2186,14 @@ class _PmaResidualFFBf16(torch.autograd.Function):
     def backward(ctx, gy):
         out, h, z, stats, w1, w2, gamma, beta, mh, mz = ctx.saved_tensors
         relu_post, p, seed, base, has_b1, has_b2 = ctx.cfg
-        need = ctx.needs_input_grad
-        dfr = _Deferred.active and all(need[1:7][i] for i, q in enumerate(ctx.params) if q is not None)
-        p_w1, p_b1, p_w2, p_b2, p_g, p_b = ctx.params
-        gs, dg, db, _ = ln_res_bwd(gy.contiguous(), out, None, z, stats, gamma, beta, relu_post, p, seed, base)     # (2048 partial rows: its own reduction)
+        # (kept as it was: one decision over all six parameters, and the LayerNorm pair -- 2048 partial rows -- passes none and reduces at once)
+        q = _queue_params(ctx, {"w1": 1, "b1": 2, "w2": 3, "b2": 4, "gamma": 5, "beta": 6})
+        gs, dg, db, _ = ln_res_bwd(gy.contiguous(), out, None, z, stats, gamma, beta, relu_post, p, seed, base)
         if mh is not None:
             gh = linear_bf16_bwd_bits(gs, w2, mz)
-            gw2, gb2 = wgrad_bf16_ex2(gs, h, bits=mz, want_bias=has_b2, defer_to=(p_w2, p_b2) if dfr else None)
+            gw2, gb2 = wgrad_bf16_ex2(gs, h, bits=mz, want_bias=has_b2, params=_pick(q, weight="w2", bias="b2"))
             gout = linear_bf16_bwd_bits(gh, w1, mh, acc_in=gs)                  # gs + the rFF branch
-            gw1, gb1 = wgrad_bf16_ex2(gh, out, bits=mh, want_bias=has_b1, defer_to=(p_w1, p_b1) if dfr else None)
+            gw1, gb1 = wgrad_bf16_ex2(gh, out, bits=mh, want_bias=has_b1, params=_pick(q, weight="w1", bias="b1"))
             return gout, gw1, gb1, gw2, gb2, dg, db, None, None, None
         gh, ga2 = linear_bf16_bwd(gs, w2, z, want_ga=True)
         gw2, gb2 = wgrad(ga2, h, want_bias=has_b2)
@@ -2233,9 +2226,9 @@ def linear_narrow_supported(gy: Tensor, x: Tensor, weight: Tensor) -> bool:
             and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0)
 
 
-def linear_narrow_bwd(gy: Tensor, x: Tensor, weight: Tensor, want_gx: bool = True, defer_to=None):
+def linear_narrow_bwd(gy: Tensor, x: Tensor, weight: Tensor, want_gx: bool = True, want_bias: bool = True, params=None):
     """``(gx, gW, gb)`` of ``y = x W^T + b`` with at most 16 outputs (a classifier head) from one kernel (csrc/narrow_linear.hip).
-    ``defer_to`` = the (weight, bias) PARAMETERS: inside ``deferred_param_grads()`` gW / gb are queued and come back as None."""
+    ``params``: see :func:`_finish_partials` (keys weight, bias)."""
     dev = require_device(gy, x, weight)
     _check_f32(gy, x, weight)
     gy, x, weight = _rowmajor(gy), _rowmajor(x), weight.contiguous()
@@ -2250,11 +2243,9 @@ def linear_narrow_bwd(gy: Tensor, x: Tensor, weight: Tensor, want_gx: bool = Tru
     with on_device(dev):
         check(lib.allset_linear_narrow_bwd(ptr(gy), _ld(gy), ptr(x), _ld(x), ptr(weight), n, N, K, ptr(gx), K, ptr(part), M, ns.value,
                                            stream_of(dev)), "allset_linear_narrow_bwd")
-    if defer_to is not None and _deferrable(part, *defer_to):
-        _defer(part, [(defer_to[0], 0, (N, K)), (defer_to[1], N * K, (N,))])
-        return gx, None, None
-    red = reduce_partials(part)
-    return gx, red[:N * K].view(N, K), red[N * K:N * K + N]
+    sections = _one_pass_sections(N, K, want_bias)
+    g = _by_key(sections, _finish_partials(part, sections, params))
+    return gx, g["weight"], g.get("bias")
 
 
 # ---- the FIRST Linear of a model: [dropout ->] LayerNorm(raw features) -> Linear on an input without gradient (csrc/input_linear.hip) ----

@@ -452,7 +452,7 @@ class _PmaPoolLn0(torch.autograd.Function):
         cb = att_r.reshape(-1)
         y, stats = dense.ln_res_fwd(pooled, cb, None, gamma, beta, eps, False, 0.0, 0, None)
         ctx.inc, ctx.slope, ctx.cshape = inc, slope, att_r.shape
-        ctx.params = (gamma, beta, att_r)           # (the objects themselves: dense.deferred_param_grads assigns their .grad)
+        ctx.params = {"gamma": gamma, "beta": beta, "colb": att_r}           # (the objects themselves: dense.deferred_param_grads assigns their .grad)
         ctx.save_for_backward(V, alpha, pooled, m, l, cb, stats, gamma, beta)
         ctx.mark_non_differentiable(m, l)
         ctx.set_materialize_grads(False)     # (m, l never carry a gradient: no [n, H] zero-fills for them in every backward)
@@ -465,16 +465,17 @@ class _PmaPoolLn0(torch.autograd.Function):
         if gy is None:
             return (None,) * 9
         V, alpha, pooled, m, l, cb, stats, gamma, beta = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        dfr = dense._Deferred.active and need[5] and need[6] and need[7] and pooled.dtype == torch.float32
         g_pooled, dg, db, dc, pstats = dense.ln_res_bwd_pma(gy.contiguous(), pooled, cb, stats, gamma, beta, m, l,
-                                                            defer_to=ctx.params if dfr else None)
+                                                            params=dense._queue_params(ctx, {"colb": 5, "gamma": 6, "beta": 7}))
         T = ctx.inc.by_src
         H = alpha.shape[1]
         gV, galpha = ops.pma_bwd_src(T.rowptr, T.col, alpha, V, g_pooled, pstats, ctx.slope,
                                      variant=_variant(T, "pma_bwd_src", V.shape[0], V, H), row_order=T.row_order,
                                      split=_split(T, V, H), sizes=_sizes(T, V, H))
         return gV, galpha, None, None, None, (dc.reshape(ctx.cshape) if dc is not None else None), dg, db, None
+
+
+_POOL_TAIL_INPUTS = dict(att_r=5, g0=6, b0=7, w1=9, b1=10, w2=11, b2=12, g1=13, bt1=14)      # (positions in _PmaPoolTail.forward)
 
 
 class _PmaPoolTail(torch.autograd.Function):
@@ -491,7 +492,7 @@ class _PmaPoolTail(torch.autograd.Function):
                                    split=_split(csr, V, heads), sizes=_sizes(csr, V, heads))
         y, saved, cfg = dense.pma_tail_fwd(pooled, att_r.reshape(-1), g0, b0, eps0, w1, b1, w2, b2, g1, bt1, eps1, relu_post, p)
         ctx.inc, ctx.slope, ctx.cshape, ctx.cfg = inc, slope, att_r.shape, cfg
-        ctx.params = (att_r, g0, b0, w1, b1, w2, b2, g1, bt1)     # (the objects themselves: dense.deferred_param_grads assigns their .grad)
+        ctx.params = dict(att_r=att_r, g0=g0, b0=b0, w1=w1, b1=b1, w2=w2, b2=b2, g1=g1, bt1=bt1)     # (the objects themselves: dense.deferred_param_grads assigns their .grad)
         ctx.save_for_backward(V, alpha, m, l, *saved)
         ctx.mark_non_differentiable(m, l)
         ctx.set_materialize_grads(False)     # (m, l never carry a gradient: no [n, H] zero-fills for them in every backward)
@@ -505,7 +506,7 @@ class _PmaPoolTail(torch.autograd.Function):
             return (None,) * 18
         V, alpha, m, l = ctx.saved_tensors[:4]
         g_pooled, dc, dg0, db0, gw1, gb1, gw2, gb2, dg1, db1, pstats = dense.pma_tail_bwd(
-            ctx.saved_tensors[4:], ctx.cfg, gy, m, l, params=dense.tail_defer_params(ctx, (5, 6, 7, 9, 10, 11, 12, 13, 14)))
+            ctx.saved_tensors[4:], ctx.cfg, gy, m, l, params=dense._queue_params(ctx, _POOL_TAIL_INPUTS))
         T = ctx.inc.by_src
         H = alpha.shape[1]
         gV, galpha = ops.pma_bwd_src(T.rowptr, T.col, alpha, V, g_pooled, pstats, ctx.slope,
@@ -680,7 +681,7 @@ def _epilogue_backward(gy, y, act, p, seed, base, epi, bias=None, need_b=False):
     gb = None
     if need_b:
         # (inside dense.deferred_param_grads(): queued for the step's one batched reduction, and None here)
-        (gb,) = dense._defer_or_reduce(part, [(bias, 0, (y.shape[1],))], defer=True)
+        (gb,) = dense._finish_partials(part, [("bias", 0, (y.shape[1],))], {"bias": bias})
     return g, gb
 
 
